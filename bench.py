@@ -10,9 +10,15 @@ random-init weights), all inputs already resident in HBM.  Multi-GPU is frame-pa
 frames r, r+N, ...; finished frames are quantised to uint8 on the device and gathered over RCCL; no other
 collective is on the data path (weak scaling: every rank renders K frames).
 
-Rank 0 prints ONE JSON line with the contract fields plus `roofline` (dominant kernel, HIP-event timed on
-its launch stream inside the timed region) and `cpu_baseline` (the oracle port of the same frame, timed on
-the host cores, N = 1 only).
+Rank 0 prints ONE JSON line with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+A plain run does only what that line needs: set-up, warm-up, the timed steps.  --full adds everything else the
+benchmark measures: `roofline` (dominant kernel, HIP-event timed on its launch stream inside the timed region), frame
+latency and sample counts, the bounded training record `train`, and `cpu_baseline` (the oracle port of the same frame,
+timed on the host cores, N = 1 only).
+
+--dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy (float32): the finished
+uint8 frame(s) the caller receives (render / tile), or the loss and a fixed seeded sample of every parameter after the
+last optimisation step (train).  The inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -74,9 +80,14 @@ def parse():
     ap.add_argument("--half-tables", action="store_true",
                     help="the kernels read persistent fp16 copies of the grid tables (opt.half_tables; what load_checkpoint(half_tables=True) "
                          "sets up) -- with --mlp f16 the reference's -O mode without its per-call table casts (gridencoder/grid.py:43-44)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the dominant kernel's roofline (HIP events inside the "
+                         "timed region), frame latency, samples per frame, the bounded training record and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--no-train-record", action="store_true",
-                    help="skip the bounded config[2] run (64 graph-replayed training steps) that the default single-GPU render line "
+                    help="--full: skip the bounded config[2] run (64 graph-replayed training steps) that the single-GPU render line "
                          "carries under the key `train`")
     ap.add_argument("--cpu-baseline-size", type=int, default=0, help="0 = same size as the GPU workload")
     return ap.parse_args()
@@ -215,6 +226,26 @@ def train_record(args, device_index=0):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     samples = int(samples.item())
+    if args.dump_outputs:
+        arrays = {"loss": torch.as_tensor(losses[-1]).reshape(1)}
+        arrays.update(("param." + name, param_sample(p)) for name, p in m.named_parameters())
+        dump_outputs(args.dump_outputs, arrays)
+    rec = {
+        "metric": "training steps/sec @4096 rays", "value": K / elapsed, "unit": "steps/s", "n_gpus": 1, "steps": K, "warmup": W,
+        "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic",
+        "config": {"workload": f"config[2]: single-GPU training step, {args.rays} rays of a {size}x{size} frame, {GRID_TEXT[args.grid]}, "
+                               "march_rays_train + network + composite_rays_train fwd/bwd + grid_encode backward + Adam, "
+                               "update_extra_state every 16 steps (inside the timed region)", "grid": args.grid,
+                   "train_engine": args.train_engine},
+        "samples_per_s": samples / elapsed, "samples_per_step": samples / K,
+        "graph_captures": getattr(trainer, "captures", None), "graph_replays": getattr(trainer, "replays", None),
+        "graph_capture_log": getattr(trainer, "capture_log", None),
+        "loss_first": float(losses[0]), "loss_last": float(losses[-1])}
+    sps = [1e3 / t for t in seg_ms]
+    rec.update(steps_per_s_by_segment=sps, spread=(max(sps) - min(sps)) / (sum(sps) / len(sps)) if sps else None)
+    if not args.full:
+        return rec
     # The dominant kernel of the step (the xyz table's gradient scatter), timed with HIP events around its own C-ABI call on the
     # stream it is launched on.  A replayed hipGraph exposes no per-kernel events, so the SAME step is enqueued eagerly a few times
     # right after the timed region (same model state, same batches' distribution, same kernels and launch parameters as the
@@ -272,21 +303,35 @@ def train_record(args, device_index=0):
                          "request per touched line (memory-side atomics: ~20 G requests/s chip-wide; LDS float atomics: 3.6 clocks per "
                          "lane): bound by those two rates, not by bytes.  The call runs on a side stream beside the weight-gradient and "
                          "audio-backward kernels, so its duration here includes that contention")
-    sps = [1e3 / t for t in seg_ms]
-    return ({
-        "metric": "training steps/sec @4096 rays", "value": K / elapsed, "unit": "steps/s", "n_gpus": 1, "steps": K, "warmup": W,
-        "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic",
-        "config": {"workload": f"config[2]: single-GPU training step, {args.rays} rays of a {size}x{size} frame, {GRID_TEXT[args.grid]}, "
-                               "march_rays_train + network + composite_rays_train fwd/bwd + grid_encode backward + Adam, "
-                               "update_extra_state every 16 steps (inside the timed region)", "grid": args.grid,
-                   "train_engine": args.train_engine},
-        "samples_per_s": samples / elapsed, "samples_per_step": samples / K,
-        "steps_per_s_by_segment": sps, "spread": (max(sps) - min(sps)) / (sum(sps) / len(sps)) if sps else None,
-        "occupancy_refresh_ms": refresh_ms, "occupancy_refresh_share_of_step": refresh_ms / 16 / (elapsed / K * 1e3),
-        "graph_captures": getattr(trainer, "captures", None), "graph_replays": getattr(trainer, "replays", None),
-        "graph_capture_log": getattr(trainer, "capture_log", None),
-        "loss_first": float(losses[0]), "loss_last": float(losses[-1]), "roofline": roof})
+    rec.update(occupancy_refresh_ms=refresh_ms, occupancy_refresh_share_of_step=refresh_ms / 16 / (elapsed / K * 1e3), roofline=roof)
+    return rec
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_PARAM_SAMPLE = 1 << 20          # elements per parameter tensor in a --dump-outputs of the training workload
+
+
+def dump_outputs(dirname, arrays):
+    """{name: tensor or ndarray} -> dirname/<name>.npy, float32 (float64 stays float64)."""
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed {DUMP_LIMIT_BYTES}")
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def param_sample(t):
+    """All of a small tensor, else a fixed seeded sample of DUMP_PARAM_SAMPLE of its elements."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() <= DUMP_PARAM_SAMPLE:
+        return flat
+    idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_PARAM_SAMPLE, replace=False))
+    return flat[torch.from_numpy(idx).to(flat.device)]
 
 
 def ctypes_field(arg, name):
@@ -346,19 +391,21 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    full = args.full
     with torch.no_grad():
         for s in range(W):
             fpr.step(s)
         fpr.finish()
-        acc = {}
-        timer = hip.KernelTimer(kernel_select(engine, acc))
-        hip.set_timer(timer)
-        # a short run still times >= 8 steps (kernel events) and >= 8 frames (latency): the driver's --steps 20 gives 10 + 10
-        args.time_every = max(1, min(args.time_every, K // 8))
-        args.latency_every = max(1, min(args.latency_every, K // 8))
-        if engine == "fused":
-            hip.prof_enable(os.environ.get("RN_BENCH_PROF", "1") != "0")   # 0: tools/trace_gaps.py checks the timing costs nothing
-            c0 = fpr.loop_counters() or [0, 0, 0]
+        if full:
+            acc = {}
+            timer = hip.KernelTimer(kernel_select(engine, acc))
+            hip.set_timer(timer)
+            # a short run still times >= 8 steps (kernel events) and >= 8 frames (latency): the driver's --steps 20 gives 10 + 10
+            args.time_every = max(1, min(args.time_every, K // 8))
+            args.latency_every = max(1, min(args.latency_every, K // 8))
+            if engine == "fused":
+                hip.prof_enable(os.environ.get("RN_BENCH_PROF", "1") != "0")   # 0: tools/trace_gaps.py checks the timing costs nothing
+                c0 = fpr.loop_counters() or [0, 0, 0]
         from radnerf.parallel import LoopHintTooSmall
         for attempt in range(2):
             barrier()
@@ -368,9 +415,9 @@ def main():
                 lat_events = []
                 le = max(args.latency_every, 1)
                 for s in range(W, W + K):
-                    if engine == "fused":
+                    if full and engine == "fused":
                         hip.prof_pause((s - W) % max(args.time_every, 1) != 0)
-                    if (s - W) % le == 1 % le:      # never a frame whose kernel dispatches carry timing events, nor one that opens an audio batch
+                    if full and (s - W) % le == 1 % le:      # never a frame whose kernel dispatches carry timing events, nor one that opens an audio batch
                         ea, eb = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                         rs = fpr.render_stream(s) if hasattr(fpr, "render_stream") else torch.cuda.current_stream()
                         ea.record(rs)
@@ -379,7 +426,7 @@ def main():
                         lat_events.append((ea, eb))
                     else:
                         fpr.step(s)
-                fpr.finish()
+                done = fpr.finish()
             except LoopHintTooSmall:        # the device flagged a frame: this timing is void, repeat with every iteration
                 short = 1
             barrier()
@@ -392,21 +439,26 @@ def main():
             fpr.speculate_loop = False
             from radnerf import fused as _fused
             _fused.set_loop_hint(scene.model, None)
-            if engine == "fused":
+            if full and engine == "fused":
                 hip.prof_collect(); hip.prof_durations()      # drop the void attempt's kernel timings
                 c0 = fpr.loop_counters() or [0, 0, 0]
-        hip.set_timer(None)
-        if engine == "fused":
-            fused_launches, fused_ms = hip.prof_collect()
-            fused_durs = sorted(hip.prof_durations(), reverse=True)
-            hip.prof_enable(False)
-            c1 = fpr.loop_counters()                        # device-side loop statistics (cumulative counters)
-            live_total = (c1[1] - c0[1]) & 0xFFFFFFFF
-            iters_total = (c1[0] - c0[0]) & 0xFFFFFFFF      # launches that had samples to process
-            live_pf, slots_pf = live_total / K, ((c1[2] - c0[2]) & 0xFFFFFFFF) / K
-        else:
-            # untimed replay of a few of the timed frames to count live samples per frame
-            live_pf, slots_pf = fpr.count_samples(list(range(W, W + min(K, 8))))
+        if args.dump_outputs and rank == 0:
+            # the last step's finished frame: [H, W, 3] uint8 values (frame-parallel over N ranks: the [N, H, W, 3] frames of the
+            # last step as gathered on rank 0)
+            dump_outputs(args.dump_outputs, {"frame": done[-1] if done else fpr.last_frame})
+        if full:
+            hip.set_timer(None)
+            if engine == "fused":
+                fused_launches, fused_ms = hip.prof_collect()
+                fused_durs = sorted(hip.prof_durations(), reverse=True)
+                hip.prof_enable(False)
+                c1 = fpr.loop_counters()                        # device-side loop statistics (cumulative counters)
+                live_total = (c1[1] - c0[1]) & 0xFFFFFFFF
+                iters_total = (c1[0] - c0[0]) & 0xFFFFFFFF      # launches that had samples to process
+                live_pf, slots_pf = live_total / K, ((c1[2] - c0[2]) & 0xFFFFFFFF) / K
+            else:
+                # untimed replay of a few of the timed frames to count live samples per frame
+                live_pf, slots_pf = fpr.count_samples(list(range(W, W + min(K, 8))))
 
     el = torch.tensor([elapsed], dtype=torch.float64, device=device if dist is None or dist.get_backend() == "nccl" else "cpu")
     if dist is not None:
@@ -416,7 +468,7 @@ def main():
     fps = total_frames / elapsed
 
     if rank == 0:
-        res = timer.results()
+        res = timer.results() if full else {}
         roof = None
         lat = sorted(a.elapsed_time(b) for a, b in lat_events)
         latency = None
@@ -424,7 +476,7 @@ def main():
             latency = dict(mean=sum(lat) / len(lat), p50=lat[len(lat) // 2], p95=lat[min(len(lat) - 1, int(0.95 * len(lat)))],
                            frames_sampled=len(lat), method="HIP events on the render stream around every "
                            f"{max(args.latency_every, 1)}-th timed frame (frames are enqueued back to back, so this is the GPU time of a frame)")
-        if engine == "fused" and fused_launches:
+        if full and engine == "fused" and fused_launches:
             # the kernel was timed on every --time-every-th step; the stream's frames hold the same number of samples to within
             # a fraction of a percent, so the timed steps' share of the counted samples is their share of the steps
             timed_steps = len(range(0, K, max(args.time_every, 1)))
@@ -506,18 +558,22 @@ def main():
                                             backend=dist.get_backend(), world_seen_by_backend=dist.get_world_size())) if world > 1 else None,
                        "loop_iterations_enqueued": (getattr(scene.model, "_fused_loop_hint", None) or scene.opt.max_steps),
                        "parallelism": f"{'tile' if tile else 'frame'}-parallel x{world}"},
-            # tile-parallel: rank 0 counts its own band's samples; the bands are interleaved, so x world is the frame's
-            "samples_per_s": live_pf * (world if tile else 1) * fps, "samples_per_frame": live_pf * (world if tile else 1),
-            "sample_slots_per_frame": slots_pf * (world if tile else 1),
-            "frame_latency_ms": latency,
-            "roofline": roof,
         }
-        if world == 1 and not tile and not args.no_train_record and engine == "fused" and args.regime == "B":
+        if full:
+            out.update({
+                # tile-parallel: rank 0 counts its own band's samples; the bands are interleaved, so x world is the frame's
+                "samples_per_s": live_pf * (world if tile else 1) * fps, "samples_per_frame": live_pf * (world if tile else 1),
+                "sample_slots_per_frame": slots_pf * (world if tile else 1),
+                "frame_latency_ms": latency,
+                "roofline": roof,
+            })
+        if full and world == 1 and not tile and not args.no_train_record and engine == "fused" and args.regime == "B":
             # BASELINE config[2] in front of the driver: a bounded run of the training step (64 replayed steps after the warm-up,
             # ~2 s), same code as `bench.py --workload train`
             import argparse
             targs = argparse.Namespace(**vars(args))
             targs.steps, targs.warmup, targs.train_engine, targs.rays, targs.workload = 64, 33, "graph", 4096, "train"
+            targs.dump_outputs = None
             del scene, fpr
             torch.cuda.empty_cache()
             rec = train_record(targs, device.index or 0)
@@ -527,7 +583,7 @@ def main():
                             "steps_per_s_by_segment": rec["steps_per_s_by_segment"], "spread": rec["spread"],
                             "occupancy_refresh_ms": rec["occupancy_refresh_ms"], "graph_captures": rec["graph_captures"],
                             "roofline": rec["roofline"]}
-        if world == 1 and not args.no_cpu_baseline and args.regime == "B":
+        if full and world == 1 and not args.no_cpu_baseline and args.regime == "B":
             cb_size = args.cpu_baseline_size or size
             out["cpu_baseline"] = cpu_baseline({}, cb_size, GRIDS[args.grid])
             if not tile:

@@ -1,8 +1,16 @@
 """Seeded INPUTS of the golden cases, shared by the generator (tests/golden/make_golden.py, which feeds them to the
 reference's own wrappers) and by the tests (which feed them to the oracle on CPU and to the HIP operators on the GPU box).
 Only numpy / torch CPU code here; nothing reads /root/reference."""
+import os
+
 import numpy as np
 import torch
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+# A golden set whose file would exceed 1 MiB is stored in parts: reference_<name>_<prefix>.npz holds the arrays whose names
+# start with "<prefix>_", reference_<name>.npz the rest.
+SPLIT = {"ops": ("grid",)}
 
 HASH19 = dict(gridtype="hash", log2_hashmap_size=19)
 
@@ -77,3 +85,23 @@ def train_pixels(n_px, n_rays=4096, seed=5):
     """Pixel subset of the train-branch case (config[2]: 4096 rays of a frame)."""
     g = torch.Generator().manual_seed(seed)
     return torch.randint(0, n_px, (n_rays,), generator=g)
+
+
+def golden_parts(name, arrays):
+    """{file name: {array name: array}} -- how make_golden.py stores the golden set `name`."""
+    prefixes = SPLIT.get(name, ())
+    parts = {f"reference_{name}.npz": {}}
+    parts.update({f"reference_{name}_{p}.npz": {} for p in prefixes})
+    for k, a in arrays.items():
+        p = next((p for p in prefixes if k.startswith(p + "_")), None)
+        parts[f"reference_{name}_{p}.npz" if p else f"reference_{name}.npz"][k] = a
+    return parts
+
+
+def load_golden(name):
+    """Every array of the golden set `name`, from all of its parts, as one {array name: ndarray} dict."""
+    out = {}
+    for fname in golden_parts(name, {}):
+        with np.load(os.path.join(HERE, fname), allow_pickle=False) as z:
+            out.update((k, z[k]) for k in z.files)
+    return out

@@ -532,9 +532,10 @@ def main():
                      ("train_stable", make_stable)):
         if name in todo:
             out = fn(env)
-            path = os.path.join(HERE, f"reference_{name}.npz")
-            np.savez_compressed(path, **out)
-            print("wrote", path, f"{os.path.getsize(path) / 1024:.0f} KiB,", len(out), "arrays")
+            for fname, arrays in cases.golden_parts(name, out).items():
+                path = os.path.join(HERE, fname)
+                np.savez_compressed(path, **arrays)
+                print("wrote", path, f"{os.path.getsize(path) / 1024:.0f} KiB,", len(arrays), "arrays")
 
 
 if __name__ == "__main__":

@@ -146,7 +146,7 @@ def test_all_19_pybind_functions_reproduce_the_reference_vectors(po, hiplib):
     from radnerf.scene import SyntheticScene, default_opt
     mods = _pybind_modules(hiplib)
     rmb, geb, shb, fqb = mods["_raymarching_face"], mods["_gridencoder"], mods["_shencoder"], mods["_freqencoder"]
-    gold = np.load(os.path.join(here, "golden", "reference_ops.npz"), allow_pickle=False)
+    gold = cases.load_golden("ops")
     flow = np.load(os.path.join(here, "golden", "reference_flow.npz"))
     dev = "cuda"
     T = lambda k: torch.from_numpy(gold[k]).to(dev)  # noqa: E731

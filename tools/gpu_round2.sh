@@ -10,22 +10,22 @@ cd "$R"
 if [ "${PART:-A}" = "A" ]; then
 timeout -k 10 1000 python -m pytest tests -q -m gpu > "$O/pytest_gpu.log" 2>&1; rc=$?; tail -3 "$O/pytest_gpu.log"; [ $rc -eq 0 ] || exit $rc
 timeout -k 10 300 python __graft_entry__.py smoke > "$O/smoke.log" 2>&1 || { tail -5 "$O/smoke.log"; exit 1; }; tail -2 "$O/smoke.log"
-timeout -k 10 400 python bench.py > "$O/bench_hash19_f32.json" 2> "$O/bench_hash19_f32.err" || { tail "$O/bench_hash19_f32.err"; exit 1; }
+timeout -k 10 400 python bench.py --full > "$O/bench_hash19_f32.json" 2> "$O/bench_hash19_f32.err" || { tail "$O/bench_hash19_f32.err"; exit 1; }
 for v in "tiled16 f32" "hash19 f32x2" "tiled16 f32x2" "hash19 f16" "tiled16 f16"; do set -- $v
-  timeout -k 10 300 python bench.py --grid $1 --mlp $2 --no-cpu-baseline > "$O/bench_$1_$2.json" 2> "$O/bench_$1_$2.err" || { tail "$O/bench_$1_$2.err"; exit 1; }
+  timeout -k 10 300 python bench.py --full --grid $1 --mlp $2 --no-cpu-baseline > "$O/bench_$1_$2.json" 2> "$O/bench_$1_$2.err" || { tail "$O/bench_$1_$2.err"; exit 1; }
 done
-timeout -k 10 300 python bench.py --streams 2 --no-cpu-baseline > "$O/bench_hash19_f32_streams2.json" 2> "$O/bench_s2.err" || { tail "$O/bench_s2.err"; exit 1; }
-timeout -k 10 300 python bench.py --regime A --no-cpu-baseline > "$O/bench_hash19_f32_regimeA.json" 2> "$O/bench_A.err" || { tail "$O/bench_A.err"; exit 1; }
-timeout -k 10 300 python bench.py --audio-batch 0 --no-cpu-baseline > "$O/bench_hash19_f32_live_audio.json" 2> "$O/bench_la.err" || { tail "$O/bench_la.err"; exit 1; }
-timeout -k 10 300 python bench.py --engine ops --steps 40 --warmup 5 --no-cpu-baseline > "$O/bench_hash19_ops_engine.json" 2> "$O/bench_ops.err" || { tail "$O/bench_ops.err"; exit 1; }
-timeout -k 10 300 python bench.py --workload train --steps 128 > "$O/bench_train.json" 2> "$O/bench_train.err" || { tail "$O/bench_train.err"; exit 1; }
-for i in 2 3 4 5; do timeout -k 10 300 python bench.py --workload train --steps 128 > "$O/bench_train_run$i.json" 2>/dev/null || exit 1; done
-timeout -k 10 300 python bench.py --loop-launch coop --no-cpu-baseline > "$O/bench_hash19_f32_loop_coop.json" 2>/dev/null || exit 1
-timeout -k 10 300 python bench.py --workload train --steps 128 --train-engine eager > "$O/bench_train_eager.json" 2> "$O/bench_train_e.err" || { tail "$O/bench_train_e.err"; exit 1; }
-timeout -k 10 300 python bench.py --workload tile --size 1024 --steps 60 --warmup 10 --no-cpu-baseline > "$O/bench_tile1024.json" 2> "$O/bench_tile.err" || { tail "$O/bench_tile.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --streams 2 --no-cpu-baseline > "$O/bench_hash19_f32_streams2.json" 2> "$O/bench_s2.err" || { tail "$O/bench_s2.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --regime A --no-cpu-baseline > "$O/bench_hash19_f32_regimeA.json" 2> "$O/bench_A.err" || { tail "$O/bench_A.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --audio-batch 0 --no-cpu-baseline > "$O/bench_hash19_f32_live_audio.json" 2> "$O/bench_la.err" || { tail "$O/bench_la.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --engine ops --steps 40 --warmup 5 --no-cpu-baseline > "$O/bench_hash19_ops_engine.json" 2> "$O/bench_ops.err" || { tail "$O/bench_ops.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --workload train --steps 128 > "$O/bench_train.json" 2> "$O/bench_train.err" || { tail "$O/bench_train.err"; exit 1; }
+for i in 2 3 4 5; do timeout -k 10 300 python bench.py --full --workload train --steps 128 > "$O/bench_train_run$i.json" 2>/dev/null || exit 1; done
+timeout -k 10 300 python bench.py --full --loop-launch coop --no-cpu-baseline > "$O/bench_hash19_f32_loop_coop.json" 2>/dev/null || exit 1
+timeout -k 10 300 python bench.py --full --workload train --steps 128 --train-engine eager > "$O/bench_train_eager.json" 2> "$O/bench_train_e.err" || { tail "$O/bench_train_e.err"; exit 1; }
+timeout -k 10 300 python bench.py --full --workload tile --size 1024 --steps 60 --warmup 10 --no-cpu-baseline > "$O/bench_tile1024.json" 2> "$O/bench_tile.err" || { tail "$O/bench_tile.err"; exit 1; }
 # multi-rank rehearsals on this one GPU (gloo; RCCL needs a GPU per rank): 4 ranks each
 for w in "render" "tile --size 1024"; do tag=${w%% *}
-  RN_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 4 --workload $w --steps 40 --warmup 10 --no-cpu-baseline 2> "$O/rehearse4_$tag.err" | tail -1 > "$O/rehearse4_gloo_one_gpu_$tag.json" || { tail "$O/rehearse4_$tag.err"; exit 1; }
+  RN_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 4 --workload $w --steps 40 --warmup 10 --no-cpu-baseline 2> "$O/rehearse4_$tag.err" | tail -1 > "$O/rehearse4_gloo_one_gpu_$tag.json" || { tail "$O/rehearse4_$tag.err"; exit 1; }
 done
 fi
 if [ "${PART:-A}" = "B" ]; then

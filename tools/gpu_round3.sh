@@ -12,34 +12,34 @@ timeout -k 10 1000 python -m pytest tests -q -m gpu > "$O/pytest_gpu.log" 2>&1; 
 fi
 [ "${ONLY_TESTS:-0}" = 1 ] && exit 0
 timeout -k 10 300 python __graft_entry__.py smoke > "$O/smoke.log" 2>&1 || { tail -5 "$O/smoke.log"; exit 1; }; tail -2 "$O/smoke.log"
-run bench_hash19_f32.json python bench.py
-run bench_hash19_f32_driver_shape.json python bench.py --steps 20 --warmup 5
+run bench_hash19_f32.json python bench.py --full
+run bench_hash19_f32_driver_shape.json python bench.py --full --steps 20 --warmup 5
 for v in "tiled16 f32" "hash19 f32x2" "hash19 f16" "tiled16 f16"; do set -- $v
-  run bench_$1_$2.json python bench.py --grid $1 --mlp $2 --no-cpu-baseline --no-train-record
+  run bench_$1_$2.json python bench.py --full --grid $1 --mlp $2 --no-cpu-baseline --no-train-record
 done
-run bench_hash19_f16_half_tables.json python bench.py --mlp f16 --half-tables --no-cpu-baseline --no-train-record
-run bench_hash19_f32_regimeA.json python bench.py --regime A --no-cpu-baseline --no-train-record
-run bench_hash19_f32_streams2.json python bench.py --streams 2 --no-cpu-baseline --no-train-record
-run bench_tile1024.json python bench.py --workload tile --size 1024 --steps 60 --warmup 10 --no-cpu-baseline
-for i in 1 2 3 4 5; do run bench_train_run$i.json python bench.py --workload train --steps 128; done
-run bench_train_eager.json python bench.py --workload train --steps 128 --train-engine eager
-RN_TRAIN_OVERLAP=0 run bench_train_no_overlap.json python bench.py --workload train --steps 128
-RN_SCATTER=lbc run bench_train_scatter_line_merge_only.json python bench.py --workload train --steps 128
-RN_TRAIN_HEAD=ops RN_TRAIN_LOSS=torch run bench_train_round2_operator_path.json python bench.py --workload train --steps 128
+run bench_hash19_f16_half_tables.json python bench.py --full --mlp f16 --half-tables --no-cpu-baseline --no-train-record
+run bench_hash19_f32_regimeA.json python bench.py --full --regime A --no-cpu-baseline --no-train-record
+run bench_hash19_f32_streams2.json python bench.py --full --streams 2 --no-cpu-baseline --no-train-record
+run bench_tile1024.json python bench.py --full --workload tile --size 1024 --steps 60 --warmup 10 --no-cpu-baseline
+for i in 1 2 3 4 5; do run bench_train_run$i.json python bench.py --full --workload train --steps 128; done
+run bench_train_eager.json python bench.py --full --workload train --steps 128 --train-engine eager
+RN_TRAIN_OVERLAP=0 run bench_train_no_overlap.json python bench.py --full --workload train --steps 128
+RN_SCATTER=lbc run bench_train_scatter_line_merge_only.json python bench.py --full --workload train --steps 128
+RN_TRAIN_HEAD=ops RN_TRAIN_LOSS=torch run bench_train_round2_operator_path.json python bench.py --full --workload train --steps 128
 timeout -k 10 400 python tools/train_step_launches.py > "$O/train_step_launches.json" 2> /dev/null || exit 1
 for w in "render" "tile --size 1024"; do tag=${w%% *}
-  RN_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 4 --workload $w --steps 40 --warmup 10 --no-cpu-baseline 2> "$O/rehearse4_$tag.err" | tail -1 > "$O/rehearse4_gloo_one_gpu_$tag.json" || { tail "$O/rehearse4_$tag.err"; exit 1; }
+  RN_DIST_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus 4 --workload $w --steps 40 --warmup 10 --no-cpu-baseline 2> "$O/rehearse4_$tag.err" | tail -1 > "$O/rehearse4_gloo_one_gpu_$tag.json" || { tail "$O/rehearse4_$tag.err"; exit 1; }
 done
 fi
 if [ "${PART:-A}" = "C" ]; then   # the training lines again (after a change that only touches the training step)
-for i in 1 2 3 4 5; do run bench_train_run$i.json python bench.py --workload train --steps 128; done
-run bench_train_eager.json python bench.py --workload train --steps 128 --train-engine eager
-RN_TRAIN_OVERLAP=0 run bench_train_no_overlap.json python bench.py --workload train --steps 128
-RN_SCATTER=binned run bench_train_scatter_binned.json python bench.py --workload train --steps 128
-RN_SCATTER_DIRECT=0 run bench_train_scatter_line_merge_only.json python bench.py --workload train --steps 128
-RN_TRAIN_HEAD=ops RN_TRAIN_LOSS=torch run bench_train_round2_operator_path.json python bench.py --workload train --steps 128
-run bench_hash19_f32_driver_shape.json python bench.py --steps 20 --warmup 5
-run bench_hash19_f32.json python bench.py
+for i in 1 2 3 4 5; do run bench_train_run$i.json python bench.py --full --workload train --steps 128; done
+run bench_train_eager.json python bench.py --full --workload train --steps 128 --train-engine eager
+RN_TRAIN_OVERLAP=0 run bench_train_no_overlap.json python bench.py --full --workload train --steps 128
+RN_SCATTER=binned run bench_train_scatter_binned.json python bench.py --full --workload train --steps 128
+RN_SCATTER_DIRECT=0 run bench_train_scatter_line_merge_only.json python bench.py --full --workload train --steps 128
+RN_TRAIN_HEAD=ops RN_TRAIN_LOSS=torch run bench_train_round2_operator_path.json python bench.py --full --workload train --steps 128
+run bench_hash19_f32_driver_shape.json python bench.py --full --steps 20 --warmup 5
+run bench_hash19_f32.json python bench.py --full
 timeout -k 10 400 python tools/train_step_launches.py > "$O/train_step_launches.json" 2> /dev/null || exit 1
 timeout -k 10 120 python tools/bench_train_head.py > "$O/train_head_kernels.json" 2>/dev/null || exit 1
 cd /tmp

@@ -5,7 +5,7 @@
 set -o pipefail
 R=${GRAFT_REPO_ROOT:-/root/repo}; O="$R/gpurun_out/tg"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/bench.py" --workload train --steps 128 > "$O/bench.json" 2> "$O/err.log" || { tail "$O/err.log"; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O" -- python3 "$R/bench.py" --full --workload train --steps 128 > "$O/bench.json" 2> "$O/err.log" || { tail "$O/err.log"; exit 1; }
 cd "$R"; find "$O" -name "*.db" -delete; find "$O" -name "*kernel_trace.csv" -delete; find "$O" -name "*agent_info*" -delete
 python - "$O" <<'PY'
 import csv, glob, sys
