@@ -136,8 +136,9 @@ class SyntheticScene:
         are two reused buffers and `ray_source` = (pose, intrinsics, W) tells the frame prologue kernel to fill them -- ray
         generation costs no launch and no cache of per-pose rays is kept."""
         i = i % self.n_frames
+        # no eye value without --exp_eye (nerf/provider.py:276-278): the network would append it as a 65th sigma_net input
         base = dict(auds=get_audio_features(self.aud_features, self.opt.att, i), bg_coords=self.bg_coords, poses=self.poses6[i:i + 1],
-                    eye=self.eye, index=0, bg_color=self.bg_color)
+                    eye=self.eye if self.opt.exp_eye else None, index=0, bg_color=self.bg_color)
         if lazy_rays and self._lazy_rays():
             bufs = self.__dict__.setdefault("_ray_bufs", {})
             key = torch.cuda.current_stream().cuda_stream          # frames in flight on different streams must not share them

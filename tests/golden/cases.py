@@ -81,6 +81,26 @@ def freq_case(D, deg, seed=41, B=300):
     return torch.from_numpy(x), torch.from_numpy(rng.standard_normal((B, D + 2 * D * deg)).astype(np.float32))
 
 
+# Model options off the defaults of scene.default_opt (reference_options.npz, tests/test_gpu_options.py): the eye input and
+# both individual codes off (A), and odd code widths whose first-layer row strides (64 + 1, 80 + 7, 96 / 128 + 3) are not
+# multiples of 4 (B).
+OPTION_SETS = {"A": dict(exp_eye=False, ind_dim=0, ind_dim_torso=0), "B": dict(exp_eye=True, ind_dim=7, ind_dim_torso=3)}
+
+
+def options_inputs(n=2048, n_px=1024, seed=23):
+    """Samples (xyz inside the head's box, a few outside [-bound, bound]), unit directions, audio code, eye value, upstream
+    gradients of (sigma, rgb, ambient) and torso pixels of the reference_options case."""
+    g = torch.Generator().manual_seed(seed)
+    x = (torch.rand(n, 3, generator=g) * 2 - 1) * 0.9
+    x[:5] = 1.25
+    d = torch.nn.functional.normalize(torch.randn(n, 3, generator=g), dim=-1)
+    enc_a = torch.randn(1, 64, generator=g) * 0.5
+    eye = torch.full((1, 1), 0.25)
+    up = (torch.randn(n, generator=g), torch.randn(n, 3, generator=g), torch.randn(n, 2, generator=g) * 0.3)
+    xy = torch.rand(n_px, 2, generator=g) * 2 - 1
+    return dict(x=x, d=d, enc_a=enc_a, eye=eye, up_sigma=up[0], up_rgb=up[1], up_ambient=up[2], torso_xy=xy)
+
+
 def train_pixels(n_px, n_rays=4096, seed=5):
     """Pixel subset of the train-branch case (config[2]: 4096 rays of a frame)."""
     g = torch.Generator().manual_seed(seed)

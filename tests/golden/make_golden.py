@@ -1,6 +1,7 @@
 """Generates the golden fixtures under tests/golden/ -- run ONLY in the build container (needs /root/reference).
 
-    python tests/golden/make_golden.py            # reference_{flow,ops,frames,mixed,train_stable}.npz
+    python tests/golden/make_golden.py            # reference_{flow,ops,frames,mixed,train_stable,options}.npz
+    python tests/golden/make_golden.py options    # one set only
 
 What runs is the reference's OWN Python, imported unmodified from /root/reference:
   * the operator wrappers raymarching/raymarching.py, gridencoder/grid.py, shencoder/sphere_harmonics.py,
@@ -445,6 +446,79 @@ def make_stable(env):
     return out
 
 
+# ----------------------------------------------------------------------------------------------- reference_options.npz
+OPTION_PARAMS = ("ambient_net.net.0.weight", "ambient_net.net.1.weight", "ambient_net.net.2.weight", "sigma_net.net.0.weight",
+                 "sigma_net.net.1.weight", "sigma_net.net.2.weight", "color_net.net.0.weight", "color_net.net.1.weight")
+
+
+def make_options(env):
+    """NeRFNetwork.forward / forward_torso of the unmodified reference at two option sets off the defaults (cases.OPTION_SETS:
+    no eye input and no individual codes; odd code widths).  Per set: the outputs on 2 048 fixed samples, every parameter
+    gradient of the network (and of enc_a / the eye / the code) under fixed upstream gradients restricted -- outside the
+    reference's code, by make_stable's hooks and mask rule -- to the samples at which the network is smooth in its parameters,
+    every 97th touched row of the two table gradients, and forward_torso on 1 024 pixels."""
+    SyntheticScene, default_opt, rm, gridencoder, _, _, ref_network, ref_utils = env
+    inp = cases.options_inputs()
+    out = {k: t2n(v) for k, v in inp.items()}
+    cell_margin, relu_margin = 2e-5, 1e-4
+    out["margins"] = np.array([cell_margin, relu_margin])
+    for tag, kw in cases.OPTION_SETS.items():
+        opt = default_opt(**kw)
+        torch.manual_seed(0)
+        scene = SyntheticScene(H=32, W=32, n_frames=8, device="cpu", opt=opt, model=ref_network.NeRFNetwork(opt))
+        m = scene.model
+        seen = {"relu": []}
+
+        def relu_hook(mod, args, o):
+            seen["relu"].append((o.detach().abs() > relu_margin).all(-1))
+
+        def cell_hook(mod, args):
+            enc = m.encoder_ambient
+            amb = args[0].detach().double().reshape(-1, 2)
+            scales = torch.tensor([2.0 ** (l * float(np.log2(enc.per_level_scale))) * enc.base_resolution - 1 for l in range(enc.num_levels)],
+                                  dtype=torch.float64)
+            pos = ((amb + 1) / 2).unsqueeze(-1) * scales + 0.5
+            frac = pos - pos.floor()
+            seen["cell"] = ((frac > cell_margin * scales) & (frac < 1 - cell_margin * scales)).all(-1).all(-1)
+
+        hooks = [layer.register_forward_hook(relu_hook) for net in (m.ambient_net, m.sigma_net, m.color_net) for layer in list(net.net)[:-1]]
+        hooks.append(m.encoder_ambient.register_forward_pre_hook(cell_hook))
+        enc_a = inp["enc_a"].clone().requires_grad_(True)
+        eye = inp["eye"].clone().requires_grad_(True) if opt.exp_eye else None
+        c = m.individual_codes[0] if opt.ind_dim > 0 else None
+        m.zero_grad(set_to_none=True)
+        sigma, rgb, amb = m(inp["x"], inp["d"], enc_a, c, eye)
+        for h in hooks:
+            h.remove()
+        mask = (torch.stack(seen["relu"]).all(0) & seen["cell"]).to(torch.float32)
+        loss = (sigma * inp["up_sigma"] * mask).sum() + (rgb * inp["up_rgb"] * mask[:, None]).sum() + (amb * inp["up_ambient"] * mask[:, None]).sum()
+        loss.backward()
+        print(f"options {tag}: stable samples {int(mask.sum())} of {mask.numel()}")
+        out[f"{tag}_mask"] = t2n(mask).astype(np.uint8)
+        out[f"{tag}_sigma"], out[f"{tag}_rgb"], out[f"{tag}_ambient"] = t2n(sigma), t2n(rgb), t2n(amb)
+        params = dict(m.named_parameters())
+        out[f"{tag}_params_sha256"] = np.array(sha(np.concatenate([t2n(params[n]).reshape(-1) for n in sorted(params)])))
+        for name in OPTION_PARAMS:
+            out[f"{tag}_grad::{name}"] = t2n(params[name].grad)
+        out[f"{tag}_grad::enc_a"] = t2n(enc_a.grad)
+        if eye is not None:
+            out[f"{tag}_grad::eye"] = t2n(eye.grad)
+        if c is not None:
+            out[f"{tag}_grad::individual_codes"] = t2n(m.individual_codes.grad[:1])
+        for name in ("encoder", "encoder_ambient"):
+            gt = getattr(m, name).embeddings.grad
+            nz = torch.nonzero(gt.abs().sum(1)).reshape(-1)
+            out[f"{tag}_gradrows::{name}"] = t2n(nz[::97].int())
+            out[f"{tag}_gradvals::{name}"] = t2n(gt[nz[::97]])
+            out[f"{tag}_gradsum::{name}"] = np.array([float(gt.double().sum()), float(gt.double().abs().sum()), float(nz.numel())])
+        with torch.no_grad():
+            ct = m.individual_codes_torso[0] if opt.ind_dim_torso > 0 else None
+            ta, tc, tdx = m.forward_torso(inp["torso_xy"], scene.poses6[0:1], enc_a.detach(), ct)
+        out[f"{tag}_torso_poses"] = t2n(scene.poses6[0:1])
+        out[f"{tag}_torso_alpha"], out[f"{tag}_torso_color"], out[f"{tag}_torso_dx"] = t2n(ta), t2n(tc), t2n(tdx)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- reference_mixed.npz
 class reference_autocast:
     """The reference's `-O` mode (main.py:111-120: fp16 + cuda_ray) as Trainer.test runs it: the whole test_step under
@@ -527,9 +601,9 @@ def make_mixed(env):
 
 def main():
     env = install_reference()
-    todo = sys.argv[1:] or ["flow", "ops", "frames", "mixed", "train_stable"]
+    todo = sys.argv[1:] or ["flow", "ops", "frames", "mixed", "train_stable", "options"]
     for name, fn in (("flow", make_flow), ("ops", make_ops), ("frames", make_frames), ("mixed", make_mixed),
-                     ("train_stable", make_stable)):
+                     ("train_stable", make_stable), ("options", make_options)):
         if name in todo:
             out = fn(env)
             for fname, arrays in cases.golden_parts(name, out).items():

@@ -28,7 +28,7 @@ def _samples(M, seed, oob=7):
 def _stable_samples(m, xyzs, dirs, enc_a, eye, ind, monkeypatch, cell_margin=2e-5, relu_margin=2e-5):
     """Samples at which NeRFNetwork.forward is smooth in its parameters: no ambient coordinate within `cell_margin` (normalised
     units) of a cell boundary of any level of the 2-D grid, no hidden pre-activation within `relu_margin` of 0 (recomputed here
-    with plain torch matmuls over the module's encoders)."""
+    with plain torch matmuls over the module's encoders).  eye / ind: None for a model without the eye input / individual code."""
     monkeypatch.setenv("RN_TRAIN_HEAD", "ops")
     with torch.no_grad():
         n = xyzs.shape[0]
@@ -44,8 +44,8 @@ def _stable_samples(m, xyzs, dirs, enc_a, eye, ind, monkeypatch, cell_margin=2e-
             return x
         amb = torch.tanh(mlp(m.ambient_net, torch.cat([enc_x, enc_a.repeat(n, 1)], -1)))
         enc_w = m.encoder_ambient(amb, bound=1)
-        h = mlp(m.sigma_net, torch.cat([enc_x, enc_w, eye.repeat(n, 1)], -1))
-        mlp(m.color_net, torch.cat([m.encoder_dir(dirs), h[:, 1:], ind.reshape(1, -1).repeat(n, 1)], -1))
+        h = mlp(m.sigma_net, torch.cat([enc_x, enc_w] + ([eye.repeat(n, 1)] if eye is not None else []), -1))
+        mlp(m.color_net, torch.cat([m.encoder_dir(dirs), h[:, 1:]] + ([ind.reshape(1, -1).repeat(n, 1)] if ind is not None else []), -1))
         relu_ok = torch.stack([(z.abs() > relu_margin).all(-1) for z in pre]).all(0)
         enc = m.encoder_ambient
         scales = torch.tensor([2.0 ** (l * float(np.log2(enc.per_level_scale))) * enc.base_resolution - 1 for l in range(16)],

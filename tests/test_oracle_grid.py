@@ -5,22 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-PRIMES = [1, 2654435761, 805459861, 3674653429, 2097192037, 1434869437, 2165219737]
-
-
-def py_grid_index(D, C, gridtype, align_corners, ch, hashmap_size, resolution, pos_grid):
-    """gridencoder.cu:66-84 with Python ints, wrapping to uint32 explicitly."""
-    M = 1 << 32
-    stride, index, d = 1, 0, 0
-    while d < D and stride <= hashmap_size:
-        index = (index + pos_grid[d] * stride) % M
-        stride = (stride * (resolution if align_corners else resolution + 1)) % M
-        d += 1
-    if gridtype == 0 and stride > hashmap_size:
-        index = 0
-        for i in range(D):
-            index ^= (pos_grid[i] * PRIMES[i]) % M
-    return (index % hashmap_size) * C + ch
+from netref64 import py_grid_index, torch_grid  # noqa: E402  (restatements shared with the float64 network reference)
 
 
 def offsets_for(D, L, log2T, desired=2048, base=16, align=False):
@@ -97,33 +82,6 @@ def test_dense_levels_against_independent_numpy_interpolation(po, rng):
                 stride *= res + 1
             acc += w[:, None] * emb[off[l] + idx]
         np.testing.assert_allclose(out[l], acc, rtol=0, atol=3e-5)
-
-
-def torch_grid(x, emb, off, S, H, D, C, L, gridtype, interp):
-    """Pure-torch float64 formulation (differentiable in emb and x) using the oracle's integer indices."""
-    outs = []
-    for l in range(L):
-        scale = float(np.float32(np.exp2(np.float32(np.float32(l) * np.float32(S)))) * np.float32(H) - np.float32(1))
-        res = int(np.ceil(scale)) + 1
-        hs = int(off[l + 1] - off[l])
-        pos = x * scale + 0.5
-        p0 = torch.floor(pos).detach()
-        fr = pos - p0
-        if interp == 1:
-            fr = fr * fr * (3 - 2 * fr)
-        acc = 0
-        p0n = p0.long().numpy()
-        for corner in range(1 << D):
-            w = 1
-            pg = p0n.copy()
-            for d in range(D):
-                bit = (corner >> d) & 1
-                w = w * (fr[:, d] if bit else 1 - fr[:, d])
-                pg[:, d] += bit
-            rows = np.array([py_grid_index(D, 1, gridtype, False, 0, hs, res, [int(v) for v in r]) for r in pg])
-            acc = acc + w[:, None] * emb[off[l] + torch.from_numpy(rows)]
-        outs.append(acc)
-    return torch.stack(outs, 0)  # [L,B,C]
 
 
 @pytest.mark.parametrize("D,gridtype,interp", [(3, 1, 0), (3, 0, 0), (2, 1, 0), (3, 0, 1)])
