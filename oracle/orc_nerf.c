@@ -58,7 +58,7 @@ static void mlp_rows(const orc_mlp_t *mlp, const float *const *wt, const float *
     }
 }
 
-/* The same stack under the arithmetic of the opt-in 16-bit matrix-core kernel (rad-nerf_amd/csrc/rn_fused_h16.hip), which
+/* The same stack under the arithmetic of the opt-in 16-bit matrix-core kernel (k_nerf_fused_h16 in rad-nerf_amd/csrc/rn_fused_f16.hip), which
  * is the reference's autocast mode (nerf/utils.py:944: nn.Linear in fp16, fp32 accumulation) with fp32 kept where the
  * kernel keeps it: inputs k < n_var of the first layer, every hidden activation and the weights that multiply them are
  * rounded to fp16 (nearest-even); the broadcast inputs k >= n_var (audio code / eye / individual code, folded into a

@@ -244,10 +244,7 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
     uint32_t M = p.M;
     if (p.m_dev) { const uint32_t d = (uint32_t)*p.m_dev; M = d < M ? d : M; }
     const uint32_t n_tiles = (M + 31u) >> 5;
-    {
-        const TileSchedule w0(n_tiles, kF32Waves, 0u);
-        if (w0.first >= w0.end) return;  // nothing for this workgroup (uniform)
-    }
+    if (workgroup_idle(n_tiles, kF32Waves)) return;
 
     for (int i = threadIdx.x; i < kPacked / 4; i += kF32Threads)
         reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.packed)[i];
@@ -1308,10 +1305,9 @@ static int run_fused(const float *xyzs, const float *dirs, const float *deltas, 
         uint32_t blocks = div_up((M + 63u) >> 6, kWavesPerBlock);
         const uint32_t cap = (uint32_t)num_cus();
         launch_fused_h16(p, gx->dtype, gw->dtype, blocks > cap ? cap : blocks, s);
-    } else if (gx->dtype == RN_F32 && gw->dtype == RN_F32) launch_fused<float, float>(p, s);
-    else if (gx->dtype == RN_F16 && gw->dtype == RN_F16) launch_fused<__half, __half>(p, s);
-    else if (gx->dtype == RN_F32) launch_fused<float, __half>(p, s);
-    else launch_fused<__half, float>(p, s);
+    } else {
+        dispatch_grid_dtypes(gx->dtype, gw->dtype, [&](auto tx, auto tw) { launch_fused<decltype(tx), decltype(tw)>(p, s); });
+    }
     return RN_OK;
 }
 

@@ -1,5 +1,6 @@
-// rn_fused_dev.h -- pieces shared by the fp32-MFMA (rn_fused.hip) and the f16-MFMA (rn_fused_h16.hip) variants of
-// the fused per-sample network kernel: accumulator tiles, the VALU output layers, kernel parameter blocks.
+// rn_fused_dev.h -- pieces shared by the fp32-MFMA (rn_fused.hip) and the 16-bit-MFMA (rn_fused_f16.hip) variants of
+// the fused per-sample network kernel: accumulator tiles, the VALU output layers, kernel parameter blocks, the tile
+// bookkeeping (sample count, slot / liveness of an entry, direction load) and the launch dispatch.
 #pragma once
 
 #include "rn_dda_dev.h"
@@ -152,11 +153,61 @@ struct TileSchedule {
     }
 };
 
-// Launch of the f16-MFMA variant (rn_fused_h16.hip); `gx_dtype` / `gw_dtype` are the grid table dtypes.
+// ---- tile bookkeeping, the same in k_nerf_fused, k_nerf_fused_h16 and k_nerf_fused_x2 -------------------------------
+// The helpers take the fields of FusedParams they need by value: a kernel that hands out a reference to its parameter
+// block is compiled to a different instruction stream.  What is NOT here although all three kernels spell it alike: the
+// fill of plan_x / plan_w and the xyz normalisation (as helpers they reorder loads / swap the operands of one packed add
+// in the 16-bit kernels), and in k_nerf_fused everything but workgroup_idle() (its register allocation changes with
+// launch_samples() and entry_slot(); that kernel's instruction stream is held fixed).
+
+// sample count of the launch: the host's upper bound, clamped by the device-side count where the frame loop keeps one
+__device__ __forceinline__ uint32_t launch_samples(uint32_t M, const int32_t *m_dev) {
+    if (m_dev) { const uint32_t d = (uint32_t)*m_dev; M = d < M ? d : M; }
+    return M;
+}
+
+// true where the schedule leaves this workgroup without a tile (uniform over the workgroup)
+__device__ __forceinline__ bool workgroup_idle(uint32_t n_tiles, uint32_t waves_per_block) {
+    const TileSchedule w0(n_tiles, waves_per_block, 0u);
+    return w0.first >= w0.end;
+}
+
+// Slot and liveness of entry `entry` of the launch (the caller derives it from tile and lane: 64 entries per tile, one
+// per lane, in the 16-bit kernels; 32 per tile, shared by both lane halves, in the fp32 kernel).  With a slot list every
+// entry below M is live and names its slot; without one, entry j is slot j and dead where deltas[2 j] == 0.
+__device__ __forceinline__ bool entry_slot(const int32_t *slots, const float *deltas, uint32_t entry, uint32_t M, uint32_t &sample) {
+    bool live = entry < M;
+    sample = entry;  // the slot this lane's sample lives in
+    if (slots) {
+        if (live) sample = (uint32_t)slots[entry];
+    } else if (live && deltas) {
+        live = deltas[2 * (size_t)sample] != 0.0f;
+    }
+    return live;
+}
+
+// view direction of a live sample into (dx, dy, dz), which the caller has zeroed (they stay 0 for a dead lane and for
+// the density query, which passes no directions)
+__device__ __forceinline__ void load_dir(const float *dirs, bool live, uint32_t sample, float &dx, float &dy, float &dz) {
+    if (live && dirs) {
+        dx = dirs[3 * (size_t)sample]; dy = dirs[3 * (size_t)sample + 1]; dz = dirs[3 * (size_t)sample + 2];
+    }
+}
+
+// (grid table dtypes) -> the <TX, TW> instantiation: calls f(TX{}, TW{}) with float or __half values as type tags
+template <typename F>
+static inline void dispatch_grid_dtypes(int gx_dtype, int gw_dtype, F &&f) {
+    if (gx_dtype == RN_F32 && gw_dtype == RN_F32) f(float{}, float{});
+    else if (gx_dtype == RN_F16 && gw_dtype == RN_F16) f(__half{}, __half{});
+    else if (gx_dtype == RN_F32) f(float{}, __half{});
+    else f(__half{}, float{});
+}
+
+// The 16-bit matrix-core variants (rn_fused_f16.hip); `gx_dtype` / `gw_dtype` are the grid table dtypes.
 void launch_fused_h16(const FusedParams &p, int gx_dtype, int gw_dtype, uint32_t blocks, hipStream_t s);
 void launch_pack_nerf_h16(const RawW &w, float *packed, hipStream_t s);
 size_t packed_floats_h16();
-// Launch of the split-precision variant (rn_fused_x2.hip): picks its own grid (one 256-thread workgroup per CU).
+// The split-precision variant picks its own grid (one 512-thread workgroup per CU).
 void launch_fused_x2(const FusedParams &p, int gx_dtype, int gw_dtype, uint32_t n_cus, hipStream_t s);
 void launch_pack_nerf_x2(const RawW &w, float *packed, hipStream_t s);
 size_t packed_floats_x2();
