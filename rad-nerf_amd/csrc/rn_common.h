@@ -19,6 +19,8 @@ constexpr int kWave = 64;  // CDNA wavefront width
 
 void set_error(const char *fmt, ...);
 int check_launch(const char *what);
+// compute units of the current device (256 where it cannot be asked); read once per process
+int num_cus();
 // HIP-event timing of the dominant kernel (rn_prof_enable / rn_prof_collect)
 bool prof_enabled();
 void prof_pair(hipEvent_t *start, hipEvent_t *stop);

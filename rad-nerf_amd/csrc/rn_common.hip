@@ -27,6 +27,17 @@ int check_launch(const char *what) {
     return RN_OK;
 }
 
+int num_cus() {
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
+        if (cus <= 0) cus = 256;
+    }
+    return cus;
+}
+
 // ---- optional HIP-event timing of one named kernel family (used by bench.py for the roofline object) ----
 static bool g_prof_on = false, g_prof_paused = false;
 static std::vector<std::pair<hipEvent_t, hipEvent_t>> g_prof_pool;

@@ -1,5 +1,5 @@
 // rn_dda_dev.h -- the occupancy-grid DDA walk, shared by the marching kernels of rn_raymarching.hip and
-// the device-side inference loop of rn_fused.hip (identical samples from both).
+// the device-side inference loop of rn_head_loop.hip (identical samples from both).
 #pragma once
 
 #include "rn_common.h"

@@ -1,11 +1,15 @@
-// rn_fused_dev.h -- pieces shared by the fp32-MFMA (rn_fused.hip) and the 16-bit-MFMA (rn_fused_f16.hip) variants of
-// the fused per-sample network kernel: accumulator tiles, the VALU output layers, kernel parameter blocks, the tile
-// bookkeeping (sample count, slot / liveness of an entry, direction load) and the launch dispatch.
+// rn_fused_dev.h -- pieces shared by the translation units of the fused inference path: the fp32-MFMA (rn_fused.hip) and
+// the 16-bit-MFMA (rn_fused_f16.hip) variants of the per-sample network kernel, the device-resident frame loop
+// (rn_head_loop.hip) and the torso pass (rn_torso.hip); the training network (rn_train_head.hip) reuses the parameter
+// pieces.  Here: 64-sample accumulator tiles and their VALU output layers (the 32-sample ones are in rn_tile32_dev.h), the
+// raw weight and grid descriptors, kernel parameter blocks, the tile bookkeeping (sample count, slot / liveness of an
+// entry, direction load) and the launch dispatch.
 #pragma once
 
 #include "rn_dda_dev.h"
 #include "rn_grid_dev.h"
 #include "rn_sh_dev.h"
+#include "rn_tile32_dev.h"
 
 #include "../../include/radnerf_fused.h"
 
@@ -18,22 +22,17 @@
 
 namespace rn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kFusedThreads = 512;
 constexpr int kWavesPerBlock = kFusedThreads / kWave;
-
-
-__host__ __device__ constexpr int rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-// k index (within a 64-wide hidden vector) that lane-half h feeds at MFMA step s when the B operand is
-// register (s & 15) of row tile (s >> 4) of the previous layer's accumulators.
-__host__ __device__ constexpr int kmap(int s, int h) { return 32 * (s >> 4) + rowmap(s & 15, h); }
 
 struct RawW {
     const float *amb_w0, *amb_w1, *amb_w2, *sig_w0, *sig_w1, *sig_w2, *col_w0, *col_w1;
     uint32_t audio_dim, has_eye, ind_dim;
 };
-
+inline RawW raw_w(const rn_nerf_weights_t *w) {
+    return RawW{w->amb_w0, w->amb_w1, w->amb_w2, w->sig_w0, w->sig_w1, w->sig_w2, w->col_w0, w->col_w1,
+                w->audio_dim, w->has_eye, w->ind_dim};
+}
 
 // acc[column tile][row tile]
 struct Acc {
@@ -59,13 +58,6 @@ __device__ __forceinline__ void acc_bias(Acc &a, const float *bias64, int h) {
             a.v[0][rt][4 * g + 0] = b.x; a.v[0][rt][4 * g + 1] = b.y; a.v[0][rt][4 * g + 2] = b.z; a.v[0][rt][4 * g + 3] = b.w;
             a.v[1][rt][4 * g + 0] = b.x; a.v[1][rt][4 * g + 1] = b.y; a.v[1][rt][4 * g + 2] = b.z; a.v[1][rt][4 * g + 3] = b.w;
         }
-}
-
-// max(x, 0) as ONE v_max_i32 on the bit pattern (a non-negative float is a non-negative integer, a negative one a negative
-// integer); fmaxf(x, 0) costs two VALU instructions because IEEE mode first quiets a possible signalling NaN.
-__device__ __forceinline__ float relu_bits(float x) {
-    const int b = __float_as_int(x);
-    return __int_as_float(b > 0 ? b : 0);
 }
 
 __device__ __forceinline__ void acc_relu(Acc &a) {
@@ -106,6 +98,9 @@ struct GridArgs {
     LevelConsts lc;
     uint32_t gridtype;
 };
+inline GridArgs grid_args(const rn_grid_t *g) {
+    return GridArgs{g->embeddings, g->offsets, make_level_consts(g->L, g->S, g->H), g->gridtype};
+}
 
 struct FusedParams {
     const float *xyzs, *dirs, *deltas;
@@ -166,6 +161,13 @@ __device__ __forceinline__ uint32_t launch_samples(uint32_t M, const int32_t *m_
     return M;
 }
 
+// the training kernels' form: a non-positive device count means no samples
+__device__ __forceinline__ uint32_t live_count(uint32_t M, const int32_t *m_dev) {
+    if (!m_dev) return M;
+    const int32_t d = *m_dev;
+    return d <= 0 ? 0u : ((uint32_t)d < M ? (uint32_t)d : M);
+}
+
 // true where the schedule leaves this workgroup without a tile (uniform over the workgroup)
 __device__ __forceinline__ bool workgroup_idle(uint32_t n_tiles, uint32_t waves_per_block) {
     const TileSchedule w0(n_tiles, waves_per_block, 0u);
@@ -203,6 +205,12 @@ static inline void dispatch_grid_dtypes(int gx_dtype, int gw_dtype, F &&f) {
     else f(__half{}, float{});
 }
 
+// Host side of the network launch (rn_fused.hip): the frame loop and the torso pass check their grids the same way, and
+// the loop launches the network kernel through run_fused() -- a kernel is launched from its own translation unit.
+int check_fused_grid(const rn_grid_t *g, uint32_t D, const char *name);
+int run_fused(const float *xyzs, const float *dirs, const float *deltas, uint32_t M, const int32_t *m_dev, const rn_grid_t *gx,
+              const rn_grid_t *gw, const float *packed, const float *bias, float bound, float *sigmas, float *rgbs, float *ambient,
+              int mlp_dtype, hipStream_t s, const int32_t *slots = nullptr);
 // The 16-bit matrix-core variants (rn_fused_f16.hip); `gx_dtype` / `gw_dtype` are the grid table dtypes.
 void launch_fused_h16(const FusedParams &p, int gx_dtype, int gw_dtype, uint32_t blocks, hipStream_t s);
 void launch_pack_nerf_h16(const RawW &w, float *packed, hipStream_t s);

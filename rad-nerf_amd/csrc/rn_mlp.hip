@@ -7,7 +7,7 @@
 // ~150 launches per step for 10 GFLOP.  Here an MLP is three launches:
 //
 //   k_mlp_fwd    one wave = 32 samples; v_mfma_f32_32x32x2_f32 with the sample on the lane and the output row on the
-//                register index (rn_fused.hip's scheme), so a layer's accumulators ARE the next layer's B operand; the
+//                register index (rn_tile32_dev.h), so a layer's accumulators ARE the next layer's B operand; the
 //                post-ReLU hidden activations are saved in that native layout (coalesced 256-B rows per register).
 //   k_mlp_bwd    the same machine run backwards: dX = W^T dY is a forward layer with the transposed weight image; ReLU
 //                masks come from the saved activations; the pre-activation gradients dZ are saved in the native layout.
@@ -18,7 +18,7 @@
 //
 // The narrow output rows (ambient 2, sigma 1, rgb 3) are VALU dot products over the accumulator registers, as in the
 // inference kernel.  fp32 throughout (exact products, fp32 accumulation): results equal torch's up to summation order.
-#include "rn_common.h"
+#include "rn_tile32_dev.h"
 
 #include <stdlib.h>
 
@@ -27,53 +27,9 @@
 namespace rn {
 namespace mlp {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kThreads = 256, kWaves = kThreads / kWave;
-constexpr int kStepF = 128;  // floats per MFMA step of a 64-row layer: [2 h][32 j][2 row tiles]
 constexpr int kStepT = 256;  // floats per MFMA step of the input-gradient layer: [2 h][32 j][4 row tiles (3 used)]
 constexpr int kTileFloats = 2048;  // native tile: [2 rt][16 r][64 lanes]
-
-__host__ __device__ constexpr int rowmap(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-__host__ __device__ constexpr int kmap(int s, int h) { return 32 * (s >> 4) + rowmap(s & 15, h); }
-
-struct Acc32 {
-    f32x16 v[2];
-};
-
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-
-__device__ __forceinline__ void acc_zero(Acc32 &a) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) a.v[rt][r] = 0.0f;
-}
-
-__device__ __forceinline__ void step32(Acc32 &a, const float *wl, int s, int lane_off, float b) {
-    const float2 w = *reinterpret_cast<const float2 *>(wl + s * kStepF + lane_off);
-    a.v[0] = mfma32(w.x, b, a.v[0]);
-    a.v[1] = mfma32(w.y, b, a.v[1]);
-}
-
-__device__ __forceinline__ void layer_from_acc(Acc32 &out, const Acc32 &in, const float *wl, int lane_off) {
-#pragma unroll
-    for (int s = 0; s < 32; s++) step32(out, wl, s, lane_off, in.v[s >> 4][s & 15]);
-}
-
-__device__ __forceinline__ void tile_store(float *__restrict__ dst, const Acc32 &a, int lane) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) dst[(rt * 16 + r) * 64 + lane] = a.v[rt][r];
-}
-
-__device__ __forceinline__ void tile_load(const float *__restrict__ src, Acc32 &a, int lane) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) a.v[rt][r] = src[(rt * 16 + r) * 64 + lane];
-}
 
 // ---- weight images ---------------------------------------------------------------------------------------------------
 // forward:    L0 [in_pad / 2 steps] | L1 [32 steps] (3 layers) | last, wide rows [32 steps] (out >= 64) | last, narrow rows
@@ -83,13 +39,13 @@ struct Dims {
     uint32_t in_dim, in_pad, out_dim, n_layers, nn, wide;   // nn = narrow rows (out_dim % 64 or out_dim), wide = out_dim >= 64
     uint32_t ld0;                                           // row stride of w0 (>= in_dim: the MLP may read a column block of a wider nn.Linear)
     __host__ __device__ uint32_t s0() const { return in_pad / 2; }
-    __host__ __device__ uint32_t off_l1() const { return s0() * kStepF; }
-    __host__ __device__ uint32_t off_lw() const { return off_l1() + (n_layers == 3 ? 32u * kStepF : 0u); }
-    __host__ __device__ uint32_t off_ln() const { return off_lw() + (wide ? 32u * kStepF : 0u); }
+    __host__ __device__ uint32_t off_l1() const { return s0() * kStep; }
+    __host__ __device__ uint32_t off_lw() const { return off_l1() + (n_layers == 3 ? 32u * kStep : 0u); }
+    __host__ __device__ uint32_t off_ln() const { return off_lw() + (wide ? 32u * kStep : 0u); }
     __host__ __device__ uint32_t fwd_floats() const { return off_ln() + nn * 64u; }
     __host__ __device__ uint32_t off_tw() const { return 0; }
-    __host__ __device__ uint32_t off_t1() const { return wide ? 32u * kStepF : 0u; }
-    __host__ __device__ uint32_t off_t0() const { return off_t1() + (n_layers == 3 ? 32u * kStepF : 0u); }
+    __host__ __device__ uint32_t off_t1() const { return wide ? 32u * kStep : 0u; }
+    __host__ __device__ uint32_t off_t0() const { return off_t1() + (n_layers == 3 ? 32u * kStep : 0u); }
     __host__ __device__ uint32_t bwd_floats() const { return off_t0() + 32u * kStepT + nn * 64u; }   // + a copy of the narrow rows
     __host__ __device__ uint32_t off_tn() const { return off_t0() + 32u * kStepT; }
     __host__ __device__ uint32_t rt_in() const { return (in_pad + 31u) / 32u; }
@@ -115,7 +71,7 @@ __global__ void __launch_bounds__(256) k_mlp_pack(const float *__restrict__ w0, 
     if (e < nf) {
         if (e < d.off_ln()) {
             const uint32_t base = e < d.off_l1() ? 0u : (e < d.off_lw() ? d.off_l1() : d.off_lw());
-            const uint32_t q = e - base, s = q / kStepF, rem = q % kStepF, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+            const uint32_t q = e - base, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
             const uint32_t row = 32 * rt + j;
             if (e < d.off_l1()) {                                  // L0: k = 4 (s / 2) + 2 h + (s & 1)
                 const uint32_t k = 4 * (s >> 1) + 2 * h + (s & 1);
@@ -133,7 +89,7 @@ __global__ void __launch_bounds__(256) k_mlp_pack(const float *__restrict__ w0, 
         const uint32_t t = e - nf;
         if (t < d.off_t0()) {                                      // (last wide)^T or L1^T: V[row][k] = W[k][row]
             const bool is_w = d.wide && t < d.off_t1();
-            const uint32_t q = t - (is_w ? 0u : d.off_t1()), s = q / kStepF, rem = q % kStepF, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+            const uint32_t q = t - (is_w ? 0u : d.off_t1()), s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
             const uint32_t row = 32 * rt + j, k = (uint32_t)kmap((int)s, (int)h);
             v = is_w ? wl[(d.nn + k) * 64 + row] : w1[k * 64 + row];
         } else if (t < d.off_tn()) {                               // L0^T: rows = input features (in_pad <= 96 -> 3 row tiles of 4)
@@ -525,17 +481,6 @@ __global__ void __launch_bounds__(256) k_mlp_wreduce(WArgs p) {
     const float total = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
     if (bias_col) job.out_bias[row] = total;
     else job.out[row * job.out_ld + col] = total;
-}
-
-static int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        hipDeviceProp_t prop;
-        n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return n;
 }
 
 template <typename K, typename A>

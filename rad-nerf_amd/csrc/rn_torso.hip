@@ -1,0 +1,444 @@
+// rn_torso.hip -- the torso pass of a frame with the final blend as its epilogue (gfx950).
+//
+// C ABI: include/radnerf_fused.h (rn_torso_*, rn_blend_frame).  What is computed: nerf/renderer.py:269-299 and
+// nerf/network.py:188-219 per background pixel, and the blend of renderer.py:306-311.  k_torso_fused keeps the older
+// 64-sample form of the fused network kernel: two column tiles per wave on v_mfma_f32_32x32x2_f32, one v_permlane32_swap
+// per feature pair to build both B operands; the weights sit in LDS, the per-frame inputs enter as accumulator biases.
+#include "rn_fused_dev.h"
+
+namespace rn {
+
+// ---- 64-sample tiles (two column tiles per wave)
+// one MFMA step of a 64-row layer: weights of step s from LDS, B operands b0 / b1 for the two column tiles
+__device__ __forceinline__ void step64(Acc &a, const float *wl, int s, int lane_off, float b0, float b1) {
+    const float2 w = *reinterpret_cast<const float2 *>(wl + s * kStep + lane_off);
+    a.v[0][0] = mfma32(w.x, b0, a.v[0][0]);
+    a.v[1][0] = mfma32(w.x, b1, a.v[1][0]);
+    a.v[0][1] = mfma32(w.y, b0, a.v[0][1]);
+    a.v[1][1] = mfma32(w.y, b1, a.v[1][1]);
+}
+
+// 64 -> 64 layer whose input is the previous layer's accumulators (32 steps)
+__device__ __forceinline__ void layer_from_acc(Acc &out, const Acc &in, const float *wl, int lane_off) {
+#pragma unroll
+    for (int s = 0; s < 32; s++) step64(out, wl, s, lane_off, in.v[0][s >> 4][s & 15], in.v[1][s >> 4][s & 15]);
+}
+
+// "one sample per lane" feature pair (f0, f1) -> B operands of column tile 0 and 1
+__device__ __forceinline__ void to_b_operands(float f0, float f1, float &b0, float &b1) {
+    const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(f0), __float_as_uint(f1), false, false);
+    b0 = __uint_as_float(r[0]);
+    b1 = __uint_as_float(r[1]);
+}
+
+// ==========================================================================================================
+// Torso pass (nerf/renderer.py:269-299, nerf/network.py:188-219) and final blend (renderer.py:306-311)
+//
+// Packed torso image: deform L0 (21 steps, freq(x) part) | deform L1 (32 steps) | deform L2 VALU [2][2][32]
+//                     | torso L0 (37 steps x 64: grid 16 + freq 21, 32 rows) | torso L1 (16 steps x 64)
+//                     | torso L2 VALU [4][2][16] | raw broadcast columns for the bias: def [64][54+ind], tor [32][54+ind]
+#ifndef RN_TORSO_GROUP
+#define RN_TORSO_GROUP 2
+#endif
+constexpr int kTorsoGroup = RN_TORSO_GROUP;  // torso-grid levels gathered together (divides 16)
+constexpr int kTStep32 = 64;  // floats per MFMA step of a 32-row layer ([2 h][32 j])
+constexpr int TOFF_D0 = 0;
+constexpr int TOFF_D1 = TOFF_D0 + 21 * kStep;
+constexpr int TOFF_D2 = TOFF_D1 + 32 * kStep;
+constexpr int TOFF_T0 = TOFF_D2 + 128;
+constexpr int TOFF_T1 = TOFF_T0 + 37 * kTStep32;
+constexpr int TOFF_T2 = TOFF_T1 + 16 * kTStep32;
+constexpr int kTorsoPacked = TOFF_T2 + 128;  // 10320 floats
+constexpr int kTorsoBias = 96;               // deform 64 | torso 32
+
+struct RawT {
+    const float *def_w0, *def_w1, *def_w2, *tor_w0, *tor_w1, *tor_w2;
+    uint32_t ind_dim;
+};
+
+// k index of a 32-wide hidden vector held in one accumulator row tile
+__host__ __device__ constexpr int kmap32(int s, int h) { return rowmap(s & 15, h); }
+
+__global__ void __launch_bounds__(256) k_pack_torso(RawT w, float *__restrict__ packed) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kTorsoPacked) return;
+    const int ldD0 = 96 + (int)w.ind_dim, ldT0 = 128 + (int)w.ind_dim;
+    float v;
+    if (e < TOFF_D1) {  // deform L0: k = 2s + h over freq(x) (42)
+        const int q = e - TOFF_D0, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+        v = w.def_w0[(32 * rt + j) * ldD0 + 2 * s + h];
+    } else if (e < TOFF_D2) {
+        const int q = e - TOFF_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+        v = w.def_w1[(32 * rt + j) * 64 + kmap(s, h)];
+    } else if (e < TOFF_T0) {
+        const int q0 = e - TOFF_D2, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
+        v = w.def_w2[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
+    } else if (e < TOFF_T1) {  // torso L0: steps 0..15 grid (cols 0..31), 16..36 freq(x) (cols 32..73)
+        const int q = e - TOFF_T0, s = q / kTStep32, rem = q % kTStep32, h = rem / 32, j = rem % 32;
+        v = w.tor_w0[j * ldT0 + 2 * s + h];
+    } else if (e < TOFF_T2) {
+        const int q = e - TOFF_T1, s = q / kTStep32, rem = q % kTStep32, h = rem / 32, j = rem % 32;
+        v = w.tor_w1[j * 32 + kmap32(s, h)];
+    } else {
+        const int q0 = e - TOFF_T2, o = q0 / 32, h = (q0 % 32) / 16, r = q0 % 16;
+        v = w.tor_w2[o * 32 + rowmap(r, h)];
+    }
+    packed[e] = v;
+}
+
+struct BlendArgs {   // final blend folded into the torso pass (renderer.py:306-311; rn_torso_blend_frame)
+    float *image;
+    const float *weights_sum;
+    float *depth;
+    const float *nears, *fars;
+    uint8_t *u8;
+};
+
+struct TorsoParams {
+    const float *bg_coords;
+    uint32_t N;
+    const float *density_grid;
+    uint32_t G;
+    float thresh;
+    const float *poses6, *ind_code;
+    float shrink;
+    RawT w;
+    const float *packed;
+    GridArgs gt;
+    const float *bg_in;
+    float *bg_out, *alpha_out, *deform_out;
+    BlendArgs blend;
+};
+
+// image = clamp(image + (1 - weights_sum) * bg, 0, 1); depth = max(depth - near, 0) / (far - near)  [, uint8 frame]
+__device__ __forceinline__ void blend_pixel(const BlendArgs &b, size_t px, const float (&bg)[3]) {
+    const float w = 1 - b.weights_sum[px];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float v = b.image[3 * px + c] + w * bg[c];
+        v = fminf(fmaxf(v, 0.0f), 1.0f);
+        b.image[3 * px + c] = v;
+        if (b.u8) b.u8[3 * px + c] = (uint8_t)(v * 255.0f);
+    }
+    const float dd = b.depth[px] - b.nears[px];
+    b.depth[px] = fmaxf(dd, 0.0f) / (b.fars[px] - b.nears[px]);
+}
+
+// F.grid_sample(bilinear, zeros, align_corners=True) of the [G,G] torso grid at (gx, gy) (renderer.py:282)
+__device__ __forceinline__ float sample_torso_grid(const float *__restrict__ img, uint32_t G, float gx, float gy) {
+    const float ix = ((gx + 1.f) / 2) * (float)(G - 1);
+    const float iy = ((gy + 1.f) / 2) * (float)(G - 1);
+    const float ix_nw = floorf(ix), iy_nw = floorf(iy);
+    const float ix_se = ix_nw + 1, iy_se = iy_nw + 1;
+    const float nw = (ix_se - ix) * (iy_se - iy), ne = (ix - ix_nw) * (iy_se - iy);
+    const float sw = (ix_se - ix) * (iy - iy_nw), se = (ix - ix_nw) * (iy - iy_nw);
+    const int x0 = (int)ix_nw, y0 = (int)iy_nw, x1 = x0 + 1, y1 = y0 + 1;
+    const int g = (int)G;
+    float out = 0.0f;
+    if (x0 >= 0 && x0 < g && y0 >= 0 && y0 < g) out += img[y0 * g + x0] * nw;
+    if (x1 >= 0 && x1 < g && y0 >= 0 && y0 < g) out += img[y0 * g + x1] * ne;
+    if (x0 >= 0 && x0 < g && y1 >= 0 && y1 < g) out += img[y1 * g + x0] * sw;
+    if (x1 >= 0 && x1 < g && y1 >= 0 && y1 < g) out += img[y1 * g + x1] * se;
+    return out;
+}
+
+template <typename TT, bool BLEND>
+__global__ void __launch_bounds__(kFusedThreads, 2) k_torso_fused(TorsoParams p) {
+    __shared__ __attribute__((aligned(16))) float lds[kTorsoPacked + kTorsoBias + 64];
+    __shared__ LevelPlan plan_t[16];
+    float *bias_def = lds + kTorsoPacked, *bias_tor = bias_def + 64, *enc_pose = bias_tor + 32;
+    if (threadIdx.x >= 64 && threadIdx.x < 80) {
+        const int t = threadIdx.x - 64;
+        const uint32_t o = (uint32_t)p.gt.offsets[t];
+        plan_t[t] = plan_level<2>(p.gt.lc.scale[t], p.gt.lc.resolution[t], o, (uint32_t)p.gt.offsets[t + 1] - o, p.gt.gridtype,
+                                  (uint32_t)sizeof(TT) * 2u);
+    }
+
+    for (int i = threadIdx.x; i < kTorsoPacked / 4; i += kFusedThreads)
+        reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.packed)[i];
+    // enc_pose = freq(poses6, deg 4) -> 54 values (network.py:197), same layout as k_freq_forward
+    if (threadIdx.x < 54) {
+        const int c = threadIdx.x;
+        float v;
+        if (c < 6) v = p.poses6[c];
+        else {
+            const int col = c / 6 - 1, d = c % 6, f = col / 2;
+            const float a = scalbnf(p.poses6[d], f);
+            v = (col & 1) ? sinf(a + 3.141592653589793f / 2) : sinf(a);
+        }
+        enc_pose[c] = v;
+    }
+    __syncthreads();
+    // broadcast columns: deform [42 .. 96+ind), torso [74 .. 128+ind)  (network.py:201, 212)
+    if (threadIdx.x < 96) {
+        const int t = threadIdx.x;
+        const bool is_def = t < 64;
+        const int row = is_def ? t : t - 64;
+        const int ld = (is_def ? 96 : 128) + (int)p.w.ind_dim;
+        const float *r = (is_def ? p.w.def_w0 : p.w.tor_w0) + row * ld + (is_def ? 42 : 74);
+        float acc = 0.0f;
+        for (int k = 0; k < 54; k++) acc += r[k] * enc_pose[k];
+        for (uint32_t c = 0; c < p.w.ind_dim; c++) acc += r[54 + c] * p.ind_code[c];
+        (is_def ? bias_def : bias_tor)[row] = acc;
+    }
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int lane_off = h * 64 + j * 2, lane_off32 = h * 32 + j;
+    const uint32_t n_tiles = (p.N + 63u) >> 6;
+
+    for (uint32_t tile = blockIdx.x * kWavesPerBlock + wave; tile < n_tiles; tile += gridDim.x * kWavesPerBlock) {
+        const uint32_t px = tile * 64 + lane;
+        const bool in_range = px < p.N;
+        float cx = 0.0f, cy = 0.0f;
+        bool on = false;
+        if (in_range) {
+            cx = p.bg_coords[2 * (size_t)px]; cy = p.bg_coords[2 * (size_t)px + 1];
+            on = sample_torso_grid(p.density_grid, p.G, cx, cy) > p.thresh;
+        }
+        float bgc[3] = {1.0f, 1.0f, 1.0f};
+        if (in_range && p.bg_in) { bgc[0] = p.bg_in[3 * (size_t)px]; bgc[1] = p.bg_in[3 * (size_t)px + 1]; bgc[2] = p.bg_in[3 * (size_t)px + 2]; }
+        if (__ballot(on) == 0ull) {  // no torso pixel in this tile: background passes through
+            if (in_range) {
+                if (p.bg_out) { p.bg_out[3 * (size_t)px] = bgc[0]; p.bg_out[3 * (size_t)px + 1] = bgc[1]; p.bg_out[3 * (size_t)px + 2] = bgc[2]; }
+                if constexpr (BLEND) blend_pixel(p.blend, px, bgc);
+                if (p.alpha_out) p.alpha_out[px] = 0.0f;
+                if (p.deform_out) { p.deform_out[2 * (size_t)px] = 0.0f; p.deform_out[2 * (size_t)px + 1] = 0.0f; }
+            }
+            continue;
+        }
+        // x = x * torso_shrink; enc_x = freq(x, deg 10) (network.py:194,198): [x, sin(2^f x), cos(2^f x)]_f
+        const float x0 = cx * p.shrink, x1 = cy * p.shrink;
+        float bq[2][21];
+        {
+            float fq[42];
+            fq[0] = x0; fq[1] = x1;
+#pragma unroll
+            for (int f = 0; f < 10; f++) {
+                const float a0 = scalbnf(x0, f), a1 = scalbnf(x1, f);
+                fq[2 + 4 * f + 0] = on ? sinf(a0) : 0.0f;
+                fq[2 + 4 * f + 1] = on ? sinf(a1) : 0.0f;
+                fq[2 + 4 * f + 2] = on ? sinf(a0 + 3.141592653589793f / 2) : 0.0f;
+                fq[2 + 4 * f + 3] = on ? sinf(a1 + 3.141592653589793f / 2) : 0.0f;
+            }
+            if (!on) { fq[0] = 0.0f; fq[1] = 0.0f; }
+#pragma unroll
+            for (int s = 0; s < 21; s++) to_b_operands(fq[2 * s], fq[2 * s + 1], bq[0][s], bq[1][s]);
+        }
+        // deform net 104 -> 64 -> 64 -> 2
+        Acc a0, a1;
+        acc_bias(a0, bias_def, h);
+#pragma unroll
+        for (int s = 0; s < 21; s++) step64(a0, lds + TOFF_D0, s, lane_off, bq[0][s], bq[1][s]);
+        acc_relu(a0);
+        acc_zero(a1);
+        layer_from_acc(a1, a0, lds + TOFF_D1, lane_off);
+        acc_relu(a1);
+        float dxy[2];
+        {
+            float part[2][2];
+            valu_out<2>(a1, lds + TOFF_D2, h, part);
+            dxy[0] = h ? part[1][0] : part[0][0];
+            dxy[1] = h ? part[1][1] : part[0][1];
+        }
+        // x = clamp(x + dx, -1, 1); torso grid (bound = 1)
+        float bg_[2][16];
+        {
+            float in[2] = {(fminf(fmaxf(x0 + dxy[0], -1.0f), 1.0f) + 1.0f) / 2.0f,
+                           (fminf(fmaxf(x1 + dxy[1], -1.0f), 1.0f) + 1.0f) / 2.0f};
+            const bool ok = on && !(in[0] < 0 || in[0] > 1 || in[1] < 0 || in[1] > 1);
+            // kTorsoGroup levels in flight (the deform net's accumulators are dead by now): the 16 gathers are a latency chain
+            // of one tile, and a torso launch is one tile per wave
+            LevelFetch<TT, 2, 2> f[kTorsoGroup];
+#pragma unroll
+            for (int g = 0; g < 16; g += kTorsoGroup) {
+                if (ok) {
+#pragma unroll
+                    for (int i = 0; i < kTorsoGroup; i++)
+                        issue_planned<TT, 2, 2, false>(static_cast<const TT *>(p.gt.table), plan_t[g + i], in, f[i]);
+                }
+#pragma unroll
+                for (int i = 0; i < kTorsoGroup; i++) {
+                    float f0 = 0.0f, f1 = 0.0f;
+                    if (ok) {
+                        TT res[2];
+                        TT dummy[1];
+                        blend_level<TT, 2, 2, false>(f[i], 0.0f, res, dummy);
+                        f0 = to_f<TT>(res[0]);
+                        f1 = to_f<TT>(res[1]);
+                    }
+                    to_b_operands(f0, f1, bg_[0][g + i], bg_[1][g + i]);
+                }
+            }
+        }
+        // torso net 136 -> 32 -> 32 -> 4 : a single 32-row tile
+        f32x16 t0[2], t1[2];
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const float4 b = *reinterpret_cast<const float4 *>(bias_tor + 8 * g + 4 * h);
+            t0[0][4 * g] = b.x; t0[0][4 * g + 1] = b.y; t0[0][4 * g + 2] = b.z; t0[0][4 * g + 3] = b.w;
+            t0[1][4 * g] = b.x; t0[1][4 * g + 1] = b.y; t0[1][4 * g + 2] = b.z; t0[1][4 * g + 3] = b.w;
+        }
+#pragma unroll
+        for (int s = 0; s < 16; s++) {
+            const float wv = lds[TOFF_T0 + s * kTStep32 + lane_off32];
+            t0[0] = mfma32(wv, bg_[0][s], t0[0]); t0[1] = mfma32(wv, bg_[1][s], t0[1]);
+        }
+#pragma unroll
+        for (int s = 0; s < 21; s++) {
+            const float wv = lds[TOFF_T0 + (16 + s) * kTStep32 + lane_off32];
+            t0[0] = mfma32(wv, bq[0][s], t0[0]); t0[1] = mfma32(wv, bq[1][s], t0[1]);
+        }
+#pragma unroll
+        for (int r = 0; r < 16; r++) { t0[0][r] = fmaxf(t0[0][r], 0.0f); t0[1][r] = fmaxf(t0[1][r], 0.0f); t1[0][r] = 0.0f; t1[1][r] = 0.0f; }
+#pragma unroll
+        for (int s = 0; s < 16; s++) {
+            const float wv = lds[TOFF_T1 + s * kTStep32 + lane_off32];
+            t1[0] = mfma32(wv, t0[0][s], t1[0]); t1[1] = mfma32(wv, t0[1][s], t1[1]);
+        }
+        float o4[4];
+#pragma unroll
+        for (int o = 0; o < 4; o++) {
+            float p0 = 0.0f, p1 = 0.0f;
+            const float *wo = lds + TOFF_T2 + (o * 2 + h) * 16;
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                p0 = __builtin_fmaf(fmaxf(t1[0][r], 0.0f), wo[r], p0);
+                p1 = __builtin_fmaf(fmaxf(t1[1][r], 0.0f), wo[r], p1);
+            }
+            p0 += __shfl_xor(p0, 32, 64);
+            p1 += __shfl_xor(p1, 32, 64);
+            o4[o] = h ? p1 : p0;
+        }
+        if (in_range) {
+            float alpha = 0.0f, col[3] = {0.0f, 0.0f, 0.0f};
+            if (on) {
+                alpha = 1.0f / (1.0f + expf(-o4[0]));
+#pragma unroll
+                for (int c = 0; c < 3; c++) col[c] = 1.0f / (1.0f + expf(-o4[1 + c]));
+            }
+            // bg = torso_color * alpha + bg * (1 - alpha)  (renderer.py:299)
+            float bgf[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) bgf[c] = col[c] * alpha + bgc[c] * (1 - alpha);
+            if (p.bg_out) {
+#pragma unroll
+                for (int c = 0; c < 3; c++) p.bg_out[3 * (size_t)px + c] = bgf[c];
+            }
+            if constexpr (BLEND) blend_pixel(p.blend, px, bgf);
+            if (p.alpha_out) p.alpha_out[px] = alpha;
+            if (p.deform_out) { p.deform_out[2 * (size_t)px] = on ? dxy[0] : 0.0f; p.deform_out[2 * (size_t)px + 1] = on ? dxy[1] : 0.0f; }
+        }
+    }
+}
+
+// Pixels the torso layer covers: bilinear occupancy of the 2-D torso grid above the threshold (renderer.py:281-283).  Used by
+// the differentiable (training) formulation, which gathers those pixels for the PyTorch layers; inference goes through
+// k_torso_fused, which tests the same expression per pixel.
+__global__ void __launch_bounds__(256)
+k_torso_mask(const float *__restrict__ bg_coords, uint32_t N, const float *__restrict__ grid, uint32_t G, float thresh,
+             uint8_t *__restrict__ mask) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    mask[n] = sample_torso_grid(grid, G, bg_coords[2 * (size_t)n], bg_coords[2 * (size_t)n + 1]) > thresh ? 1 : 0;
+}
+
+// renderer.py:306-311
+__global__ void __launch_bounds__(256)
+k_blend(float *__restrict__ image, const float *__restrict__ weights_sum, const float *__restrict__ bg,
+        float *__restrict__ depth, const float *__restrict__ nears, const float *__restrict__ fars, uint32_t N,
+        uint8_t *__restrict__ u8) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n >= N) return;
+    const float w = 1 - weights_sum[n];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float b = bg ? bg[3 * (size_t)n + c] : 1.0f;
+        float v = image[3 * (size_t)n + c] + w * b;
+        v = fminf(fmaxf(v, 0.0f), 1.0f);
+        image[3 * (size_t)n + c] = v;
+        if (u8) u8[3 * (size_t)n + c] = (uint8_t)(v * 255.0f);
+    }
+    const float dd = depth[n] - nears[n];
+    depth[n] = fmaxf(dd, 0.0f) / (fars[n] - nears[n]);
+}
+
+}  // namespace rn
+
+using namespace rn;
+
+extern "C" {
+
+size_t rn_torso_packed_floats(void) { return (size_t)kTorsoPacked; }
+
+int rn_torso_pack_weights(const rn_torso_weights_t *w, float *packed, rn_stream_t stream) {
+    RN_REQUIRE(w && w->def_w0 && w->def_w1 && w->def_w2 && w->tor_w0 && w->tor_w1 && w->tor_w2 && packed,
+               "torso_pack_weights: null pointer");
+    RN_REQUIRE(((uintptr_t)packed & 15u) == 0, "torso_pack_weights: packed must be 16-byte aligned");
+    RawT r{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
+    hipLaunchKernelGGL(k_pack_torso, dim3(div_up(kTorsoPacked, 256)), dim3(256), 0, as_stream(stream), r, packed);
+    return check_launch("torso_pack_weights");
+}
+
+int rn_torso_fused(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,
+                   const float *poses6, const float *ind_code, float torso_shrink, const rn_torso_weights_t *w,
+                   const float *packed, const rn_grid_t *grid_torso, const float *bg_in, float *bg_out,
+                   float *torso_alpha, float *deform, rn_stream_t stream) {
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(bg_coords && density_grid_torso && poses6 && w && packed && (bg_out || torso_alpha), "torso_fused: null pointer");
+    RN_REQUIRE(ind_code || w->ind_dim == 0, "torso_fused: ind_code required when ind_dim > 0");
+    RN_REQUIRE(((uintptr_t)packed & 15u) == 0, "torso_fused: packed must be 16-byte aligned");
+    if (int rc = check_fused_grid(grid_torso, 2, "torso_fused(torso grid)")) return rc;
+    RawT r{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
+    TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, r, packed,
+                  grid_args(grid_torso), bg_in, bg_out, torso_alpha, deform, BlendArgs{}};
+    uint32_t blocks = div_up((N + 63u) >> 6, kWavesPerBlock);
+    const uint32_t cap = (uint32_t)num_cus() * 2;
+    if (blocks > cap) blocks = cap;
+    if (grid_torso->dtype == RN_F32) hipLaunchKernelGGL((k_torso_fused<float, false>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
+    else hipLaunchKernelGGL((k_torso_fused<__half, false>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
+    return check_launch("torso_fused");
+}
+
+int rn_torso_blend_frame(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,
+                         const float *poses6, const float *ind_code, float torso_shrink, const rn_torso_weights_t *w,
+                         const float *packed, const rn_grid_t *grid_torso, const float *bg_in, float *bg_out, float *torso_alpha,
+                         float *image, const float *weights_sum, float *depth, const float *nears, const float *fars,
+                         uint8_t *image_u8, rn_stream_t stream) {
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(bg_coords && density_grid_torso && poses6 && w && packed, "torso_blend_frame: null pointer");
+    RN_REQUIRE(image && weights_sum && depth && nears && fars, "torso_blend_frame: null frame buffers");
+    RN_REQUIRE(ind_code || w->ind_dim == 0, "torso_blend_frame: ind_code required when ind_dim > 0");
+    RN_REQUIRE(((uintptr_t)packed & 15u) == 0, "torso_blend_frame: packed must be 16-byte aligned");
+    if (int rc = check_fused_grid(grid_torso, 2, "torso_blend_frame(torso grid)")) return rc;
+    RawT r{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
+    TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, r, packed,
+                  grid_args(grid_torso), bg_in, bg_out, torso_alpha, nullptr, BlendArgs{image, weights_sum, depth, nears, fars, image_u8}};
+    uint32_t blocks = div_up((N + 63u) >> 6, kWavesPerBlock);
+    const uint32_t cap = (uint32_t)num_cus() * 2;
+    if (blocks > cap) blocks = cap;
+    if (grid_torso->dtype == RN_F32) hipLaunchKernelGGL((k_torso_fused<float, true>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
+    else hipLaunchKernelGGL((k_torso_fused<__half, true>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
+    return check_launch("torso_blend_frame");
+}
+
+int rn_torso_mask(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,
+                  uint8_t *mask, rn_stream_t stream) {
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(bg_coords && density_grid_torso && mask && grid_size >= 2, "torso_mask: bad arguments");
+    hipLaunchKernelGGL(k_torso_mask, dim3(div_up(N, 256)), dim3(256), 0, as_stream(stream), bg_coords, N, density_grid_torso, grid_size,
+                       thresh, mask);
+    return check_launch("torso_mask");
+}
+
+int rn_blend_frame(float *image, const float *weights_sum, const float *bg, float *depth, const float *nears,
+                   const float *fars, uint32_t N, uint8_t *image_u8, rn_stream_t stream) {
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(image && weights_sum && depth && nears && fars, "blend_frame: null pointer");
+    hipLaunchKernelGGL(k_blend, dim3(div_up(N, 256)), dim3(256), 0, as_stream(stream), image, weights_sum, bg, depth, nears,
+                       fars, N, image_u8);
+    return check_launch("blend_frame");
+}
+
+}  // extern "C"

@@ -19,12 +19,8 @@
 //    workgroup's tiles; per-workgroup partial sums are folded by k_train_wreduce into the nn.Linear layout.  The columns of
 //    the per-call constants (audio code, eye, individual code) ride along as one more feature that is 1 for every sample:
 //    its gradient column is the bias gradient, from which k_train_const derives the constants' and their columns' gradients.
-//  * k_grid_scatter: table gradient.  Float atomics run at the memory side, one request per touched 64-B line per
-//    instruction (MI355X_MICROARCH.md, "Global float atomics"), so a workgroup first sums its 128 samples x 2^D corners of
-//    one level in an LDS table keyed by the 64-B LINE of the gradient table (8 rows x 2 channels = 16 floats per slot; the
-//    two x-neighbours of a corner pair share a line 7 times out of 8, on hashed levels too: the x prime is 1) and then
-//    issues the 16 floats of a slot from 16 adjacent lanes -- one request per touched line instead of one per row.
-#include "rn_fused_dev.h"
+// The table gradient of the two grids is rn_grid_scatter.hip.
+#include "rn_nerf_image_dev.h"
 
 #include <stdlib.h>
 
@@ -33,18 +29,7 @@
 namespace rn {
 namespace th {
 
-constexpr int kStep = 128;   // floats per MFMA step of a 64-row layer: [2 h][32 j][2 row tiles]
-// ---- forward image (the inference kernel's layout) ------------------------------------------------------------------
-constexpr int F_A0 = 0;                    // ambient L0, enc_x part : 16 steps
-constexpr int F_A1 = F_A0 + 16 * kStep;    // ambient L1            : 32 steps
-constexpr int F_A2 = F_A1 + 32 * kStep;    // ambient L2 (VALU)     : [2 out][2 h][32]
-constexpr int F_S0 = F_A2 + 128;           // sigma L0 (enc_x|enc_w): 32 steps
-constexpr int F_S1 = F_S0 + 32 * kStep;    // sigma L1              : 32 steps
-constexpr int F_S2 = F_S1 + 32 * kStep;    // sigma L2 rows 1..64   : 32 steps
-constexpr int F_S2R = F_S2 + 32 * kStep;   // sigma L2 row 0 (VALU) : [2 h][32]
-constexpr int F_C0 = F_S2R + 64;           // color L0 (sh | geo)   : 8 + 32 steps
-constexpr int F_C1 = F_C0 + 40 * kStep;    // color L1 (VALU)       : [3 out][2 h][32]
-constexpr int kFwd = F_C1 + 192;           // 23936 floats
+// The weight image of a step: forward image (rn_nerf_image_dev.h, the inference kernel's) | transposed image | biases.
 // ---- transposed image: T[s][h][j][rt] = W[kmap(s, h)][column(32 rt + j)] ---------------------------------------------
 constexpr int T_C0 = 0;                    // d geo_feat   = W_col0[:, 16:80]^T dZ_c0
 constexpr int T_S2 = T_C0 + 32 * kStep;    // d h_s1       = W_sig2[1:65]^T d geo_feat
@@ -56,8 +41,7 @@ constexpr int N_C1 = T_A0 + 32 * 64;       // narrow rows again: [3][2 h][32]
 constexpr int N_S2R = N_C1 + 192;          // [2 h][32]
 constexpr int N_A2 = N_S2R + 64;           // [2][2 h][32]
 constexpr int kBwd = N_A2 + 128;           // 22912 floats
-constexpr int kBias = 192;
-constexpr int kImage = kFwd + kBwd + kBias;
+constexpr int kImage = kPacked + kBwd + kBias;
 
 // Output row j of a 32-row tile sits in register r of lane half hh with rowmap(r, hh) == j.  The grid-feature gradients want
 // register 2 q + c of lane half hh to be (level 2 q + hh, channel c), the layout the forward gathers in: feature 4 q + 2 hh + c.
@@ -72,40 +56,18 @@ __global__ void __launch_bounds__(256) k_train_pack(RawW w, const float *__restr
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= kImage) return;
     if (ind_index) ind_code += (size_t)ind_index[0] * w.ind_dim;   // ind_code = the table individual_codes, row picked on the device
-    const int ldA0 = 32 + (int)w.audio_dim, ldS0 = 64 + (int)w.has_eye, ldC0 = 80 + (int)w.ind_dim;
+    const int ldA0 = 32 + (int)w.audio_dim, ldS0 = 64 + (int)w.has_eye, ldC0 = 80 + (int)w.ind_dim;   // row strides of the first layers
     float v;
-    auto mfma_elem = [&](int q, const float *src, int ld, int kind) -> float {
-        const int s = q / kStep, rem = q % kStep;
-        const int h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
-        const int row = 32 * rt + j;
-        int k;
-        if (kind == 3) k = 4 * (s >> 1) + 2 * h + (s & 1);       // gather rounds: half h holds level 2 (s / 2) + h
-        else if (kind == 1) k = kmap(s, h);                       // previous accumulators
-        else k = (s < 8) ? 2 * s + h : 16 + kmap(s - 8, h);      // color L0: sh pairs then geo accumulators
-        return src[row * ld + k];
-    };
-    auto valu_elem = [&](int q0, const float *src) -> float {    // [out][h][q], q = rt * 16 + r
-        const int o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
-        return src[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
-    };
     auto t_elem = [&](int q, const float *src, int ld, int col0, bool gather) -> float {   // transposed 64-row layer
         const int s = q / kStep, rem = q % kStep;
         const int h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
         const int col = gather ? 32 * rt + gather_feature(j) : 32 * rt + j;
         return src[kmap(s, h) * ld + col0 + col];
     };
-    if (e < kFwd) {
-        if (e < F_A1) v = mfma_elem(e - F_A0, w.amb_w0, ldA0, 3);
-        else if (e < F_A2) v = mfma_elem(e - F_A1, w.amb_w1, 64, 1);
-        else if (e < F_S0) v = valu_elem(e - F_A2, w.amb_w2);
-        else if (e < F_S1) v = mfma_elem(e - F_S0, w.sig_w0, ldS0, 3);
-        else if (e < F_S2) v = mfma_elem(e - F_S1, w.sig_w1, 64, 1);
-        else if (e < F_S2R) v = mfma_elem(e - F_S2, w.sig_w2 + 64, 64, 1);   // rows 1..64 = geo_feat
-        else if (e < F_C0) v = valu_elem(e - F_S2R, w.sig_w2);               // row 0 = sigma
-        else if (e < F_C1) v = mfma_elem(e - F_C0, w.col_w0, ldC0, 2);
-        else v = valu_elem(e - F_C1, w.col_w1);
-    } else if (e < kFwd + kBwd) {
-        const int t = e - kFwd;
+    if (e < kPacked) {
+        v = nerf_image_elem(w, e);
+    } else if (e < kPacked + kBwd) {
+        const int t = e - kPacked;
         if (t < T_S2) v = t_elem(t - T_C0, w.col_w0, ldC0, 16, false);
         else if (t < T_S1) v = t_elem(t - T_S2, w.sig_w2 + 64, 64, 0, false);
         else if (t < T_S0) v = t_elem(t - T_S1, w.sig_w1, 64, 0, false);
@@ -114,22 +76,11 @@ __global__ void __launch_bounds__(256) k_train_pack(RawW w, const float *__restr
         else if (t < N_C1) {
             const int q = t - T_A0, s = q / 64, rem = q % 64, h = rem / 32, j = rem % 32;
             v = w.amb_w0[kmap(s, h) * ldA0 + gather_feature(j)];
-        } else if (t < N_S2R) v = valu_elem(t - N_C1, w.col_w1);
-        else if (t < N_A2) v = valu_elem(t - N_S2R, w.sig_w2);
-        else v = valu_elem(t - N_A2, w.amb_w2);
-    } else {   // first-layer biases of the per-call constants (nerf/network.py:236, 262, 274)
-        const int t = e - kFwd - kBwd, row = t & 63;
-        float acc = 0.0f;
-        if (t < 64) {
-            const float *r = w.amb_w0 + row * ldA0 + 32;
-            for (uint32_t a = 0; a < w.audio_dim; a++) acc += r[a] * enc_a[a];
-        } else if (t < 128) {
-            if (w.has_eye) acc = w.sig_w0[row * ldS0 + 64] * eye[0];
-        } else {
-            const float *r = w.col_w0 + row * ldC0 + 80;
-            for (uint32_t c = 0; c < w.ind_dim; c++) acc += r[c] * ind_code[c];
-        }
-        v = acc;
+        } else if (t < N_S2R) v = valu_image_elem(t - N_C1, w.col_w1);
+        else if (t < N_A2) v = valu_image_elem(t - N_S2R, w.sig_w2);
+        else v = valu_image_elem(t - N_A2, w.amb_w2);
+    } else {   // first-layer biases of the per-call constants
+        v = nerf_const_bias(w, enc_a, eye, ind_code, e - kPacked - kBwd);
     }
     image[e] = v;
 }
@@ -175,59 +126,7 @@ __host__ __device__ inline Ws make_ws(float *base, uint32_t M) {
     return w;
 }
 
-// ---- MFMA helpers (32-sample tiles) ---------------------------------------------------------------------------------------
-struct Acc32 {
-    f32x16 v[2];
-};
-__device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c, 0, 0, 0); }
-__device__ __forceinline__ void acc_zero(Acc32 &a) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) a.v[rt][r] = 0.0f;
-}
-__device__ __forceinline__ void acc_bias(Acc32 &a, const float *bias64, int h) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const float4 b = *reinterpret_cast<const float4 *>(bias64 + 32 * rt + 8 * g + 4 * h);
-            a.v[rt][4 * g + 0] = b.x; a.v[rt][4 * g + 1] = b.y; a.v[rt][4 * g + 2] = b.z; a.v[rt][4 * g + 3] = b.w;
-        }
-}
-__device__ __forceinline__ void acc_relu(Acc32 &a) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) a.v[rt][r] = relu_bits(a.v[rt][r]);
-}
-__device__ __forceinline__ void step32(Acc32 &a, const float *wl, int s, int lane_off, float b) {
-    const float2 w = *reinterpret_cast<const float2 *>(wl + s * kStep + lane_off);
-    a.v[0] = mfma32(w.x, b, a.v[0]);
-    a.v[1] = mfma32(w.y, b, a.v[1]);
-}
-__device__ __forceinline__ void layer_from_acc(Acc32 &out, const Acc32 &in, const float *wl, int lane_off) {
-#pragma unroll
-    for (int s = 0; s < 32; s++) step32(out, wl, s, lane_off, in.v[s >> 4][s & 15]);
-}
-template <int NOUT>
-__device__ __forceinline__ void valu_out(const Acc32 &in, const float *wl, int h, float (&out)[NOUT]) {
-#pragma unroll
-    for (int o = 0; o < NOUT; o++) {
-        float p = 0.0f;
-        const float *wo = wl + (o * 2 + h) * 32;
-#pragma unroll
-        for (int g = 0; g < 8; g++) {
-            const float4 w = *reinterpret_cast<const float4 *>(wo + 4 * g);
-            const int rt = g >> 2, r = (g & 3) * 4;
-            p = __builtin_fmaf(in.v[rt][r + 0], w.x, p);
-            p = __builtin_fmaf(in.v[rt][r + 1], w.y, p);
-            p = __builtin_fmaf(in.v[rt][r + 2], w.z, p);
-            p = __builtin_fmaf(in.v[rt][r + 3], w.w, p);
-        }
-        out[o] = p + __shfl_xor(p, 32, 64);
-    }
-}
+// ---- MFMA helpers of the backward pass (the forward ones: rn_tile32_dev.h) ------------------------------------------------
 // g[k] += sum_o W[o][k] d[o] for the k's this lane holds (the transposed narrow layer)
 template <int NOUT>
 __device__ __forceinline__ void valu_out_T(Acc32 &g, const float *wl, int h, const float (&d)[NOUT]) {
@@ -244,12 +143,6 @@ __device__ __forceinline__ void valu_out_T(Acc32 &g, const float *wl, int h, con
             g.v[rt][r + 3] = __builtin_fmaf(w.w, d[o], g.v[rt][r + 3]);
         }
     }
-}
-__device__ __forceinline__ void tile_store(float *__restrict__ dst, const Acc32 &a, int lane) {
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) dst[(rt * 16 + r) * 64 + lane] = a.v[rt][r];
 }
 // g = (saved activation > 0) ? g : 0, the saved tile read row by row
 __device__ __forceinline__ void relu_mask(Acc32 &g, const float *__restrict__ saved, int lane) {
@@ -275,21 +168,15 @@ struct FwdParams {
     float *ws;
 };
 
-__device__ __forceinline__ uint32_t live_count(uint32_t M, const int32_t *m_dev) {
-    if (!m_dev) return M;
-    const int32_t d = *m_dev;
-    return d <= 0 ? 0u : ((uint32_t)d < M ? (uint32_t)d : M);
-}
-
 template <int GX, int GA>   // gather rounds in flight per wave (xyz grid / ambient grid): independent load chains hide each other's latency
 __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
-    __shared__ __attribute__((aligned(16))) float lds[kFwd + kBias];
+    __shared__ __attribute__((aligned(16))) float lds[kPacked + kBias];
     __shared__ LevelPlan plan_x[16], plan_w[16];
     const uint32_t M = live_count(p.M, p.m_dev);
     const uint32_t n_tiles = (M + 31u) >> 5;
     if (blockIdx.x * kWaves >= n_tiles) return;
-    for (int i = threadIdx.x; i < kFwd / 4; i += kThreads) reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image)[i];
-    if (threadIdx.x < kBias) lds[kFwd + threadIdx.x] = p.image[kFwd + kBwd + threadIdx.x];
+    for (int i = threadIdx.x; i < kPacked / 4; i += kThreads) reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image)[i];
+    if (threadIdx.x < kBias) lds[kPacked + threadIdx.x] = p.image[kPacked + kBwd + threadIdx.x];
     if (threadIdx.x < 16) {
         const int t = threadIdx.x;
         const uint32_t ox = (uint32_t)p.gx.offsets[t], ow = (uint32_t)p.gw.offsets[t];
@@ -301,7 +188,7 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int lane_off = h * 64 + j * 2;
-    const float *bias_amb = lds + kFwd, *bias_sig = lds + kFwd + 64, *bias_col = lds + kFwd + 128;
+    const float *bias_amb = lds + kPacked, *bias_sig = lds + kPacked + 64, *bias_col = lds + kPacked + 128;
     const float *tx = static_cast<const float *>(p.gx.table), *tw = static_cast<const float *>(p.gw.table);
 
     for (uint32_t tile = blockIdx.x * kWaves + wave; tile < n_tiles; tile += gridDim.x * kWaves) {
@@ -340,10 +227,10 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
                         f0 = res[0];
                         f1 = res[1];
                     }
-                    step32(a0, lds + F_A0, 2 * r, lane_off, f0);
-                    step32(a2, lds + F_S0, 2 * r, lane_off, f0);
-                    step32(a0, lds + F_A0, 2 * r + 1, lane_off, f1);
-                    step32(a2, lds + F_S0, 2 * r + 1, lane_off, f1);
+                    step32(a0, lds + OFF_A0, 2 * r, lane_off, f0);
+                    step32(a2, lds + OFF_S0, 2 * r, lane_off, f0);
+                    step32(a0, lds + OFF_A0, 2 * r + 1, lane_off, f1);
+                    step32(a2, lds + OFF_S0, 2 * r + 1, lane_off, f1);
                     ex[(2 * r) * 64 + lane] = f0;
                     ex[(2 * r + 1) * 64 + lane] = f1;
                 }
@@ -353,11 +240,11 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
         acc_relu(a0);
         tile_store(ws.ha0 + (size_t)tile * kTile32, a0, lane);
         acc_zero(a1);
-        layer_from_acc(a1, a0, lds + F_A1, lane_off);
+        layer_from_acc(a1, a0, lds + OFF_A1, lane_off);
         acc_relu(a1);
         tile_store(ws.ha1 + (size_t)tile * kTile32, a1, lane);
         float amb[2];
-        valu_out<2>(a1, lds + F_A2, h, amb);
+        valu_out<2>(a1, lds + OFF_A2, h, amb);
         amb[0] = tanhf(amb[0]);
         amb[1] = tanhf(amb[1]);
         // ---- ambient grid (+ d enc_w / d input): enc_w -> sigma L0 steps 16..31
@@ -391,8 +278,8 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
 #pragma unroll
                         for (int q = 0; q < 4; q++) g[q] = grads[q];
                     }
-                    step32(a2, lds + F_S0, 16 + 2 * r, lane_off, f0);
-                    step32(a2, lds + F_S0, 16 + 2 * r + 1, lane_off, f1);
+                    step32(a2, lds + OFF_S0, 16 + 2 * r, lane_off, f0);
+                    step32(a2, lds + OFF_S0, 16 + 2 * r + 1, lane_off, f1);
                     ew[(2 * r) * 64 + lane] = f0;
                     ew[(2 * r + 1) * 64 + lane] = f1;
 #pragma unroll
@@ -404,19 +291,19 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
         acc_relu(a2);
         tile_store(ws.hs0 + (size_t)tile * kTile32, a2, lane);
         acc_zero(a1);
-        layer_from_acc(a1, a2, lds + F_S1, lane_off);
+        layer_from_acc(a1, a2, lds + OFF_S1, lane_off);
         acc_relu(a1);
         tile_store(ws.hs1 + (size_t)tile * kTile32, a1, lane);
         {
             float raw[1];
-            valu_out<1>(a1, lds + F_S2R, h, raw);
+            valu_out<1>(a1, lds + OFF_S2R, h, raw);
             if (h == 0) {
                 ws.sraw[sample] = raw[0];
                 if (live) p.sigmas[sample] = expf(raw[0]);   // trunc_exp forward (activation.py:9-11)
             }
         }
         acc_zero(a0);
-        layer_from_acc(a0, a1, lds + F_S2, lane_off);   // geo_feat (no activation)
+        layer_from_acc(a0, a1, lds + OFF_S2, lane_off);   // geo_feat (no activation)
         tile_store(ws.geo + (size_t)tile * kTile32, a0, lane);
         // ---- color net: [SH(d) | geo_feat | ind_code] 84 -> 64 -> 3, sigmoid
         acc_bias(a1, bias_col, h);
@@ -432,17 +319,17 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
             for (int s = 0; s < 8; s++) {
                 const uint32_t m = 0u - (uint32_t)h;   // lane half h supplies k = 2 s + h (bit-select: no dynamic indexing of sh[])
                 const float b = __uint_as_float((__float_as_uint(sh[2 * s]) & ~m) | (__float_as_uint(sh[2 * s + 1]) & m));
-                step32(a1, lds + F_C0, s, lane_off, b);
+                step32(a1, lds + OFF_C0, s, lane_off, b);
                 st[s * 64 + lane] = b;
             }
         }
 #pragma unroll
-        for (int s = 0; s < 32; s++) step32(a1, lds + F_C0, 8 + s, lane_off, a0.v[s >> 4][s & 15]);
+        for (int s = 0; s < 32; s++) step32(a1, lds + OFF_C0, 8 + s, lane_off, a0.v[s >> 4][s & 15]);
         acc_relu(a1);
         tile_store(ws.hc0 + (size_t)tile * kTile32, a1, lane);
         {
             float rgb[3];
-            valu_out<3>(a1, lds + F_C1, h, rgb);
+            valu_out<3>(a1, lds + OFF_C1, h, rgb);
             if (live && h == 0) {
 #pragma unroll
                 for (int c = 0; c < 3; c++) p.rgbs[3 * (size_t)sample + c] = 1.0f / (1.0f + expf(-rgb[c]));
@@ -467,7 +354,7 @@ __global__ void __launch_bounds__(kThreads) k_train_bwd(BwdParams p) {
     const uint32_t n_tiles = (M + 31u) >> 5;
     if (blockIdx.x * kWaves >= n_tiles) return;
     for (int i = threadIdx.x; i < kBwd / 4; i += kThreads)
-        reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image + kFwd)[i];
+        reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image + kPacked)[i];
     __syncthreads();
     const Ws ws = make_ws(p.ws, p.M);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -826,356 +713,6 @@ __global__ void __launch_bounds__(256) k_train_const(CArgs p) {
     }
 }
 
-// ---- table gradient -------------------------------------------------------------------------------------------------------
-#ifndef RN_SC_SLOTS
-#define RN_SC_SLOTS 512
-#endif
-// 256 threads = (256 / 2^(D-1)) samples x 2^(D-1) x-pairs of corners; 512 slots of 16 floats + key = 35 KB of LDS: four
-// workgroups per CU, so one workgroup's burst of atomics (its flush) runs under the others' loads and LDS inserts
-constexpr uint32_t kScThreads = 256, kScSlots = RN_SC_SLOTS, kScProbes = 24;
-constexpr uint32_t kScSlotBits = kScSlots == 1024 ? 10 : (kScSlots == 512 ? 9 : 8);
-static_assert((1u << kScSlotBits) == kScSlots, "slot count must be 256, 512 or 1024");
-constexpr uint32_t kScEmpty = 0xffffffffu;
-
-// Lanes hold (key, v[4]); consecutive lanes with equal keys form a run (ray-ordered samples stay in one coarse cell for many
-// steps).  A segmented inclusive scan sums each run into its last lane, which alone goes on to the LDS table.
-__device__ __forceinline__ bool merge_runs4(uint32_t key, uint32_t key2, float (&v)[4]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64), prev2 = (uint32_t)__shfl_up((int)key2, 1, 64);
-    const bool head = lane == 0 || key != prev || key2 != prev2;   // a run = both destination rows equal
-    const unsigned long long heads = __ballot(head);
-    if (__popcll(heads) > 40) return key != kScEmpty;
-    const unsigned long long below = heads & ((2ull << lane) - 1ull);
-    const uint32_t start = 63u - (uint32_t)__clzll(below);
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        float up[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) up[c] = __shfl_up(v[c], off, 64);
-        if (lane >= start + off) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) v[c] += up[c];
-        }
-    }
-    const bool tail = lane == 63u || ((heads >> (lane + 1)) & 1ull);
-    return tail && key != kScEmpty;
-}
-
-// One level of one chunk of samples through the LDS line merge (the non-binned levels).
-struct ScatterJob {
-    const float *grad, *inputs;
-    const int32_t *offsets;
-    float *grad_grid;
-    LevelConsts lc;
-    uint32_t gridtype, n_levels;
-    uint32_t level_of[kMaxLevels];    // the levels this job covers (blockIdx.y indexes this list)
-    uint32_t direct_mask;             // bit i: entry i of level_of goes straight to memory (a hashed level: nothing to merge)
-    uint32_t chunks_of[kMaxLevels];   // line-merged levels: chunks of samples a workgroup sums in its LDS table before it flushes
-};
-
-template <uint32_t D>
-__device__ __forceinline__ void scatter_lines(const ScatterJob &j, uint32_t Mcap, uint32_t M, uint32_t *keys, float *vals, uint32_t *occupied,
-                                              uint32_t block_x) {
-    constexpr uint32_t P = 1u << (D - 1);            // x-pairs of corners per sample
-    constexpr uint32_t kScSamples = kScThreads / P;  // lanes 0 .. S-1: pair 0 of the S samples, lanes S .. 2S-1: pair 1, ...
-    if (blockIdx.y >= j.n_levels) return;
-    const uint32_t level = j.level_of[blockIdx.y];
-    const bool direct = (j.direct_mask >> blockIdx.y) & 1u;   // workgroup-uniform
-    // small levels (few lines in all): a workgroup sums several chunks of samples in its table before it flushes -- the more
-    // samples share a table, the more of their rows coincide (the ambient coordinates of a step cluster in a few cells)
-    const uint32_t chunks = direct ? 1u : j.chunks_of[blockIdx.y];
-    if (block_x * chunks * kScSamples >= M) return;
-    if (!direct) {
-        for (uint32_t i = threadIdx.x; i < kScSlots; i += kScThreads) keys[i] = kScEmpty;
-        for (uint32_t i = threadIdx.x; i < kScSlots * 16; i += kScThreads) vals[i] = 0.0f;
-        if (threadIdx.x == 0) *occupied = 0u;
-        __syncthreads();
-    }
-    const uint32_t off = (uint32_t)j.offsets[level];
-    const uint32_t hashmap_size = (uint32_t)j.offsets[level + 1] - off;
-    float *gg = j.grad_grid + (size_t)off * 2;
-    const uint32_t q = threadIdx.x / kScSamples;      // this thread's x-pair: bits of q = the y (, z) corner
-    const uint32_t resolution = j.lc.resolution[level];
-  for (uint32_t chunk = 0; chunk < chunks; chunk++) {
-    const uint32_t b = (block_x * chunks + chunk) * kScSamples + (threadIdx.x & (kScSamples - 1u));
-    float in[D];
-    bool live = b < M;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        in[d] = live ? j.inputs[(size_t)b * D + d] : 0.0f;
-        live = live && !(in[d] < 0 || in[d] > 1);     // gridencoder.cu:275-280
-    }
-    float pos[D], pos_deriv[D];
-    uint32_t pos_grid[D];
-    lattice_pos<D>(in, j.lc.scale[level], false, 0, pos, pos_deriv, pos_grid);
-    float2 g = make_float2(0.0f, 0.0f);
-    if (live) g = *reinterpret_cast<const float2 *>(j.grad + ((size_t)level * Mcap + b) * 2);
-    {
-        uint32_t pgl[D];
-        pgl[0] = pos_grid[0];
-        float wyz[2] = {1.0f - pos[0], pos[0]};       // the reference multiplies the x term first (gridencoder.cu:298-308)
-#pragma unroll
-        for (uint32_t d = 1; d < D; d++) {
-            const bool hi = (q >> (d - 1)) & 1u;
-            const float wd = hi ? pos[d] : 1 - pos[d];
-            wyz[0] *= wd;
-            wyz[1] *= wd;
-            pgl[d] = pos_grid[d] + (hi ? 1u : 0u);
-        }
-        uint32_t row0 = kScEmpty, row1 = kScEmpty;
-        if (live) {
-            row0 = grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl);
-            pgl[0] += 1u;
-            row1 = grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl);
-        }
-        float v[4] = {wyz[0] * g.x, wyz[0] * g.y, wyz[1] * g.x, wyz[1] * g.y};
-        if (direct) {
-            // A hashed level: the workgroup's samples never touch a line twice, so an LDS merge would spend ~3.6 clocks per lane
-            // and float on LDS atomics to remove nothing.  The four floats of an x-pair (two rows that share a 64-B line 7 times out
-            // of 8) leave from four ADJACENT lanes of one instruction -- one memory-side request per pair: instruction k serves the
-            // pairs of lanes 16 k .. 16 k + 15, lane l carrying float (l & 3) of pair 16 k + (l >> 2).
-            const uint32_t lane = threadIdx.x & 63u, f = lane & 3u;
-#pragma unroll
-            for (uint32_t k = 0; k < 4; k++) {
-                const int src = (int)(16u * k + (lane >> 2));
-                const uint32_t r0 = (uint32_t)__shfl((int)row0, src, 64), r1 = (uint32_t)__shfl((int)row1, src, 64);
-                const float a0 = __shfl(v[0], src, 64), a1 = __shfl(v[1], src, 64), a2 = __shfl(v[2], src, 64), a3 = __shfl(v[3], src, 64);
-                const uint32_t row = f < 2u ? r0 : r1;
-                const float val = f == 0u ? a0 : (f == 1u ? a1 : (f == 2u ? a2 : a3));
-                if (row != kScEmpty && val != 0.0f) atomicAdd(gg + (size_t)row * 2 + (f & 1u), val);
-            }
-            return;
-        }
-        if (merge_runs4(row0, row1, v)) {
-            const uint32_t rows[2] = {row0, row1};
-#pragma unroll
-            for (int e = 0; e < 2; e++) {
-                const uint32_t line = rows[e] >> 3, sub = rows[e] & 7u;
-                uint32_t slot = (line * 2654435761u) >> (32u - kScSlotBits);
-                bool placed = false;
-                for (uint32_t probe = 0; probe < kScProbes; probe++) {
-                    const uint32_t prev = atomicCAS(&keys[slot], kScEmpty, line);
-                    if (prev == kScEmpty) atomicAdd(occupied, 1u);
-                    if (prev == kScEmpty || prev == line) { placed = true; break; }
-                    slot = (slot + 1u) & (kScSlots - 1u);
-                }
-                if (placed) {
-                    atomicAdd(&vals[slot * 16 + sub * 2], v[2 * e]);
-                    atomicAdd(&vals[slot * 16 + sub * 2 + 1], v[2 * e + 1]);
-                } else {   // table full around this line (never with 2-D grids): straight to memory
-                    atomicAdd(gg + (size_t)rows[e] * 2, v[2 * e]);
-                    atomicAdd(gg + (size_t)rows[e] * 2 + 1, v[2 * e + 1]);
-                }
-            }
-        }
-    }
-    // flush when the table is filling up (spread-out samples: every chunk; clustered ones: rarely) or after the last chunk.
-    // 16 adjacent lanes = the 16 floats of one 64-B line of the gradient table: one memory-side request per touched line
-    __syncthreads();
-    const bool last = chunk + 1 == chunks || (block_x * chunks + chunk + 1) * kScSamples >= M;
-    if (last || *occupied > kScSlots / 2 - kScSlots / 8) {
-        for (uint32_t i = threadIdx.x; i < kScSlots * 16; i += kScThreads) {
-            const uint32_t line = keys[i >> 4];
-            if (line != kScEmpty) {
-                const float v = vals[i];
-                if (v != 0.0f) atomicAdd(gg + (size_t)line * 16 + (i & 15u), v);
-                if (!last) {                                    // leave an empty table for the next chunk
-                    vals[i] = 0.0f;
-                    if ((i & 15u) == 15u) keys[i >> 4] = kScEmpty;   // the 16 lanes of the slot have read the key above
-                }
-            }
-        }
-        if (last) return;
-        __syncthreads();
-        if (threadIdx.x == 0) *occupied = 0u;
-        __syncthreads();
-    }
-  }
-}
-
-
-// One launch for the levels of up to two grids that are not binned (the 3-D grid's and the 2-D grid's)
-template <uint32_t D0, uint32_t D1>
-__global__ void __launch_bounds__(kScThreads) k_grid_scatter(ScatterJob j0, ScatterJob j1, uint32_t n_jobs, uint32_t Mcap,
-                                                             const int32_t *__restrict__ m_dev) {
-    __shared__ uint32_t keys[kScSlots];
-    __shared__ __attribute__((aligned(16))) float vals[kScSlots * 16];
-    const uint32_t M = live_count(Mcap, m_dev);
-    // two jobs: their workgroups ALTERNATE along x, so that the two grids' work is resident together -- one grid's levels are bound
-    // by memory-side atomic requests, the other's by LDS atomics
-    __shared__ uint32_t occupied;
-    if (n_jobs == 1) scatter_lines<D0>(j0, Mcap, M, keys, vals, &occupied, blockIdx.x);
-    else if ((blockIdx.x & 1u) == 0) scatter_lines<D0>(j0, Mcap, M, keys, vals, &occupied, blockIdx.x >> 1);
-    else scatter_lines<D1>(j1, Mcap, M, keys, vals, &occupied, blockIdx.x >> 1);
-}
-
-// Binned levels.  A level whose gradient table is much larger than what one workgroup's samples touch (the hashed levels of the
-// T = 2^19 table: 65 536 lines each, touched ~5 times per launch, never twice by the same workgroup) gains nothing from a
-// per-workgroup merge: every (sample, corner) is a memory-side atomic request of its own line.  Those levels are summed by TABLE
-// REGION instead: pass A (k_grid_bin) appends (row, w g0, w g1) entries to the bucket that owns the row -- a bucket = 2^shift
-// consecutive rows of one level -- and pass B (k_grid_scatter_buckets) has one workgroup per bucket add the bucket's entries in
-// LDS and update the region with plain coalesced loads and stores: no global float atomic at all on those levels.  A workgroup
-// of pass A reserves room in the buckets with one returning atomic per bucket (LDS histogram of its 256 samples x 2^D corners).
-constexpr uint32_t kMaxBucketsPerLevel = 128;
-struct BinPlan {
-    uint32_t n_levels, level_of[kMaxLevels];   // the binned levels
-    uint32_t bucket0[kMaxLevels];     // first bucket of level_of[i]
-    uint32_t n_buckets[kMaxLevels];
-    uint32_t shift, cap;              // rows per bucket = 1 << shift; entries a bucket has room for
-    uint32_t *cursor;                 // [total buckets] entries appended (zero before pass A; pass B leaves it zero)
-    uint32_t *e_row;                  // [total buckets][cap] level-local row
-    float2 *e_val;                    // [total buckets][cap]
-    // Entries that find their bucket full go to ONE spill list with room for every entry of a launch (it cannot overflow); each
-    // pass-B workgroup picks its own out of it.  Hashed rows load the buckets evenly, so the list stays empty unless many samples
-    // coincide -- correctness does not depend on the bucket size, only speed does.
-    uint32_t *spill_count;            // [2]: entries spilled | pass-B workgroups that have read it (the last one resets both)
-    uint32_t *spill_key;              // [spill capacity] bucket << 16 | bucket-local row (rows per bucket <= 2^13)
-    float2 *spill_val;
-};
-constexpr uint32_t kBinThreads = 256;
-
-template <uint32_t D>
-__global__ void __launch_bounds__(kBinThreads) k_grid_bin(ScatterJob j, uint32_t Mcap, const int32_t *__restrict__ m_dev, BinPlan bp) {
-    constexpr uint32_t NC = 1u << D;
-    __shared__ uint32_t hist[kMaxBucketsPerLevel], base[kMaxBucketsPerLevel];
-    const uint32_t M = live_count(Mcap, m_dev);
-    if (blockIdx.x * kBinThreads >= M) return;
-    const uint32_t li = blockIdx.y, level = bp.level_of[li];
-    if (threadIdx.x < kMaxBucketsPerLevel) hist[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t off = (uint32_t)j.offsets[level];
-    const uint32_t hashmap_size = (uint32_t)j.offsets[level + 1] - off;
-    const uint32_t b = blockIdx.x * kBinThreads + threadIdx.x;      // one sample per thread, all 2^D corners
-    float in[D];
-    bool live = b < M;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        in[d] = live ? j.inputs[(size_t)b * D + d] : 0.0f;
-        live = live && !(in[d] < 0 || in[d] > 1);
-    }
-    float pos[D], pos_deriv[D];
-    uint32_t pos_grid[D];
-    lattice_pos<D>(in, j.lc.scale[level], false, 0, pos, pos_deriv, pos_grid);
-    float2 g = make_float2(0.0f, 0.0f);
-    if (live) g = *reinterpret_cast<const float2 *>(j.grad + ((size_t)level * Mcap + b) * 2);
-    const uint32_t resolution = j.lc.resolution[level];
-    uint32_t rows[NC], rank[NC];
-    float w[NC];
-#pragma unroll
-    for (uint32_t idx = 0; idx < NC; idx++) {
-        float wt = 1;                                 // gridencoder.cu:298-308: x term first
-        uint32_t pgl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            const bool hi = (idx >> d) & 1u;
-            wt *= hi ? pos[d] : 1 - pos[d];
-            pgl[d] = pos_grid[d] + (hi ? 1u : 0u);
-        }
-        w[idx] = wt;
-        rows[idx] = live ? grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl) : 0u;
-        rank[idx] = live ? atomicAdd(&hist[rows[idx] >> bp.shift], 1u) : 0u;
-    }
-    __syncthreads();
-    if (threadIdx.x < bp.n_buckets[li]) {
-        const uint32_t n = hist[threadIdx.x];
-        base[threadIdx.x] = n ? atomicAdd(&bp.cursor[bp.bucket0[li] + threadIdx.x], n) : 0u;
-    }
-    __syncthreads();
-    if (!live) return;
-    uint32_t full = 0;                                  // corners whose bucket had no room left (normally none)
-#pragma unroll
-    for (uint32_t idx = 0; idx < NC; idx++) {
-        const uint32_t b_ = rows[idx] >> bp.shift, at = base[b_] + rank[idx];
-        if (at < bp.cap) {
-            const size_t slot = (size_t)(bp.bucket0[li] + b_) * bp.cap + at;
-            bp.e_row[slot] = rows[idx];
-            bp.e_val[slot] = make_float2(w[idx] * g.x, w[idx] * g.y);
-        } else {
-            full |= 1u << idx;
-        }
-    }
-    if (full) {                                         // the spill list (sized for every entry of the launch)
-#pragma unroll
-        for (uint32_t idx = 0; idx < NC; idx++) {
-            if (full & (1u << idx)) {
-                const uint32_t sp = atomicAdd(&bp.spill_count[0], 1u);
-                bp.spill_key[sp] = ((bp.bucket0[li] + (rows[idx] >> bp.shift)) << 16) | (rows[idx] & ((1u << bp.shift) - 1u));
-                bp.spill_val[sp] = make_float2(w[idx] * g.x, w[idx] * g.y);
-            }
-        }
-    }
-}
-
-// Pass B: one workgroup per bucket.  acc[rows of the bucket][2] in LDS (32 KB for 4096 rows), the bucket's entries (and its share
-// of the spill list, normally empty) added with LDS atomics from all lanes, then the region WRITTEN with plain 16-byte stores:
-// every row of a binned level is written by exactly one workgroup, so those levels need neither a memset nor a global atomic.
-constexpr uint32_t kBkThreads = 512;
-__global__ void __launch_bounds__(kBkThreads) k_grid_scatter_buckets(const int32_t *__restrict__ offsets, float *__restrict__ grad_grid,
-                                                                     BinPlan bp, uint32_t total_buckets) {
-    extern __shared__ __attribute__((aligned(16))) float acc[];
-    __shared__ uint32_t n_sh, spill_sh;
-    const uint32_t b = blockIdx.x;
-    if (b >= total_buckets) return;
-    uint32_t li = 0;
-    for (uint32_t i = 0; i < bp.n_levels; i++)
-        if (b >= bp.bucket0[i] && b < bp.bucket0[i] + bp.n_buckets[i]) li = i;
-    const uint32_t level = bp.level_of[li];
-    const uint32_t rows_pb = 1u << bp.shift, local = b - bp.bucket0[li];
-    const uint32_t off = (uint32_t)offsets[level], rows_level = (uint32_t)offsets[level + 1] - off;
-    const uint32_t row_first = local << bp.shift;
-    const uint32_t n_rows = rows_level - row_first < rows_pb ? rows_level - row_first : rows_pb;
-    if (threadIdx.x == 0) {
-        const uint32_t n = bp.cursor[b];
-        n_sh = n < bp.cap ? n : bp.cap;
-        bp.cursor[b] = 0u;                     // ready for the next launch of pass A
-        spill_sh = __hip_atomic_load(&bp.spill_count[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    for (uint32_t i = threadIdx.x; i < rows_pb * 2; i += kBkThreads) acc[i] = 0.0f;
-    __syncthreads();
-    const uint32_t n = n_sh, n_spill = spill_sh;
-    const uint32_t *er = bp.e_row + (size_t)b * bp.cap;
-    const float2 *ev = bp.e_val + (size_t)b * bp.cap;
-    // eight entries per thread in flight: the loads of a batch are issued together, then added (a load-add-load-add chain would
-    // pay the memory latency once per entry)
-    for (uint32_t i0 = 0; i0 < n; i0 += kBkThreads * 8) {
-        uint32_t r[8];
-        float2 v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const uint32_t i = i0 + u * kBkThreads + threadIdx.x;
-            const uint32_t ic = i < n ? i : n - 1u;
-            r[u] = er[ic] & (rows_pb - 1u);
-            v[u] = ev[ic];
-            if (i >= n) v[u] = make_float2(0.0f, 0.0f);
-        }
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            if (v[u].x != 0.0f) atomicAdd(&acc[2 * r[u]], v[u].x);
-            if (v[u].y != 0.0f) atomicAdd(&acc[2 * r[u] + 1], v[u].y);
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < n_spill; i += kBkThreads) {     // normally n_spill == 0
-        const uint32_t key = bp.spill_key[i];
-        if ((key >> 16) == b) {
-            const float2 v = bp.spill_val[i];
-            atomicAdd(&acc[2 * (key & 0xffffu)], v.x);
-            atomicAdd(&acc[2 * (key & 0xffffu) + 1], v.y);
-        }
-    }
-    __syncthreads();
-    float4 *dst = reinterpret_cast<float4 *>(grad_grid + ((size_t)off + row_first) * 2);   // rows are 8 B, regions start on 64-B lines
-    const float4 *src = reinterpret_cast<const float4 *>(acc);
-    for (uint32_t i = threadIdx.x; i < n_rows / 2; i += kBkThreads) dst[i] = src[i];
-    // the last workgroup to have read the spill list empties it for the next launch
-    if (threadIdx.x == 0) {
-        const uint32_t done = atomicAdd(&bp.spill_count[1], 1u) + 1u;
-        if (done == total_buckets) {
-            __hip_atomic_store(&bp.spill_count[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(&bp.spill_count[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
-
 // ---- loss on the composited rays -----------------------------------------------------------------------------------------
 constexpr int kLossThreads = 1024;
 __global__ void __launch_bounds__(kLossThreads) k_train_head_loss(const float *__restrict__ image, const float *__restrict__ ws,
@@ -1242,16 +779,6 @@ __global__ void __launch_bounds__(256) k_batch_gather(const float *__restrict__ 
     out[a.out0[sec] + r * a.width[sec] + (c - a.col0[sec])] = table[(size_t)idx[r] * a.row_floats + c];
 }
 
-static int num_cus() {
-    static int n = 0;
-    if (!n) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        hipDeviceProp_t prop;
-        n = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return n;
-}
 constexpr uint32_t kWPartsMax = 256;
 static uint32_t wparts() {   // workgroups (= partial sums) per weight-gradient job
     static uint32_t n = 0;
@@ -1261,9 +788,6 @@ static uint32_t wparts() {   // workgroups (= partial sums) per weight-gradient 
         n = (uint32_t)(v < 1 ? 1 : (v > (long)kWPartsMax ? (long)kWPartsMax : v));
     }
     return n;
-}
-static RawW raw_w(const rn_nerf_weights_t *w) {
-    return RawW{w->amb_w0, w->amb_w1, w->amb_w2, w->sig_w0, w->sig_w1, w->sig_w2, w->col_w0, w->col_w1, w->audio_dim, w->has_eye, w->ind_dim};
 }
 static int check_w(const rn_nerf_weights_t *w) {
     RN_REQUIRE(w && w->amb_w0 && w->amb_w1 && w->amb_w2 && w->sig_w0 && w->sig_w1 && w->sig_w2 && w->col_w0 && w->col_w1,
@@ -1275,9 +799,6 @@ static int check_grid(const rn_grid_t *g, uint32_t D, const char *name) {
     RN_REQUIRE(g && g->embeddings && g->offsets, "train_head: %s grid is null", name);
     RN_REQUIRE(g->D == D && g->L == 16 && g->dtype == RN_F32, "train_head: %s grid must be D=%u, L=16, fp32 with C=2", name, D);
     return RN_OK;
-}
-static GridArgs grid_args(const rn_grid_t *g) {
-    return GridArgs{g->embeddings, g->offsets, make_level_consts(g->L, g->S, g->H), g->gridtype};
 }
 
 }  // namespace th
@@ -1398,199 +919,7 @@ int rn_train_head_weight_grads_row(const rn_nerf_weights_t *w, const float *enc_
 
 }  // extern "C"
 
-namespace rn {
-namespace th {
-
-// Which levels are binned: the HASHED ones with at least kMinBuckets buckets of 2^shift rows.  A hash spreads the rows evenly
-// over the buckets whatever the samples' positions, so a bucket's load is known in advance (2x the mean + slack is never
-// reached) and pass B has hundreds of equal workgroups.  Dense and tiled levels keep the per-workgroup line merge: their rows
-// follow the samples' positions (the ambient coordinates of a call cluster in a few cells), which is where neighbouring samples
-// share lines and where a fixed bucket size would overflow.
-constexpr uint32_t kMinBuckets = 16;
-static uint32_t bucket_shift() {
-    static uint32_t sh = 0;
-    if (!sh) {
-        const char *e = getenv("RN_SCATTER_BUCKET_SHIFT");
-        const long v = e ? atol(e) : 12;           // 4096 rows = 32 KB of LDS per bucket: four pass-B workgroups per CU
-        sh = (uint32_t)(v < 10 ? 10 : (v > 13 ? 13 : v));
-    }
-    return sh;
-}
-static uint32_t plan_bins(const rn_grid_t *grid, const int32_t *offsets_host, uint32_t M, BinPlan &bp, bool *binned /* [L] */) {
-    bp = BinPlan{};
-    bp.shift = bucket_shift();
-    const LevelConsts lc = make_level_consts(grid->L, grid->S, grid->H);
-    uint32_t total = 0, min_b = kMaxBucketsPerLevel;
-    for (uint32_t l = 0; l < grid->L; l++) {
-        const uint32_t rows = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
-        uint64_t stride = 1;                                      // gridencoder.cu:66-84: hashed when the dense index does not fit
-        for (uint32_t d = 0; d < grid->D; d++)
-            if (stride <= rows) stride *= (uint64_t)lc.resolution[l] + 1u;
-        const bool hashed = grid->gridtype == 0 && stride > rows;
-        const uint32_t nb = (rows + (1u << bp.shift) - 1u) >> bp.shift;
-        const bool bin = hashed && nb >= kMinBuckets && nb <= kMaxBucketsPerLevel;
-        if (binned) binned[l] = bin;
-        if (bin) {
-            bp.level_of[bp.n_levels] = l;
-            bp.bucket0[bp.n_levels] = total;
-            bp.n_buckets[bp.n_levels] = nb;
-            bp.n_levels++;
-            total += nb;
-            if (nb < min_b) min_b = nb;
-        }
-    }
-    bp.cap = total ? (uint32_t)(2u * (((uint64_t)M << grid->D) / min_b) + 2048u) : 0u;   // 2 x the mean load of a bucket + slack
-    return total;
-}
-static bool scatter_direct_enabled() {
-    static int on = -1;
-    if (on < 0) { const char *e = getenv("RN_SCATTER_DIRECT"); on = e ? atoi(e) : 1; }
-    return on != 0;
-}
-static uint32_t scatter_chunks() {
-    static int n = 0;
-    if (!n) { const char *e = getenv("RN_SCATTER_CHUNKS"); n = e ? atoi(e) : 8; if (n < 1) n = 1; if (n > 16) n = 16; }
-    return (uint32_t)n;
-}
-static ScatterJob make_job(const rn_scatter_job_t &j) {
-    ScatterJob s{};
-    s.grad = j.grad;
-    s.inputs = j.inputs;
-    s.offsets = j.grid->offsets;
-    s.grad_grid = j.grad_table;
-    s.lc = make_level_consts(j.grid->L, j.grid->S, j.grid->H);
-    s.gridtype = j.grid->gridtype;
-    return s;
-}
-template <uint32_t D0>
-static void launch_lines(uint32_t D1, dim3 g, hipStream_t s, const ScatterJob &a, const ScatterJob &b, uint32_t n_jobs, uint32_t M,
-                         const int32_t *m_dev) {
-    if (D1 == 3) hipLaunchKernelGGL((k_grid_scatter<D0, 3>), g, dim3(kScThreads), 0, s, a, b, n_jobs, M, m_dev);
-    else hipLaunchKernelGGL((k_grid_scatter<D0, 2>), g, dim3(kScThreads), 0, s, a, b, n_jobs, M, m_dev);
-}
-
-}  // namespace th
-}  // namespace rn
-
-using namespace rn;
-using namespace rn::th;
-
 extern "C" {
-
-size_t rn_grid_scatter_workspace(uint32_t M, const rn_grid_t *grid, const int32_t *offsets_host) {
-    if (!grid || !offsets_host || grid->L > kMaxLevels) return 0;
-    BinPlan bp;
-    const uint32_t total = plan_bins(grid, offsets_host, M, bp, nullptr);
-    if (!total) return 256;
-    const size_t spill = ((size_t)M << grid->D) * bp.n_levels;        // every entry of a launch fits the spill list
-    return (((size_t)(total + 2) * sizeof(uint32_t) + 255u) & ~(size_t)255u) + ((size_t)total * bp.cap + spill) * (sizeof(uint32_t) + sizeof(float2)) + 256;
-}
-
-uint32_t rn_grid_scatter_binned_levels(const rn_grid_t *grid, const int32_t *offsets_host) {
-    if (!grid || !offsets_host || grid->L > kMaxLevels) return 0;
-    BinPlan bp;
-    bool binned[kMaxLevels] = {};
-    (void)plan_bins(grid, offsets_host, 1, bp, binned);
-    uint32_t mask = 0;
-    for (uint32_t l = 0; l < grid->L; l++) mask |= binned[l] ? (1u << l) : 0u;
-    return mask;
-}
-
-int rn_grid_scatter_jobs(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t M, const int32_t *m_dev, void *workspace,
-                         size_t workspace_bytes, rn_stream_t stream) {
-    if (M == 0) return RN_OK;
-    RN_REQUIRE(jobs && (n_jobs == 1 || n_jobs == 2), "grid_scatter_jobs: one or two jobs");
-    for (uint32_t i = 0; i < n_jobs; i++) {
-        const rn_scatter_job_t &j = jobs[i];
-        RN_REQUIRE(j.grad && j.inputs && j.grid && j.grid->offsets && j.grad_table, "grid_scatter_jobs: null pointer in job %u", i);
-        RN_REQUIRE((j.grid->D == 2 || j.grid->D == 3) && j.grid->L >= 1 && j.grid->L <= kMaxLevels, "grid_scatter_jobs: D must be 2 or 3, L <= 32");
-        RN_REQUIRE(((uintptr_t)j.grad_table & 63u) == 0 && ((uintptr_t)j.grad & 7u) == 0, "grid_scatter_jobs: grad_table must be 64-byte, grad 8-byte aligned");
-    }
-    hipStream_t s = as_stream(stream);
-    ScatterJob sj[2] = {make_job(jobs[0]), n_jobs == 2 ? make_job(jobs[1]) : ScatterJob{}};
-    // job 0 may have binned levels (needs the host copy of its offsets and the workspace)
-    bool binned[kMaxLevels] = {};
-    BinPlan bp{};
-    uint32_t total = 0;
-    if (jobs[0].offsets_host && workspace && workspace_bytes > 256) {
-        total = plan_bins(jobs[0].grid, jobs[0].offsets_host, M, bp, binned);
-        if (total) {
-            RN_REQUIRE(((uintptr_t)workspace & 255u) == 0 && workspace_bytes >= rn_grid_scatter_workspace(M, jobs[0].grid, jobs[0].offsets_host),
-                       "grid_scatter_jobs: workspace too small / not 256-byte aligned");
-            // workspace = cursors (zeroed once by the caller; pass B leaves them zero) | values | rows
-            char *w = static_cast<char *>(workspace);
-            const size_t spill = ((size_t)M << jobs[0].grid->D) * bp.n_levels;
-            bp.cursor = reinterpret_cast<uint32_t *>(w);
-            bp.spill_count = bp.cursor + total;
-            size_t at = ((size_t)(total + 2) * sizeof(uint32_t) + 255u) & ~(size_t)255u;
-            bp.e_val = reinterpret_cast<float2 *>(w + at);
-            at += (size_t)total * bp.cap * sizeof(float2);
-            bp.spill_val = reinterpret_cast<float2 *>(w + at);
-            at += spill * sizeof(float2);
-            bp.e_row = reinterpret_cast<uint32_t *>(w + at);
-            at += (size_t)total * bp.cap * sizeof(uint32_t);
-            bp.spill_key = reinterpret_cast<uint32_t *>(w + at);
-        }
-    }
-    uint32_t max_levels = 0, max_blocks = 0;
-    for (uint32_t i = 0; i < n_jobs; i++) {
-        const rn_grid_t *gr = jobs[i].grid;
-        const LevelConsts lc = make_level_consts(gr->L, gr->S, gr->H);
-        for (uint32_t l = 0; l < gr->L; l++) {
-            if (i == 0 && total && binned[l]) continue;
-            // hashed (gridencoder.cu:66-84) AND large (>= 2^17 rows: a workgroup's 64 samples x 8 corners land on distinct
-            // lines): straight to memory.  Needs a host view of the level sizes: jobs[i].offsets_host (else: line merge)
-            bool direct = false;
-            if (jobs[i].offsets_host && scatter_direct_enabled()) {
-                const uint32_t rows = (uint32_t)(jobs[i].offsets_host[l + 1] - jobs[i].offsets_host[l]);
-                uint64_t stride = 1;
-                for (uint32_t d = 0; d < gr->D; d++)
-                    if (stride <= rows) stride *= (uint64_t)lc.resolution[l] + 1u;
-                direct = gr->gridtype == 0 && stride > rows && rows >= (1u << 17);
-            }
-            if (direct) sj[i].direct_mask |= 1u << sj[i].n_levels;
-            uint32_t chunks = 1;
-            if (!direct && jobs[i].offsets_host) {
-                const uint32_t rows = (uint32_t)(jobs[i].offsets_host[l + 1] - jobs[i].offsets_host[l]);
-                chunks = rows <= (1u << 16) ? scatter_chunks() : 1u;
-            }
-            sj[i].chunks_of[sj[i].n_levels] = chunks;
-            sj[i].level_of[sj[i].n_levels++] = l;
-        }
-        if (sj[i].n_levels > max_levels) max_levels = sj[i].n_levels;
-        const uint32_t blocks = div_up(M, kScThreads >> (jobs[i].grid->D - 1));
-        if (blocks > max_blocks) max_blocks = blocks;
-    }
-    if (total) {
-        const dim3 gb(div_up(M, kBinThreads), bp.n_levels);
-        if (jobs[0].grid->D == 3) hipLaunchKernelGGL(k_grid_bin<3>, gb, dim3(kBinThreads), 0, s, sj[0], M, m_dev, bp);
-        else hipLaunchKernelGGL(k_grid_bin<2>, gb, dim3(kBinThreads), 0, s, sj[0], M, m_dev, bp);
-        const size_t shm = (size_t)2 * sizeof(float) << bp.shift;
-        if (shm > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_grid_scatter_buckets), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-        hipLaunchKernelGGL(k_grid_scatter_buckets, dim3(total), dim3(kBkThreads), shm, s, jobs[0].grid->offsets, jobs[0].grad_table, bp, total);
-    }
-    if (max_levels) {
-        const dim3 g(n_jobs == 2 ? 2 * max_blocks : max_blocks, max_levels);
-        const uint32_t D1 = n_jobs == 2 ? jobs[1].grid->D : 2u;
-        if (jobs[0].grid->D == 3) launch_lines<3>(D1, g, s, sj[0], sj[1], n_jobs, M, m_dev);
-        else launch_lines<2>(D1, g, s, sj[0], sj[1], n_jobs, M, m_dev);
-    }
-    return check_launch("grid_scatter_jobs");
-}
-
-int rn_grid_scatter_binned(const float *grad, const float *inputs, uint32_t M, const int32_t *m_dev, const rn_grid_t *grid,
-                           const int32_t *offsets_host, float *grad_table, void *workspace, size_t workspace_bytes, rn_stream_t stream) {
-    RN_REQUIRE(offsets_host && workspace, "grid_scatter_binned: null pointer");
-    const rn_scatter_job_t j{grad, inputs, grid, offsets_host, grad_table};
-    return rn_grid_scatter_jobs(&j, 1, M, m_dev, workspace, workspace_bytes, stream);
-}
-
-int rn_grid_scatter_lbc(const float *grad, const float *inputs, uint32_t M, const int32_t *m_dev, const rn_grid_t *grid,
-                        float *grad_table, rn_stream_t stream) {
-    const rn_scatter_job_t j{grad, inputs, grid, nullptr, grad_table};
-    return rn_grid_scatter_jobs(&j, 1, M, m_dev, nullptr, 0, stream);
-}
 
 int rn_train_batch_gather(const float *table, uint32_t row_floats, const int64_t *idx, uint32_t n, const uint32_t *widths,
                           uint32_t sections, float *out, rn_stream_t stream) {

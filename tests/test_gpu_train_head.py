@@ -1,4 +1,4 @@
-"""GPU parity of the fused training pass of the per-sample network (csrc/rn_train_head.hip, include/radnerf_train.h) against the
+"""GPU parity of the fused training pass of the per-sample network (csrc/rn_train_head.hip, csrc/rn_grid_scatter.hip, include/radnerf_train.h) against the
 per-operator path it replaces: NeRFNetwork.forward (nerf/network.py:222-283) over grid_encode / MLP / activation operators with
 torch.autograd, which tests/test_gpu_mlp_train.py, tests/test_gpu_ops.py and the reference-generated gradients of
 tests/test_golden_frames.py pin.  Also: the line-keyed table scatter against the operator's scatter, the one-kernel head loss
