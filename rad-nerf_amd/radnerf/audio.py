@@ -9,40 +9,9 @@ import ctypes as C
 import torch
 
 import radnerf_hip as hip
+from radnerf_hip.abi import AudioGradsT, AudioWeightsT
 
 _lib = hip._lib
-_ptr, _u32 = C.c_void_p, C.c_uint32
-
-
-class AudioWeightsT(C.Structure):
-    _fields_ = [("conv_w", _ptr * 4), ("conv_b", _ptr * 4), ("fc_w", _ptr * 2), ("fc_b", _ptr * 2),
-                ("att_conv_w", _ptr * 5), ("att_conv_b", _ptr * 5), ("att_fc_w", _ptr), ("att_fc_b", _ptr),
-                ("dim_in", _u32), ("dim_aud", _u32), ("has_att", _u32)]
-
-
-class AudioGradsT(C.Structure):
-    _fields_ = [("conv_w", _ptr * 4), ("conv_b", _ptr * 4), ("fc_w", _ptr * 2), ("fc_b", _ptr * 2),
-                ("att_conv_w", _ptr * 5), ("att_conv_b", _ptr * 5), ("att_fc_w", _ptr), ("att_fc_b", _ptr)]
-
-
-_SIGS = {
-    "rn_audio_encode_windows": [C.POINTER(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _ptr],
-    "rn_audio_encode_windows_backward": [C.POINTER(AudioWeightsT), _ptr, _u32, _ptr, _ptr, C.POINTER(AudioGradsT), _ptr, _ptr],
-    "rn_audio_encode_windows_train": [C.POINTER(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _ptr, _ptr],
-    "rn_audio_encode_windows_backward_acts": [C.POINTER(AudioWeightsT), _ptr, _u32, _ptr, _ptr, C.POINTER(AudioGradsT), _ptr, _ptr, _ptr],
-    "rn_audio_encode_stream": [C.POINTER(AudioWeightsT), _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr],
-    "rn_audio_smooth": [_ptr, _u32, _u32, C.c_float, _ptr, C.c_int, _ptr],
-    "rn_audio_smooth_seq": [_ptr, _u32, _u32, C.c_float, _ptr, C.c_int, _ptr, _ptr],
-}
-for _n, _a in _SIGS.items():
-    getattr(_lib, _n).argtypes = _a
-    getattr(_lib, _n).restype = C.c_int
-_lib.rn_audio_train_acts_floats.argtypes = [_u32, C.c_int]
-_lib.rn_audio_train_acts_floats.restype = C.c_size_t
-
-
-def exported_symbols():
-    return sorted(list(_SIGS) + ["rn_audio_train_acts_floats"])
 
 
 def supported(model):

@@ -21,82 +21,11 @@ import os
 import torch
 
 import radnerf_hip as hip
+from radnerf_hip.abi import (RN_F16, RN_F32, RN_F32_SPLIT, RN_HEAD_ST_HIST, RN_HEAD_ST_ITERS, RN_HEAD_ST_SLOTS, RN_HEAD_ST_STALLED,
+                             RN_HEAD_ST_UNFINISHED, RN_HEAD_STATE_INTS, RN_LOOP_CLOSE_FRAME, RN_LOOP_COOP, RN_LOOP_FIRST_MARCHED,
+                             GridT, HeadT, NerfWeightsT, TorsoWeightsT)
 
 _lib = hip._lib
-_u32, _f32, _i32, _ptr = C.c_uint32, C.c_float, C.c_int, C.c_void_p
-
-
-class GridT(C.Structure):
-    _fields_ = [("embeddings", _ptr), ("offsets", _ptr), ("D", _u32), ("L", _u32), ("H", _u32), ("S", _f32),
-                ("gridtype", _u32), ("dtype", _i32)]
-
-
-class NerfWeightsT(C.Structure):
-    _fields_ = [("amb_w0", _ptr), ("amb_w1", _ptr), ("amb_w2", _ptr), ("sig_w0", _ptr), ("sig_w1", _ptr),
-                ("sig_w2", _ptr), ("col_w0", _ptr), ("col_w1", _ptr), ("audio_dim", _u32), ("has_eye", _u32),
-                ("ind_dim", _u32)]
-
-
-class TorsoWeightsT(C.Structure):
-    _fields_ = [("def_w0", _ptr), ("def_w1", _ptr), ("def_w2", _ptr), ("tor_w0", _ptr), ("tor_w1", _ptr),
-                ("tor_w2", _ptr), ("ind_dim", _u32)]
-
-
-class HeadT(C.Structure):
-    _fields_ = [("rays_o", _ptr), ("rays_d", _ptr), ("N", _u32), ("aabb", _ptr), ("min_near", _f32),
-                ("bitfield", _ptr), ("bound", _f32), ("dt_gamma", _f32), ("max_steps", _u32), ("cascade", _u32),
-                ("grid_size", _u32), ("T_thresh", _f32), ("nears", _ptr), ("fars", _ptr), ("weights_sum", _ptr),
-                ("depth", _ptr), ("image", _ptr), ("rays_alive_a", _ptr), ("rays_alive_b", _ptr), ("rays_t", _ptr),
-                ("xyzs", _ptr), ("dirs", _ptr), ("deltas", _ptr), ("sigmas", _ptr), ("rgbs", _ptr), ("state", _ptr),
-                ("block_counts", _ptr), ("live_slots", _ptr), ("order_w", _u32)]
-
-
-RN_HEAD_STATE_INTS = 64
-ST_HIST = 32
-ST_UNFINISHED = 19
-ST_STALLED = 22
-ST_ACTIVE, ST_ITERS, ST_LIVE, ST_SLOTS = 4, 16, 17, 18
-
-_SIGS = {
-    "rn_nerf_pack_weights": [C.POINTER(NerfWeightsT), _ptr, _ptr],
-    "rn_nerf_pack_weights_h16": [C.POINTER(NerfWeightsT), _ptr, _ptr],
-    "rn_nerf_pack_weights_split": [C.POINTER(NerfWeightsT), _ptr, _ptr],
-    "rn_nerf_frame_bias": [C.POINTER(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_nerf_fused_forward": [_ptr, _ptr, _ptr, _u32, _ptr, C.POINTER(GridT), C.POINTER(GridT), _ptr, _ptr, _f32, _ptr,
-                              _ptr, _ptr, C.c_int, _ptr],
-    "rn_head_begin": [C.POINTER(HeadT), _ptr],
-    "rn_head_iterate": [C.POINTER(HeadT), C.POINTER(GridT), C.POINTER(GridT), _ptr, _ptr, _u32, _u32, C.c_int, _ptr],
-    "rn_head_iterate_ex": [C.POINTER(HeadT), C.POINTER(GridT), C.POINTER(GridT), _ptr, _ptr, _u32, _u32, C.c_int, _u32, _ptr],
-    "rn_frame_begin": [C.POINTER(HeadT), _ptr, _f32, _f32, _f32, _f32, _u32, _ptr],
-    "rn_torso_blend_frame": [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr, _f32, C.POINTER(TorsoWeightsT), _ptr, C.POINTER(GridT),
-                             _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_nerf_frame_bias_batch": [C.POINTER(NerfWeightsT), _ptr, _u32, _ptr, _ptr, _ptr, _ptr],
-    "rn_head_reschedule": [C.POINTER(HeadT), _u32, _u32, _ptr, _ptr],
-    "rn_head_check_done": [C.POINTER(HeadT), _u32, _ptr],
-    "rn_get_rays": [_ptr, _f32, _f32, _f32, _f32, _u32, _u32, _ptr, _ptr, _ptr],
-    "rn_get_bg_coords": [_u32, _u32, _ptr, _ptr],
-    "rn_convert_poses": [_ptr, _u32, _ptr, _ptr],
-    "rn_torso_pack_weights": [C.POINTER(TorsoWeightsT), _ptr, _ptr],
-    "rn_torso_fused": [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr, _f32, C.POINTER(TorsoWeightsT), _ptr, C.POINTER(GridT),
-                       _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_blend_frame": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr],
-}
-for _n, _a in _SIGS.items():
-    _f = getattr(_lib, _n)
-    _f.argtypes = _a
-    _f.restype = C.c_int
-_lib.rn_nerf_packed_floats.restype = C.c_size_t
-_lib.rn_nerf_packed_floats_h16.restype = C.c_size_t
-_lib.rn_nerf_packed_floats_split.restype = C.c_size_t
-RN_F32_SPLIT = 2
-RN_LOOP_FIRST_MARCHED, RN_LOOP_CLOSE_FRAME, RN_LOOP_COOP = 1, 2, 4
-_lib.rn_nerf_bias_floats.restype = C.c_size_t
-_lib.rn_torso_packed_floats.restype = C.c_size_t
-
-
-def exported_symbols():
-    return sorted(list(_SIGS) + ["rn_nerf_packed_floats", "rn_nerf_packed_floats_h16", "rn_nerf_packed_floats_split", "rn_nerf_bias_floats",
-                                 "rn_torso_packed_floats"])
 
 
 def _grid_desc(enc, table):
@@ -105,8 +34,20 @@ def _grid_desc(enc, table):
     g.D, g.L, g.H = enc.input_dim, enc.num_levels, enc.base_resolution
     g.S = float(np.log2(enc.per_level_scale))
     g.gridtype = enc.gridtype_id
-    g.dtype = hip.RN_F16 if table.dtype == torch.float16 else hip.RN_F32
+    g.dtype = RN_F16 if table.dtype == torch.float16 else RN_F32
     return g
+
+
+def head_weights(model):
+    """The eight nn.Linear weights of the per-sample MLPs, in the order of rn_nerf_weights_t."""
+    return [l.weight for l in model.ambient_net.net] + [l.weight for l in model.sigma_net.net] + [l.weight for l in model.color_net.net]
+
+
+def weights_desc(ws, audio_dim, has_eye, ind_dim):
+    nw = NerfWeightsT()
+    (nw.amb_w0, nw.amb_w1, nw.amb_w2, nw.sig_w0, nw.sig_w1, nw.sig_w2, nw.col_w0, nw.col_w1) = [w.data_ptr() for w in ws]
+    nw.audio_dim, nw.has_eye, nw.ind_dim = audio_dim, has_eye, ind_dim
+    return nw
 
 
 def supported(model):
@@ -139,7 +80,7 @@ class FusedState:
         n_packed = max(int(_lib.rn_nerf_packed_floats()), int(_lib.rn_nerf_packed_floats_h16()),
                        int(_lib.rn_nerf_packed_floats_split()))
         self.packed = torch.empty(n_packed, dtype=torch.float32, device=self.dev)
-        self.mlp_dtype = hip.RN_F32
+        self.mlp_dtype = RN_F32
         self.loop_hint = None
         self.bias = torch.empty(int(_lib.rn_nerf_bias_floats()), dtype=torch.float32, device=self.dev)
         self.tpacked = (torch.empty(int(_lib.rn_torso_packed_floats()), dtype=torch.float32, device=self.dev)
@@ -151,7 +92,7 @@ class FusedState:
     # -- weights --------------------------------------------------------------------------------------
     def _weights(self):
         m = self.model
-        ws = [l.weight for l in m.ambient_net.net] + [l.weight for l in m.sigma_net.net] + [l.weight for l in m.color_net.net]
+        ws = head_weights(m)
         if m.torso:
             ws += [l.weight for l in m.torso_deform_net.net] + [l.weight for l in m.torso_net.net]
         return ws
@@ -163,7 +104,7 @@ class FusedState:
             tables.append(self.model.torso_encoder.embeddings)
         # opt.mlp_dtype = "f16": contractions on the 16-bit matrix cores (fp32 accumulate), the reference's -O arithmetic
         # "f32x2": fp32-grade products from two fp16 halves per operand on the same matrix cores (include/radnerf_fused.h)
-        mlp = {"f32": hip.RN_F32, "f16": hip.RN_F16, "f32x2": RN_F32_SPLIT}[
+        mlp = {"f32": RN_F32, "f16": RN_F16, "f32x2": RN_F32_SPLIT}[
             getattr(getattr(self.model, "opt", None), "mlp_dtype", "f32")]
         # opt.half_tables (load_checkpoint(half_tables=True) sets it): the kernels read persistent fp16 copies of the grid tables
         # (GridEncoder.half_table, re-cast only when the parameter changes) -- the reference's -O mode casts every table on every
@@ -176,14 +117,11 @@ class FusedState:
         for w in ws:
             if w.dtype != torch.float32 or not w.is_contiguous():
                 raise RuntimeError("fused engine: MLP weights must be contiguous float32")
-        self.nw = NerfWeightsT()
-        (self.nw.amb_w0, self.nw.amb_w1, self.nw.amb_w2, self.nw.sig_w0, self.nw.sig_w1, self.nw.sig_w2, self.nw.col_w0,
-         self.nw.col_w1) = [w.data_ptr() for w in ws[:8]]
-        self.nw.audio_dim, self.nw.has_eye, self.nw.ind_dim = m.audio_dim, int(m.exp_eye), m.individual_dim
+        self.nw = weights_desc(ws[:8], m.audio_dim, int(m.exp_eye), m.individual_dim)
         assert tuple(ws[0].shape) == (64, 32 + m.audio_dim) and tuple(ws[3].shape) == (64, 64 + int(m.exp_eye))
         assert tuple(ws[5].shape) == (65, 64) and tuple(ws[6].shape) == (64, 80 + m.individual_dim)
         self.mlp_dtype = mlp
-        packer = {hip.RN_F32: "rn_nerf_pack_weights", hip.RN_F16: "rn_nerf_pack_weights_h16",
+        packer = {RN_F32: "rn_nerf_pack_weights", RN_F16: "rn_nerf_pack_weights_h16",
                   RN_F32_SPLIT: "rn_nerf_pack_weights_split"}[mlp]
         hip.call(packer, C.byref(self.nw), hip.ptr(self.packed), hip.stream())
         if m.torso:
@@ -234,7 +172,7 @@ class LoopStats(dict):
     def _load(self):
         if not self._loaded:
             st = self._st
-            cur = st.state[ST_ITERS:ST_SLOTS + 1].cpu().tolist()
+            cur = st.state[RN_HEAD_ST_ITERS:RN_HEAD_ST_SLOTS + 1].cpu().tolist()
             prev = st.stats_prev
             st.stats_prev = cur
             super().update(iterations=(cur[0] - prev[0]) & 0xFFFFFFFF, live_samples=(cur[1] - prev[1]) & 0xFFFFFFFF,
@@ -300,7 +238,7 @@ def loop_counters(model):
         return None
     tot = [0, 0, 0]
     for st in states:
-        cur = st.state[ST_ITERS:ST_SLOTS + 1].cpu().tolist()
+        cur = st.state[RN_HEAD_ST_ITERS:RN_HEAD_ST_SLOTS + 1].cpu().tolist()
         tot = [(a + b) & 0xFFFFFFFF for a, b in zip(tot, cur)]
     return tot
 
@@ -309,18 +247,18 @@ def loop_history(model, n):
     """Device view of the live-ray count entering each of the first n loop iterations of the frame just enqueued (0 once the
     loop is over); see RN_HEAD_ST_HIST."""
     st = _state(model)
-    return st.state[ST_HIST:ST_HIST + n]
+    return st.state[RN_HEAD_ST_HIST:RN_HEAD_ST_HIST + n]
 
 
 def unfinished_frames(model):
     """Frames (cumulative) whose loop was cut short by a speculative iteration count (set_loop_hint); synchronises."""
-    return sum(int(st.state[ST_UNFINISHED].item()) for st in _all_states(model))
+    return sum(int(st.state[RN_HEAD_ST_UNFINISHED].item()) for st in _all_states(model))
 
 
 def stalled_workgroups(model):
     """Workgroups (cumulative) that gave up at the in-launch barrier of the one-launch loop step (RN_LOOP_COOP); must be 0 --
     a frame rendered while this moved is invalid.  Synchronises."""
-    return sum(int(st.state[ST_STALLED].item()) for st in _all_states(model))
+    return sum(int(st.state[RN_HEAD_ST_STALLED].item()) for st in _all_states(model))
 
 
 def loop_flags(model):
@@ -357,16 +295,30 @@ def _state(model):
     return st
 
 
+def _frame_bias(st, enc_a, eye, ind_code, batch=False):
+    """Fold the broadcast inputs (audio code, eye or the zero eye, individual code or NULL) into the first-layer biases:
+    rn_nerf_frame_bias into st.bias for one code, or -- batch -- rn_nerf_frame_bias_batch into a new [n, 192] block for the n
+    rows of enc_a [n, audio_dim]."""
+    eye_t = eye.reshape(-1).contiguous().float() if eye is not None else st._zero_eye
+    ind = ind_code.detach().reshape(-1).contiguous().float() if ind_code is not None else None
+    if batch:
+        codes = enc_a.contiguous().float()
+        n = codes.shape[0]
+        out = torch.empty(n, st.bias.numel(), dtype=torch.float32, device=codes.device)
+        hip.call("rn_nerf_frame_bias_batch", C.byref(st.nw), hip.ptr(codes), n, hip.ptr(eye_t), hip.ptr(ind), hip.ptr(out), hip.stream())
+        return out
+    enc_a = enc_a.reshape(-1).contiguous().float()
+    hip.call("rn_nerf_frame_bias", C.byref(st.nw), hip.ptr(enc_a), hip.ptr(eye_t), hip.ptr(ind), hip.ptr(st.bias), hip.stream())
+    return st.bias
+
+
 def network_forward(model, xyzs, dirs, enc_a, ind_code, eye, deltas=None, want_ambient=True):
     """NeRFNetwork.forward through the fused kernel: (sigma [M], color [M,3], ambient [M,2])."""
     st = _state(model)
     st.refresh()
     xyzs, dirs = xyzs.contiguous().float(), dirs.contiguous().float()
     M = xyzs.shape[0]
-    enc_a = enc_a.reshape(-1).contiguous().float()
-    eye_t = eye.reshape(-1).contiguous().float() if eye is not None else st._zero_eye
-    ind = ind_code.detach().reshape(-1).contiguous().float() if ind_code is not None else None
-    hip.call("rn_nerf_frame_bias", C.byref(st.nw), hip.ptr(enc_a), hip.ptr(eye_t), hip.ptr(ind), hip.ptr(st.bias), hip.stream())
+    _frame_bias(st, enc_a, eye, ind_code)
     sigmas = torch.empty(M, dtype=torch.float32, device=xyzs.device)
     rgbs = torch.empty(M, 3, dtype=torch.float32, device=xyzs.device)
     ambient = torch.empty(M, 2, dtype=torch.float32, device=xyzs.device) if want_ambient else None
@@ -385,10 +337,7 @@ def density_forward(model, xyzs, enc_a, eye, out=None):
     st.refresh()
     xyzs = xyzs.contiguous().float()
     M = xyzs.shape[0]
-    enc_a = enc_a.reshape(-1).contiguous().float()
-    eye_t = eye.reshape(-1).contiguous().float() if eye is not None else st._zero_eye
-    ind = model.individual_codes[0].detach().reshape(-1).contiguous().float() if model.individual_dim > 0 else None
-    hip.call("rn_nerf_frame_bias", C.byref(st.nw), hip.ptr(enc_a), hip.ptr(eye_t), hip.ptr(ind), hip.ptr(st.bias), hip.stream())
+    _frame_bias(st, enc_a, eye, model.individual_codes[0] if model.individual_dim > 0 else None)
     sigmas = out if out is not None else torch.empty(M, dtype=torch.float32, device=xyzs.device)
     hip.call("rn_nerf_fused_forward", hip.ptr(xyzs), None, None, M, None, C.byref(st.gx), C.byref(st.gw), hip.ptr(st.packed),
              hip.ptr(st.bias), float(model.bound), hip.ptr(sigmas), None, None, st.mlp_dtype, hip.stream())
@@ -419,13 +368,7 @@ def frame_bias_batch(model, codes, eye, ind_code):
     """Per-frame bias blocks of n consecutive frames' audio codes [n, audio_dim] -> [n, 192] (one launch)."""
     st = _state(model)
     st.refresh()
-    codes = codes.contiguous().float()
-    n = codes.shape[0]
-    eye_t = eye.reshape(-1).contiguous().float() if eye is not None else st._zero_eye
-    ind = ind_code.detach().reshape(-1).contiguous().float() if ind_code is not None else None
-    out = torch.empty(n, int(_lib.rn_nerf_bias_floats()), dtype=torch.float32, device=codes.device)
-    hip.call("rn_nerf_frame_bias_batch", C.byref(st.nw), hip.ptr(codes), n, hip.ptr(eye_t), hip.ptr(ind), hip.ptr(out), hip.stream())
-    return out
+    return _frame_bias(st, codes, eye, ind_code, batch=True)
 
 
 def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, ind_code_torso, bg_color, dt_gamma,
@@ -444,11 +387,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
     s = hip.stream()
 
     if frame_bias is None:
-        enc_a = enc_a.reshape(-1).contiguous().float()
-        eye_t = eye.reshape(-1).contiguous().float() if eye is not None else st._zero_eye
-        ind = ind_code.detach().reshape(-1).contiguous().float() if ind_code is not None else None
-        hip.call("rn_nerf_frame_bias", C.byref(st.nw), hip.ptr(enc_a), hip.ptr(eye_t), hip.ptr(ind), hip.ptr(st.bias), s)
-        bias = st.bias
+        bias = _frame_bias(st, enc_a, eye, ind_code)
     else:
         bias = frame_bias.reshape(-1)
         assert bias.numel() == st.bias.numel() and bias.is_contiguous() and bias.dtype == torch.float32

@@ -5,32 +5,12 @@ forward (2 launches) and backward-data + weight gradients + their reduction (3 l
 three more kernels per layer; hidden activations are kept in the matrix-core register layout between the passes.
 Used by radnerf.network.MLP when the input is a CUDA fp32 matrix and gradients are on; shapes outside what the kernels
 are built for (supported()) keep the nn.Linear path."""
-import ctypes as C
 
 import torch
 
 import radnerf_hip as hip
 
 _lib = hip._lib
-_ptr, _u32 = C.c_void_p, C.c_uint32
-_SIGS = {
-    "rn_mlp64_pack": [_ptr, _u32, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr],
-    "rn_mlp64_forward": [_ptr, _u32, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr],
-    "rn_mlp64_backward": [_ptr, _u32, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_mlp64_weight_grads": [_ptr, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr],
-}
-for _n, _a in _SIGS.items():
-    getattr(_lib, _n).argtypes = _a
-    getattr(_lib, _n).restype = C.c_int
-for _n in ("rn_mlp64_image_floats", "rn_mlp64_tile_floats", "rn_mlp64_wgrad_workspace"):
-    getattr(_lib, _n).restype = C.c_size_t
-_lib.rn_mlp64_image_floats.argtypes = [_u32, _u32, _u32]
-_lib.rn_mlp64_tile_floats.argtypes = [_u32]
-_lib.rn_mlp64_wgrad_workspace.argtypes = [_u32]
-
-
-def exported_symbols():
-    return sorted(list(_SIGS) + ["rn_mlp64_image_floats", "rn_mlp64_tile_floats", "rn_mlp64_wgrad_workspace"])
 
 
 def supported(dim_in, dim_out, dim_hidden, num_layers):

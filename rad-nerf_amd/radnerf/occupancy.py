@@ -14,7 +14,6 @@ the probe-point buffer, of the sigma buffer and of `density_grid[c]` is the same
 `mean_density` / `mean_density_torso` stay in device memory; the renderer reads them lazily the first time Python needs the
 number (checkpoint, torso threshold of the next frame).
 """
-import ctypes as C
 import random
 
 import torch
@@ -22,26 +21,6 @@ import torch
 import radnerf_hip as hip
 
 _lib = hip._lib
-_u32, _f32, _ptr = C.c_uint32, C.c_float, C.c_void_p
-_SIGS = {
-    "rn_occupancy_points": [_u32, _u32, _f32, _ptr, _u32, _ptr, _ptr],
-    "rn_occupancy_update": [_ptr, _f32, _ptr, _u32, _u32, _f32, _f32, _ptr, _ptr, _ptr, _ptr],
-    "rn_mark_untrained_grid": [_ptr, _u32, _u32, C.c_double, C.c_double, C.c_double, C.c_double, _u32, _u32, _f32, _ptr, _ptr],
-    "rn_torso_grid_points": [_u32, _ptr, _u32, _ptr, _ptr],
-    "rn_torso_grid_update": [_ptr, _ptr, _u32, _f32, _ptr, _ptr],
-    "rn_torso_mask": [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr],
-}
-for _n, _a in _SIGS.items():
-    getattr(_lib, _n).argtypes = _a
-    getattr(_lib, _n).restype = C.c_int
-_lib.rn_occupancy_workspace.argtypes = [_u32, _u32]
-_lib.rn_occupancy_workspace.restype = C.c_size_t
-_lib.rn_hash_u01_bits.argtypes = [_u32, _u32]
-_lib.rn_hash_u01_bits.restype = _u32
-
-
-def exported_symbols():
-    return sorted(list(_SIGS) + ["rn_occupancy_workspace", "rn_hash_u01_bits"])
 
 
 class _Scratch:

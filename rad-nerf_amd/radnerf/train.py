@@ -40,17 +40,8 @@ class HipAdam:
                                 fused=None, decoupled_weight_decay=False)
 
     def __init__(self, params, betas=(0.9, 0.99), eps=1e-15):
-        import ctypes as C
         import radnerf_hip as hip
-        self._C, self._hip = C, hip
-
-        class AdamTensorT(C.Structure):
-            _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
-                        ("numel", C.c_uint32), ("lr", C.c_float)]
-        self._T = AdamTensorT
-        fn = hip._lib.rn_adam_step_lr
-        fn.argtypes = [C.POINTER(AdamTensorT), C.c_uint32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        fn.restype = C.c_int
+        self._hip = hip
         self.param_groups = []
         for g in params:
             g = dict(g)
@@ -121,7 +112,7 @@ class HipAdam:
                 st = self.state[p]
                 keep.append(grad)
                 entries.append((p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), float(g["lr"])))
-        arr = (self._T * max(len(entries), 1))()
+        arr = (self._hip.abi.AdamTensorT * max(len(entries), 1))()
         for i, e in enumerate(entries):
             arr[i].param, arr[i].grad, arr[i].exp_avg, arr[i].exp_avg_sq, arr[i].numel, arr[i].lr = e
         if groups != self._lr_groups:

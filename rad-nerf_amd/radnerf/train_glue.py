@@ -3,29 +3,11 @@
 The expressions are the reference's (nerf/network.py:266-276, nerf/renderer.py:216, nerf/utils.py:772-803); PyTorch evaluates
 each as 3 - 15 kernels per direction, which at 2 - 5 us apiece is a third of a 1.5 ms training step.  RN_TRAIN_GLUE=torch keeps
 the PyTorch expressions (the parity tests compare the two)."""
-import ctypes as C
 import os
 
 import torch
 
 import radnerf_hip as hip
-
-_lib = hip._lib
-_ptr, _u32 = C.c_void_p, C.c_uint32
-_SIGS = {
-    "rn_head_mid_forward": [_ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr],
-    "rn_head_mid_backward": [_ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr],
-    "rn_abs_sum2_forward": [_ptr, _u32, _ptr, _ptr],
-    "rn_abs_sum2_backward": [_ptr, _ptr, _u32, _ptr, _ptr],
-    "rn_train_loss": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr],
-}
-for _n, _a in _SIGS.items():
-    getattr(_lib, _n).argtypes = _a
-    getattr(_lib, _n).restype = C.c_int
-
-
-def exported_symbols():
-    return sorted(_SIGS)
 
 
 def enabled(*tensors):

@@ -14,51 +14,11 @@ import ctypes as C
 import torch
 
 import radnerf_hip as hip
+from radnerf_hip.abi import HeadGradsT, ScatterJobT
 
-from .fused import GridT, NerfWeightsT, _grid_desc
+from .fused import _grid_desc, head_weights, weights_desc
 
 _lib = hip._lib
-_ptr, _u32, _f32 = C.c_void_p, C.c_uint32, C.c_float
-
-
-class ScatterJobT(C.Structure):
-    _fields_ = [("grad", _ptr), ("inputs", _ptr), ("grid", C.POINTER(GridT)), ("offsets_host", _ptr), ("grad_table", _ptr)]
-
-
-class HeadGradsT(C.Structure):
-    _fields_ = [(n, _ptr) for n in ("amb_w0", "amb_w1", "amb_w2", "sig_w0", "sig_w1", "sig_w2", "col_w0", "col_w1", "enc_a", "eye", "ind_code")]
-
-
-_SIGS = {
-    "rn_train_head_pack": [C.POINTER(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_train_head_pack_row": [C.POINTER(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_train_head_weight_grads_row": [C.POINTER(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, C.POINTER(HeadGradsT), _ptr,
-                                       _ptr],
-    "rn_train_head_forward": [_ptr, _ptr, _u32, _ptr, C.POINTER(GridT), C.POINTER(GridT), _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
-                              _ptr, _ptr],
-    "rn_train_head_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_train_head_weight_grads": [C.POINTER(NerfWeightsT), _ptr, _ptr, _ptr, _u32, _ptr, _ptr, C.POINTER(HeadGradsT), _ptr, _ptr],
-    "rn_grid_scatter_lbc": [_ptr, _ptr, _u32, _ptr, C.POINTER(GridT), _ptr, _ptr],
-    "rn_train_head_loss": [_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_train_batch_gather": [_ptr, _u32, _ptr, _u32, C.POINTER(_u32), _u32, _ptr, _ptr],
-    "rn_grid_scatter_binned": [_ptr, _ptr, _u32, _ptr, C.POINTER(GridT), _ptr, _ptr, _ptr, C.c_size_t, _ptr],
-    "rn_grid_scatter_jobs": [C.POINTER(ScatterJobT), _u32, _u32, _ptr, _ptr, C.c_size_t, _ptr],
-}
-for _n, _a in _SIGS.items():
-    getattr(_lib, _n).argtypes = _a
-    getattr(_lib, _n).restype = C.c_int
-for _n in ("rn_train_head_image_floats", "rn_train_head_workspace_floats", "rn_train_head_wgrad_workspace"):
-    getattr(_lib, _n).restype = C.c_size_t
-_lib.rn_train_head_workspace_floats.argtypes = [_u32]
-_lib.rn_grid_scatter_workspace.restype = C.c_size_t
-_lib.rn_grid_scatter_workspace.argtypes = [_u32, C.POINTER(GridT), _ptr]
-_lib.rn_grid_scatter_binned_levels.restype = C.c_uint32
-_lib.rn_grid_scatter_binned_levels.argtypes = [C.POINTER(GridT), _ptr]
-
-
-def exported_symbols():
-    return sorted(list(_SIGS) + ["rn_train_head_image_floats", "rn_train_head_workspace_floats", "rn_train_head_wgrad_workspace",
-                                 "rn_grid_scatter_workspace", "rn_grid_scatter_binned_levels"])
 
 
 def supported(model):
@@ -66,17 +26,6 @@ def supported(model):
     from . import fused
     return (fused.supported(model) and model.encoder.embeddings.dtype == torch.float32 and model.encoder_ambient.embeddings.dtype == torch.float32
             and model.audio_dim > 0 and not model.train_camera)
-
-
-def _weights_of(model):
-    return [l.weight for l in model.ambient_net.net] + [l.weight for l in model.sigma_net.net] + [l.weight for l in model.color_net.net]
-
-
-def _weights_desc(ws, audio_dim, has_eye, ind_dim):
-    nw = NerfWeightsT()
-    (nw.amb_w0, nw.amb_w1, nw.amb_w2, nw.sig_w0, nw.sig_w1, nw.sig_w2, nw.col_w0, nw.col_w1) = [w.data_ptr() for w in ws]
-    nw.audio_dim, nw.has_eye, nw.ind_dim = audio_dim, has_eye, ind_dim
-    return nw
 
 
 class _HeadTrain(torch.autograd.Function):
@@ -100,7 +49,7 @@ class _HeadTrain(torch.autograd.Function):
         else:
             ind_c = ind_code.reshape(-1).contiguous().float() if ind_dim else None
         tx, tw = hip.aligned(table_x.detach(), 64), hip.aligned(table_w.detach(), 64)
-        nw = _weights_desc(ws, audio_dim, has_eye, ind_dim)
+        nw = weights_desc(ws, audio_dim, has_eye, ind_dim)
         gx, gw = _grid_desc(enc_x, tx), _grid_desc(enc_w, tw)
         s = hip.stream()
         image = torch.empty(int(_lib.rn_train_head_image_floats()), dtype=torch.float32, device=dev)
@@ -186,7 +135,7 @@ class _HeadTrain(torch.autograd.Function):
                     _PENDING.append((ev, g_tx.data_ptr(), g_tw.data_ptr()))
                 else:
                     joined = ev
-            nw = _weights_desc(ws, audio_dim, has_eye, ind_dim)
+            nw = weights_desc(ws, audio_dim, has_eye, ind_dim)
             hg = HeadGradsT()
             (hg.amb_w0, hg.amb_w1, hg.amb_w2, hg.sig_w0, hg.sig_w1, hg.sig_w2, hg.col_w0, hg.col_w1) = [g.data_ptr() for g in grads]
             hg.enc_a, hg.eye, hg.ind_code = g_enc_a.data_ptr(), hip.ptr(g_eye), hip.ptr(g_ind)
@@ -317,7 +266,7 @@ def grid_scatter(jobs, M, m_dev):
     for i, (grad, inputs, enc, gd, table) in enumerate(jobs):
         arr[i].grad, arr[i].inputs, arr[i].grid, arr[i].grad_table = hip.ptr(grad), hip.ptr(inputs), C.pointer(gd), hip.ptr(table)
         off = hip.host_offsets(enc.offsets)        # lets the library tell hashed levels (straight to memory) from dense ones
-        arr[i].offsets_host = C.cast(off, _ptr)
+        arr[i].offsets_host = C.cast(off, C.c_void_p)
         keep += [gd, off]
     ws, ws_bytes = None, 0
     if binning_active():
@@ -334,7 +283,7 @@ def grid_scatter(jobs, M, m_dev):
                     raise RuntimeError("grid_scatter: the bucket workspace must exist before a step is captured (take one eager step first)")
                 buf = _SCATTER_WS[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
             ws, ws_bytes = buf, buf.numel()
-            arr[0].offsets_host = C.cast(off_host, _ptr)
+            arr[0].offsets_host = C.cast(off_host, C.c_void_p)
     hip.call("rn_grid_scatter_jobs", arr, len(jobs), M, hip.ptr(m_dev), hip.ptr(ws), ws_bytes, s)
 
 
@@ -343,7 +292,7 @@ def head_forward(model, xyzs, dirs, enc_a, ind_code, eye, m_dev=None, ind_index=
     fused training kernels.  m_dev: optional int32 device scalar, the number of live sample rows (the marcher's counter).
     ind_index (int64 device tensor, one element) instead of ind_code: the code is model.individual_codes[ind_index], picked by the
     kernels; the gradient of individual_codes comes back whole from the backward pass (no index_select / memset / index_add)."""
-    ws = _weights_of(model)
+    ws = head_weights(model)
     ind = None
     if model.individual_dim > 0:
         ind = model.individual_codes if ind_index is not None else ind_code
@@ -435,7 +384,7 @@ def batch_gather(table, idx, widths):
     n, row = idx.shape[0], table.shape[1]
     assert sum(widths) == row and table.is_contiguous() and table.dtype == torch.float32 and idx.dtype == torch.int64
     flat = torch.empty(n * row, dtype=torch.float32, device=table.device)
-    w = (_u32 * len(widths))(*widths)
+    w = (C.c_uint32 * len(widths))(*widths)
     hip.call("rn_train_batch_gather", hip.ptr(table), row, hip.ptr(idx), n, w, len(widths), hip.ptr(flat), hip.stream())
     return flat, split_sections(flat, n, widths)
 

@@ -1,4 +1,4 @@
-"""ctypes binding of libradnerf_hip.so -- the C ABI declared in include/radnerf_hip.h.
+"""Loads libradnerf_hip.so and declares its C ABI (include/*.h) on it, once, from the table in radnerf_hip/abi.py.
 
 PyTorch is only plumbing here: it owns device memory and the current HIP stream; every kernel
 of the render hot path lives in the shared object.  There is NO CPU or eager fallback: if the
@@ -11,6 +11,9 @@ import os
 
 import torch
 
+from . import abi
+from .abi import RN_F16, RN_F32, RN_LAYOUT_BLC, RN_LAYOUT_BLC_LEVELMAJOR, RN_LAYOUT_LBC  # noqa: F401
+
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.path.join(_ROOT, "lib", "libradnerf_hip.so")
 
@@ -20,86 +23,12 @@ if not os.path.exists(LIB_PATH):
         "(or __graft_entry__.build()). There is no fallback path.")
 
 _lib = C.CDLL(LIB_PATH)
-
-_u32, _f32, _i32, _ptr, _sz = C.c_uint32, C.c_float, C.c_int, C.c_void_p, C.c_size_t
-
-# name -> argtypes, in the order of include/radnerf_hip.h
-_SIGNATURES = {
-    "rn_near_far_from_aabb": [_ptr, _ptr, _ptr, _u32, _f32, _ptr, _ptr, _ptr],
-    "rn_sph_from_ray": [_ptr, _ptr, _f32, _u32, _ptr, _ptr],
-    "rn_morton3D": [_ptr, _u32, _ptr, _ptr],
-    "rn_morton3D_invert": [_ptr, _u32, _ptr, _ptr],
-    "rn_packbits": [_ptr, _u32, _f32, _ptr, _ptr],
-    "rn_morton3D_dilation": [_ptr, _u32, _u32, _ptr, _ptr],
-    "rn_march_rays_train": [_ptr, _ptr, _ptr, _f32, _f32, _u32, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr,
-                            _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_march_rays_train_budget": [_ptr, _ptr, _ptr, _f32, _f32, _u32, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr,
-                                   _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_march_rays_train_step": [_ptr, _ptr, _ptr, _ptr, _f32, _f32, _f32, _u32, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr,
-                                 _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr],
-    "rn_march_rays_train_backward": [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr],
-    "rn_composite_rays_train_forward": [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _f32, _ptr, _ptr, _ptr, _ptr,
-                                        _ptr],
-    "rn_composite_rays_train_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32,
-                                         _u32, _f32, _ptr, _ptr, _ptr, _ptr],
-    "rn_march_rays": [_u32, _u32, _ptr, _ptr, _ptr, _ptr, _f32, _f32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr,
-                      _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_composite_rays": [_u32, _u32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_compact_rays": [_ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr],
-    "rn_grid_encode_forward": [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _u32, _f32, _u32, _ptr, _u32, _i32, _u32,
-                               _i32, _i32, _ptr],
-    "rn_grid_encode_forward_ws": [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _u32, _f32, _u32, _ptr, _u32, _i32, _u32,
-                                  _i32, _i32, _ptr, _sz, _ptr],
-    "rn_grid_encode_forward_bound": [_ptr, _f32, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32, _i32,
-                                     _ptr, _sz, _ptr],
-    "rn_grid_encode_backward": [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _u32, _f32, _u32, _ptr, _ptr,
-                                _u32, _i32, _u32, _i32, _i32, _ptr],
-    "rn_grad_total_variation": [_ptr, _ptr, _ptr, _ptr, _f32, _u32, _u32, _u32, _u32, _f32, _u32, _u32, _i32,
-                                _ptr],
-    "rn_sh_encode_forward": [_ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr],
-    "rn_sh_encode_backward": [_ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr],
-    "rn_freq_encode_forward": [_ptr, _u32, _u32, _u32, _u32, _ptr, _ptr],
-    "rn_freq_encode_backward": [_ptr, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr],
-}
-
-RN_F32, RN_F16 = 0, 1
-RN_LAYOUT_LBC, RN_LAYOUT_BLC, RN_LAYOUT_BLC_LEVELMAJOR = 0, 1, 2
-
-for _name, _args in _SIGNATURES.items():
-    _fn = getattr(_lib, _name)
-    _fn.argtypes = _args
-    _fn.restype = C.c_int
-_lib.rn_last_error.restype = C.c_char_p
-_lib.rn_version.restype = C.c_int
-_lib.rn_device_count.restype = C.c_int
-_lib.rn_march_rays_train_workspace.restype = _sz
-_lib.rn_march_rays_train_workspace.argtypes = [_u32]
-_lib.rn_march_rays_train_step_state.restype = _sz
-_lib.rn_march_rays_train_step_state.argtypes = [_u32]
-_lib.rn_compact_rays_workspace.restype = _sz
-_lib.rn_compact_rays_workspace.argtypes = [_u32]
-_lib.rn_grid_encode_forward_workspace.restype = _sz
-_lib.rn_grid_encode_forward_workspace.argtypes = [_u32, _u32, _u32, _i32]
-
-
-_lib.rn_prof_enable.argtypes = [C.c_int]
-_lib.rn_prof_enable.restype = C.c_int
-_lib.rn_prof_pause.argtypes = [C.c_int]
-_lib.rn_prof_pause.restype = C.c_int
-_lib.rn_prof_collect.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
-_lib.rn_prof_collect.restype = C.c_int
-
-
-_lib.rn_prof_durations.argtypes = [C.POINTER(C.c_float), C.c_uint32]
-_lib.rn_prof_durations.restype = C.c_int
+abi.bind(_lib)
 
 
 def exported_symbols():
-    """Every symbol include/radnerf_hip.h declares (used by the CPU-side load test)."""
-    return sorted(list(_SIGNATURES) + ["rn_last_error", "rn_version", "rn_device_count", "rn_prof_enable", "rn_prof_pause",
-                                       "rn_prof_collect", "rn_prof_durations", "rn_march_rays_train_workspace", "rn_march_rays_train_step_state",
-                                       "rn_compact_rays_workspace",
-                                       "rn_grid_encode_forward_workspace"])
+    """Every function include/*.h declares (abi.FUNCTIONS has one entry for each; tests/test_abi.py checks it)."""
+    return sorted(abi.FUNCTIONS)
 
 
 def prof_enable(on=True):

@@ -26,7 +26,6 @@ def _dense_from_morton(v, H):
 
 # ------------------------------------------------------------------------------------------------------------ CPU
 def test_builtin_jitter_hash_is_the_same_on_both_sides_and_uniform(po, hiplib):
-    import radnerf.occupancy  # noqa: F401  (declares the ctypes signature)
     lib = po.lib()
     lib.orc_hash_u01_bits.restype = C.c_uint32
     vals = []
