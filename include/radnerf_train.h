@@ -14,6 +14,9 @@
  *   rn_train_head_backward   the same tile walked back: pre-activation gradients of all eight layers, the
  *                            gradient of the ambient coordinates through the 2-D grid, and the feature
  *                            gradients of both grids in level-major [L, M, 2] layout                          1 launch
+ *   rn_train_head_input_grads    only with --train_camera: d/d xyzs (the corners of the xyz grid gathered again, DYDX
+ *                            blend) and d/d dirs (W_col0[:, 0:16]^T dZ_col0 through the SH Jacobian); zero rows past
+ *                            the live count                                                                    1 launch
  *   rn_train_head_weight_grads   dW = dZ X^T for all eight layers in one launch (+ one reduction launch, + one
  *                            launch for the constant columns: audio code / eye / individual code and their
  *                            weight columns)                                                                   3 launches
@@ -68,6 +71,18 @@ int rn_train_head_backward(const float *grad_sigmas, const float *grad_rgbs, con
                            const float *grad_ambient_abs, const float *rgbs, const float *ambient, uint32_t M,
                            const int32_t *m_dev, const float *image, float *workspace, float *grad_enc_x, float *grad_enc_w,
                            rn_stream_t stream);
+
+/* Gradients of the sample positions and directions (only a caller that trains the camera pose needs them; call after
+ * rn_train_head_backward, before the tables or the weights change).  xn [M,3]: the forward's normalised positions; dirs [M,3]:
+ * the forward's directions; grad_enc_x [16, M, 2]: the backward's feature gradients of the xyz grid (ambient-net + sigma-net
+ * paths already summed); image / workspace: the forward's and backward's.  The table corners are gathered again:
+ *   grad_xyzs[b, d] = 1 / (2 bound) * sum_l sum_c grad_enc_x[l, b, c] * dy_dx[b, l, d, c]   (gridencoder.cu:189-240, 342-368;
+ *                     exactly 0 for a sample whose normalised position lies outside [0, 1])
+ *   grad_dirs[b, :] = J_SH(dirs[b])^T g_sh[b],  g_sh[b, k] = sum_o W_col0[o][k] dZ_col0[b, o], k < 16   (shencoder.cu:359-382)
+ * Rows b >= live count of both outputs are written as zeros.  fp32 table, D = 3, C = 2, align_corners = false, linear. */
+int rn_train_head_input_grads(const float *xn, const float *dirs, const float *grad_enc_x, uint32_t M, const int32_t *m_dev,
+                              const rn_grid_t *grid_xyz, const float *image, const float *workspace, float bound,
+                              float *grad_xyzs, float *grad_dirs, rn_stream_t stream);
 
 /* Gradients of the eight weight matrices in the nn.Linear layout (written, not accumulated; the full [64, 32 + audio_dim]
  * etc. shapes including the constant columns) and of the constants: grad_enc_a [audio_dim], grad_eye [1] (nullable when

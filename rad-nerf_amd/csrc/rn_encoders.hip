@@ -10,95 +10,6 @@ namespace rn {
 
 constexpr int kBlockE = 256;
 
-// Jacobian rows d/dx, d/dy, d/dz (shencoder.cu:130-350).  AXIS: 0 = x, 1 = y, 2 = z.
-template <uint32_t C, int AXIS>
-__device__ __forceinline__ void sh_jac(float x, float y, float z, float *d) {
-    const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;
-    const float x4 = x2 * x2, y4 = y2 * y2, z4 = z2 * z2;
-    const float x6 = x4 * x2, y6 = y4 * y2, z6 = z4 * z2;
-    (void)xy; (void)xz; (void)yz; (void)x6; (void)y6; (void)z6;
-#define SH3(i, ex, ey, ez) d[i] = (AXIS == 0) ? (ex) : (AXIS == 1) ? (ey) : (ez)
-    SH3(0, 0.0f, 0.0f, 0.0f);
-    if constexpr (C > 1) {
-        SH3(1, 0.0f, -0.48860251190291992f, 0.0f);
-        SH3(2, 0.0f, 0.0f, 0.48860251190291992f);
-        SH3(3, -0.48860251190291992f, 0.0f, 0.0f);
-    }
-    if constexpr (C > 2) {
-        SH3(4, 1.0925484305920792f * y, 1.0925484305920792f * x, 0.0f);
-        SH3(5, 0.0f, -1.0925484305920792f * z, -1.0925484305920792f * y);
-        SH3(6, 0.0f, 0.0f, 1.8923493915151202f * z);
-        SH3(7, -1.0925484305920792f * z, 0.0f, -1.0925484305920792f * x);
-        SH3(8, 1.0925484305920792f * x, -1.0925484305920792f * y, 0.0f);
-    }
-    if constexpr (C > 3) {
-        SH3(9, -3.5402615395598609f * xy, -1.7701307697799304f * x2 + 1.7701307697799304f * y2, 0.0f);
-        SH3(10, 2.8906114426405538f * yz, 2.8906114426405538f * xz, 2.8906114426405538f * xy);
-        SH3(11, 0.0f, 0.45704579946446572f - 2.2852289973223288f * z2, -4.5704579946446566f * yz);
-        SH3(12, 0.0f, 0.0f, 5.597644988851731f * z2 - 1.1195289977703462f);
-        SH3(13, 0.45704579946446572f - 2.2852289973223288f * z2, 0.0f, -4.5704579946446566f * xz);
-        SH3(14, 2.8906114426405538f * xz, -2.8906114426405538f * yz, 1.4453057213202769f * x2 - 1.4453057213202769f * y2);
-        SH3(15, -1.7701307697799304f * x2 + 1.7701307697799304f * y2, 3.5402615395598609f * xy, 0.0f);
-    }
-    if constexpr (C > 4) {
-        SH3(16, 2.5033429417967046f * y * (3.0f * x2 - y2), 2.5033429417967046f * x * (x2 - 3.0f * y2), 0.0f);
-        SH3(17, -10.620784618679583f * xy * z, 5.3103923093397913f * z * (-x2 + y2), 1.7701307697799304f * y * (-3.0f * x2 + y2));
-        SH3(18, 0.94617469575756008f * y * (7.0f * z2 - 1.0f), 0.94617469575756008f * x * (7.0f * z2 - 1.0f), 13.246445740605839f * xy * z);
-        SH3(19, 0.0f, 0.66904654355728921f * z * (3.0f - 7.0f * z2), 2.0071396306718676f * y * (1.0f - 7.0f * z2));
-        SH3(20, 0.0f, 0.0f, 14.809976568128603f * (z2 * z) - 6.3471328149122579f * z);
-        SH3(21, 0.66904654355728921f * z * (3.0f - 7.0f * z2), 0.0f, 2.0071396306718676f * x * (1.0f - 7.0f * z2));
-        SH3(22, 0.94617469575756008f * x * (7.0f * z2 - 1.0f), 0.94617469575756008f * y * (1.0f - 7.0f * z2), 6.6232228703029197f * z * (x2 - y2));
-        SH3(23, 5.3103923093397913f * z * (-x2 + y2), 10.620784618679583f * xy * z, 1.7701307697799304f * x * (-x2 + 3.0f * y2));
-        SH3(24, 2.5033429417967046f * x * (x2 - 3.0f * y2), 2.5033429417967046f * y * (-3.0f * x2 + y2), 0.0f);
-    }
-    if constexpr (C > 5) {
-        SH3(25, 13.127641136803401f * xy * (-x2 + y2), 19.6914617052051f * x2 * y2 - 3.2819102842008503f * x4 - 3.2819102842008503f * y4, 0.0f);
-        SH3(26, 8.3026492595241645f * yz * (3.0f * x2 - y2), 8.3026492595241645f * xz * (x2 - 3.0f * y2), 8.3026492595241645f * xy * (x2 - y2));
-        SH3(27, 2.9354297966115022f * xy * (1.0f - 9.0f * z2), -1.4677148983057511f * (x2 - y2) * (9.0f * z2 - 1.0f), 8.8062893898345074f * yz * (-3.0f * x2 + y2));
-        SH3(28, 4.7935367849733241f * yz * (3.0f * z2 - 1.0f), 4.7935367849733241f * xz * (3.0f * z2 - 1.0f), 4.7935367849733241f * xy * (9.0f * z2 - 1.0f));
-        SH3(29, 0.0f, 6.3412531167397574f * z2 - 9.5118796751096362f * z4 - 0.45294665119569694f, 12.682506233479513f * yz * (1.0f - 3.0f * z2));
-        SH3(30, 0.0f, 0.0f, -24.559567715218954f * z2 + 36.839351572828434f * z4 + 1.754254836801354f);
-        SH3(31, 6.3412531167397574f * z2 - 9.5118796751096362f * z4 - 0.45294665119569694f, 0.0f, 12.682506233479513f * xz * (1.0f - 3.0f * z2));
-        SH3(32, 4.7935367849733241f * xz * (3.0f * z2 - 1.0f), 4.7935367849733241f * yz * (1.0f - 3.0f * z2), 2.3967683924866621f * (x2 - y2) * (9.0f * z2 - 1.0f));
-        SH3(33, -13.209434084751759f * x2 * z2 + 1.4677148983057511f * x2 + 13.209434084751759f * y2 * z2 - 1.4677148983057511f * y2, 2.9354297966115022f * xy * (9.0f * z2 - 1.0f), 8.8062893898345074f * xz * (-x2 + 3.0f * y2));
-        SH3(34, 8.3026492595241645f * xz * (x2 - 3.0f * y2), 8.3026492595241645f * yz * (-3.0f * x2 + y2), -12.453973889286246f * x2 * y2 + 2.0756623148810411f * x4 + 2.0756623148810411f * y4);
-        SH3(35, 19.6914617052051f * x2 * y2 - 3.2819102842008503f * x4 - 3.2819102842008503f * y4, 13.127641136803401f * xy * (x2 - y2), 0.0f);
-    }
-    if constexpr (C > 6) {
-        SH3(36, 4.0991046311514854f * y * (-10.0f * x2 * y2 + 5.0f * x4 + y4), 4.0991046311514854f * x * (-10.0f * x2 * y2 + x4 + 5.0f * y4), 0.0f);
-        SH3(37, 47.332383244635047f * xy * z * (-x2 + y2), 11.833095811158762f * z * (6.0f * x2 * y2 - x4 - y4), 2.3666191622317521f * y * (10.0f * x2 * y2 - 5.0f * x4 - y4));
-        SH3(38, 2.0182596029148963f * y * (3.0f * x2 - y2) * (11.0f * z2 - 1.0f), 2.0182596029148963f * x * (x2 - 3.0f * y2) * (11.0f * z2 - 1.0f), 44.401711264127719f * xy * z * (x2 - y2));
-        SH3(39, 5.5272315570895412f * xy * z * (3.0f - 11.0f * z2), -2.7636157785447706f * z * (x2 - y2) * (11.0f * z2 - 3.0f), -2.7636157785447706f * y * (3.0f * x2 - y2) * (11.0f * z2 - 1.0f));
-        SH3(40, 0.92120525951492349f * y * (-18.0f * z2 + 33.0f * z4 + 1.0f), 0.92120525951492349f * x * (-18.0f * z2 + 33.0f * z4 + 1.0f), 11.054463114179082f * xy * z * (11.0f * z2 - 3.0f));
-        SH3(41, 0.0f, 0.58262136251873131f * z * (30.0f * z2 - 33.0f * z4 - 5.0f), 2.9131068125936568f * y * (18.0f * z2 - 33.0f * z4 - 1.0f));
-        SH3(42, 0.0f, 0.0f, 2.6699064952403937f * z * (-30.0f * z2 + 33.0f * z4 + 5.0f));
-        SH3(43, 0.58262136251873131f * z * (30.0f * z2 - 33.0f * z4 - 5.0f), 0.0f, 2.9131068125936568f * x * (18.0f * z2 - 33.0f * z4 - 1.0f));
-        SH3(44, 0.92120525951492349f * x * (-18.0f * z2 + 33.0f * z4 + 1.0f), 0.92120525951492349f * y * (18.0f * z2 - 33.0f * z4 - 1.0f), 5.5272315570895412f * z * (x2 - y2) * (11.0f * z2 - 3.0f));
-        SH3(45, -2.7636157785447706f * z * (x2 - y2) * (11.0f * z2 - 3.0f), 5.5272315570895412f * xy * z * (11.0f * z2 - 3.0f), -2.7636157785447706f * x * (x2 - 3.0f * y2) * (11.0f * z2 - 1.0f));
-        SH3(46, 2.0182596029148963f * x * (x2 - 3.0f * y2) * (11.0f * z2 - 1.0f), -2.0182596029148963f * y * (3.0f * x2 - y2) * (11.0f * z2 - 1.0f), 11.10042781603193f * z * (-6.0f * x2 * y2 + x4 + y4));
-        SH3(47, 11.833095811158762f * z * (6.0f * x2 * y2 - x4 - y4), 47.332383244635047f * xy * z * (x2 - y2), 2.3666191622317521f * x * (10.0f * x2 * y2 - x4 - 5.0f * y4));
-        SH3(48, 4.0991046311514854f * x * (-10.0f * x2 * y2 + x4 + 5.0f * y4), 4.0991046311514854f * y * (10.0f * x2 * y2 - 5.0f * x4 - y4), 0.0f);
-    }
-    if constexpr (C > 7) {
-        SH3(49, 9.9002782553443485f * xy * (10.0f * x2 * y2 - 3.0f * x4 - 3.0f * y4), -74.252086915082614f * x2 * y4 + 74.252086915082614f * x4 * y2 - 4.9501391276721742f * x6 + 4.9501391276721742f * y6, 0.0f);
-        SH3(50, 15.875763970811402f * yz * (-10.0f * x2 * y2 + 5.0f * x4 + y4), 15.875763970811402f * xz * (-10.0f * x2 * y2 + x4 + 5.0f * y4), 5.2919213236038001f * xy * (-10.0f * x2 * y2 + 3.0f * x4 + 3.0f * y4));
-        SH3(51, -10.378311574405206f * xy * (x2 - y2) * (13.0f * z2 - 1.0f), 0.51891557872026028f * (13.0f * z2 - 1.0f) * (10.0f * x2 * y2 - 5.0f * x4 + 4.0f * y2 * (5.0f * x2 - y2) - y4), 13.491805046726766f * yz * (10.0f * x2 * y2 - 5.0f * x4 - y4));
-        SH3(52, 4.1513246297620823f * yz * (3.0f * x2 - y2) * (13.0f * z2 - 3.0f), 4.1513246297620823f * xz * (x2 - 3.0f * y2) * (13.0f * z2 - 3.0f), 12.453973889286248f * xy * (x2 - y2) * (13.0f * z2 - 1.0f));
-        SH3(53, 0.93875360317376422f * xy * (66.0f * z2 - 143.0f * z4 - 3.0f), -0.46937680158688211f * (x2 - y2) * (13.0f * z2 * (11.0f * z2 - 3.0f) - 27.0f * z2 + 3.0f), -6.8841930899409371f * yz * (3.0f * x2 - y2) * (13.0f * z2 - 3.0f));
-        SH3(54, 0.44253269244498261f * yz * (-110.0f * z2 + 143.0f * z4 + 15.0f), 0.44253269244498261f * xz * (-110.0f * z2 + 143.0f * z4 + 15.0f), 2.2126634622249131f * xy * (-66.0f * z2 + 143.0f * z4 + 3.0f));
-        SH3(55, 0.0f, -12.194767023639836f * z2 + 44.714145753346067f * z4 - 38.752259652899923f * z6 + 0.45165803791258652f, 1.6259689364853116f * yz * (110.0f * z2 - 143.0f * z4 - 15.0f));
-        SH3(56, 0.0f, 0.0f, 64.528641681844675f * z2 - 236.60501950009714f * z4 + 205.05768356675085f * z6 - 2.3899496919201733f);
-        SH3(57, -12.194767023639836f * z2 + 44.714145753346067f * z4 - 38.752259652899923f * z6 + 0.45165803791258652f, 0.0f, 1.6259689364853116f * xz * (110.0f * z2 - 143.0f * z4 - 15.0f));
-        SH3(58, 0.44253269244498261f * xz * (-110.0f * z2 + 143.0f * z4 + 15.0f), 0.44253269244498261f * yz * (110.0f * z2 - 143.0f * z4 - 15.0f), 0.07375544874083044f * (x2 - y2) * (143.0f * z2 * (3.0f * z2 - 1.0f) + 132.0f * z2 * (13.0f * z2 - 5.0f) - 187.0f * z2 + 45.0f));
-        SH3(59, 30.97886890473422f * x2 * z2 - 67.120882626924143f * x2 * z4 - 1.4081304047606462f * x2 - 30.97886890473422f * y2 * z2 + 67.120882626924143f * y2 * z4 + 1.4081304047606462f * y2, 0.93875360317376422f * xy * (-66.0f * z2 + 143.0f * z4 + 3.0f), -6.8841930899409371f * xz * (x2 - 3.0f * y2) * (13.0f * z2 - 3.0f));
-        SH3(60, 4.1513246297620823f * xz * (x2 - 3.0f * y2) * (13.0f * z2 - 3.0f), -4.1513246297620823f * yz * (3.0f * x2 - y2) * (13.0f * z2 - 3.0f), 3.1134934723215619f * (13.0f * z2 - 1.0f) * (-6.0f * x2 * y2 + x4 + y4));
-        SH3(61, -0.51891557872026028f * (13.0f * z2 - 1.0f) * (-10.0f * x2 * y2 + 4.0f * x2 * (x2 - 5.0f * y2) + x4 + 5.0f * y4), 10.378311574405206f * xy * (x2 - y2) * (13.0f * z2 - 1.0f), 13.491805046726766f * xz * (10.0f * x2 * y2 - x4 - 5.0f * y4));
-        SH3(62, 15.875763970811402f * xz * (-10.0f * x2 * y2 + x4 + 5.0f * y4), 15.875763970811402f * yz * (10.0f * x2 * y2 - 5.0f * x4 - y4), 39.6894099270285f * x2 * y4 - 39.6894099270285f * x4 * y2 + 2.6459606618019f * x6 - 2.6459606618019f * y6);
-        SH3(63, -74.252086915082614f * x2 * y4 + 74.252086915082614f * x4 * y2 - 4.9501391276721742f * x6 + 4.9501391276721742f * y6, 9.9002782553443485f * xy * (-10.0f * x2 * y2 + 3.0f * x4 + 3.0f * y4), 0.0f);
-    }
-#undef SH3
-}
-
 template <uint32_t N>
 __device__ __forceinline__ void store_f32_row(float *dst, const float *v) {
     if constexpr (N % 4 == 0) {

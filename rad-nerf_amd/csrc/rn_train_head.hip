@@ -465,6 +465,136 @@ __global__ void __launch_bounds__(kThreads) k_train_bwd(BwdParams p) {
     }
 }
 
+// ---- input gradients (--train_camera) -----------------------------------------------------------------------------------
+// d loss / d xyzs and d loss / d dirs from what k_train_bwd left behind.  The tile and lane roles are the forward's: one wavefront
+// owns 32 samples, lane half h walks levels 2 r + h.
+//  * xyzs: the corners of every level are gathered AGAIN (same plan, same loads as k_train_fwd, so the same cell) and blended
+//    with the DYDX form of blend_level; grad = sum_l sum_c g_enc_x[l, b, c] * dy_dx[b, l, :, c] / (2 bound)
+//    (gridencoder.cu:342-368 + the normalisation of gridencoder/grid.py:151).  A sample outside [0, 1] gets exactly 0
+//    (gridencoder.cu:146-156 leaves its dy_dx zero).
+//  * dirs: g_sh[k] = sum_o W_col0[o][k] dzc0[b, o] (k < 16) from the native dzc0 tile -- a lane holds 32 of the 64 rows o of
+//    its sample, W_col0[:, 0:16] sits in LDS row-major, both lane halves read one row each (broadcast) -- then
+//    J_SH(dirs[b])^T g_sh (shencoder.cu:359-382); the two halves' partial sums meet in one shuffle per component.
+// Rows from the live count up to the capacity M are written as zeros (they belong to no ray; a consumer that sums every row
+// must not meet uninitialised memory).
+struct IgParams {
+    const float *xn, *dirs, *g_enc_x;
+    uint32_t M;
+    const int32_t *m_dev;
+    GridArgs gx;
+    const float *image;
+    float *ws;
+    float bound;
+    float *g_xyzs, *g_dirs;
+};
+constexpr int kIgThreads = 256, kIgWaves = kIgThreads / kWave;
+
+template <int G>   // gather rounds in flight per wave: nothing but the blend sits between two rounds here, so two hide more latency
+__global__ void __launch_bounds__(kIgThreads) k_train_input_grads(IgParams p) {
+    __shared__ __attribute__((aligned(16))) float wc0[64 * 16];   // W_col0[o][k], k < 16
+    __shared__ LevelPlan plan_x[16];
+    const uint32_t M = live_count(p.M, p.m_dev);
+    const uint32_t n_live = (M + 31u) >> 5, n_tiles = (p.M + 31u) >> 5;
+    for (int e = threadIdx.x; e < 64 * 16; e += kIgThreads) {   // forward image, colour L0, SH steps: [k / 2][k % 2][o % 32][o / 32]
+        const int o = e >> 4, k = e & 15;
+        wc0[e] = p.image[OFF_C0 + (k >> 1) * kStep + (k & 1) * 64 + (o & 31) * 2 + (o >> 5)];
+    }
+    if (threadIdx.x < 16) {
+        const int t = threadIdx.x;
+        const uint32_t ox = (uint32_t)p.gx.offsets[t];
+        plan_x[t] = plan_level<3>(p.gx.lc.scale[t], p.gx.lc.resolution[t], ox, (uint32_t)p.gx.offsets[t + 1] - ox, p.gx.gridtype, 8u);
+    }
+    __syncthreads();
+    const Ws ws = make_ws(p.ws, p.M);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const float *tx = static_cast<const float *>(p.gx.table);
+
+    for (uint32_t tile = blockIdx.x * kIgWaves + wave; tile < n_tiles; tile += gridDim.x * kIgWaves) {
+        const uint32_t sample = tile * 32 + j;
+        const bool live = sample < M;
+        float gx[3] = {0.0f, 0.0f, 0.0f}, gd[3] = {0.0f, 0.0f, 0.0f};
+        if (tile < n_live) {   // wave-uniform: the tiles past the live count have no saved state, only zeros to write
+            // ---- xyz grid
+            float in[3] = {0.0f, 0.0f, 0.0f};
+            bool on = live;
+            if (live) {
+#pragma unroll
+                for (int d = 0; d < 3; d++) {
+                    in[d] = p.xn[3 * (size_t)sample + d];
+                    on = on && !(in[d] < 0 || in[d] > 1);
+                }
+            }
+            LevelFetch<float, 3, 2> f[G];
+#pragma unroll 1
+            for (int r0 = 0; r0 < 8; r0 += G) {
+                float2 g[G];
+                if (on) {
+#pragma unroll
+                    for (int i = 0; i < G; i++) {
+                        issue_planned<float, 3, 2, false, false>(tx, plan_x[2 * (r0 + i) + h], in, f[i]);
+                        g[i] = *reinterpret_cast<const float2 *>(p.g_enc_x + ((size_t)(2 * (r0 + i) + h) * p.M + sample) * 2);
+                    }
+#pragma unroll
+                    for (int i = 0; i < G; i++) {
+                        float res[2], dydx[6];
+                        blend_level<float, 3, 2, true>(f[i], plan_x[2 * (r0 + i) + h].scale, res, dydx);
+#pragma unroll
+                        for (int d = 0; d < 3; d++) {
+                            gx[d] = __builtin_fmaf(g[i].x, dydx[2 * d], gx[d]);
+                            gx[d] = __builtin_fmaf(g[i].y, dydx[2 * d + 1], gx[d]);
+                        }
+                    }
+                }
+            }
+            // ---- SH: this lane's 32 rows of dzc0 against W_col0[:, 0:16]
+            float gs[16];
+#pragma unroll
+            for (int k = 0; k < 16; k++) gs[k] = 0.0f;
+            const float *dz = ws.dzc0 + (size_t)tile * kTile32;
+            // (a rolled loop on purpose: fully unrolled, the 512 weights a lane reads are invariant over the tile loop and the
+            // compiler keeps them all in registers)
+#pragma unroll 4
+            for (int q = 0; q < 32; q++) {
+                const float d = dz[q * 64 + lane];
+                const float4 *wr = reinterpret_cast<const float4 *>(wc0 + (32 * (q >> 4) + rowmap(q & 15, 0) + 4 * h) * 16);
+#pragma unroll
+                for (int u = 0; u < 4; u++) {
+                    const float4 w = wr[u];
+                    gs[4 * u + 0] = __builtin_fmaf(w.x, d, gs[4 * u + 0]);
+                    gs[4 * u + 1] = __builtin_fmaf(w.y, d, gs[4 * u + 1]);
+                    gs[4 * u + 2] = __builtin_fmaf(w.z, d, gs[4 * u + 2]);
+                    gs[4 * u + 3] = __builtin_fmaf(w.w, d, gs[4 * u + 3]);
+                }
+            }
+            float dx = 0.0f, dy = 0.0f, dzz = 0.0f;
+            if (live) {
+                dx = p.dirs[3 * (size_t)sample]; dy = p.dirs[3 * (size_t)sample + 1]; dzz = p.dirs[3 * (size_t)sample + 2];
+            }
+            float jac[16];
+            sh_jac<4, 0>(dx, dy, dzz, jac);
+#pragma unroll
+            for (int k = 1; k < 16; k++) gd[0] = __builtin_fmaf(jac[k], gs[k], gd[0]);   // k = 0: the constant term
+            sh_jac<4, 1>(dx, dy, dzz, jac);
+#pragma unroll
+            for (int k = 1; k < 16; k++) gd[1] = __builtin_fmaf(jac[k], gs[k], gd[1]);
+            sh_jac<4, 2>(dx, dy, dzz, jac);
+#pragma unroll
+            for (int k = 1; k < 16; k++) gd[2] = __builtin_fmaf(jac[k], gs[k], gd[2]);
+        }
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            gx[d] += __shfl_xor(gx[d], 32, 64);
+            gd[d] += __shfl_xor(gd[d], 32, 64);
+        }
+        if (sample < p.M) {   // lane half 0 writes the position row, lane half 1 the direction row
+            float *dst = (h == 0 ? p.g_xyzs : p.g_dirs) + 3 * (size_t)sample;
+#pragma unroll
+            for (int d = 0; d < 3; d++) dst[d] = live ? (h == 0 ? gx[d] / (2 * p.bound) : gd[d]) : 0.0f;
+        }
+    }
+}
+
 // ---- weight gradients ---------------------------------------------------------------------------------------------------
 constexpr int kWThreads = 256;
 constexpr int kTS = 36;                  // LDS row stride of a staged tile: [feature][sample parity][sample / 2]
@@ -869,6 +999,23 @@ int rn_train_head_backward(const float *grad_sigmas, const float *grad_rgbs, con
     if (blocks > cap) blocks = cap;
     hipLaunchKernelGGL(k_train_bwd, dim3(blocks), dim3(kThreads), 0, as_stream(stream), p);
     return check_launch("train_head_backward");
+}
+
+int rn_train_head_input_grads(const float *xn, const float *dirs, const float *grad_enc_x, uint32_t M, const int32_t *m_dev,
+                              const rn_grid_t *grid_xyz, const float *image, const float *workspace, float bound,
+                              float *grad_xyzs, float *grad_dirs, rn_stream_t stream) {
+    if (M == 0) return RN_OK;
+    if (int rc = check_grid(grid_xyz, 3, "xyz")) return rc;
+    RN_REQUIRE(xn && dirs && grad_enc_x && image && workspace && grad_xyzs && grad_dirs, "train_head_input_grads: null pointer");
+    RN_REQUIRE(((uintptr_t)grad_enc_x & 7u) == 0, "train_head_input_grads: feature gradients must be 8-byte aligned");
+    RN_REQUIRE(bound > 0.0f, "train_head_input_grads: bound must be positive");
+    IgParams p{xn, dirs, grad_enc_x, M, m_dev, grid_args(grid_xyz), image, const_cast<float *>(workspace), bound, grad_xyzs, grad_dirs};
+    const uint32_t n_tiles = (M + 31u) >> 5;   // of the capacity: the rows past the live count are zero-filled by the same launch
+    uint32_t blocks = div_up(n_tiles, kIgWaves);
+    const uint32_t cap = 4u * (uint32_t)num_cus();   // 110 VGPRs: 4 waves per SIMD = 4 workgroups of 4 waves per CU
+    if (blocks > cap) blocks = cap;
+    hipLaunchKernelGGL((k_train_input_grads<2>), dim3(blocks), dim3(kIgThreads), 0, as_stream(stream), p);
+    return check_launch("train_head_input_grads");
 }
 
 static int weight_grads(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_code, const int64_t *ind_index,

@@ -6,8 +6,11 @@ Reference: NeRFNetwork.forward (nerf/network.py:222-283) in the train branch of 
 `head_forward` is 2 launches (weight images + the network), its backward 6 (network, weight gradients + reduction + constant
 columns, one table scatter per grid) plus the two memsets of the table gradients -- against ~130 launches of grid / MLP /
 activation / concatenation kernels.  Differentiable in both grid tables, the eight weight matrices, the audio code, the eye
-value and the individual code; the sample positions and directions receive no gradient (as in the reference: the grid inputs
-do not require grad unless --train_camera, which keeps the per-operator path).
+value and the individual code -- and, when they require grad (--train_camera: the rays carry the gradient of camera_dR /
+camera_dT, nerf/renderer.py:104-107, 170-174), in the sample positions and directions: one more launch in the backward
+(rn_train_head_input_grads) gathers the corners of the xyz grid again for d/d xyzs and takes d/d dirs through the SH Jacobian;
+it is not made, and nothing is allocated for it, when neither input needs a gradient.  While a stream is capturing, a call whose
+positions require grad keeps the per-operator path (usable()).
 """
 import ctypes as C
 
@@ -22,10 +25,10 @@ _lib = hip._lib
 
 
 def supported(model):
-    """The network shape the kernels are built for (= the fused inference engine's), fp32 tables, no --emb / --train_camera."""
+    """The network shape the kernels are built for (= the fused inference engine's), fp32 tables, no --emb."""
     from . import fused
     return (fused.supported(model) and model.encoder.embeddings.dtype == torch.float32 and model.encoder_ambient.embeddings.dtype == torch.float32
-            and model.audio_dim > 0 and not model.train_camera)
+            and model.audio_dim > 0)
 
 
 class _HeadTrain(torch.autograd.Function):
@@ -72,16 +75,19 @@ class _HeadTrain(torch.autograd.Function):
                      float(bound), sigmas.data_ptr(), rgbs.data_ptr(), ambient.data_ptr(), amb_abs.data_ptr(), xn.data_ptr(), wn.data_ptr(),
                      hip.ptr(work), s)
         ctx.set_materialize_grads(False)      # an output nobody differentiates (ambient) costs no [M, 2] memset
-        ctx.save_for_backward(image, work, out, m_dev, tx, tw, enc_a_c, eye_c, ind_c, *ws)
+        # the directions are kept only for a backward that returns the input gradients (--train_camera)
+        ctx.save_for_backward(image, work, out, m_dev, tx, tw, enc_a_c, eye_c, ind_c, dirs if any(ctx.needs_input_grad[:2]) else None, *ws)
         ctx.meta = (enc_x, enc_w, M, audio_dim, has_eye, ind_dim, enc_a.shape, None if eye is None else eye.shape,
-                    None if ind_code is None else ind_code.shape, table_x.dtype)
+                    None if ind_code is None else ind_code.shape, float(bound))
         ctx.ind_index = ind_index
         return sigmas, rgbs, ambient, amb_abs
 
     @staticmethod
     def backward(ctx, g_sigma, g_rgb, g_ambient, g_amb_abs):
-        image, work, out, m_dev, tx, tw, enc_a_c, eye_c, ind_c, *ws = ctx.saved_tensors
-        enc_x, enc_w, M, audio_dim, has_eye, ind_dim, enc_a_shape, eye_shape, ind_shape, _ = ctx.meta
+        image, work, out, m_dev, tx, tw, enc_a_c, eye_c, ind_c, dirs, *ws = ctx.saved_tensors
+        enc_x, enc_w, M, audio_dim, has_eye, ind_dim, enc_a_shape, eye_shape, ind_shape, bound = ctx.meta
+        need_in = dirs is not None and any(ctx.needs_input_grad[:2])
+        g_in = None
         dev = image.device
         s = hip.stream()
         flat = out.view(-1)
@@ -135,6 +141,13 @@ class _HeadTrain(torch.autograd.Function):
                     _PENDING.append((ev, g_tx.data_ptr(), g_tw.data_ptr()))
                 else:
                     joined = ev
+            if need_in:
+                # d/d xyzs, d/d dirs: one launch on this stream (the marcher's backward is next in line for them).  It reads the
+                # xyz table -- still the forward's, the optimizer has not run -- beside the scatter, which only reads g_feat too.
+                g_in = torch.empty(2, M, 3, dtype=torch.float32, device=dev)
+                gxi = _grid_desc(enc_x, tx)
+                hip.call("rn_train_head_input_grads", xn.data_ptr(), hip.ptr(dirs), g_feat[0].data_ptr(), M, hip.ptr(m_dev), C.byref(gxi),
+                         hip.ptr(image), hip.ptr(work), bound, g_in[0].data_ptr(), g_in[1].data_ptr(), s)
             nw = weights_desc(ws, audio_dim, has_eye, ind_dim)
             hg = HeadGradsT()
             (hg.amb_w0, hg.amb_w1, hg.amb_w2, hg.sig_w0, hg.sig_w1, hg.sig_w2, hg.col_w0, hg.col_w1) = [g.data_ptr() for g in grads]
@@ -161,7 +174,10 @@ class _HeadTrain(torch.autograd.Function):
                 g_eye.zero_()
             if g_ind is not None:
                 g_ind.zero_()
-        return (None, None, g_enc_a.view(enc_a_shape), g_eye.view(eye_shape) if g_eye is not None else None,
+            if need_in:
+                g_in = torch.zeros(2, 0, 3, dtype=torch.float32, device=dev)
+        return (g_in[0] if need_in and ctx.needs_input_grad[0] else None, g_in[1] if need_in and ctx.needs_input_grad[1] else None,
+                g_enc_a.view(enc_a_shape), g_eye.view(eye_shape) if g_eye is not None else None,
                 g_ind.view(ind_shape) if g_ind is not None else None, None, None, g_tx, g_tw, *grads)
 
 
@@ -304,10 +320,12 @@ def head_forward(model, xyzs, dirs, enc_a, ind_code, eye, m_dev=None, ind_index=
 
 
 def usable(model, x, enc_a):
-    """Training call of the supported shape on the GPU in fp32 (autocast keeps the per-operator path)."""
+    """Training call of the supported shape on the GPU in fp32 (autocast keeps the per-operator path; so does a call whose
+    positions require grad while a stream is capturing: a captured --train_camera step replays the operator chain)."""
     import os
     return (os.environ.get("RN_TRAIN_HEAD", "fused") == "fused" and x.is_cuda and torch.is_grad_enabled() and x.dim() == 2
-            and x.dtype == torch.float32 and not torch.is_autocast_enabled() and enc_a is not None and not x.requires_grad
+            and x.dtype == torch.float32 and not torch.is_autocast_enabled() and enc_a is not None
+            and not (x.requires_grad and torch.cuda.is_current_stream_capturing())
             and getattr(model, "_train_head_ok", None) is not False and _check(model))
 
 

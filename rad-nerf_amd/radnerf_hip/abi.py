@@ -201,6 +201,7 @@ FUNCTIONS = {
     "rn_train_head_forward": (_int, [_ptr, _ptr, _u32, _ptr, _P(GridT), _P(GridT), _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _ptr,
                                      _ptr, _ptr, _ptr]),
     "rn_train_head_backward": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_head_input_grads": (_int, [_ptr, _ptr, _ptr, _u32, _ptr, _P(GridT), _ptr, _ptr, _f32, _ptr, _ptr, _ptr]),
     "rn_train_head_weight_grads": (_int, [_P(NerfWeightsT), _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _P(HeadGradsT), _ptr, _ptr]),
     "rn_train_head_weight_grads_row": (_int, [_P(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _P(HeadGradsT),
                                               _ptr, _ptr]),
