@@ -69,7 +69,9 @@ int rn_nerf_pack_weights_h16(const rn_nerf_weights_t *w, float *packed, rn_strea
 size_t rn_nerf_packed_floats_split(void);
 int rn_nerf_pack_weights_split(const rn_nerf_weights_t *w, float *packed, rn_stream_t stream);
 size_t rn_nerf_bias_floats(void);
-/* Re-order the raw weights into the image the fused kernel stages into LDS (call when weights change). */
+/* Re-order the raw weights into the image the fused kernel stages into LDS (call when weights change).  The fp32 and the
+ * split image hold color_net's geo_feat columns already multiplied by sigma_net's geo_feat rows (one 64 x 64 product,
+ * summed in double): those kernels feed the colour net from the sigma net's last hidden layer and never form geo_feat. */
 int rn_nerf_pack_weights(const rn_nerf_weights_t *w, float *packed, rn_stream_t stream);
 /* Per-frame bias vectors: W0_amb[:,32:] enc_a | W0_sig[:,64] eye | W0_col[:,80:] ind_code  (3 x 64). */
 int rn_nerf_frame_bias(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_code,
@@ -82,7 +84,7 @@ int rn_nerf_frame_bias_batch(const rn_nerf_weights_t *w, const float *enc_a, uin
  * dead (raymarching.cu:982) and skipped -- their outputs are left untouched.  m_dev (nullable): device
  * count of slots, overrides M (M is then only the launch bound).  ambient (nullable): [M,2] output.
  * rgbs == NULL (dirs may then be NULL too): density query -- NeRFNetwork.density (nerf/network.py:286-325), sigma only; the
- * fp32 kernel then skips the geo_feat layer, the SH basis and the colour network (a third of its matrix instructions). */
+ * fp32 kernel then skips the SH basis and the colour network (a quarter of its matrix instructions). */
 int rn_nerf_fused_forward(const float *xyzs, const float *dirs, const float *deltas, uint32_t M,
                           const int32_t *m_dev, const rn_grid_t *grid_xyz, const rn_grid_t *grid_amb,
                           const float *packed, const float *bias, float bound, float *sigmas, float *rgbs,

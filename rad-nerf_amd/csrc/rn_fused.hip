@@ -10,13 +10,16 @@
 //    B operand of an MFMA step (no cross-lane move) and a grid costs 8 rounds, not 16 levels, of latency.
 //  * a 32x32 accumulator has the sample on the lane and the output row on the register index, i.e. it already IS the
 //    B operand of the next layer (k order permuted -- the weight image is packed in that order once, on the device).
-//  * all weights (95.7 KB fp32) sit in LDS for the lifetime of a persistent 768-thread workgroup (one per CU, three
+//  * all weights (79.4 KB fp32) sit in LDS for the lifetime of a persistent 768-thread workgroup (one per CU, three
 //    waves per SIMD: 3 x 32 accumulator VGPRs leave room for that).  fp32 MFMA and fp32 VALU work share the FMA rate of a SIMD ("where the time goes"),
 //    so the instruction stream around the MFMAs is kept short: per-level plans (rn_grid_dev.h), one-instruction ReLU.
 //  * inputs that are the same for every sample of a frame (audio code, eye, individual code) never enter
 //    the per-sample GEMMs: they are folded into 3 x 64 bias values per frame, used as the accumulators'
 //    initial value.  Outputs narrower than a tile (ambient 2, sigma 1, rgb 3) are VALU dot products over
 //    the accumulator registers + one cross-half shuffle.
+//  * the geo_feat layer is not run: sigma_net's last layer and color_net's first are linear with nothing in between, so
+//    the packer multiplies their 64 x 64 blocks once (rn_nerf_image_dev.h: nerf_infer_image_elem) and the colour net's
+//    first layer reads the sigma net's last hidden activations directly -- 64 of a tile's 368 MFMAs and 16 KB of LDS less.
 #include "rn_nerf_image_dev.h"
 
 namespace rn {
@@ -37,12 +40,12 @@ constexpr int kXyzGroup = RN_F32_XYZ_GROUP, kAmbGroup = RN_F32_AMB_GROUP;  // ga
 constexpr int kF32Waves = RN_F32_WAVES, kF32Threads = kF32Waves * kWave;  // 3 waves per SIMD (accumulators: 3 x 32 VGPRs), one workgroup per CU
 constexpr bool kPairHashed = RN_FUSED_PAIR_HASHED;  // aligned x-pair loads on hashed levels inside the fused kernels
 
-constexpr int kLdsFloats = kPacked + kBias;          // forward image + biases: 96512 B of LDS
+constexpr int kLdsFloats = kInferPacked + kBias;     // inference image + biases: 80128 B of LDS
 
 __global__ void __launch_bounds__(256) k_pack_nerf(RawW w, float *__restrict__ packed) {
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= kPacked) return;
-    packed[e] = nerf_image_elem(w, e);
+    if (e >= kInferPacked) return;
+    packed[e] = nerf_infer_image_elem(w, e);
 }
 
 // Per-frame bias vectors (the broadcast columns of the three first layers).
@@ -79,9 +82,9 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
     const uint32_t n_tiles = (M + 31u) >> 5;
     if (workgroup_idle(n_tiles, kF32Waves)) return;
 
-    for (int i = threadIdx.x; i < kPacked / 4; i += kF32Threads)
+    for (int i = threadIdx.x; i < kInferPacked / 4; i += kF32Threads)
         reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.packed)[i];
-    if (threadIdx.x < kBias) lds[kPacked + threadIdx.x] = p.bias[threadIdx.x];
+    if (threadIdx.x < kBias) lds[kInferPacked + threadIdx.x] = p.bias[threadIdx.x];
     if (threadIdx.x < 16) {
         const int t = threadIdx.x;
         const uint32_t ox = (uint32_t)p.gx.offsets[t], ow = (uint32_t)p.gw.offsets[t];
@@ -95,7 +98,7 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, h = lane >> 5;
     const int lane_off = h * 64 + j * 2;
-    const float *bias_amb = lds + kPacked, *bias_sig = lds + kPacked + 64, *bias_col = lds + kPacked + 128;
+    const float *bias_amb = lds + kInferPacked, *bias_sig = lds + kInferPacked + 64, *bias_col = lds + kInferPacked + 128;
 
     const TileSchedule sched(n_tiles, kF32Waves, (uint32_t)wave);
     for (uint32_t tile = sched.first; tile < sched.end; tile += sched.stride) {
@@ -197,7 +200,7 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
             }
         }
 
-        // ---- sigma net: [enc_x | enc_w | eye] 65 -> 64 -> 64 -> 1 + 64
+        // ---- sigma net: [enc_x | enc_w | eye] 65 -> 64 -> 64 -> 1 (+ 64 geo_feat rows, folded into the colour net)
         RN_PHASE_MARK(3);
         acc_relu(a2);
         acc_zero(a1);
@@ -206,18 +209,17 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
         float sigma;
         {
             float raw[1];
-            valu_out<1>(a1, lds + OFF_S2R, h, raw);
+            valu_out<1>(a1, lds + IOFF_S2R, h, raw);
             sigma = expf(raw[0]);  // trunc_exp forward (activation.py:9-11)
         }
-        if (!p.rgbs) {  // density query (NeRFNetwork.density, nerf/network.py:286-325): no geo_feat layer, no SH, no colour net
+        if (!p.rgbs) {  // density query (NeRFNetwork.density, nerf/network.py:286-325): no SH, no colour net
             if (live && h == 0) p.sigmas[sample] = sigma;
             continue;
         }
-        acc_zero(a0);
-        layer_from_acc(a0, a1, lds + OFF_S2, lane_off);  // geo_feat (no activation)
 
-        // ---- color net: [SH(d) | geo_feat | ind_code] 84 -> 64 -> 3, sigmoid
-        acc_bias(a1, bias_col, h);
+        // ---- color net: [SH(d) | geo_feat | ind_code] 84 -> 64 -> 3, sigmoid; the geo_feat columns of its first layer are
+        // packed times sigma L2's geo_feat rows, so their 32 steps take the sigma net's hidden activations (a1)
+        acc_bias(a0, bias_col, h);
         {
             float sh[16];
             float dx = 0.0f, dy = 0.0f, dz = 0.0f;
@@ -231,15 +233,15 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
                 // index sh[] dynamically and move it to LDS
                 const uint32_t m = 0u - (uint32_t)h;
                 const uint32_t b = (__float_as_uint(sh[2 * s]) & ~m) | (__float_as_uint(sh[2 * s + 1]) & m);
-                step32(a1, lds + OFF_C0, s, lane_off, __uint_as_float(b));
+                step32(a0, lds + IOFF_C0, s, lane_off, __uint_as_float(b));
             }
         }
 #pragma unroll
-        for (int s = 0; s < 32; s++) step32(a1, lds + OFF_C0, 8 + s, lane_off, a0.v[s >> 4][s & 15]);
-        acc_relu(a1);
+        for (int s = 0; s < 32; s++) step32(a0, lds + IOFF_C0, 8 + s, lane_off, a1.v[s >> 4][s & 15]);
+        acc_relu(a0);
         {
             float rgb[3];
-            valu_out<3>(a1, lds + OFF_C1, h, rgb);
+            valu_out<3>(a0, lds + IOFF_C1, h, rgb);
             if (live && h == 0) {
                 p.sigmas[sample] = sigma;
 #pragma unroll
@@ -270,7 +272,7 @@ template <typename TX, typename TW>
 static void launch_fused(const FusedParams &p, hipStream_t s) {
     const uint32_t n_tiles = (p.M + 31u) >> 5;
     uint32_t blocks = div_up(n_tiles, kF32Waves);
-    const uint32_t cap = (uint32_t)num_cus();  // one persistent workgroup per CU (96.5 KB of LDS each)
+    const uint32_t cap = (uint32_t)num_cus();  // one persistent workgroup per CU (80.1 KB of LDS each)
     if (blocks > cap) blocks = cap;
     RN_LAUNCH_TIMED((k_nerf_fused<TX, TW>), dim3(blocks), dim3(kF32Threads), s, p);
 }
@@ -297,7 +299,7 @@ using namespace rn;
 
 extern "C" {
 
-size_t rn_nerf_packed_floats(void) { return (size_t)kPacked; }
+size_t rn_nerf_packed_floats(void) { return (size_t)kInferPacked; }
 size_t rn_nerf_packed_floats_h16(void) { return packed_floats_h16(); }
 size_t rn_nerf_packed_floats_split(void) { return packed_floats_x2(); }
 
@@ -319,7 +321,7 @@ size_t rn_nerf_bias_floats(void) { return (size_t)kBias; }
 int rn_nerf_pack_weights(const rn_nerf_weights_t *w, float *packed, rn_stream_t stream) {
     if (int rc = check_w(w)) return rc;
     RN_REQUIRE(packed && ((uintptr_t)packed & 15u) == 0, "nerf_pack_weights: packed must be 16-byte aligned");
-    hipLaunchKernelGGL(k_pack_nerf, dim3(div_up(kPacked, 256)), dim3(256), 0, as_stream(stream), raw_w(w), packed);
+    hipLaunchKernelGGL(k_pack_nerf, dim3(div_up(kInferPacked, 256)), dim3(256), 0, as_stream(stream), raw_w(w), packed);
     return check_launch("nerf_pack_weights");
 }
 

@@ -21,18 +21,21 @@
 // a_lo b_hi with fp32 accumulation; the dropped a_lo b_lo term is below 2^-22 |a b|.  Per-product error is ~3e-7 |a b|
 // (fp32: 6e-8), so the kernel meets the SAME tolerances against the fp32 oracle as the fp32-MFMA kernel (sigma rel 2e-4,
 // rgb / ambient abs 2e-5), at 3 MFMA k-steps of 32 cycles per 16 k instead of 8 fp32 MFMAs of 64 cycles: 5.3x less
-// matrix-core time.  Layout differences from the f16 kernel: both halves of the weights live in LDS (94 KB), the narrow
+// matrix-core time.  Layout differences from the f16 kernel: both halves of the weights live in LDS (77.8 KB), the narrow
 // fp32 output layers and the per-frame bias are read from global memory (L1/L2 hits), the staging tile holds hi and lo of
 // enc_x only (32 words per sample, XOR-swizzled 16-byte chunks instead of padding) while the ambient-grid features go
 // from registers to fragments with v_permlane32_swap (so the enc_x half of sigma L0 runs before the ambient grid) --
-// 65.5 + 94.2 KB of LDS for one 512-thread workgroup per CU, two waves per SIMD.
+// 65.5 + 77.8 KB of LDS for one 512-thread workgroup per CU, two waves per SIMD.  The split kernel does not run the
+// geo_feat layer: like the fp32 kernel it reads an image in which that layer is multiplied into the colour net's first
+// layer (rn_nerf_image_dev.h: nerf_folded_elem; the product is split into hi + lo like every other weight).  The f16
+// kernel keeps the layer: the reference's autocast arithmetic rounds geo_feat to fp16 between the two.
 //
 // Shared by both, once: the k-step table and hmap (the layout of the packed image), the pack kernel body, mfma16,
 // stage_sync, the launch dispatch, and (rn_fused_dev.h) the tile bookkeeping.  The two tile loops stay two __global__
 // bodies: built from one body in a __device__ function instantiated with an arithmetic policy, both kernels came out
 // with a different register allocation and schedule (the compiler simplifies a kernel differently once its parameter
 // block is handed to a callee); these kernels sit at 220-255 of 256 VGPRs, and their instruction stream is kept as it is.
-#include "rn_fused_dev.h"
+#include "rn_nerf_image_dev.h"
 
 namespace rn {
 
@@ -56,6 +59,10 @@ constexpr int KS_S2 = KS_S1 + 4;              // sigma L2 rows 1..64      : 4
 constexpr int KS_C0 = KS_S2 + 4;              // color L0, sh | geo       : 1 + 4
 constexpr int kHSteps = KS_C0 + 5;            // 23
 constexpr int kImageHalves = kHSteps * kHStep;  // one fp16 image
+// the split kernel's images have no geo_feat k-steps (folded into color L0): the f16 image's steps up to KS_S2, then
+constexpr int XKS_C0 = KS_S2;                 // color L0, sh | folded geo: 1 + 4
+constexpr int kXSteps = XKS_C0 + 5;           // 19
+constexpr int kXImageHalves = kXSteps * kHStep;
 // VALU section, fp32, after the fp16 image(s) (same [out][h][q] layout as the fp32 kernel), relative to its start:
 constexpr int NOFF_A2 = 0;                    // ambient L2
 constexpr int NOFF_S2R = NOFF_A2 + 128;       // sigma L2 row 0
@@ -72,12 +79,12 @@ constexpr int kHStageWords = 64 * kHStageRow; // per wave
 constexpr int kHXyzGroup = 2;  // xyz levels fetched together; measured with planned levels, hash19: 2 is best (+1.5 % over 1; 4: -6 %)
 constexpr int kHAmbGroup = 4;  // ambient-grid levels fetched together (each: 8 row words + 3)
 
-// split kernel: hi image followed by lo image in LDS (94.2 KB); bias and narrow layers are read from global memory
+// split kernel: hi image followed by lo image in LDS (77.8 KB); bias and narrow layers are read from global memory
 constexpr int kX2Threads = 512;               // one workgroup per CU, two waves per SIMD (one wave per SIMD: 0.152 against 0.119 ms per launch)
 constexpr int kX2Waves = kX2Threads / kWave;
-constexpr int kLoOff = kImageHalves;          // halves: the lo image follows the hi image
-constexpr int kX2MfmaFloats = kImageHalves;   // both fp16 images, counted in 4-byte units
-constexpr int kX2Packed = kX2MfmaFloats + kNarrowFloats;  // 23936 four-byte units (as large as the fp32 image)
+constexpr int kLoOff = kXImageHalves;         // halves: the lo image follows the hi image
+constexpr int kX2MfmaFloats = kXImageHalves;  // both fp16 images, counted in 4-byte units
+constexpr int kX2Packed = kX2MfmaFloats + kNarrowFloats;  // 19840 four-byte units (as large as the fp32 inference image)
 constexpr int kXStageRow = 32;                // words per sample: hi of 16 feature pairs | lo of them (enc_x, later SH)
 constexpr int kXStageWords = 64 * kXStageRow; // per wave
 constexpr int kXXyzGroup = 1;  // xyz levels fetched together (each: 16 row words + 4 in flight)
@@ -89,11 +96,13 @@ __host__ __device__ constexpr int hmap(int rt, int g, int h, int j) { return 32 
 // element e of the pack launch: one fp16 image (kSplit: hi image followed by lo image), then the fp32 narrow layers
 template <bool kSplit>
 __device__ __forceinline__ void pack_nerf_16(const RawW &w, float *__restrict__ packed) {
-    constexpr int kNarrow = (kSplit ? 2 : 1) * kImageHalves / 2;  // start of the fp32 section, in 4-byte units
+    constexpr int kHalves = kSplit ? kXImageHalves : kImageHalves;  // one fp16 image
+    constexpr int kNarrow = (kSplit ? 2 : 1) * kHalves / 2;         // start of the fp32 section, in 4-byte units
     const int e = blockIdx.x * 256 + threadIdx.x;
     const int ldA0 = 32 + (int)w.audio_dim, ldS0 = 64 + (int)w.has_eye, ldC0 = 80 + (int)w.ind_dim;
-    if (e < kImageHalves) {  // one fp16 element
-        const int ks = e / kHStep, rem = e % kHStep;
+    if (e < kHalves) {  // one fp16 element
+        const int ks0 = e / kHStep, rem = e % kHStep;
+        const int ks = (kSplit && ks0 >= XKS_C0) ? ks0 - XKS_C0 + KS_C0 : ks0;  // k-step in the f16 image's numbering
         const int rt_out = rem / 512, h = (rem % 512) / 256, i = (rem % 256) / 8, j = rem % 8;
         const int row = 32 * rt_out + i;
         const int nat = 8 * h + j;  // natural k inside a k-step
@@ -104,13 +113,16 @@ __device__ __forceinline__ void pack_nerf_16(const RawW &w, float *__restrict__ 
         else if (ks < KS_S2) { const int q = ks - KS_S1; v = w.sig_w1[row * 64 + hmap(q >> 1, q & 1, h, j)]; }
         else if (ks < KS_C0) { const int q = ks - KS_S2; v = w.sig_w2[(1 + row) * 64 + hmap(q >> 1, q & 1, h, j)]; }
         else if (ks == KS_C0) v = w.col_w0[row * ldC0 + nat];
-        else { const int q = ks - KS_C0 - 1; v = w.col_w0[row * ldC0 + 16 + hmap(q >> 1, q & 1, h, j)]; }
+        else {
+            const int q = ks - KS_C0 - 1, k = hmap(q >> 1, q & 1, h, j);
+            v = kSplit ? nerf_folded_elem(w, row, k) : w.col_w0[row * ldC0 + 16 + k];  // split: k = sigma L1's accumulators
+        }
         const _Float16 hi = (_Float16)v;
         reinterpret_cast<_Float16 *>(packed)[e] = hi;
-        if (kSplit) reinterpret_cast<_Float16 *>(packed)[kImageHalves + e] = (_Float16)(v - (float)hi);
+        if (kSplit) reinterpret_cast<_Float16 *>(packed)[kHalves + e] = (_Float16)(v - (float)hi);
         return;
     }
-    const int f = e - kImageHalves + kNarrow;  // fp32 section
+    const int f = e - kHalves + kNarrow;  // fp32 section
     if (f >= kNarrow + kNarrowFloats) return;
     auto valu_elem = [&](int base, const float *src) -> float {  // [out][h][q], q = rt*16 + r
         const int q0 = f - base, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
@@ -595,7 +607,7 @@ __global__ void __launch_bounds__(kX2Threads, 2) k_nerf_fused_x2(FusedParams p) 
             }
         }
 
-        // ---- sigma net: 65 -> 64 -> 64 -> 1 + 64
+        // ---- sigma net: 65 -> 64 -> 64 -> 1 (+ 64 geo_feat rows, folded into the colour net)
         acc_relu(a0);
         acc_zero(a1);
         xlayer_from_acc(a1, a0, wl, KS_S1, lane_off8);
@@ -606,10 +618,9 @@ __global__ void __launch_bounds__(kX2Threads, 2) k_nerf_fused_x2(FusedParams p) 
             valu_out<1>(a1, valu_w + NOFF_S2R, h, part);
             sigma = expf(h ? part[1][0] : part[0][0]);  // trunc_exp forward (activation.py:9-11)
         }
-        acc_zero(a0);
-        xlayer_from_acc(a0, a1, wl, KS_S2, lane_off8);  // geo_feat (no activation)
 
-        // ---- color net: [SH(d) | geo_feat | ind_code] 84 -> 64 -> 3, sigmoid
+        // ---- color net: [SH(d) | geo_feat | ind_code] 84 -> 64 -> 3, sigmoid; the geo_feat columns of its first layer are
+        // packed times sigma L2's geo_feat rows, so their k-steps take the sigma net's hidden activations (a1)
         stage_sync();
         {
             float sh[16];
@@ -620,17 +631,17 @@ __global__ void __launch_bounds__(kX2Threads, 2) k_nerf_fused_x2(FusedParams p) 
             for (int s = 0; s < 8; s++) stage_pair(stage, lane, s, sh[2 * s], sh[2 * s + 1]);
         }
         stage_sync();
-        acc_bias(a1, bias_col, h);
+        acc_bias(a0, bias_col, h);
         {
             Frag2 b0, b1;
             stage_frags2(stage, 0, j, h, b0, b1);
-            xstep(a1, wl, KS_C0, lane_off8, b0, b1);
+            xstep(a0, wl, XKS_C0, lane_off8, b0, b1);
         }
-        xlayer_from_acc(a1, a0, wl, KS_C0 + 1, lane_off8);
-        acc_relu(a1);
+        xlayer_from_acc(a0, a1, wl, XKS_C0 + 1, lane_off8);
+        acc_relu(a0);
         {
             float part[2][3];
-            valu_out<3>(a1, valu_w + NOFF_C1, h, part);
+            valu_out<3>(a0, valu_w + NOFF_C1, h, part);
             if (live) {
                 p.sigmas[sample] = sigma;
 #pragma unroll
@@ -663,7 +674,7 @@ void launch_pack_nerf_h16(const RawW &w, float *packed, hipStream_t s) {
     hipLaunchKernelGGL(k_pack_nerf_h16, dim3(div_up(n, 256)), dim3(256), 0, s, w, packed);
 }
 void launch_pack_nerf_x2(const RawW &w, float *packed, hipStream_t s) {
-    const int n = kImageHalves + kNarrowFloats;
+    const int n = kXImageHalves + kNarrowFloats;
     hipLaunchKernelGGL(k_pack_nerf_x2, dim3(div_up(n, 256)), dim3(256), 0, s, w, packed);
 }
 

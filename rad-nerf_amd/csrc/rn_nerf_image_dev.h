@@ -1,6 +1,7 @@
 // rn_nerf_image_dev.h -- the packed fp32 FORWARD weight image of the per-sample network and the first-layer biases of the
-// per-call constants: one layout, read by the inference kernel (k_nerf_fused, image built by k_pack_nerf) and by the
-// training network (k_train_fwd / k_train_bwd, image built by k_train_pack, which appends its transposed image).
+// per-call constants.  The training network (k_train_fwd / k_train_bwd, image built by k_train_pack, which appends its
+// transposed image) reads the layout below layer by layer; the inference kernel (k_nerf_fused, image built by k_pack_nerf)
+// reads the same layout with the geo_feat layer folded into the colour net's first layer (further down).
 #pragma once
 
 #include "rn_fused_dev.h"
@@ -50,6 +51,38 @@ __device__ __forceinline__ float nerf_image_elem(const RawW &w, int e) {
     if (e < OFF_C0) return valu_image_elem(e - OFF_S2R, w.sig_w2);                 // row 0 = sigma
     if (e < OFF_C1) return mfma_elem(e - OFF_C0, w.col_w0, ldC0, COLOR);
     return valu_image_elem(e - OFF_C1, w.col_w1);
+}
+
+// ---- inference image (floats) ---------------------------------------------------------------------------
+// sigma_net's last layer and color_net's first are both linear without a bias, and at inference nothing but the colour
+// net reads geo_feat (nerf/network.py:266-276), so W_col0[:, 16:80] (W_sig2[1:65, :] a) is ONE 64 x 64 matrix applied to
+// the sigma net's last hidden activations a.  The inference image holds that product in place of the geo_feat layer:
+// the training image up to and including sigma L1 (same offsets), then
+constexpr int IOFF_S2R = OFF_S2;                     // sigma L2 row 0 (VALU)          : [2 h][32]
+constexpr int IOFF_C0 = IOFF_S2R + 64;               // color L0 (sh | folded geo_feat): 8 + 32 steps
+constexpr int IOFF_C1 = IOFF_C0 + 40 * kStep;        // color L1 (VALU)                : [3 out][2 h][32]
+constexpr int kInferPacked = IOFF_C1 + 192;          // 19840 floats
+static_assert(kInferPacked == kPacked - 32 * kStep && kInferPacked % 4 == 0, "inference image = training image less the geo_feat layer");
+
+// (W_col0[:, 16:80] W_sig2[1:65, :])[row][k]: a 64-term sum accumulated in double and rounded once, so the image costs the
+// product one rounding, not 64.
+__device__ __forceinline__ float nerf_folded_elem(const RawW &w, int row, int k) {
+    const float *c0 = w.col_w0 + row * (80 + (int)w.ind_dim) + 16;   // this row's geo_feat columns
+    const float *s2 = w.sig_w2 + 64 + k;                             // column k of rows 1..64
+    double acc = 0.0;
+    for (int m = 0; m < 64; m++) acc += (double)c0[m] * (double)s2[m * 64];
+    return (float)acc;
+}
+
+// Element e (< kInferPacked) of the inference image.
+__device__ __forceinline__ float nerf_infer_image_elem(const RawW &w, int e) {
+    if (e < IOFF_S2R) return nerf_image_elem(w, e);
+    if (e < IOFF_C0) return nerf_image_elem(w, e - IOFF_S2R + OFF_S2R);
+    if (e >= IOFF_C1) return nerf_image_elem(w, e - IOFF_C1 + OFF_C1);
+    const int q = e - IOFF_C0, s = q / kStep;
+    if (s < 8) return nerf_image_elem(w, q + OFF_C0);   // sh steps
+    const int rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+    return nerf_folded_elem(w, 32 * rt + j, kmap(s - 8, h));   // previous accumulators = the sigma net's hidden activations
 }
 
 // Value t (< kBias) of the first-layer biases of the per-call constants: the columns of the three first layers that
