@@ -21,6 +21,8 @@ void set_error(const char *fmt, ...);
 int check_launch(const char *what);
 // compute units of the current device (256 where it cannot be asked); read once per process
 int num_cus();
+// tuning knob from the environment: the variable's value (`def` when unset) clamped to 1 .. max
+uint32_t env_uint_clamped(const char *name, uint32_t def, uint32_t max);
 // HIP-event timing of the dominant kernel (rn_prof_enable / rn_prof_collect)
 bool prof_enabled();
 void prof_pair(hipEvent_t *start, hipEvent_t *stop);

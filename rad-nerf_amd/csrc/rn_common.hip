@@ -3,6 +3,7 @@
 
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 
 #include <utility>
 #include <vector>
@@ -36,6 +37,12 @@ int num_cus() {
         if (cus <= 0) cus = 256;
     }
     return cus;
+}
+
+uint32_t env_uint_clamped(const char *name, uint32_t def, uint32_t max) {
+    const char *e = getenv(name);
+    const long v = e ? atol(e) : (long)def;
+    return (uint32_t)(v < 1 ? 1 : (v > (long)max ? (long)max : v));
 }
 
 // ---- optional HIP-event timing of one named kernel family (used by bench.py for the roofline object) ----

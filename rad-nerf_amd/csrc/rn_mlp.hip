@@ -11,23 +11,20 @@
 //                post-ReLU hidden activations are saved in that native layout (coalesced 256-B rows per register).
 //   k_mlp_bwd    the same machine run backwards: dX = W^T dY is a forward layer with the transposed weight image; ReLU
 //                masks come from the saved activations; the pre-activation gradients dZ are saved in the native layout.
-//   k_mlp_wgrad  dW = dZ X^T for every layer of the MLP in ONE launch: a wave stages a 32-sample tile of dZ and of X
-//                transposed in LDS ([feature][sample], stride 33), the sample index becomes the k of the MFMA, and the
-//                accumulators (one 32 x 32 block of dW each) stay in registers over the wave's tiles; partial sums per
-//                wave go to a workspace, k_mlp_wreduce adds them up into the nn.Linear [out, in] layout.
+//   k_mlp_wgrad  dW = dZ X^T for every layer of the MLP in ONE launch, on the weight-gradient machine of rn_wgrad_dev.h
+//                (shared with rn_train_head.hip); k_mlp_wreduce adds its per-workgroup partial sums up into the nn.Linear
+//                [out, in] layout.
 //
 // The narrow output rows (ambient 2, sigma 1, rgb 3) are VALU dot products over the accumulator registers, as in the
 // inference kernel.  fp32 throughout (exact products, fp32 accumulation): results equal torch's up to summation order.
-#include "rn_tile32_dev.h"
-
-#include <stdlib.h>
+#include "rn_wgrad_dev.h"
 
 #include "../../include/radnerf_fused.h"
 
 namespace rn {
 namespace mlp {
 
-constexpr int kThreads = 256, kWaves = kThreads / kWave;
+constexpr int kThreads = wgrad::kThreads, kWaves = kThreads / kWave;
 constexpr int kStepT = 256;  // floats per MFMA step of the input-gradient layer: [2 h][32 j][4 row tiles (3 used)]
 constexpr int kTileFloats = 2048;  // native tile: [2 rt][16 r][64 lanes]
 
@@ -162,24 +159,11 @@ __global__ void __launch_bounds__(kThreads) k_mlp_fwd(FwdArgs p) {
         }
         // `a` = input of the last layer
         float *orow = p.out + (size_t)sample * d.out_dim;
-        {
-            const float *wn = lds + d.off_ln();
 #pragma unroll
-            for (int o = 0; o < NN; o++) {
-                float s = 0.0f;
-                const float *wo = wn + (o * 2 + h) * 32;
-#pragma unroll
-                for (int g = 0; g < 8; g++) {
-                    const float4 w = *reinterpret_cast<const float4 *>(wo + 4 * g);
-                    const int rt = g >> 2, r = (g & 3) * 4;
-                    s = __builtin_fmaf(a.v[rt][r + 0], w.x, s);
-                    s = __builtin_fmaf(a.v[rt][r + 1], w.y, s);
-                    s = __builtin_fmaf(a.v[rt][r + 2], w.z, s);
-                    s = __builtin_fmaf(a.v[rt][r + 3], w.w, s);
-                }
-                s += __shfl_xor(s, 32, 64);
-                if (live && h == 0) orow[o] = s;
-            }
+        for (int o = 0; o < NN; o++) {   // the narrow rows; one valu_out per row keeps store o ahead of row o + 1 (valu_out<NN>: up to 40 more VGPRs)
+            float s[1];
+            valu_out<1>(a, lds + d.off_ln() + o * 64, h, s);
+            if (live && h == 0) orow[o] = s[0];
         }
         if constexpr (WIDE) {
             acc_zero(b);
@@ -219,7 +203,7 @@ __global__ void __launch_bounds__(kThreads) k_mlp_bwd(BwdArgs p) {
         const uint32_t sample = tile * 32 + j;
         const bool live = sample < p.M;
         const float *grow = p.grad_out + (size_t)sample * d.out_dim;
-        Acc32 g, hh, w;
+        Acc32 g, w;
         acc_zero(g);
         if constexpr (WIDE) {   // dH = Ww^T dWide
             acc_zero(w);
@@ -231,38 +215,19 @@ __global__ void __launch_bounds__(kThreads) k_mlp_bwd(BwdArgs p) {
             }
             layer_from_acc(g, w, lds + d.off_tw(), lane_off);
         }
-        {                       // + Wn^T g_narrow
-            const float *wn = lds + d.off_tn();
+        if constexpr (NN > 0) {   // + Wn^T g_narrow
+            float go[NN];
 #pragma unroll
-            for (int o = 0; o < NN; o++) {
-                const float go = live ? grow[o] : 0.0f;
-                const float *wo = wn + (o * 2 + h) * 32;
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const float4 ww = *reinterpret_cast<const float4 *>(wo + 4 * q);
-                    const int rt = q >> 2, r = (q & 3) * 4;
-                    g.v[rt][r + 0] = __builtin_fmaf(ww.x, go, g.v[rt][r + 0]);
-                    g.v[rt][r + 1] = __builtin_fmaf(ww.y, go, g.v[rt][r + 1]);
-                    g.v[rt][r + 2] = __builtin_fmaf(ww.z, go, g.v[rt][r + 2]);
-                    g.v[rt][r + 3] = __builtin_fmaf(ww.w, go, g.v[rt][r + 3]);
-                }
-            }
+            for (int o = 0; o < NN; o++) go[o] = live ? grow[o] : 0.0f;
+            valu_out_T<NN>(g, lds + d.off_tn(), h, go);
         }
-        // ReLU of the last hidden layer
-        tile_load((HID2 ? p.h1 : p.h0) + (size_t)tile * kTileFloats, hh, lane);
-#pragma unroll
-        for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) g.v[rt][r] = hh.v[rt][r] > 0.0f ? g.v[rt][r] : 0.0f;
+        relu_mask(g, (HID2 ? p.h1 : p.h0) + (size_t)tile * kTileFloats, lane);   // ReLU of the last hidden layer
         if constexpr (HID2) {
             tile_store(p.dz1 + (size_t)tile * kTileFloats, g, lane);
             acc_zero(w);
             layer_from_acc(w, g, lds + d.off_t1(), lane_off);
-            tile_load(p.h0 + (size_t)tile * kTileFloats, hh, lane);
-#pragma unroll
-            for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-                for (int r = 0; r < 16; r++) g.v[rt][r] = hh.v[rt][r] > 0.0f ? w.v[rt][r] : 0.0f;
+            relu_mask(w, p.h0 + (size_t)tile * kTileFloats, lane);
+            g = w;
         }
         tile_store(p.dz0 + (size_t)tile * kTileFloats, g, lane);
         // dX = W0^T dZ0: up to three row tiles of input features
@@ -301,7 +266,7 @@ struct Operand {
 };
 struct WJob {
     Operand a, b;
-    float *partial;             // [parts][96 * 96], this job's slice of the workspace
+    float *partial;             // [parts][wgrad::kPartial], this job's slice of the workspace
     float *out;                 // [a.rows, out_ld] nn.Linear layout
     uint32_t out_ld, out_cols;  // columns written (= b real features)
     float *out_bias;            // [a.rows]: the column of b's `ones` feature (nullable)
@@ -311,176 +276,77 @@ struct WArgs {
     WJob job[kMaxJobs];
     uint32_t n_jobs, M, parts;  // parts: workgroups per job
 };
-constexpr int kTS = 36;         // LDS row stride of a staged tile: [feature][sample parity][sample / 2] -> a lane's 16 k-steps are contiguous
-constexpr int kStageFloats = 96 * kTS;   // one operand tile: up to 96 features x 32 samples
+using wgrad::kTS;
 
-// Staging of one operand tile [feature][sample] by the whole workgroup, in two halves so that the global loads of the NEXT
-// tile are in flight while the current one is multiplied: fetch() global -> registers, commit() registers -> LDS.
+// The two operand kinds, for the pipeline of rn_wgrad_dev.h: fetch() global -> registers, commit() registers -> staged tile.
 constexpr int kFetch = 12;   // 96 features x 32 samples / 256 threads
-struct Fetched {
-    float v[kFetch];
-};
-
 template <bool NATIVE>
-__device__ __forceinline__ void fetch(Fetched &f, const Operand &op, uint32_t tile, uint32_t M) {
-    if constexpr (NATIVE) {
-        const float *src = op.p + (size_t)tile * kTileFloats;
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int q = 0; q < 8; q++) f.v[q] = src[(wave * 8 + q) * 64 + lane];
-    } else {
-        const uint32_t rows_pad = (op.rows + op.ones + 31u) & ~31u, n = rows_pad * 32u;
-#pragma unroll
-        for (int q = 0; q < kFetch; q++) {   // consecutive threads: consecutive features of one sample
-            const uint32_t e = threadIdx.x + (uint32_t)q * kThreads, s = e / rows_pad, o = e - s * rows_pad, sample = tile * 32 + s;
-            // unconditional load from a clamped address (a predicated load would be a branch with its own wait); what lies
-            // outside the operand is zeroed in commit(), so nothing here waits for the load
-            (void)n;
-            f.v[q] = op.p[(size_t)(sample < M ? sample : M - 1u) * op.ld + (o < op.rows ? o : 0u)];
-        }
-    }
-}
-
-template <bool NATIVE>
-__device__ __forceinline__ void commit(float *t, const Fetched &f, const Operand &op, uint32_t tile, uint32_t M) {
-    if constexpr (NATIVE) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const int idx = wave * 8 + q, rt = idx >> 4, r = idx & 15;
-            t[(32 * rt + rowmap(r, h)) * kTS + (j & 1) * 16 + (j >> 1)] = f.v[q];
-        }
-    } else {
-        const uint32_t rows_pad = (op.rows + op.ones + 31u) & ~31u, n = rows_pad * 32u;
-#pragma unroll
-        for (int q = 0; q < kFetch; q++) {
-            const uint32_t e = threadIdx.x + (uint32_t)q * kThreads, s = e / rows_pad, o = e - s * rows_pad;
-            const bool in_tile = tile * 32 + s < M;
-            if (e < n) t[o * kTS + (s & 1u) * 16u + (s >> 1)] = (in_tile && o < op.rows) ? f.v[q] : ((in_tile && op.ones && o == op.rows) ? 1.0f : 0.0f);
-        }
-    }
-}
-
-// One workgroup = one job x one slice of the sample tiles.  The four waves share the staged tiles; the up to 3 x 3 output
-// blocks of 32 x 32 are dealt round-robin to the waves (<= 3 each), whose accumulators stay in registers over all tiles.
-template <bool A_NATIVE, bool B_NATIVE>
-__device__ __forceinline__ void wgrad_job(const WArgs &p, const WJob &job, uint32_t part, float *lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-    const uint32_t na = (job.a.rows + job.a.ones + 31u) / 32u, nb = (job.b.rows + job.b.ones + 31u) / 32u, n_blocks = na * nb;
-    f32x16 acc[3];
-#pragma unroll
-    for (int q = 0; q < 3; q++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[q][r] = 0.0f;
-    uint32_t bx[3], by[3];   // block q of this wave: index wave + 4 q -> (x, y)
-#pragma unroll
-    for (int q = 0; q < 3; q++) { const uint32_t b = (uint32_t)wave + 4u * q; bx[q] = b / nb; by[q] = b - bx[q] * nb; }
-    const uint32_t n_tiles = (p.M + 31u) >> 5;
-    float *ta = lds, *tb = lds + kStageFloats;
-    // Tiles travel global -> registers two iterations ahead of their use (two register sets, alternating): the HBM latency
-    // of a tile that is read exactly once (~3 us) is longer than the ~1 us of MFMA work per tile.
-    Fetched fa0, fb0, fa1, fb1;
-    const uint32_t stride = p.parts;
-    if (part < n_tiles) {
-        fetch<A_NATIVE>(fa0, job.a, part, p.M);
-        fetch<B_NATIVE>(fb0, job.b, part, p.M);
-    }
-    if (part + stride < n_tiles) {
-        fetch<A_NATIVE>(fa1, job.a, part + stride, p.M);
-        fetch<B_NATIVE>(fb1, job.b, part + stride, p.M);
-    }
-    if (part < n_tiles) {
-        commit<A_NATIVE>(ta, fa0, job.a, part, p.M);
-        commit<B_NATIVE>(tb, fb0, job.b, part, p.M);
-    }
-    __syncthreads();
-    auto multiply = [&]() {
-        // k-step t of the MFMA = samples 2 t + h of the tile: 16 consecutive floats per lane and operand
-#pragma unroll
-        for (int q = 0; q < 3; q++)
-            if ((uint32_t)wave + 4u * q < n_blocks) {
-                const float4 *pa = reinterpret_cast<const float4 *>(ta + (32 * bx[q] + i) * kTS + h * 16);
-                const float4 *pb = reinterpret_cast<const float4 *>(tb + (32 * by[q] + i) * kTS + h * 16);
-                float4 av[4], bv[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) { av[u] = pa[u]; bv[u] = pb[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    acc[q] = mfma32(av[u].x, bv[u].x, acc[q]);
-                    acc[q] = mfma32(av[u].y, bv[u].y, acc[q]);
-                    acc[q] = mfma32(av[u].z, bv[u].z, acc[q]);
-                    acc[q] = mfma32(av[u].w, bv[u].w, acc[q]);
-                }
-            }
+struct Op {
+    const Operand &op;
+    uint32_t M;
+    struct Fetched {
+        float v[kFetch];
     };
-    // iteration on tile T (in LDS): registers set `cur` is free (it was committed) -> fetch T + 2 strides into it; set
-    // `cur ^ 1` holds T + 1 stride, committed after the multiply
-    for (uint32_t tile = part; tile < n_tiles; tile += 2 * stride) {
-        if (tile + 2 * stride < n_tiles) {
-            fetch<A_NATIVE>(fa0, job.a, tile + 2 * stride, p.M);
-            fetch<B_NATIVE>(fb0, job.b, tile + 2 * stride, p.M);
+    static constexpr int kMaxBlocks = 3;
+    static constexpr bool kZeroStage = false;   // a native tile has no pad features, the row-major commit() writes its pad zeros
+    __device__ __forceinline__ uint32_t blocks() const { return (op.rows + op.ones + 31u) / 32u; }
+    __device__ __forceinline__ void fetch(Fetched &f, uint32_t tile) const {
+        if constexpr (NATIVE) {
+            const float *src = op.p + (size_t)tile * kTileFloats;
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+            for (int q = 0; q < 8; q++) f.v[q] = src[(wave * 8 + q) * 64 + lane];
+        } else {
+            const uint32_t rows_pad = (op.rows + op.ones + 31u) & ~31u;
+#pragma unroll
+            for (int q = 0; q < kFetch; q++) {   // consecutive threads: consecutive features of one sample
+                const uint32_t e = threadIdx.x + (uint32_t)q * kThreads, s = e / rows_pad, o = e - s * rows_pad, sample = tile * 32 + s;
+                // unconditional load from a clamped address (a predicated load would be a branch with its own wait); what lies
+                // outside the operand is zeroed in commit(), so nothing here waits for the load
+                f.v[q] = op.p[(size_t)(sample < M ? sample : M - 1u) * op.ld + (o < op.rows ? o : 0u)];
+            }
         }
-        multiply();
-        __syncthreads();      // everybody has read this tile
-        if (tile + stride < n_tiles) {
-            commit<A_NATIVE>(ta, fa1, job.a, tile + stride, p.M);
-            commit<B_NATIVE>(tb, fb1, job.b, tile + stride, p.M);
-        }
-        __syncthreads();
-        if (tile + stride >= n_tiles) break;
-        if (tile + 3 * stride < n_tiles) {
-            fetch<A_NATIVE>(fa1, job.a, tile + 3 * stride, p.M);
-            fetch<B_NATIVE>(fb1, job.b, tile + 3 * stride, p.M);
-        }
-        multiply();
-        __syncthreads();
-        if (tile + 2 * stride < n_tiles) {
-            commit<A_NATIVE>(ta, fa0, job.a, tile + 2 * stride, p.M);
-            commit<B_NATIVE>(tb, fb0, job.b, tile + 2 * stride, p.M);
-        }
-        __syncthreads();
     }
-    // partial [row][col] of this workgroup: row = 32 x + rowmap(r, h), col = 32 y + i
-    float *dst = job.partial + (size_t)part * (96 * 96);
+    __device__ __forceinline__ void commit(float *t, const Fetched &f, uint32_t tile, uint32_t) const {
+        if constexpr (NATIVE) {
+            const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
 #pragma unroll
-    for (int q = 0; q < 3; q++)
-        if ((uint32_t)wave + 4u * q < n_blocks) {
+            for (int q = 0; q < 8; q++) {
+                const int idx = wave * 8 + q, rt = idx >> 4, r = idx & 15;
+                t[(32 * rt + rowmap(r, h)) * kTS + (j & 1) * 16 + (j >> 1)] = f.v[q];
+            }
+        } else {
+            const uint32_t rows_pad = (op.rows + op.ones + 31u) & ~31u, n = rows_pad * 32u;
 #pragma unroll
-            for (int r = 0; r < 16; r++) dst[(32 * bx[q] + rowmap(r, h)) * 96 + 32 * by[q] + i] = acc[q][r];
+            for (int q = 0; q < kFetch; q++) {
+                const uint32_t e = threadIdx.x + (uint32_t)q * kThreads, s = e / rows_pad, o = e - s * rows_pad;
+                const bool in_tile = tile * 32 + s < M;
+                if (e < n) t[o * kTS + (s & 1u) * 16u + (s >> 1)] = (in_tile && o < op.rows) ? f.v[q] : ((in_tile && op.ones && o == op.rows) ? 1.0f : 0.0f);
+            }
         }
-}
+    }
+};
 
 // the operand kinds are compile-time inside a job (three combinations occur: dZ native x x row-major, native x native,
 // grad_out row-major x native): no value of the fetch pipeline crosses a data-dependent branch
 __global__ void __launch_bounds__(kThreads, 3) k_mlp_wgrad(WArgs p) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * kStageFloats];
+    __shared__ __attribute__((aligned(16))) float lds[wgrad::kLdsFloats];
     const uint32_t jb = blockIdx.x / p.parts, part = blockIdx.x % p.parts;
     if (jb >= p.n_jobs) return;
     const WJob &job = p.job[jb];
-    if (job.a.native && job.b.native) wgrad_job<true, true>(p, job, part, lds);
-    else if (job.a.native) wgrad_job<true, false>(p, job, part, lds);
-    else wgrad_job<false, true>(p, job, part, lds);
+    const uint32_t n_tiles = (p.M + 31u) >> 5;
+    auto run = [&](const auto &a, const auto &b) { wgrad::run(a, b, n_tiles, p.M, part, p.parts, job.partial, lds); };
+    if (job.a.native && job.b.native) run(Op<true>{job.a, p.M}, Op<true>{job.b, p.M});
+    else if (job.a.native) run(Op<true>{job.a, p.M}, Op<false>{job.b, p.M});
+    else run(Op<false>{job.a, p.M}, Op<true>{job.b, p.M});
 }
 
 __global__ void __launch_bounds__(256) k_mlp_wreduce(WArgs p) {
     const uint32_t jb = blockIdx.y;
     if (jb >= p.n_jobs) return;
     const WJob &job = p.job[jb];
-    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t row = e / 96, col = e % 96;
-    const bool bias_col = job.out_bias && job.b.ones && col == job.b.rows;
-    if (row >= job.a.rows || (col >= job.out_cols && !bias_col)) return;
-    const float *src = job.partial + row * 96 + col;
-    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t q = 0;
-    for (; q + 8 <= p.parts; q += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) s[u] += src[(size_t)(q + u) * (96 * 96)];
-    }
-    for (; q < p.parts; q++) s[0] += src[(size_t)q * (96 * 96)];
-    const float total = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    if (bias_col) job.out_bias[row] = total;
-    else job.out[row * job.out_ld + col] = total;
+    wgrad::wreduce(job.partial, p.parts, blockIdx.x * 256 + threadIdx.x, job.a.rows, job.out_cols,
+                   job.out_bias && job.b.ones ? (int32_t)job.b.rows : -1, job.out, job.out_ld, job.out_bias);
 }
 
 template <typename K, typename A>
@@ -490,12 +356,7 @@ static void launch_with_lds(K kernel, dim3 grid, size_t shm, hipStream_t s, cons
 }
 constexpr uint32_t kWPartsMax = 512;  // workspace is sized for this many partial sums per job
 static uint32_t wparts() {            // workgroups (= partial sums) per weight-gradient job: 3 jobs x 256 = 3 workgroups per CU
-    static uint32_t n = 0;
-    if (!n) {
-        const char *e = getenv("RN_MLP_WPARTS");
-        const long v = e ? atol(e) : 256;
-        n = (uint32_t)(v < 1 ? 1 : (v > (long)kWPartsMax ? (long)kWPartsMax : v));
-    }
+    static const uint32_t n = env_uint_clamped("RN_MLP_WPARTS", 256, kWPartsMax);
     return n;
 }
 
@@ -515,7 +376,7 @@ size_t rn_mlp64_image_floats(uint32_t in_dim, uint32_t out_dim, uint32_t n_layer
 
 size_t rn_mlp64_tile_floats(uint32_t M) { return (size_t)((M + 31u) >> 5) * kTileFloats; }
 
-size_t rn_mlp64_wgrad_workspace(uint32_t n_layers) { return (size_t)n_layers * kWPartsMax * 96 * 96 * sizeof(float); }
+size_t rn_mlp64_wgrad_workspace(uint32_t n_layers) { return (size_t)n_layers * kWPartsMax * wgrad::kPartial * sizeof(float); }
 
 int rn_mlp64_pack(const float *w0, uint32_t ld0, const float *w1, const float *w_last, uint32_t in_dim, uint32_t out_dim, uint32_t n_layers,
                   float *image, rn_stream_t stream) {
@@ -591,7 +452,7 @@ int rn_mlp64_weight_grads(const float *x, const float *grad_out, uint32_t M, uin
     p.M = M;
     p.parts = wparts();
     float *ws = static_cast<float *>(workspace);
-    const size_t per_job = (size_t)kWPartsMax * 96 * 96;
+    const size_t per_job = (size_t)kWPartsMax * wgrad::kPartial;
     uint32_t n = 0;
     // L0: dW0 = dZ0 x^T
     p.job[n] = WJob{Operand{dz0, 1u, 0u, 64u, 0u}, Operand{x, 0u, d.in_pad, d.in_pad, grad_bias0 ? 1u : 0u}, ws + n * per_job, gw0, ld0, d.in_dim, grad_bias0};
@@ -604,7 +465,7 @@ int rn_mlp64_weight_grads(const float *x, const float *grad_out, uint32_t M, uin
     n++;
     p.n_jobs = n;
     hipLaunchKernelGGL(k_mlp_wgrad, dim3(n * p.parts), dim3(kThreads), 0, as_stream(stream), p);
-    hipLaunchKernelGGL(k_mlp_wreduce, dim3(div_up(96 * 96, 256), n), dim3(256), 0, as_stream(stream), p);
+    hipLaunchKernelGGL(k_mlp_wreduce, dim3(div_up(wgrad::kPartial, 256), n), dim3(256), 0, as_stream(stream), p);
     return check_launch("mlp64_weight_grads");
 }
 

@@ -99,6 +99,34 @@ __device__ __forceinline__ void valu_out(const Acc32 &in, const float *wl, int h
     }
 }
 
+// the backward pass of valu_out: g[k] += sum_o W[o][k] d[o] for the k's this lane holds (the transposed narrow layer)
+template <int NOUT>
+__device__ __forceinline__ void valu_out_T(Acc32 &g, const float *wl, int h, const float (&d)[NOUT]) {
+#pragma unroll
+    for (int o = 0; o < NOUT; o++) {
+        const float *wo = wl + (o * 2 + h) * 32;
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const float4 w = *reinterpret_cast<const float4 *>(wo + 4 * q);
+            const int rt = q >> 2, r = (q & 3) * 4;
+            g.v[rt][r + 0] = __builtin_fmaf(w.x, d[o], g.v[rt][r + 0]);
+            g.v[rt][r + 1] = __builtin_fmaf(w.y, d[o], g.v[rt][r + 1]);
+            g.v[rt][r + 2] = __builtin_fmaf(w.z, d[o], g.v[rt][r + 2]);
+            g.v[rt][r + 3] = __builtin_fmaf(w.w, d[o], g.v[rt][r + 3]);
+        }
+    }
+}
+// the backward pass of a ReLU: g = (saved activation > 0) ? g : 0, the saved native tile read row by row
+__device__ __forceinline__ void relu_mask(Acc32 &g, const float *__restrict__ saved, int lane) {
+    float hv[32];
+#pragma unroll
+    for (int q = 0; q < 32; q++) hv[q] = saved[q * 64 + lane];
+#pragma unroll
+    for (int rt = 0; rt < 2; rt++)
+#pragma unroll
+        for (int r = 0; r < 16; r++) g.v[rt][r] = hv[rt * 16 + r] > 0.0f ? g.v[rt][r] : 0.0f;
+}
+
 // accumulators <-> native tile
 __device__ __forceinline__ void tile_store(float *__restrict__ dst, const Acc32 &a, int lane) {
 #pragma unroll

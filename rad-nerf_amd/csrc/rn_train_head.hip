@@ -14,13 +14,13 @@
 //    come from the saved activations, tanh' / sigmoid' / trunc_exp' from the saved outputs.  The gradient with respect to
 //    the ambient coordinates (sum over levels of g * dy_dx, gridencoder.cu:342-368) is taken inside the tile.  Feature
 //    gradients of both grids leave level-major ([L, M, 2]: one coalesced 256-B row per level and lane half).
-//  * k_train_wgrad: dW = dZ X^T for all eight layers in one launch.  A workgroup stages a 32-sample tile of both operands
-//    transposed in LDS ([feature][sample]); the sample index is the k of the MFMA; accumulators stay in registers over the
-//    workgroup's tiles; per-workgroup partial sums are folded by k_train_wreduce into the nn.Linear layout.  The columns of
-//    the per-call constants (audio code, eye, individual code) ride along as one more feature that is 1 for every sample:
-//    its gradient column is the bias gradient, from which k_train_const derives the constants' and their columns' gradients.
+//  * k_train_wgrad: dW = dZ X^T for all eight layers in one launch, on the weight-gradient machine of rn_wgrad_dev.h (shared
+//    with rn_mlp.hip); k_train_wreduce folds its per-workgroup partial sums into the nn.Linear layout.  The columns of the
+//    per-call constants (audio code, eye, individual code) ride along as one more feature that is 1 for every sample: its
+//    gradient column is the bias gradient, from which k_train_const derives the constants' and their columns' gradients.
 // The table gradient of the two grids is rn_grid_scatter.hip.
 #include "rn_nerf_image_dev.h"
+#include "rn_wgrad_dev.h"
 
 #include <stdlib.h>
 
@@ -124,35 +124,6 @@ __host__ __device__ inline Ws make_ws(float *base, uint32_t M) {
     w.dsraw = p; p += nt * 32;
     w.dprec = p; p += nt * 96;
     return w;
-}
-
-// ---- MFMA helpers of the backward pass (the forward ones: rn_tile32_dev.h) ------------------------------------------------
-// g[k] += sum_o W[o][k] d[o] for the k's this lane holds (the transposed narrow layer)
-template <int NOUT>
-__device__ __forceinline__ void valu_out_T(Acc32 &g, const float *wl, int h, const float (&d)[NOUT]) {
-#pragma unroll
-    for (int o = 0; o < NOUT; o++) {
-        const float *wo = wl + (o * 2 + h) * 32;
-#pragma unroll
-        for (int q = 0; q < 8; q++) {
-            const float4 w = *reinterpret_cast<const float4 *>(wo + 4 * q);
-            const int rt = q >> 2, r = (q & 3) * 4;
-            g.v[rt][r + 0] = __builtin_fmaf(w.x, d[o], g.v[rt][r + 0]);
-            g.v[rt][r + 1] = __builtin_fmaf(w.y, d[o], g.v[rt][r + 1]);
-            g.v[rt][r + 2] = __builtin_fmaf(w.z, d[o], g.v[rt][r + 2]);
-            g.v[rt][r + 3] = __builtin_fmaf(w.w, d[o], g.v[rt][r + 3]);
-        }
-    }
-}
-// g = (saved activation > 0) ? g : 0, the saved tile read row by row
-__device__ __forceinline__ void relu_mask(Acc32 &g, const float *__restrict__ saved, int lane) {
-    float hv[32];
-#pragma unroll
-    for (int q = 0; q < 32; q++) hv[q] = saved[q * 64 + lane];
-#pragma unroll
-    for (int rt = 0; rt < 2; rt++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) g.v[rt][r] = hv[rt * 16 + r] > 0.0f ? g.v[rt][r] : 0.0f;
 }
 
 constexpr int kThreads = 512, kWaves = kThreads / kWave;   // two waves per SIMD: a 4096-ray step is ~1 tile per wave slot
@@ -596,9 +567,9 @@ __global__ void __launch_bounds__(kIgThreads) k_train_input_grads(IgParams p) {
 }
 
 // ---- weight gradients ---------------------------------------------------------------------------------------------------
-constexpr int kWThreads = 256;
-constexpr int kTS = 36;                  // LDS row stride of a staged tile: [feature][sample parity][sample / 2]
-constexpr int kStage = 96 * kTS;         // one operand tile: up to 96 features x 32 samples
+// The pipeline (staged tiles, prefetch schedule, multiply, partial store, reduce) is rn_wgrad_dev.h; here are the operands
+// of the head's eight jobs, whose layouts are known at compile time.
+using wgrad::kTS;
 constexpr int PHI_STD = 0, PHI_ENC = 1, PHI_SH = 2;
 template <int PHI>
 __device__ __forceinline__ int phi(int q, int h) {   // feature of register q, lane half h of a native tile
@@ -607,136 +578,60 @@ __device__ __forceinline__ int phi(int q, int h) {   // feature of register q, l
     else return 2 * q + h;
 }
 // An operand = [RM row-major columns | native segment 0 (R0 registers) | native segment 1 (R1 registers) | ones]
-template <int RM_, int R0_, int PHI0_, int R1_, int PHI1_, bool ONES_>
+template <int RM, int R0, int PHI0, int R1, int PHI1, bool ONES>
 struct OpT {
-    static constexpr int RM = RM_, R0 = R0_, PHI0 = PHI0_, R1 = R1_, PHI1 = PHI1_;
-    static constexpr bool ONES = ONES_;
-    static constexpr int NF = RM + 2 * R0 + 2 * R1 + (ONES ? 1 : 0);   // features
-    static constexpr int NB = (NF + 31) / 32;                          // 32-row blocks
-    static constexpr int S0 = R0 / 4, S1 = R1 / 4;                     // registers per thread (4 waves)
-};
-struct OpPtr {
     const float *rm;   // [M_pad, RM]
     const float *s0, *s1;
-};
-template <typename Op>
-struct Fetched {
-    float v0[Op::S0 > 0 ? Op::S0 : 1], v1[Op::S1 > 0 ? Op::S1 : 1], rm;
-};
-template <typename Op>
-__device__ __forceinline__ void fetch(Fetched<Op> &f, const OpPtr &o, uint32_t tile) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if constexpr (Op::S0 > 0) {
-        const float *src = o.s0 + (size_t)tile * (Op::R0 * 64);
+    static constexpr int NF = RM + 2 * R0 + 2 * R1 + (ONES ? 1 : 0);   // features
+    static constexpr int S0 = R0 / 4, S1 = R1 / 4;                     // registers per thread (4 waves)
+    static constexpr int kMaxBlocks = (NF + 31) / 32;
+    static constexpr bool kZeroStage = true;                           // commit() writes the NF real features only
+    __device__ __forceinline__ static constexpr uint32_t blocks() { return kMaxBlocks; }
+    struct Fetched {
+        float v0[S0 > 0 ? S0 : 1], v1[S1 > 0 ? S1 : 1], rm;
+    };
+    __device__ __forceinline__ void fetch(Fetched &f, uint32_t tile) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if constexpr (S0 > 0) {
+            const float *src = s0 + (size_t)tile * (R0 * 64);
 #pragma unroll
-        for (int i = 0; i < Op::S0; i++) f.v0[i] = src[(wave * Op::S0 + i) * 64 + lane];
-    }
-    if constexpr (Op::S1 > 0) {
-        const float *src = o.s1 + (size_t)tile * (Op::R1 * 64);
+            for (int i = 0; i < S0; i++) f.v0[i] = src[(wave * S0 + i) * 64 + lane];
+        }
+        if constexpr (S1 > 0) {
+            const float *src = s1 + (size_t)tile * (R1 * 64);
 #pragma unroll
-        for (int i = 0; i < Op::S1; i++) f.v1[i] = src[(wave * Op::S1 + i) * 64 + lane];
-    }
-    if constexpr (Op::RM > 0) {
-        f.rm = 0.0f;
-        if (threadIdx.x < 32 * Op::RM) f.rm = o.rm[(size_t)tile * (32 * Op::RM) + threadIdx.x];
-    }
-}
-template <typename Op>
-__device__ __forceinline__ void commit(float *t, const Fetched<Op> &f, uint32_t tile, uint32_t M) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-    const int col = (j & 1) * 16 + (j >> 1);
-    if constexpr (Op::S0 > 0) {
-#pragma unroll
-        for (int i = 0; i < Op::S0; i++) t[(Op::RM + phi<Op::PHI0>(wave * Op::S0 + i, h)) * kTS + col] = f.v0[i];
-    }
-    if constexpr (Op::S1 > 0) {
-#pragma unroll
-        for (int i = 0; i < Op::S1; i++) t[(Op::RM + 2 * Op::R0 + phi<Op::PHI1>(wave * Op::S1 + i, h)) * kTS + col] = f.v1[i];
-    }
-    if constexpr (Op::RM > 0) {
-        if (threadIdx.x < 32 * Op::RM) {
-            const int s = threadIdx.x / Op::RM, c = threadIdx.x % Op::RM;
-            t[c * kTS + (s & 1) * 16 + (s >> 1)] = f.rm;
+            for (int i = 0; i < S1; i++) f.v1[i] = src[(wave * S1 + i) * 64 + lane];
+        }
+        if constexpr (RM > 0) {
+            f.rm = 0.0f;
+            if (threadIdx.x < 32 * RM) f.rm = rm[(size_t)tile * (32 * RM) + threadIdx.x];
         }
     }
-    if constexpr (Op::ONES) {
-        if (threadIdx.x >= 64 && threadIdx.x < 96) {
-            const int s = threadIdx.x - 64;
-            t[(Op::NF - 1) * kTS + (s & 1) * 16 + (s >> 1)] = (tile * 32 + s < M) ? 1.0f : 0.0f;
+    __device__ __forceinline__ void commit(float *t, const Fetched &f, uint32_t tile, uint32_t M) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+        const int col = (j & 1) * 16 + (j >> 1);
+        if constexpr (S0 > 0) {
+#pragma unroll
+            for (int i = 0; i < S0; i++) t[(RM + phi<PHI0>(wave * S0 + i, h)) * kTS + col] = f.v0[i];
         }
-    }
-}
-
-// One workgroup = one job x one slice of the sample tiles; the NBa x NBb output blocks of 32 x 32 are dealt round-robin to
-// the 4 waves (<= 3 each), accumulators stay in registers over all tiles; tiles travel global -> registers two iterations
-// ahead of their use (the latency of a once-read tile is longer than its MFMA work).
-template <typename OpA, typename OpB>
-__device__ __forceinline__ void wgrad_job(const OpPtr &pa, const OpPtr &pb, uint32_t n_tiles, uint32_t M, uint32_t part, uint32_t parts,
-                                          float *__restrict__ partial, float *lds) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 31, h = lane >> 5;
-    constexpr int NBLK = OpA::NB * OpB::NB;
-    static_assert(NBLK <= 12, "too many output blocks");
-    constexpr int NQ = (NBLK + 3) / 4;
-    f32x16 acc[NQ];
+        if constexpr (S1 > 0) {
 #pragma unroll
-    for (int q = 0; q < NQ; q++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[q][r] = 0.0f;
-    float *ta = lds, *tb = lds + kStage;
-    for (int e = threadIdx.x; e < 2 * kStage; e += kWThreads) lds[e] = 0.0f;   // pad features stay zero
-    __syncthreads();
-    Fetched<OpA> fa0, fa1;
-    Fetched<OpB> fb0, fb1;
-    const uint32_t stride = parts;
-    if (part < n_tiles) { fetch<OpA>(fa0, pa, part); fetch<OpB>(fb0, pb, part); }
-    if (part + stride < n_tiles) { fetch<OpA>(fa1, pa, part + stride); fetch<OpB>(fb1, pb, part + stride); }
-    if (part < n_tiles) { commit<OpA>(ta, fa0, part, M); commit<OpB>(tb, fb0, part, M); }
-    __syncthreads();
-    auto multiply = [&]() {
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const int b = wave + 4 * q;
-            if (b < NBLK) {
-                const int bx = b / OpB::NB, by = b - bx * OpB::NB;
-                const float4 *qa = reinterpret_cast<const float4 *>(ta + (32 * bx + i) * kTS + h * 16);
-                const float4 *qb = reinterpret_cast<const float4 *>(tb + (32 * by + i) * kTS + h * 16);
-                float4 av[4], bv[4];
-#pragma unroll
-                for (int u = 0; u < 4; u++) { av[u] = qa[u]; bv[u] = qb[u]; }
-#pragma unroll
-                for (int u = 0; u < 4; u++) {
-                    acc[q] = mfma32(av[u].x, bv[u].x, acc[q]);
-                    acc[q] = mfma32(av[u].y, bv[u].y, acc[q]);
-                    acc[q] = mfma32(av[u].z, bv[u].z, acc[q]);
-                    acc[q] = mfma32(av[u].w, bv[u].w, acc[q]);
-                }
+            for (int i = 0; i < S1; i++) t[(RM + 2 * R0 + phi<PHI1>(wave * S1 + i, h)) * kTS + col] = f.v1[i];
+        }
+        if constexpr (RM > 0) {
+            if (threadIdx.x < 32 * RM) {
+                const int s = threadIdx.x / RM, c = threadIdx.x % RM;
+                t[c * kTS + (s & 1) * 16 + (s >> 1)] = f.rm;
             }
         }
-    };
-    for (uint32_t tile = part; tile < n_tiles; tile += 2 * stride) {
-        if (tile + 2 * stride < n_tiles) { fetch<OpA>(fa0, pa, tile + 2 * stride); fetch<OpB>(fb0, pb, tile + 2 * stride); }
-        multiply();
-        __syncthreads();
-        if (tile + stride < n_tiles) { commit<OpA>(ta, fa1, tile + stride, M); commit<OpB>(tb, fb1, tile + stride, M); }
-        __syncthreads();
-        if (tile + stride >= n_tiles) break;
-        if (tile + 3 * stride < n_tiles) { fetch<OpA>(fa1, pa, tile + 3 * stride); fetch<OpB>(fb1, pb, tile + 3 * stride); }
-        multiply();
-        __syncthreads();
-        if (tile + 2 * stride < n_tiles) { commit<OpA>(ta, fa0, tile + 2 * stride, M); commit<OpB>(tb, fb0, tile + 2 * stride, M); }
-        __syncthreads();
-    }
-    float *dst = partial + (size_t)part * (96 * 96);
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const int b = wave + 4 * q;
-        if (b < NBLK) {
-            const int bx = b / OpB::NB, by = b - bx * OpB::NB;
-#pragma unroll
-            for (int r = 0; r < 16; r++) dst[(32 * bx + rowmap(r, h)) * 96 + 32 * by + i] = acc[q][r];
+        if constexpr (ONES) {
+            if (threadIdx.x >= 64 && threadIdx.x < 96) {
+                const int s = threadIdx.x - 64;
+                t[(NF - 1) * kTS + (s & 1) * 16 + (s >> 1)] = (tile * 32 + s < M) ? 1.0f : 0.0f;
+            }
         }
     }
-}
+};
 
 constexpr int kJobs = 8;
 enum { J_A0 = 0, J_A1, J_A2, J_S0, J_S1, J_S2, J_C0, J_C1 };
@@ -753,24 +648,24 @@ struct WArgs {
     uint32_t M;
     const int32_t *m_dev;
     uint32_t parts;
-    float *partial;     // [kJobs][parts][96 * 96]
+    float *partial;     // [kJobs][parts][wgrad::kPartial]
 };
 
-__global__ void __launch_bounds__(kWThreads, 2) k_train_wgrad(WArgs p) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * kStage];
+__global__ void __launch_bounds__(wgrad::kThreads, 2) k_train_wgrad(WArgs p) {
+    __shared__ __attribute__((aligned(16))) float lds[wgrad::kLdsFloats];
     const uint32_t job = blockIdx.x / p.parts, part = blockIdx.x % p.parts;
     const uint32_t M = live_count(p.M, p.m_dev), n_tiles = (M + 31u) >> 5;
     const Ws w = make_ws(p.ws, p.M);
-    float *partial = p.partial + (size_t)job * p.parts * (96 * 96);
+    float *partial = p.partial + (size_t)job * p.parts * wgrad::kPartial;
     switch (job) {
-    case J_A0: wgrad_job<OpStd, OpEncX1>(OpPtr{nullptr, w.dza0, nullptr}, OpPtr{nullptr, w.ex, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
-    case J_A1: wgrad_job<OpStd, OpStd>(OpPtr{nullptr, w.dza1, nullptr}, OpPtr{nullptr, w.ha0, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
-    case J_A2: wgrad_job<OpRm2, OpStd>(OpPtr{w.daraw, nullptr, nullptr}, OpPtr{nullptr, w.ha1, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
-    case J_S0: wgrad_job<OpStd, OpEncXW1>(OpPtr{nullptr, w.dzs0, nullptr}, OpPtr{nullptr, w.ex, w.ew}, n_tiles, M, part, p.parts, partial, lds); break;
-    case J_S1: wgrad_job<OpStd, OpStd>(OpPtr{nullptr, w.dzs1, nullptr}, OpPtr{nullptr, w.hs0, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
-    case J_S2: wgrad_job<OpRm1Std, OpStd>(OpPtr{w.dsraw, w.dgeo, nullptr}, OpPtr{nullptr, w.hs1, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
-    case J_C0: wgrad_job<OpStd, OpShGeo1>(OpPtr{nullptr, w.dzc0, nullptr}, OpPtr{nullptr, w.sh, w.geo}, n_tiles, M, part, p.parts, partial, lds); break;
-    default: wgrad_job<OpRm3, OpStd>(OpPtr{w.dprec, nullptr, nullptr}, OpPtr{nullptr, w.hc0, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_A0: wgrad::run(OpStd{nullptr, w.dza0, nullptr}, OpEncX1{nullptr, w.ex, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_A1: wgrad::run(OpStd{nullptr, w.dza1, nullptr}, OpStd{nullptr, w.ha0, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_A2: wgrad::run(OpRm2{w.daraw, nullptr, nullptr}, OpStd{nullptr, w.ha1, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_S0: wgrad::run(OpStd{nullptr, w.dzs0, nullptr}, OpEncXW1{nullptr, w.ex, w.ew}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_S1: wgrad::run(OpStd{nullptr, w.dzs1, nullptr}, OpStd{nullptr, w.hs0, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_S2: wgrad::run(OpRm1Std{w.dsraw, w.dgeo, nullptr}, OpStd{nullptr, w.hs1, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_C0: wgrad::run(OpStd{nullptr, w.dzc0, nullptr}, OpShGeo1{nullptr, w.sh, w.geo}, n_tiles, M, part, p.parts, partial, lds); break;
+    default: wgrad::run(OpRm3{w.dprec, nullptr, nullptr}, OpStd{nullptr, w.hc0, nullptr}, n_tiles, M, part, p.parts, partial, lds); break;
     }
 }
 
@@ -787,21 +682,8 @@ struct RArgs {
 };
 __global__ void __launch_bounds__(256) k_train_wreduce(RArgs p) {
     const RJob &job = p.job[blockIdx.y];
-    const uint32_t e = blockIdx.x * 256 + threadIdx.x;
-    const uint32_t row = e / 96, col = e % 96;
-    const bool bias = job.bias_col >= 0 && (int32_t)col == job.bias_col;
-    if (row >= job.rows || (col >= job.cols && !bias)) return;
-    const float *src = p.partial + (size_t)blockIdx.y * p.parts * (96 * 96) + row * 96 + col;
-    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint32_t q = 0;
-    for (; q + 8 <= p.parts; q += 8) {
-#pragma unroll
-        for (int u = 0; u < 8; u++) s[u] += src[(size_t)(q + u) * (96 * 96)];
-    }
-    for (; q < p.parts; q++) s[0] += src[(size_t)q * (96 * 96)];
-    const float total = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
-    if (bias) job.bias_out[row] = total;
-    else job.out[row * job.ld + col] = total;
+    wgrad::wreduce(p.partial + (size_t)blockIdx.y * p.parts * wgrad::kPartial, p.parts, blockIdx.x * 256 + threadIdx.x, job.rows, job.cols,
+                   job.bias_col, job.out, job.ld, job.bias_out);
 }
 
 // The per-call constants enter the first layers as biases (k_train_pack).  With gb = the bias gradient [64]:
@@ -911,12 +793,7 @@ __global__ void __launch_bounds__(256) k_batch_gather(const float *__restrict__ 
 
 constexpr uint32_t kWPartsMax = 256;
 static uint32_t wparts() {   // workgroups (= partial sums) per weight-gradient job
-    static uint32_t n = 0;
-    if (!n) {
-        const char *e = getenv("RN_TRAIN_WPARTS");
-        const long v = e ? atol(e) : 128;          // measured at 62 k samples: 64 parts 76 us, 96: 80, 128: 71, 192: 85
-        n = (uint32_t)(v < 1 ? 1 : (v > (long)kWPartsMax ? (long)kWPartsMax : v));
-    }
+    static const uint32_t n = env_uint_clamped("RN_TRAIN_WPARTS", 128, kWPartsMax);   // measured at 62 k samples: 64 parts 76 us, 96: 80, 128: 71, 192: 85
     return n;
 }
 static int check_w(const rn_nerf_weights_t *w) {
@@ -941,7 +818,7 @@ extern "C" {
 
 size_t rn_train_head_image_floats(void) { return (size_t)kImage; }
 size_t rn_train_head_workspace_floats(uint32_t M) { return (size_t)((M + 31u) >> 5) * kWsPerTile; }
-size_t rn_train_head_wgrad_workspace(void) { return ((size_t)kJobs * kWPartsMax * 96 * 96 + 192) * sizeof(float); }
+size_t rn_train_head_wgrad_workspace(void) { return ((size_t)kJobs * kWPartsMax * wgrad::kPartial + 192) * sizeof(float); }
 
 int rn_train_head_pack(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_code, float *image,
                        rn_stream_t stream) {
@@ -1028,9 +905,9 @@ static int weight_grads(const rn_nerf_weights_t *w, const float *enc_a, const fl
     RN_REQUIRE((enc_a || w->audio_dim == 0) && (eye || !w->has_eye) && (ind_code || w->ind_dim == 0), "train_head_weight_grads: null constant");
     hipStream_t s = as_stream(stream);
     float *partial = static_cast<float *>(wgrad_workspace);
-    float *gb = partial + (size_t)kJobs * kWPartsMax * 96 * 96;
+    float *gb = partial + (size_t)kJobs * kWPartsMax * wgrad::kPartial;
     WArgs a{const_cast<float *>(workspace), M, m_dev, wparts(), partial};
-    hipLaunchKernelGGL(k_train_wgrad, dim3(kJobs * a.parts), dim3(kWThreads), 0, s, a);
+    hipLaunchKernelGGL(k_train_wgrad, dim3(kJobs * a.parts), dim3(wgrad::kThreads), 0, s, a);
     const uint32_t ldA0 = 32 + w->audio_dim, ldS0 = 64 + w->has_eye, ldC0 = 80 + w->ind_dim;
     RArgs r{};
     r.partial = partial;
@@ -1043,7 +920,7 @@ static int weight_grads(const rn_nerf_weights_t *w, const float *enc_a, const fl
     r.job[J_S2] = RJob{g->sig_w2, 65, 64, 64, -1, nullptr};
     r.job[J_C0] = RJob{g->col_w0, 64, 80, ldC0, 80, gb + 128};
     r.job[J_C1] = RJob{g->col_w1, 3, 64, 64, -1, nullptr};
-    hipLaunchKernelGGL(k_train_wreduce, dim3(div_up(96 * 96, 256), kJobs), dim3(256), 0, s, r);
+    hipLaunchKernelGGL(k_train_wreduce, dim3(div_up(wgrad::kPartial, 256), kJobs), dim3(256), 0, s, r);
     CArgs c{raw_w(w), enc_a, eye, ind_code, gb, g->amb_w0, g->sig_w0, g->col_w0, g->enc_a, g->eye, g->ind_code, ind_index, ind_rows};
     const uint32_t zero_blocks = ind_index ? (div_up(ind_rows * w->ind_dim, 1024) < 64u ? div_up(ind_rows * w->ind_dim, 1024) : 64u) : 0u;
     hipLaunchKernelGGL(k_train_const, dim3(3 + zero_blocks), dim3(256), 0, s, c);
