@@ -21,8 +21,8 @@ def _reference(x, ws):
     return x
 
 
-def _weights(dim_in, dim_out, n_layers, gen):
-    dims = [dim_in] + [64] * (n_layers - 1) + [dim_out]
+def _weights(dim_in, dim_out, n_layers, gen, hidden=64):
+    dims = [dim_in] + [hidden] * (n_layers - 1) + [dim_out]
     return [((torch.rand(dims[l + 1], dims[l], device="cuda", generator=gen) * 2 - 1) / np.sqrt(dims[l])).requires_grad_(True)
             for l in range(n_layers)]
 
@@ -68,15 +68,22 @@ def test_fused_mlp_matches_torch_autograd(hiplib, shape, M):
         _close(g, r, 1e-4)
 
 
+# the torso layer's two nets as forward_torso hands them to MLP.forward_split (nerf/network.py:188-219): freq(x) [42] resp.
+# grid [32] + freq(x) [42] vary per pixel, freq(pose) [54] + the individual code [8 / 3 / 0] are constants.  The only users of
+# dim_out = 4, of the width-32 stack zero-padded to 64, and of in_x = 42 / 74 (no multiples of 4: fused_mlp pads them)
+TORSO_SHAPES = [(42, 54 + ind, 2, 3, 64) for ind in (8, 3, 0)] + [(74, 54 + ind, 4, 3, 32) for ind in (8, 3, 0)]
+
+
 @pytest.mark.parametrize("in_x,in_c,dim_out,n_layers", [(32, 64, 2, 3), (64, 1, 65, 3), (80, 4, 3, 2), (30, 7, 65, 3)])
 @pytest.mark.parametrize("M", [33, 20011])
-def test_constant_inputs_enter_as_a_bias(hiplib, in_x, in_c, dim_out, n_layers, M):
+def test_constant_inputs_enter_as_a_bias(hiplib, in_x, in_c, dim_out, n_layers, M, hidden=64):
     """fused_mlp(x, weights, constants): the columns that are the same for every sample (audio code, eye, individual code --
     nerf/network.py:236, 262, 274 repeat them N times and concatenate) are folded into a first-layer bias; outputs and ALL
     gradients (x, the constants, every weight incl. the constant columns of the first layer) equal the concatenated formulation."""
     from radnerf import mlp_train
+    assert mlp_train.supported(in_x, dim_out, hidden, n_layers)
     gen = torch.Generator(device="cuda").manual_seed(M + in_x)
-    ws = _weights(in_x + in_c, dim_out, n_layers, gen)
+    ws = _weights(in_x + in_c, dim_out, n_layers, gen, hidden)
     x = (torch.rand(M, in_x, device="cuda", generator=gen) * 2 - 1).requires_grad_(True)
     c = (torch.rand(1, in_c, device="cuda", generator=gen) * 2 - 1).requires_grad_(True)
     gy = torch.rand(M, dim_out, device="cuda", generator=gen) * 2 - 1
@@ -88,6 +95,7 @@ def test_constant_inputs_enter_as_a_bias(hiplib, in_x, in_c, dim_out, n_layers, 
             ambiguous |= (z.abs() < 1e-5).any(1)
             z = z.clamp_min(0)
         gy[ambiguous] = 0
+        assert int(ambiguous.sum()) <= max(2, M // 50)
     y = mlp_train.fused_mlp(x, ws, c)
     grads = torch.autograd.grad(y, [x, c] + ws, gy)
     xr, cr = x.detach().clone().requires_grad_(True), c.detach().clone().requires_grad_(True)
@@ -99,6 +107,22 @@ def test_constant_inputs_enter_as_a_bias(hiplib, in_x, in_c, dim_out, n_layers, 
     for g, r in zip(grads[1:], ref[1:]):
         assert g.shape == r.shape
         _close(g, r, 1e-4)
+
+
+@pytest.mark.parametrize("in_x,in_c,dim_out,n_layers,hidden", TORSO_SHAPES)
+@pytest.mark.parametrize("M", [1, 31, 32, 33, 1024, 1057, 20011])
+def test_constant_inputs_enter_as_a_bias_at_the_torso_shapes(hiplib, in_x, in_c, dim_out, n_layers, hidden, M):
+    """The same at the shapes of torso_deform_net and torso_net, at the 32-row tile edges and at the rows from which
+    MLP.forward_split takes the kernels (1024): same bars."""
+    test_constant_inputs_enter_as_a_bias(hiplib, in_x, in_c, dim_out, n_layers, M, hidden)
+
+
+def test_torso_shapes_are_supported_only_with_their_constants_split_off(hiplib):
+    """With the constants concatenated (136 and 104 input columns) the torso nets are wider than the kernels' 96: supported()
+    must say so, and MLP.forward keeps nn.Linear for them (test_unsupported_shapes_fall_back_to_linear_layers)."""
+    from radnerf import mlp_train
+    assert not mlp_train.supported(136, 4, 32, 3) and not mlp_train.supported(104, 2, 64, 3)
+    assert mlp_train.supported(74, 4, 32, 3) and mlp_train.supported(42, 2, 64, 3)
 
 
 def test_mlp_module_uses_the_kernels_and_trains_like_the_linear_stack(hiplib, monkeypatch):
@@ -135,7 +159,8 @@ def test_unsupported_shapes_fall_back_to_linear_layers(hiplib):
 def test_torso_branch_trains_on_the_mlp_kernels(hiplib, monkeypatch):
     """nerf/network.py:188-219 under autograd (the 200 k torso iterations of the reference's schedule): torso_deform_net (width 64)
     and torso_net (width 32, zero-padded to the kernels' 64) through rn_mlp64_* give the loss and gradients of the nn.Linear
-    formulation; the launches of the HIP MLP path really are these kernels."""
+    formulation; the launches of the HIP MLP path really are these kernels.  The tight bar (float64 truth, every tile edge) now
+    lives in test_gpu_torso.py::test_forward_torso_gradients_against_float64."""
     from radnerf.scene import SyntheticScene, default_opt
     from radnerf.train import SyntheticTrainStream, train_step
     import radnerf_hip as hip
