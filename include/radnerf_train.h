@@ -155,6 +155,60 @@ int rn_train_head_loss(const float *image, const float *weights_sum, const float
 int rn_train_batch_gather(const float *table, uint32_t row_floats, const int64_t *idx, uint32_t n, const uint32_t *widths,
                           uint32_t sections, float *out, rn_stream_t stream);
 
+/*
+ * The torso layer under autograd: NeRFNetwork.forward_torso (nerf/network.py:188-219) per covered pixel -- two frequency
+ * encodings, the deformation net (104 + ind -> 64 -> 64 -> 2), x = clamp(x + dx, -1, 1), the 2-D grid (L = 16, C = 2, fp32,
+ * bound 1) with dy_dx, the torso net (136 + ind -> 32 -> 32 -> 4), sigmoid -- and the gradients of the six weight matrices, the
+ * table and the individual code.  Eight launches for a forward + backward:
+ *
+ *   rn_train_torso_pack          weight images (forward + transposed), enc_pose = freq(poses6, 4) and the first-layer biases
+ *                                W_def0[:, 42:] [enc_pose | c], W_tor0[:, 74:] [enc_pose | c]                         1 launch
+ *   rn_train_torso_forward       per 32-pixel tile on fp32 MFMA, the torso net at its true width of 32 rows         1 launch
+ *   rn_train_torso_backward      the tile walked back; feature gradients of the grid level-major [16, P, 2]         1 launch
+ *   rn_train_torso_weight_grads  the six dW = dZ X^T in one launch, a reduction, the constant columns and the code  3 launches
+ *   rn_grid_scatter_jobs         the table gradient (one D = 2 job) after a memset of grad_table                    1 + 1
+ *
+ * p_dev: device int32 live count, clipped to P; NULL = P.  Pixel rows at or past it are neither read nor written and
+ * contribute to no gradient.  P == 0: nothing is launched.  No gradient is returned for the pixel coordinates.
+ */
+/* Floats of the image rn_train_torso_pack writes: forward image | transposed image | biases [96] and enc_pose [54]. */
+size_t rn_train_torso_image_floats(void);
+/* Floats of the activation / gradient workspace for a capacity of P pixel rows (opaque; written by forward and backward,
+ * read by backward and weight_grads). */
+size_t rn_train_torso_workspace_floats(uint32_t P);
+/* Bytes of the weight-gradient workspace (partial sums of the reduction over the pixels). */
+size_t rn_train_torso_wgrad_workspace(void);
+
+/* Pack the weights (once per step: the optimizer changed them) and fold the per-call constants -- poses6 [6] and the
+ * individual code [w->ind_dim] (nullable when ind_dim == 0) -- into the first-layer biases. */
+int rn_train_torso_pack(const rn_torso_weights_t *w, const float *poses6, const float *ind_code, float *image,
+                        rn_stream_t stream);
+
+/* Forward for P pixels.  xy [P,2] in [-1, 1] (before torso_shrink).  Outputs: alpha [P,1] and color [P,3] after the sigmoid,
+ * dx [P,2] the deformation, wn [P,2] = (clamp(xy * torso_shrink + dx, -1, 1) + 1) / 2, the grid's normalised input, kept for
+ * the table scatter. */
+int rn_train_torso_forward(const float *xy, uint32_t P, const int32_t *p_dev, float torso_shrink, const rn_grid_t *grid_torso,
+                           const float *image, float *alpha, float *color, float *dx, float *wn, float *workspace,
+                           rn_stream_t stream);
+
+/* Backward.  grad_alpha [P,1], grad_color [P,3], grad_dx [P,2]: gradients of the forward's outputs, each nullable (= zeros);
+ * alpha / color: its saved outputs.  Writes grad_feat [16, P, 2], the level-major feature gradients of the grid (rows >= live
+ * count are not written: the scatter takes the same p_dev), and the pre-activation gradients into the workspace. */
+int rn_train_torso_backward(const float *grad_alpha, const float *grad_color, const float *grad_dx, const float *alpha,
+                            const float *color, uint32_t P, const int32_t *p_dev, const float *image, float *workspace,
+                            float *grad_feat, rn_stream_t stream);
+
+/* Gradients of the six weight matrices in the nn.Linear layout at full shape ([64, 96 + ind_dim], [64, 64], [2, 64],
+ * [32, 128 + ind_dim], [32, 32], [4, 32]; written, not accumulated) and of the individual code [ind_dim] (nullable when
+ * ind_dim == 0).  xy / torso_shrink / ind_code / image: the forward's. */
+typedef struct {
+    float *def_w0, *def_w1, *def_w2, *tor_w0, *tor_w1, *tor_w2;
+    float *ind_code;
+} rn_train_torso_grads_t;
+int rn_train_torso_weight_grads(const rn_torso_weights_t *w, const float *xy, float torso_shrink, const float *ind_code, uint32_t P,
+                                const int32_t *p_dev, const float *image, const float *workspace,
+                                const rn_train_torso_grads_t *grads, void *wgrad_workspace, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -567,71 +567,13 @@ __global__ void __launch_bounds__(kIgThreads) k_train_input_grads(IgParams p) {
 }
 
 // ---- weight gradients ---------------------------------------------------------------------------------------------------
-// The pipeline (staged tiles, prefetch schedule, multiply, partial store, reduce) is rn_wgrad_dev.h; here are the operands
-// of the head's eight jobs, whose layouts are known at compile time.
-using wgrad::kTS;
-constexpr int PHI_STD = 0, PHI_ENC = 1, PHI_SH = 2;
-template <int PHI>
-__device__ __forceinline__ int phi(int q, int h) {   // feature of register q, lane half h of a native tile
-    if constexpr (PHI == PHI_STD) return 32 * (q >> 4) + rowmap(q & 15, h);
-    else if constexpr (PHI == PHI_ENC) return 4 * (q >> 1) + 2 * h + (q & 1);
-    else return 2 * q + h;
-}
-// An operand = [RM row-major columns | native segment 0 (R0 registers) | native segment 1 (R1 registers) | ones]
-template <int RM, int R0, int PHI0, int R1, int PHI1, bool ONES>
-struct OpT {
-    const float *rm;   // [M_pad, RM]
-    const float *s0, *s1;
-    static constexpr int NF = RM + 2 * R0 + 2 * R1 + (ONES ? 1 : 0);   // features
-    static constexpr int S0 = R0 / 4, S1 = R1 / 4;                     // registers per thread (4 waves)
-    static constexpr int kMaxBlocks = (NF + 31) / 32;
-    static constexpr bool kZeroStage = true;                           // commit() writes the NF real features only
-    __device__ __forceinline__ static constexpr uint32_t blocks() { return kMaxBlocks; }
-    struct Fetched {
-        float v0[S0 > 0 ? S0 : 1], v1[S1 > 0 ? S1 : 1], rm;
-    };
-    __device__ __forceinline__ void fetch(Fetched &f, uint32_t tile) const {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        if constexpr (S0 > 0) {
-            const float *src = s0 + (size_t)tile * (R0 * 64);
-#pragma unroll
-            for (int i = 0; i < S0; i++) f.v0[i] = src[(wave * S0 + i) * 64 + lane];
-        }
-        if constexpr (S1 > 0) {
-            const float *src = s1 + (size_t)tile * (R1 * 64);
-#pragma unroll
-            for (int i = 0; i < S1; i++) f.v1[i] = src[(wave * S1 + i) * 64 + lane];
-        }
-        if constexpr (RM > 0) {
-            f.rm = 0.0f;
-            if (threadIdx.x < 32 * RM) f.rm = rm[(size_t)tile * (32 * RM) + threadIdx.x];
-        }
-    }
-    __device__ __forceinline__ void commit(float *t, const Fetched &f, uint32_t tile, uint32_t M) const {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
-        const int col = (j & 1) * 16 + (j >> 1);
-        if constexpr (S0 > 0) {
-#pragma unroll
-            for (int i = 0; i < S0; i++) t[(RM + phi<PHI0>(wave * S0 + i, h)) * kTS + col] = f.v0[i];
-        }
-        if constexpr (S1 > 0) {
-#pragma unroll
-            for (int i = 0; i < S1; i++) t[(RM + 2 * R0 + phi<PHI1>(wave * S1 + i, h)) * kTS + col] = f.v1[i];
-        }
-        if constexpr (RM > 0) {
-            if (threadIdx.x < 32 * RM) {
-                const int s = threadIdx.x / RM, c = threadIdx.x % RM;
-                t[c * kTS + (s & 1) * 16 + (s >> 1)] = f.rm;
-            }
-        }
-        if constexpr (ONES) {
-            if (threadIdx.x >= 64 && threadIdx.x < 96) {
-                const int s = threadIdx.x - 64;
-                t[(NF - 1) * kTS + (s & 1) * 16 + (s >> 1)] = (tile * 32 + s < M) ? 1.0f : 0.0f;
-            }
-        }
-    }
-};
+// The pipeline (staged tiles, prefetch schedule, multiply, partial store, reduce) and the operand family OpT are
+// rn_wgrad_dev.h; here are the operands of the head's eight jobs.
+using wgrad::OpT;
+using wgrad::PHI_ENC;
+using wgrad::PHI_SH;
+using wgrad::PHI_STD;
+using wgrad::RJob;
 
 constexpr int kJobs = 8;
 enum { J_A0 = 0, J_A1, J_A2, J_S0, J_S1, J_S2, J_C0, J_C1 };
@@ -669,12 +611,6 @@ __global__ void __launch_bounds__(wgrad::kThreads, 2) k_train_wgrad(WArgs p) {
     }
 }
 
-struct RJob {
-    float *out;
-    uint32_t rows, cols, ld;      // out[row * ld + col] for row < rows, col < cols
-    int32_t bias_col;             // column of the partial that is the bias gradient (-1: none)
-    float *bias_out;              // [rows]
-};
 struct RArgs {
     RJob job[kJobs];
     const float *partial;

@@ -1,0 +1,620 @@
+// rn_train_torso.hip -- the torso layer of the TRAINING step as one forward and one backward kernel (gfx950).
+//
+// C ABI: include/radnerf_train.h (rn_train_torso_*).  What is computed: NeRFNetwork.forward_torso (nerf/network.py:188-219) and
+// its autograd per covered pixel.  The machine is rn_train_head.hip's (one wavefront owns 32 pixels, v_mfma_f32_32x32x2_f32,
+// native tiles), the arithmetic k_torso_fused's (rn_torso.hip):
+//
+//  * k_train_torso_fwd: x = xy * shrink; enc_x = freq(x, 10) in registers (lane half h holds the features of coordinate h: they
+//    are the k = 2 s + h of MFMA step s); deformation net 42 (+ bias) -> 64 -> 64 -> 2; u = clamp(x + dx, -1, 1); the 16 levels of
+//    the 2-D grid with dy_dx (lane half h gathers level 2 r + h in round r); torso net 32 + 42 (+ bias) -> 32 -> 32 -> 4 on ONE row
+//    tile (its true width); sigmoid.  Saved as native tiles: the four post-ReLU hidden activations, the grid features,
+//    d enc / d wn and the clamp mask.  enc_x is recomputed where it is needed.
+//  * k_train_torso_bwd: the same tile walked back: sigmoid', the torso net transposed with ReLU masks, the feature gradients of the
+//    grid out level-major ([16, P, 2]), d wn = sum g dy_dx inside the tile, the clamp's mask, the deformation net transposed.
+//  * k_train_torso_wgrad / _wreduce / _const: the six weight gradients on the machine of rn_wgrad_dev.h; [enc_x | 1] is an operand
+//    computed from xy while a tile is staged; the column of ones gives the bias gradients, from which the gradients of the
+//    constant columns (pose encoding, individual code) and of the code follow.
+// The table gradient is rn_grid_scatter_jobs (rn_grid_scatter.hip) with one D = 2 job.
+#include "rn_fused_dev.h"
+#include "rn_wgrad_dev.h"
+
+#include "../../include/radnerf_train.h"
+
+namespace rn {
+namespace tt {
+
+constexpr int kS32 = 64;   // floats per MFMA step of a 32-row layer: [2 h][32 j]
+constexpr float kHalfPi = 3.141592653589793f / 2;
+
+// ---- the weight image of a step: forward | transposed | constants ------------------------------------------------------------
+constexpr int F_D0 = 0;                    // deform L0, 21 steps over enc_x: k = 2 s + h
+constexpr int F_D1 = F_D0 + 21 * kStep;
+constexpr int F_D2 = F_D1 + 32 * kStep;    // VALU rows [2][2 h][32]
+constexpr int F_T0 = F_D2 + 128;           // torso L0, 37 steps x 64: 16 grid steps in gather order, 21 over enc_x
+constexpr int F_T1 = F_T0 + 37 * kS32;
+constexpr int F_T2 = F_T1 + 16 * kS32;     // VALU rows [4][2 h][16]
+constexpr int kFwd = F_T2 + 128;           // 10432 floats
+constexpr int B_T2 = 0;                    // (relative to the transposed image) the narrow rows again
+constexpr int B_T1 = B_T2 + 128;           // d h_t0 = W_tor1^T dZ_t1
+constexpr int B_T0 = B_T1 + 16 * kS32;     // d grid features = W_tor0[:, 0:32]^T dZ_t0, output rows in gather order
+constexpr int B_D2 = B_T0 + 16 * kS32;
+constexpr int B_D1 = B_D2 + 128;           // d h_d0 = W_def1^T dZ_d1
+constexpr int kBwd = B_D1 + 32 * kStep;    // 6400 floats
+constexpr int C_DEF = 0, C_TOR = 64, C_POSE = 96;   // first-layer biases of the constant columns, enc_pose [54]
+constexpr int kConst = 152;
+constexpr int kImage = kFwd + kBwd + kConst;
+constexpr int kPackBlocks = (kFwd + kBwd + 255) / 256;   // workgroups of k_train_torso_pack that write weights; one more: the constants
+
+struct RawT {
+    const float *def_w0, *def_w1, *def_w2, *tor_w0, *tor_w1, *tor_w2;
+    uint32_t ind_dim;
+};
+static inline RawT raw_t(const rn_torso_weights_t *w) {
+    return RawT{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
+}
+
+// Output row j of a 32-row tile sits in register r of lane half hh with rowmap(r, hh) == j; the grid features want register
+// 2 q + c of lane half hh to be (level 2 q + hh, channel c), the order the forward gathers in: feature 4 q + 2 hh + c.
+__host__ __device__ constexpr int gather_feature(int j) {
+    const int hh = (j >> 2) & 1, r = (j & 3) + 4 * (j >> 3);
+    return 4 * (r >> 1) + 2 * hh + (r & 1);
+}
+
+// freq(poses6, 4) -> 54 values (network.py:197), the layout of k_freq_forward
+__device__ __forceinline__ float enc_pose_elem(const float *poses6, int c) {
+    if (c < 6) return poses6[c];
+    const int col = c / 6 - 1, d = c % 6, f = col / 2;
+    const float a = scalbnf(poses6[d], f);
+    return (col & 1) ? sinf(a + kHalfPi) : sinf(a);
+}
+
+__global__ void __launch_bounds__(256) k_train_torso_pack(RawT w, const float *__restrict__ poses6, const float *__restrict__ ind_code,
+                                                          float *__restrict__ image) {
+    const int ldD0 = 96 + (int)w.ind_dim, ldT0 = 128 + (int)w.ind_dim;
+    if (blockIdx.x == kPackBlocks) {
+        // the last workgroup: enc_pose once, then the constant columns [enc_pose | c] folded into the first layers as biases
+        // (network.py:201, 212).  enc_pose stays in the image: the constants' gradients need it
+        __shared__ float enc_pose[54];
+        float *c = image + kFwd + kBwd;
+        const int t = threadIdx.x;
+        if (t < 54) enc_pose[t] = enc_pose_elem(poses6, t);
+        __syncthreads();
+        if (t < C_POSE) {
+            const float *r = t < C_TOR ? w.def_w0 + (t - C_DEF) * ldD0 + 42 : w.tor_w0 + (t - C_TOR) * ldT0 + 74;
+            float acc = 0.0f;
+            for (int k = 0; k < 54; k++) acc += r[k] * enc_pose[k];
+            for (uint32_t k = 0; k < w.ind_dim; k++) acc += r[54 + k] * ind_code[k];
+            c[t] = acc;
+        } else if (t < kConst) {
+            c[t] = t < C_POSE + 54 ? enc_pose[t - C_POSE] : 0.0f;
+        }
+        return;
+    }
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= kFwd + kBwd) return;
+    float v = 0.0f;
+    if (e < F_D1) {
+        const int q = e - F_D0, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+        v = w.def_w0[(32 * rt + j) * ldD0 + 2 * s + h];
+    } else if (e < F_D2) {
+        const int q = e - F_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+        v = w.def_w1[(32 * rt + j) * 64 + kmap(s, h)];
+    } else if (e < F_T0) {
+        const int q0 = e - F_D2, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
+        v = w.def_w2[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
+    } else if (e < F_T1) {
+        const int q = e - F_T0, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
+        v = w.tor_w0[j * ldT0 + (s < 16 ? 4 * (s >> 1) + 2 * h + (s & 1) : 32 + 2 * (s - 16) + h)];
+    } else if (e < F_T2) {
+        const int q = e - F_T1, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
+        v = w.tor_w1[j * 32 + rowmap(s, h)];
+    } else if (e < kFwd) {
+        const int q0 = e - F_T2, o = q0 / 32, h = (q0 % 32) / 16, r = q0 % 16;
+        v = w.tor_w2[o * 32 + rowmap(r, h)];
+    } else {
+        const int t = e - kFwd;
+        if (t < B_T1) {
+            const int o = t / 32, h = (t % 32) / 16, r = t % 16;
+            v = w.tor_w2[o * 32 + rowmap(r, h)];
+        } else if (t < B_T0) {
+            const int q = t - B_T1, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
+            v = w.tor_w1[rowmap(s, h) * 32 + j];
+        } else if (t < B_D2) {
+            const int q = t - B_T0, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
+            v = w.tor_w0[rowmap(s, h) * ldT0 + gather_feature(j)];
+        } else if (t < B_D1) {
+            const int q0 = t - B_D2, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
+            v = w.def_w2[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
+        } else {
+            const int q = t - B_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+            v = w.def_w1[kmap(s, h) * 64 + 32 * rt + j];
+        }
+    }
+    image[e] = v;
+}
+
+// ---- workspace: native tiles ([registers][64 lanes] floats per 32-pixel tile) and per-pixel rows -------------------------------
+struct Ws {
+    float *hd0, *hd1;          // deformation net, post-ReLU, 32 registers
+    float *ht0, *ht1;          // torso net, post-ReLU, 16 registers
+    float *eg;                 // grid features, 16 registers: register 2 q + c of half h = level 2 q + h, channel c
+    float *dw;                 // d enc / d wn, 32 registers: 4 q + 2 d + c of half h
+    float *mask;               // the clamp passes the gradient of coordinate d: 2 registers (both halves alike)
+    float *dzd0, *dzd1, *dzt0, *dzt1;   // pre-activation gradients (backward)
+    float *ddx, *dto;          // [P_pad, 2], [P_pad, 4]: gradients of the narrow layers' outputs
+};
+constexpr uint32_t kTile32 = 32 * 64, kTile16 = 16 * 64, kTile2 = 2 * 64;
+constexpr uint32_t kWsPerTile = 4 * kTile32 + 4 * kTile16 + kTile16 + kTile32 + kTile2 + 32 * 6;
+
+__host__ __device__ inline Ws make_ws(float *base, uint32_t P) {
+    const size_t nt = (P + 31u) >> 5;
+    Ws w;
+    float *p = base;
+    w.hd0 = p; p += nt * kTile32;
+    w.hd1 = p; p += nt * kTile32;
+    w.dzd0 = p; p += nt * kTile32;
+    w.dzd1 = p; p += nt * kTile32;
+    w.dw = p; p += nt * kTile32;
+    w.ht0 = p; p += nt * kTile16;
+    w.ht1 = p; p += nt * kTile16;
+    w.dzt0 = p; p += nt * kTile16;
+    w.dzt1 = p; p += nt * kTile16;
+    w.eg = p; p += nt * kTile16;
+    w.mask = p; p += nt * kTile2;
+    w.ddx = p; p += nt * 64;
+    w.dto = p; p += nt * 128;
+    return w;
+}
+
+// 32-row layers: one row tile of 16 registers
+__device__ __forceinline__ void store16(float *__restrict__ dst, const f32x16 &a, int lane) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) dst[r * 64 + lane] = a[r];
+}
+__device__ __forceinline__ void relu_mask16(f32x16 &g, const float *__restrict__ saved, int lane) {
+    float hv[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) hv[r] = saved[r * 64 + lane];
+#pragma unroll
+    for (int r = 0; r < 16; r++) g[r] = hv[r] > 0.0f ? g[r] : 0.0f;
+}
+__device__ __forceinline__ f32x16 zero16() {
+    f32x16 a;
+#pragma unroll
+    for (int r = 0; r < 16; r++) a[r] = 0.0f;
+    return a;
+}
+
+constexpr int kThreads = 256, kWaves = kThreads / kWave;   // a 4096-ray torso step is ~41 tiles: spread them over many CUs
+
+struct FwdParams {
+    const float *xy;
+    uint32_t P;
+    const int32_t *p_dev;
+    float shrink;
+    GridArgs gt;
+    const float *image;
+    float *alpha, *color, *dx, *wn;
+    float *ws;
+};
+
+__global__ void __launch_bounds__(kThreads) k_train_torso_fwd(FwdParams p) {
+    __shared__ __attribute__((aligned(16))) float lds[kFwd + C_POSE];
+    __shared__ LevelPlan plan_t[16];
+    const uint32_t P = live_count(p.P, p.p_dev);
+    const uint32_t n_tiles = (P + 31u) >> 5;
+    if (blockIdx.x * kWaves >= n_tiles) return;
+    for (int i = threadIdx.x; i < kFwd / 4; i += kThreads) reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image)[i];
+    if (threadIdx.x < C_POSE) lds[kFwd + threadIdx.x] = p.image[kFwd + kBwd + threadIdx.x];
+    if (threadIdx.x < 16) {
+        const int t = threadIdx.x;
+        const uint32_t o = (uint32_t)p.gt.offsets[t];
+        plan_t[t] = plan_level<2>(p.gt.lc.scale[t], p.gt.lc.resolution[t], o, (uint32_t)p.gt.offsets[t + 1] - o, p.gt.gridtype, 8u);
+    }
+    __syncthreads();
+    const Ws ws = make_ws(p.ws, p.P);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int lane_off = h * 64 + j * 2, lane_off32 = h * 32 + j;
+    const float *bias_def = lds + kFwd + C_DEF, *bias_tor = lds + kFwd + C_TOR;
+    const float *table = static_cast<const float *>(p.gt.table);
+
+    for (uint32_t tile = blockIdx.x * kWaves + wave; tile < n_tiles; tile += gridDim.x * kWaves) {
+        const uint32_t px = tile * 32 + j;   // both lane halves work on the same 32 pixels
+        const bool live = px < P;
+        // x = x * torso_shrink; enc_x = freq(x, 10) (network.py:194, 198): [x, sin(2^f x), cos(2^f x)]_f.  Feature 2 s + h
+        // belongs to coordinate h for every s: a lane computes the 21 features of its half's coordinate
+        float x0 = 0.0f, x1 = 0.0f;
+        if (live) { x0 = p.xy[2 * (size_t)px] * p.shrink; x1 = p.xy[2 * (size_t)px + 1] * p.shrink; }
+        float fq[21];
+        {
+            const float xs = h ? x1 : x0;
+            fq[0] = xs;
+#pragma unroll
+            for (int f = 0; f < 10; f++) {
+                const float a = scalbnf(xs, f);
+                fq[1 + 2 * f] = sinf(a);
+                fq[2 + 2 * f] = sinf(a + kHalfPi);
+            }
+        }
+        // ---- deformation net: [enc_x | enc_pose | c] -> 64 -> 64 -> 2
+        Acc32 a0, a1;
+        acc_bias(a0, bias_def, h);
+#pragma unroll
+        for (int s = 0; s < 21; s++) step32(a0, lds + F_D0, s, lane_off, fq[s]);
+        acc_relu(a0);
+        tile_store(ws.hd0 + (size_t)tile * kTile32, a0, lane);
+        acc_zero(a1);
+        layer_from_acc(a1, a0, lds + F_D1, lane_off);
+        acc_relu(a1);
+        tile_store(ws.hd1 + (size_t)tile * kTile32, a1, lane);
+        float dxy[2];
+        valu_out<2>(a1, lds + F_D2, h, dxy);
+        // ---- x = clamp(x + dx, -1, 1); the torso grid (bound = 1) with d enc / d input
+        f32x16 t0;
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const float4 b = *reinterpret_cast<const float4 *>(bias_tor + 8 * g + 4 * h);
+            t0[4 * g] = b.x; t0[4 * g + 1] = b.y; t0[4 * g + 2] = b.z; t0[4 * g + 3] = b.w;
+        }
+        {
+            const float u0 = x0 + dxy[0], u1 = x1 + dxy[1];
+            float in[2] = {(fminf(fmaxf(u0, -1.0f), 1.0f) + 1.0f) / 2.0f, (fminf(fmaxf(u1, -1.0f), 1.0f) + 1.0f) / 2.0f};
+            const bool on = live && !(in[0] < 0 || in[0] > 1 || in[1] < 0 || in[1] > 1);
+            if (live && h == 0) {
+                p.dx[2 * (size_t)px] = dxy[0];
+                p.dx[2 * (size_t)px + 1] = dxy[1];
+                p.wn[2 * (size_t)px] = in[0];
+                p.wn[2 * (size_t)px + 1] = in[1];
+            }
+            float *mk = ws.mask + (size_t)tile * kTile2;   // torch's clamp passes the gradient on [-1, 1], the ends included
+            mk[lane] = (u0 >= -1.0f && u0 <= 1.0f) ? 1.0f : 0.0f;
+            mk[64 + lane] = (u1 >= -1.0f && u1 <= 1.0f) ? 1.0f : 0.0f;
+            float *eg = ws.eg + (size_t)tile * kTile16, *dw = ws.dw + (size_t)tile * kTile32;
+            LevelFetch<float, 2, 2> f;
+#pragma unroll 1
+            for (int r = 0; r < 8; r++) {
+                float f0 = 0.0f, f1 = 0.0f, g[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (on) {
+                    issue_planned<float, 2, 2, false, false>(table, plan_t[2 * r + h], in, f);
+                    float res[2], grads[4];
+                    blend_level<float, 2, 2, true>(f, plan_t[2 * r + h].scale, res, grads);
+                    f0 = res[0];
+                    f1 = res[1];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) g[q] = grads[q];
+                }
+                t0 = mfma32(lds[F_T0 + (2 * r) * kS32 + lane_off32], f0, t0);
+                t0 = mfma32(lds[F_T0 + (2 * r + 1) * kS32 + lane_off32], f1, t0);
+                eg[(2 * r) * 64 + lane] = f0;
+                eg[(2 * r + 1) * 64 + lane] = f1;
+#pragma unroll
+                for (int q = 0; q < 4; q++) dw[(4 * r + q) * 64 + lane] = g[q];
+            }
+        }
+        // ---- torso net: [grid | enc_x | enc_pose | c] -> 32 -> 32 -> 4, sigmoid
+#pragma unroll
+        for (int s = 0; s < 21; s++) t0 = mfma32(lds[F_T0 + (16 + s) * kS32 + lane_off32], fq[s], t0);
+#pragma unroll
+        for (int r = 0; r < 16; r++) t0[r] = relu_bits(t0[r]);
+        store16(ws.ht0 + (size_t)tile * kTile16, t0, lane);
+        f32x16 t1 = zero16();
+#pragma unroll
+        for (int s = 0; s < 16; s++) t1 = mfma32(lds[F_T1 + s * kS32 + lane_off32], t0[s], t1);
+#pragma unroll
+        for (int r = 0; r < 16; r++) t1[r] = relu_bits(t1[r]);
+        store16(ws.ht1 + (size_t)tile * kTile16, t1, lane);
+        float o4[4];
+#pragma unroll
+        for (int o = 0; o < 4; o++) {
+            float s = 0.0f;
+            const float *wo = lds + F_T2 + (o * 2 + h) * 16;
+#pragma unroll
+            for (int r = 0; r < 16; r++) s = __builtin_fmaf(t1[r], wo[r], s);
+            o4[o] = s + __shfl_xor(s, 32, 64);
+        }
+        if (live && h == 0) {
+            p.alpha[px] = 1.0f / (1.0f + expf(-o4[0]));
+#pragma unroll
+            for (int c = 0; c < 3; c++) p.color[3 * (size_t)px + c] = 1.0f / (1.0f + expf(-o4[1 + c]));
+        }
+    }
+}
+
+struct BwdParams {
+    const float *g_alpha, *g_color, *g_dx;   // each may be null
+    const float *alpha, *color;
+    uint32_t P;
+    const int32_t *p_dev;
+    const float *image;
+    float *ws;
+    float *g_feat;   // [16, P, 2]
+};
+
+__global__ void __launch_bounds__(kThreads) k_train_torso_bwd(BwdParams p) {
+    __shared__ __attribute__((aligned(16))) float lds[kBwd];
+    const uint32_t P = live_count(p.P, p.p_dev);
+    const uint32_t n_tiles = (P + 31u) >> 5;
+    if (blockIdx.x * kWaves >= n_tiles) return;
+    for (int i = threadIdx.x; i < kBwd / 4; i += kThreads)
+        reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image + kFwd)[i];
+    __syncthreads();
+    const Ws ws = make_ws(p.ws, p.P);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int lane_off = h * 64 + j * 2, lane_off32 = h * 32 + j;
+
+    for (uint32_t tile = blockIdx.x * kWaves + wave; tile < n_tiles; tile += gridDim.x * kWaves) {
+        const uint32_t px = tile * 32 + j;
+        const bool live = px < P;
+        // ---- torso net: sigmoid', last layer transposed, ReLU masks
+        f32x16 g = zero16();
+        {
+            float d[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (live) {
+                if (p.g_alpha) {
+                    const float y = p.alpha[px];
+                    d[0] = p.g_alpha[px] * ((1.0f - y) * y);
+                }
+                if (p.g_color) {
+#pragma unroll
+                    for (int c = 0; c < 3; c++) {
+                        const float y = p.color[3 * (size_t)px + c];
+                        d[1 + c] = p.g_color[3 * (size_t)px + c] * ((1.0f - y) * y);
+                    }
+                }
+            }
+            if (h == 0) {
+#pragma unroll
+                for (int o = 0; o < 4; o++) ws.dto[4 * (size_t)px + o] = d[o];
+            }
+#pragma unroll
+            for (int o = 0; o < 4; o++) {
+                const float *wo = lds + B_T2 + (o * 2 + h) * 16;
+#pragma unroll
+                for (int r = 0; r < 16; r++) g[r] = __builtin_fmaf(wo[r], d[o], g[r]);
+            }
+        }
+        relu_mask16(g, ws.ht1 + (size_t)tile * kTile16, lane);
+        store16(ws.dzt1 + (size_t)tile * kTile16, g, lane);
+        f32x16 w = zero16();
+#pragma unroll
+        for (int s = 0; s < 16; s++) w = mfma32(lds[B_T1 + s * kS32 + lane_off32], g[s], w);
+        relu_mask16(w, ws.ht0 + (size_t)tile * kTile16, lane);
+        store16(ws.dzt0 + (size_t)tile * kTile16, w, lane);
+        // d grid features: register 2 q + c of half h = (level 2 q + h, channel c); nothing flows back into enc_x
+        f32x16 xg = zero16();
+#pragma unroll
+        for (int s = 0; s < 16; s++) xg = mfma32(lds[B_T0 + s * kS32 + lane_off32], w[s], xg);
+        // ---- the grid: feature gradients out (level-major), input gradient = sum_l g . dy_dx (gridencoder.cu:342-368); the
+        // encoder sees (u + 1) / 2 (gridencoder/grid.py:151, bound = 1): a factor 1/2 on the way back
+        float da[2] = {0.0f, 0.0f};
+        {
+            const float *dw = ws.dw + (size_t)tile * kTile32;
+#pragma unroll
+            for (int q = 0; q < 8; q++) {
+                const float g0 = xg[2 * q], g1 = xg[2 * q + 1];
+                const float d00 = dw[(4 * q + 0) * 64 + lane], d01 = dw[(4 * q + 1) * 64 + lane];
+                const float d10 = dw[(4 * q + 2) * 64 + lane], d11 = dw[(4 * q + 3) * 64 + lane];
+                da[0] = __builtin_fmaf(g0, d00, da[0]); da[0] = __builtin_fmaf(g1, d01, da[0]);
+                da[1] = __builtin_fmaf(g0, d10, da[1]); da[1] = __builtin_fmaf(g1, d11, da[1]);
+                if (live) *reinterpret_cast<float2 *>(p.g_feat + ((size_t)(2 * q + h) * p.P + px) * 2) = make_float2(g0, g1);
+            }
+            da[0] += __shfl_xor(da[0], 32, 64);
+            da[1] += __shfl_xor(da[1], 32, 64);
+        }
+        // ---- the clamp (passes where -1 <= x + dx <= 1), + the direct gradient of dx; deformation net transposed
+        Acc32 gd, wd;
+        {
+            float d[2] = {0.0f, 0.0f};
+            if (live) {
+                const float *mk = ws.mask + (size_t)tile * kTile2;
+                d[0] = mk[lane] != 0.0f ? 0.5f * da[0] : 0.0f;
+                d[1] = mk[64 + lane] != 0.0f ? 0.5f * da[1] : 0.0f;
+                if (p.g_dx) { d[0] += p.g_dx[2 * (size_t)px]; d[1] += p.g_dx[2 * (size_t)px + 1]; }
+            }
+            if (h == 0) { ws.ddx[2 * (size_t)px] = d[0]; ws.ddx[2 * (size_t)px + 1] = d[1]; }
+            acc_zero(gd);
+            valu_out_T<2>(gd, lds + B_D2, h, d);
+        }
+        relu_mask(gd, ws.hd1 + (size_t)tile * kTile32, lane);
+        tile_store(ws.dzd1 + (size_t)tile * kTile32, gd, lane);
+        acc_zero(wd);
+        layer_from_acc(wd, gd, lds + B_D1, lane_off);
+        relu_mask(wd, ws.hd0 + (size_t)tile * kTile32, lane);
+        tile_store(ws.dzd0 + (size_t)tile * kTile32, wd, lane);
+    }
+}
+
+// ---- weight gradients ---------------------------------------------------------------------------------------------------
+// The pipeline and the operand family OpT are rn_wgrad_dev.h; here are the operands of the torso's six jobs.
+using wgrad::OpT;
+using wgrad::PHI_ENC;
+using wgrad::PHI_STD;
+using wgrad::RJob;
+
+constexpr int kJobs = 6;
+enum { J_D0 = 0, J_D1, J_D2, J_T0, J_T1, J_T2 };
+typedef OpT<0, 32, PHI_STD, 0, 0, false> OpN64;            // a 64-feature native tile
+typedef OpT<0, 16, PHI_STD, 0, 0, false> OpN32;            // a 32-feature native tile
+typedef OpT<2, 0, 0, 0, 0, false> OpRm2;
+typedef OpT<4, 0, 0, 0, 0, false> OpRm4;
+typedef OpT<0, 0, 0, 0, 0, true, true> OpFreq1;            // [enc_x | 1], enc_x computed from xy
+typedef OpT<0, 16, PHI_ENC, 0, 0, true, true> OpEncFreq1;  // [grid | enc_x | 1]
+
+struct WArgs {
+    float *ws;
+    const float *xy;
+    float shrink;
+    uint32_t P;
+    const int32_t *p_dev;
+    uint32_t parts;
+    float *partial;     // [kJobs][parts][wgrad::kPartial]
+};
+
+__global__ void __launch_bounds__(wgrad::kThreads, 2) k_train_torso_wgrad(WArgs p) {
+    __shared__ __attribute__((aligned(16))) float lds[wgrad::kLdsFloats];
+    const uint32_t job = blockIdx.x / p.parts, part = blockIdx.x % p.parts;
+    const uint32_t M = live_count(p.P, p.p_dev), n_tiles = (M + 31u) >> 5;
+    const Ws w = make_ws(p.ws, p.P);
+    float *partial = p.partial + (size_t)job * p.parts * wgrad::kPartial;
+    auto nat64 = [&](const float *s) { return OpN64{nullptr, s}; };
+    auto nat32 = [&](const float *s) { return OpN32{nullptr, s}; };
+    switch (job) {
+    case J_D0: wgrad::run(nat64(w.dzd0), OpFreq1{nullptr, nullptr, nullptr, p.xy, p.shrink, M}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_D1: wgrad::run(nat64(w.dzd1), nat64(w.hd0), n_tiles, M, part, p.parts, partial, lds); break;
+    case J_D2: wgrad::run(OpRm2{w.ddx}, nat64(w.hd1), n_tiles, M, part, p.parts, partial, lds); break;
+    case J_T0: wgrad::run(nat32(w.dzt0), OpEncFreq1{nullptr, w.eg, nullptr, p.xy, p.shrink, M}, n_tiles, M, part, p.parts, partial, lds); break;
+    case J_T1: wgrad::run(nat32(w.dzt1), nat32(w.ht0), n_tiles, M, part, p.parts, partial, lds); break;
+    default: wgrad::run(OpRm4{w.dto}, nat32(w.ht1), n_tiles, M, part, p.parts, partial, lds); break;
+    }
+}
+
+struct RArgs {
+    RJob job[kJobs];
+    const float *partial;
+    uint32_t parts;
+};
+__global__ void __launch_bounds__(256) k_train_torso_wreduce(RArgs p) {
+    const RJob &job = p.job[blockIdx.y];
+    wgrad::wreduce(p.partial + (size_t)blockIdx.y * p.parts * wgrad::kPartial, p.parts, blockIdx.x * 256 + threadIdx.x, job.rows, job.cols,
+                   job.bias_col, job.out, job.ld, job.bias_out);
+}
+
+// The constant columns [enc_pose | c] entered the first layers as biases (k_train_torso_pack).  With b_def [64] / b_tor [32] the
+// bias gradients:  gW_def0[:, 42:] = b_def (x) [enc_pose | c],  gW_tor0[:, 74:] = b_tor (x) [enc_pose | c],
+//                  g_c = W_def0[:, 96:]^T b_def + W_tor0[:, 128:]^T b_tor
+struct CArgs {
+    RawT w;
+    const float *enc_pose, *ind_code;
+    const float *gb;    // b_def [64] | b_tor [32]
+    float *g_d0, *g_t0, *g_c;
+};
+__global__ void __launch_bounds__(256) k_train_torso_const(CArgs p) {
+    const uint32_t n = 54 + p.w.ind_dim, ldD0 = 96 + p.w.ind_dim, ldT0 = 128 + p.w.ind_dim;
+    if (blockIdx.x < 2) {
+        const bool is_def = blockIdx.x == 0;
+        const uint32_t rows = is_def ? 64 : 32, ld = is_def ? ldD0 : ldT0, c0 = is_def ? 42 : 74;
+        const float *gb = p.gb + (is_def ? 0 : 64);
+        float *gW = is_def ? p.g_d0 : p.g_t0;
+        for (uint32_t e = threadIdx.x; e < rows * n; e += 256) {
+            const uint32_t u = e / n, a = e - u * n;
+            gW[u * ld + c0 + a] = gb[u] * (a < 54 ? p.enc_pose[a] : p.ind_code[a - 54]);
+        }
+    } else if (p.g_c) {
+        for (uint32_t a = threadIdx.x; a < p.w.ind_dim; a += 256) {
+            float s = 0.0f;
+            for (uint32_t u = 0; u < 64; u++) s += p.w.def_w0[u * ldD0 + 96 + a] * p.gb[u];
+            for (uint32_t u = 0; u < 32; u++) s += p.w.tor_w0[u * ldT0 + 128 + a] * p.gb[64 + u];
+            p.g_c[a] = s;
+        }
+    }
+}
+
+constexpr uint32_t kWPartsMax = 128;
+constexpr uint32_t kBlocksMax = 1u << 16;
+// workgroups of the forward / backward launch: one per kWaves tiles, at most one round of two per CU; RN_TORSO_TRAIN_BLOCKS caps
+// it further (read at every launch: a test runs the grid-stride loop at a small P with it)
+static uint32_t tile_blocks(uint32_t P) {
+    const uint32_t n_tiles = (P + 31u) >> 5;
+    uint32_t blocks = div_up(n_tiles, kWaves);
+    const uint32_t cap = 2u * (uint32_t)num_cus();
+    if (blocks > cap) blocks = cap;
+    const uint32_t knob = env_uint_clamped("RN_TORSO_TRAIN_BLOCKS", kBlocksMax, kBlocksMax);
+    return blocks < knob ? blocks : knob;
+}
+static uint32_t wparts(uint32_t P) {   // workgroups (= partial sums) per weight-gradient job: never more than tiles
+    static const uint32_t n = env_uint_clamped("RN_TORSO_TRAIN_WPARTS", 64, kWPartsMax);
+    const uint32_t n_tiles = (P + 31u) >> 5;
+    return n < n_tiles ? n : n_tiles;
+}
+static int check_w(const rn_torso_weights_t *w, const char *what) {
+    RN_REQUIRE(w && w->def_w0 && w->def_w1 && w->def_w2 && w->tor_w0 && w->tor_w1 && w->tor_w2, "%s: null weight pointer", what);
+    return RN_OK;
+}
+static int check_grid(const rn_grid_t *g, const char *what) {
+    RN_REQUIRE(g && g->embeddings && g->offsets, "%s: torso grid is null", what);
+    RN_REQUIRE(g->D == 2 && g->L == 16 && g->dtype == RN_F32, "%s: torso grid must be D=2, L=16, fp32 with C=2", what);
+    return RN_OK;
+}
+
+}  // namespace tt
+}  // namespace rn
+
+using namespace rn;
+using namespace rn::tt;
+
+extern "C" {
+
+size_t rn_train_torso_image_floats(void) { return (size_t)kImage; }
+size_t rn_train_torso_workspace_floats(uint32_t P) { return (size_t)((P + 31u) >> 5) * kWsPerTile; }
+size_t rn_train_torso_wgrad_workspace(void) { return ((size_t)kJobs * kWPartsMax * wgrad::kPartial + 128) * sizeof(float); }
+
+int rn_train_torso_pack(const rn_torso_weights_t *w, const float *poses6, const float *ind_code, float *image, rn_stream_t stream) {
+    if (int rc = check_w(w, "train_torso_pack")) return rc;
+    RN_REQUIRE(poses6 && image, "train_torso_pack: null pointer");
+    RN_REQUIRE(ind_code || w->ind_dim == 0, "train_torso_pack: null pointer (ind_code with ind_dim > 0)");
+    RN_REQUIRE(((uintptr_t)image & 15u) == 0, "train_torso_pack: image must be 16-byte aligned");
+    hipLaunchKernelGGL(k_train_torso_pack, dim3(kPackBlocks + 1), dim3(256), 0, as_stream(stream), raw_t(w), poses6, ind_code, image);
+    return check_launch("train_torso_pack");
+}
+
+int rn_train_torso_forward(const float *xy, uint32_t P, const int32_t *p_dev, float torso_shrink, const rn_grid_t *grid_torso,
+                           const float *image, float *alpha, float *color, float *dx, float *wn, float *workspace,
+                           rn_stream_t stream) {
+    if (P == 0) return RN_OK;
+    if (int rc = check_grid(grid_torso, "train_torso_forward")) return rc;
+    RN_REQUIRE(xy && image && alpha && color && dx && wn && workspace, "train_torso_forward: null pointer");
+    RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_torso_forward: image / workspace must be 16-byte aligned");
+    RN_REQUIRE(((uintptr_t)grid_torso->embeddings & 7u) == 0, "train_torso_forward: the table must be 8-byte aligned");
+    RN_REQUIRE(torso_shrink > 0.0f, "train_torso_forward: torso_shrink must be positive");
+    FwdParams p{xy, P, p_dev, torso_shrink, grid_args(grid_torso), image, alpha, color, dx, wn, workspace};
+    hipLaunchKernelGGL(k_train_torso_fwd, dim3(tile_blocks(P)), dim3(kThreads), 0, as_stream(stream), p);
+    return check_launch("train_torso_forward");
+}
+
+int rn_train_torso_backward(const float *grad_alpha, const float *grad_color, const float *grad_dx, const float *alpha,
+                            const float *color, uint32_t P, const int32_t *p_dev, const float *image, float *workspace,
+                            float *grad_feat, rn_stream_t stream) {
+    if (P == 0) return RN_OK;
+    RN_REQUIRE(alpha && color && image && workspace && grad_feat, "train_torso_backward: null pointer");
+    RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_torso_backward: image / workspace must be 16-byte aligned");
+    RN_REQUIRE(((uintptr_t)grad_feat & 7u) == 0, "train_torso_backward: feature gradients must be 8-byte aligned");
+    BwdParams p{grad_alpha, grad_color, grad_dx, alpha, color, P, p_dev, image, workspace, grad_feat};
+    hipLaunchKernelGGL(k_train_torso_bwd, dim3(tile_blocks(P)), dim3(kThreads), 0, as_stream(stream), p);
+    return check_launch("train_torso_backward");
+}
+
+int rn_train_torso_weight_grads(const rn_torso_weights_t *w, const float *xy, float torso_shrink, const float *ind_code, uint32_t P,
+                                const int32_t *p_dev, const float *image, const float *workspace,
+                                const rn_train_torso_grads_t *g, void *wgrad_workspace, rn_stream_t stream) {
+    if (P == 0) return RN_OK;
+    if (int rc = check_w(w, "train_torso_weight_grads")) return rc;
+    RN_REQUIRE(xy && image && workspace && g && wgrad_workspace, "train_torso_weight_grads: null pointer");
+    RN_REQUIRE(g->def_w0 && g->def_w1 && g->def_w2 && g->tor_w0 && g->tor_w1 && g->tor_w2, "train_torso_weight_grads: null gradient pointer");
+    RN_REQUIRE(w->ind_dim == 0 || (ind_code && g->ind_code), "train_torso_weight_grads: null pointer (ind_code with ind_dim > 0)");
+    RN_REQUIRE(((uintptr_t)workspace & 15u) == 0 && ((uintptr_t)wgrad_workspace & 15u) == 0,
+               "train_torso_weight_grads: workspaces must be 16-byte aligned");
+    RN_REQUIRE(torso_shrink > 0.0f, "train_torso_weight_grads: torso_shrink must be positive");
+    hipStream_t s = as_stream(stream);
+    float *partial = static_cast<float *>(wgrad_workspace);
+    float *gb = partial + (size_t)kJobs * kWPartsMax * wgrad::kPartial;
+    WArgs a{const_cast<float *>(workspace), xy, torso_shrink, P, p_dev, wparts(P), partial};
+    hipLaunchKernelGGL(k_train_torso_wgrad, dim3(kJobs * a.parts), dim3(wgrad::kThreads), 0, s, a);
+    const uint32_t ldD0 = 96 + w->ind_dim, ldT0 = 128 + w->ind_dim;
+    RArgs r{};
+    r.partial = partial;
+    r.parts = a.parts;
+    r.job[J_D0] = RJob{g->def_w0, 64, 42, ldD0, 42, gb};
+    r.job[J_D1] = RJob{g->def_w1, 64, 64, 64, -1, nullptr};
+    r.job[J_D2] = RJob{g->def_w2, 2, 64, 64, -1, nullptr};
+    r.job[J_T0] = RJob{g->tor_w0, 32, 74, ldT0, 74, gb + 64};
+    r.job[J_T1] = RJob{g->tor_w1, 32, 32, 32, -1, nullptr};
+    r.job[J_T2] = RJob{g->tor_w2, 4, 32, 32, -1, nullptr};
+    hipLaunchKernelGGL(k_train_torso_wreduce, dim3(div_up(wgrad::kPartial, 256), kJobs), dim3(256), 0, s, r);
+    CArgs c{raw_t(w), image + kFwd + kBwd + C_POSE, ind_code, gb, g->def_w0, g->tor_w0, w->ind_dim ? g->ind_code : nullptr};
+    hipLaunchKernelGGL(k_train_torso_const, dim3(3), dim3(256), 0, s, c);
+    return check_launch("train_torso_weight_grads");
+}
+
+}  // extern "C"

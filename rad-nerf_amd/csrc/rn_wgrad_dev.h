@@ -1,5 +1,6 @@
 // rn_wgrad_dev.h -- the weight-gradient machine of training, shared by the fused head (k_train_wgrad / k_train_wreduce,
-// rn_train_head.hip) and the per-MLP kernels (k_mlp_wgrad / k_mlp_wreduce, rn_mlp.hip).
+// rn_train_head.hip), the fused torso (k_train_torso_wgrad / k_train_torso_wreduce, rn_train_torso.hip) and the per-MLP
+// kernels (k_mlp_wgrad / k_mlp_wreduce, rn_mlp.hip).
 //
 // A job is dW[o][i] = sum over samples of A[o][s] * B[i][s] with up to 96 features per operand.  One workgroup of 256
 // threads = one job x one slice of the 32-sample tiles (part, part + parts, ...).  It stages a tile of both operands
@@ -16,8 +17,8 @@
 //   kMaxBlocks, blocks()             32-row blocks: compile-time bound and actual count (a constant where the type knows it)
 //   fetch(f, tile)                   global -> registers
 //   commit(t, f, tile, M)            registers -> staged tile t; M = live samples (rows past it stage as zeros)
-// The two families: OpT<...> of rn_train_head.hip (layout known at compile time) and Op<NATIVE> of rn_mlp.hip (run-time
-// native tile / row-major matrix).
+// The two families: OpT<...> below (layout known at compile time: the fused head, rn_train_head.hip, and the fused torso,
+// rn_train_torso.hip) and Op<NATIVE> of rn_mlp.hip (run-time native tile / row-major matrix).
 #pragma once
 
 #include "rn_tile32_dev.h"
@@ -104,6 +105,109 @@ __device__ __forceinline__ void run(const OpA oa, const OpB ob, uint32_t n_tiles
         }
     }
 }
+
+// ---- operands whose layout is known at compile time (the fused training kernels) ------------------------------------------------
+constexpr int PHI_STD = 0, PHI_ENC = 1, PHI_SH = 2;
+template <int PHI>
+__device__ __forceinline__ int phi(int q, int h) {   // feature of register q, lane half h of a native tile
+    if constexpr (PHI == PHI_STD) return 32 * (q >> 4) + rowmap(q & 15, h);
+    else if constexpr (PHI == PHI_ENC) return 4 * (q >> 1) + 2 * h + (q & 1);
+    else return 2 * q + h;
+}
+// An operand = [RM row-major columns | native segment 0 (R0 registers) | native segment 1 (R1 registers) |
+//               FREQ: freq(xy * shrink, 10), 42 features computed while the tile is staged | ONES: a column of ones]
+template <int RM, int R0, int PHI0, int R1, int PHI1, bool ONES, bool FREQ = false>
+struct OpT {
+    const float *rm;   // [M_pad, RM]
+    const float *s0, *s1;
+    const float *xy;   // FREQ: [M, 2]; rows at or past `live` are not read
+    float shrink;
+    uint32_t live;
+    static constexpr int kFreq = 42, kFreq0 = RM + 2 * R0 + 2 * R1;                 // features of freq(., 10) on 2 coordinates
+    static constexpr int NF = kFreq0 + (FREQ ? kFreq : 0) + (ONES ? 1 : 0);         // features
+    static constexpr int S0 = R0 / 4, S1 = R1 / 4;                                  // registers per thread (4 waves)
+    static constexpr int kMaxBlocks = (NF + 31) / 32;
+    static constexpr bool kZeroStage = true;                                        // commit() writes the NF real features only
+    __device__ __forceinline__ static constexpr uint32_t blocks() { return kMaxBlocks; }
+    struct Fetched {
+        float v0[S0 > 0 ? S0 : 1], v1[S1 > 0 ? S1 : 1], rm, x0, x1;
+    };
+    __device__ __forceinline__ void fetch(Fetched &f, uint32_t tile) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if constexpr (S0 > 0) {
+            const float *src = s0 + (size_t)tile * (R0 * 64);
+#pragma unroll
+            for (int i = 0; i < S0; i++) f.v0[i] = src[(wave * S0 + i) * 64 + lane];
+        }
+        if constexpr (S1 > 0) {
+            const float *src = s1 + (size_t)tile * (R1 * 64);
+#pragma unroll
+            for (int i = 0; i < S1; i++) f.v1[i] = src[(wave * S1 + i) * 64 + lane];
+        }
+        if constexpr (RM > 0) {
+            f.rm = 0.0f;
+            if (threadIdx.x < 32 * RM) f.rm = rm[(size_t)tile * (32 * RM) + threadIdx.x];
+        }
+        if constexpr (FREQ) {   // thread t: sample t % 32 of the tile, features t / 32, t / 32 + 8, ...
+            const uint32_t row = tile * 32 + (threadIdx.x & 31);
+            f.x0 = 0.0f;
+            f.x1 = 0.0f;
+            if (row < live) { f.x0 = xy[2 * (size_t)row] * shrink; f.x1 = xy[2 * (size_t)row + 1] * shrink; }
+        }
+    }
+    // The native and row-major segments are committed as they were saved, without a test against M: the contract (rows past
+    // M stage as zeros) holds for them because their producers keep it.  The backward kernels write exact zeros into every
+    // gradient row of a dead sample of the last tile, and the forward kernels compute finite activations for dead samples
+    // (from zero inputs), so a dead row contributes 0 x finite.  A producer that leaves such rows unwritten, or writes
+    // Inf / NaN into a dead activation row, breaks the weight gradients silently.
+    __device__ __forceinline__ void commit(float *t, const Fetched &f, uint32_t tile, uint32_t M) const {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+        const int col = (j & 1) * 16 + (j >> 1);
+        if constexpr (S0 > 0) {
+#pragma unroll
+            for (int i = 0; i < S0; i++) t[(RM + phi<PHI0>(wave * S0 + i, h)) * kTS + col] = f.v0[i];
+        }
+        if constexpr (S1 > 0) {
+#pragma unroll
+            for (int i = 0; i < S1; i++) t[(RM + 2 * R0 + phi<PHI1>(wave * S1 + i, h)) * kTS + col] = f.v1[i];
+        }
+        if constexpr (RM > 0) {
+            if (threadIdx.x < 32 * RM) {
+                const int s = threadIdx.x / RM, c = threadIdx.x % RM;
+                t[c * kTS + (s & 1) * 16 + (s >> 1)] = f.rm;
+            }
+        }
+        if constexpr (FREQ) {   // the forward's arithmetic (k_torso_fused): scalbnf, sinf(a + pi / 2) for the cosine
+            const int s = threadIdx.x & 31, c0 = threadIdx.x >> 5;
+            const bool on = tile * 32 + s < M;
+            float *dst = t + kFreq0 * kTS + (s & 1) * 16 + (s >> 1);
+            for (int c = c0; c < kFreq; c += 8) {
+                float v;
+                if (c < 2) v = c ? f.x1 : f.x0;
+                else {
+                    const int q = c - 2;
+                    const float a = scalbnf((q & 1) ? f.x1 : f.x0, q >> 2);
+                    v = (q & 2) ? sinf(a + 3.141592653589793f / 2) : sinf(a);
+                }
+                dst[c * kTS] = on ? v : 0.0f;
+            }
+        }
+        if constexpr (ONES) {   // its gradient column is the bias gradient
+            if (threadIdx.x >= 64 && threadIdx.x < 96) {
+                const int s = threadIdx.x - 64;
+                t[(NF - 1) * kTS + (s & 1) * 16 + (s >> 1)] = (tile * 32 + s < M) ? 1.0f : 0.0f;
+            }
+        }
+    }
+};
+
+// One job of a reduce launch (wreduce() below): where the sum of a job's partials goes
+struct RJob {
+    float *out;
+    uint32_t rows, cols, ld;      // out[row * ld + col] for row < rows, col < cols
+    int32_t bias_col;             // column of the partial that is the bias gradient (-1: none)
+    float *bias_out;              // [rows]
+};
 
 // Element e = row * 96 + col of a job: the sum of its `parts` partials goes to out[row * ld + col] (row < rows, col < cols),
 // or to bias_out[row] when col is bias_col (< 0: the job has none).

@@ -92,6 +92,7 @@ _MLP_KERNELS = []
 _AUDIO_KERNELS = []
 _TRAIN_GLUE = []
 _TRAIN_HEAD = []
+_TRAIN_TORSO = []
 
 
 def _train_head():
@@ -103,6 +104,18 @@ def _train_head():
         from . import train_head
         _TRAIN_HEAD.append(train_head)
     return _TRAIN_HEAD[0]
+
+
+def _train_torso():
+    """radnerf.train_torso when RN_TORSO_TRAIN=fused asks for it (the torso layer as one forward + one backward kernel; needs the
+    HIP library and a GPU), else None: the default path imports nothing."""
+    import os
+    if os.environ.get("RN_TORSO_TRAIN") != "fused" or not torch.cuda.is_available():
+        return None
+    if not _TRAIN_TORSO:
+        from . import train_torso
+        _TRAIN_TORSO.append(train_torso)
+    return _TRAIN_TORSO[0]
 
 
 def _train_glue():
@@ -248,6 +261,10 @@ class NeRFNetwork(NeRFRenderer):
 
     def forward_torso(self, x, poses, enc_a, c=None):
         # nerf/network.py:188-219; x: [N,2] in [-1,1], poses: [1,6], c: [ind_dim_torso]
+        tt = _train_torso()
+        if tt is not None and tt.usable(self, x):
+            # opt-in (RN_TORSO_TRAIN=fused): the whole layer as one forward and one backward kernel (radnerf/train_torso.py)
+            return tt.torso_forward(self, x, poses, c)
         x = x * self.opt.torso_shrink
         enc_pose = self.pose_encoder(poses)
         enc_x = self.torso_deform_encoder(x)

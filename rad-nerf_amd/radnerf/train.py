@@ -189,7 +189,10 @@ def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, am
             w = amb_weight if amb_weight is not None else torch.full((1,), min(global_step / iters, 1.0) * lambda_amb, device=pred.device)
             loss = train_glue.train_loss(pred, rgb, out["weights_sum"], out["ambient"], face if face.dtype == torch.float32 else face.float(), w)
             return pred, rgb, loss
-    loss = torch.nn.functional.mse_loss(pred, rgb, reduction="none").mean(-1).mean()
+    # the torso prediction is [n, 3], its target [1, n, 3]: the same values without the broadcast (and its warning); a target
+    # of another size is an error (reshape raises), not something to broadcast
+    target = rgb.reshape(pred.shape) if torso else rgb
+    loss = torch.nn.functional.mse_loss(pred, target, reduction="none").mean(-1).mean()
     if torso:
         loss = loss + 1e-4 * entropy_of(out["torso_alpha"]).mean()
     else:

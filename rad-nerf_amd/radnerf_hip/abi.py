@@ -84,6 +84,11 @@ class ScatterJobT(C.Structure):
     _fields_ = [("grad", _ptr), ("inputs", _ptr), ("grid", _P(GridT)), ("offsets_host", _ptr), ("grad_table", _ptr)]
 
 
+class TorsoGradsT(C.Structure):
+    c_name = "rn_train_torso_grads_t"
+    _fields_ = [(n, _ptr) for n in ("def_w0", "def_w1", "def_w2", "tor_w0", "tor_w1", "tor_w2", "ind_code")]
+
+
 # name -> (restype, argtypes).  rn_stream_t and pointers to device or host buffers are void *; pointers to the structs above
 # are typed, as are the few host arrays the callers hand over as ctypes objects.
 FUNCTIONS = {
@@ -213,6 +218,14 @@ FUNCTIONS = {
     "rn_train_head_loss": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _ptr, _ptr, _ptr,
                                   _ptr, _ptr]),
     "rn_train_batch_gather": (_int, [_ptr, _u32, _ptr, _u32, C.POINTER(_u32), _u32, _ptr, _ptr]),
+    "rn_train_torso_image_floats": (_sz, []),
+    "rn_train_torso_workspace_floats": (_sz, [_u32]),
+    "rn_train_torso_wgrad_workspace": (_sz, []),
+    "rn_train_torso_pack": (_int, [_P(TorsoWeightsT), _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_torso_forward": (_int, [_ptr, _u32, _ptr, _f32, _P(GridT), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_torso_backward": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_torso_weight_grads": (_int, [_P(TorsoWeightsT), _ptr, _f32, _ptr, _u32, _ptr, _ptr, _ptr, _P(TorsoGradsT), _ptr,
+                                           _ptr]),
 }
 
 
