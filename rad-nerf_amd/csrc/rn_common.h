@@ -35,6 +35,11 @@ void prof_pair(hipEvent_t *start, hipEvent_t *stop);
     } while (0)
 
 static inline uint32_t div_up(uint32_t a, uint32_t b) { return (a + b - 1) / b; }
+// workgroups of a launch whose waves walk n_tiles tiles with a grid stride: one per `waves` tiles, at most `per_cu` on each CU
+static inline uint32_t tile_blocks(uint32_t n_tiles, uint32_t waves, uint32_t per_cu) {
+    const uint32_t blocks = div_up(n_tiles, waves), cap = per_cu * (uint32_t)num_cus();
+    return blocks < cap ? blocks : cap;
+}
 static inline hipStream_t as_stream(rn_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 #define RN_REQUIRE(cond, ...)                 \

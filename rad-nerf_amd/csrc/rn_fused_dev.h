@@ -1,9 +1,10 @@
 // rn_fused_dev.h -- pieces shared by the translation units of the fused inference path: the fp32-MFMA (rn_fused.hip) and
 // the 16-bit-MFMA (rn_fused_f16.hip) variants of the per-sample network kernel, the device-resident frame loop
-// (rn_head_loop.hip) and the torso pass (rn_torso.hip); the training network (rn_train_head.hip) reuses the parameter
-// pieces.  Here: 64-sample accumulator tiles and their VALU output layers (the 32-sample ones are in rn_tile32_dev.h), the
-// raw weight and grid descriptors, kernel parameter blocks, the tile bookkeeping (sample count, slot / liveness of an
-// entry, direction load) and the launch dispatch.
+// (rn_head_loop.hip) and the torso pass (rn_torso.hip); the training kernels (rn_train_head.hip, rn_train_torso.hip)
+// reuse the parameter pieces and the grid check.  Here: 64-sample accumulator tiles and their VALU output layers (the
+// 32-sample ones are in rn_tile32_dev.h), the raw weight and grid descriptors of the per-sample network (the torso layer's:
+// rn_torso_dev.h), kernel parameter blocks, the tile bookkeeping (sample count, slot / liveness of an entry, direction
+// load) and the launch dispatch.
 #pragma once
 
 #include "rn_dda_dev.h"
@@ -203,6 +204,13 @@ static inline void dispatch_grid_dtypes(int gx_dtype, int gw_dtype, F &&f) {
     else if (gx_dtype == RN_F16 && gw_dtype == RN_F16) f(__half{}, __half{});
     else if (gx_dtype == RN_F32) f(float{}, __half{});
     else f(__half{}, float{});
+}
+
+// The grid check of the training entries (rn_train_head.hip, rn_train_torso.hip): `what` names the entry and the grid
+static inline int check_train_grid(const rn_grid_t *g, uint32_t D, const char *what) {
+    RN_REQUIRE(g && g->embeddings && g->offsets, "%s grid is null", what);
+    RN_REQUIRE(g->D == D && g->L == 16 && g->dtype == RN_F32, "%s grid must be D=%u, L=16, fp32 with C=2", what, D);
+    return RN_OK;
 }
 
 // Host side of the network launch (rn_fused.hip): the frame loop and the torso pass check their grids the same way, and

@@ -412,10 +412,7 @@ int rn_mlp64_forward(const float *x, uint32_t M, const float *image, const float
     RN_REQUIRE(x && image && out && h0 && (n_layers == 2 || h1), "mlp64_forward: null pointer");
     RN_REQUIRE(((uintptr_t)x & 7u) == 0 && ((uintptr_t)image & 15u) == 0, "mlp64_forward: x must be 8-byte, image 16-byte aligned");
     FwdArgs p{x, M, image, d, out, h0, h1, bias0};
-    const uint32_t n_tiles = (M + 31u) >> 5;
-    uint32_t blocks = div_up(n_tiles, kWaves);
-    const uint32_t cap = (uint32_t)num_cus() * 2u;
-    if (blocks > cap) blocks = cap;
+    const uint32_t blocks = tile_blocks((M + 31u) >> 5, kWaves, 2);
     const size_t shm = (size_t)d.fwd_floats() * sizeof(float);
     RN_MLP_DISPATCH(k_mlp_fwd, dim3(blocks), shm, as_stream(stream), p);
     return check_launch("mlp64_forward");
@@ -430,10 +427,7 @@ int rn_mlp64_backward(const float *grad_out, uint32_t M, const float *image, uin
     RN_REQUIRE(((uintptr_t)grad_x & 15u) == 0 && ((uintptr_t)image & 15u) == 0, "mlp64_backward: grad_x / image must be 16-byte aligned");
     BwdArgs p{grad_out, M, image + d.fwd_floats(), d, h0, h1, grad_x, dz0, dz1};
     RN_REQUIRE((d.fwd_floats() & 3u) == 0, "mlp64_backward: internal image alignment");
-    const uint32_t n_tiles = (M + 31u) >> 5;
-    uint32_t blocks = div_up(n_tiles, kWaves);
-    const uint32_t cap = (uint32_t)num_cus() * 2u;
-    if (blocks > cap) blocks = cap;
+    const uint32_t blocks = tile_blocks((M + 31u) >> 5, kWaves, 2);
     const size_t shm = (size_t)d.bwd_floats() * sizeof(float);
     RN_MLP_DISPATCH(k_mlp_bwd, dim3(blocks), shm, as_stream(stream), p);
     return check_launch("mlp64_backward");

@@ -1,5 +1,6 @@
 // rn_tile32_dev.h -- the fp32 matrix-core machine on 32-sample tiles, shared by the inference kernel (rn_fused.hip), the
-// fused training network (rn_train_head.hip) and the per-MLP training kernels (rn_mlp.hip).
+// fused training network (rn_train_head.hip), the torso layer (rn_torso.hip, rn_train_torso.hip) and the per-MLP training
+// kernels (rn_mlp.hip).
 //
 // One wavefront owns 32 samples.  v_mfma_f32_32x32x2_f32 puts the output row on the register index and the sample on the
 // lane, so the accumulators of a 64-row layer (two row tiles of 16 registers) ARE the B operand of the next layer; the k
@@ -21,6 +22,8 @@ __host__ __device__ constexpr int kmap(int s, int h) { return 32 * (s >> 4) + ro
 
 // floats per MFMA step of a 64-row layer in a packed weight image: [2 h][32 j][2 row tiles] -> lane (j, h) reads one float2
 constexpr int kStep = 128;
+// the same for a 32-row layer (one row tile): [2 h][32 j] -> lane (j, h) reads one float
+constexpr int kS32 = 64;
 
 // max(x, 0) as ONE v_max_i32 on the bit pattern (a non-negative float is a non-negative integer, a negative one a negative
 // integer); fmaxf(x, 0) costs two VALU instructions because IEEE mode first quiets a possible signalling NaN.
@@ -139,6 +142,25 @@ __device__ __forceinline__ void tile_load(const float *__restrict__ src, Acc32 &
     for (int rt = 0; rt < 2; rt++)
 #pragma unroll
         for (int r = 0; r < 16; r++) a.v[rt][r] = src[(rt * 16 + r) * 64 + lane];
+}
+
+// ---- 32-row layers: one row tile of 16 registers
+__device__ __forceinline__ f32x16 zero16() {
+    f32x16 a;
+#pragma unroll
+    for (int r = 0; r < 16; r++) a[r] = 0.0f;
+    return a;
+}
+__device__ __forceinline__ void store16(float *__restrict__ dst, const f32x16 &a, int lane) {
+#pragma unroll
+    for (int r = 0; r < 16; r++) dst[r * 64 + lane] = a[r];
+}
+__device__ __forceinline__ void relu_mask16(f32x16 &g, const float *__restrict__ saved, int lane) {
+    float hv[16];
+#pragma unroll
+    for (int r = 0; r < 16; r++) hv[r] = saved[r * 64 + lane];
+#pragma unroll
+    for (int r = 0; r < 16; r++) g[r] = hv[r] > 0.0f ? g[r] : 0.0f;
 }
 
 }  // namespace rn

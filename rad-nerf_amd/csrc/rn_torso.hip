@@ -4,7 +4,7 @@
 // nerf/network.py:188-219 per background pixel, and the blend of renderer.py:306-311.  k_torso_fused keeps the older
 // 64-sample form of the fused network kernel: two column tiles per wave on v_mfma_f32_32x32x2_f32, one v_permlane32_swap
 // per feature pair to build both B operands; the weights sit in LDS, the per-frame inputs enter as accumulator biases.
-#include "rn_fused_dev.h"
+#include "rn_torso_dev.h"
 
 namespace rn {
 
@@ -34,56 +34,16 @@ __device__ __forceinline__ void to_b_operands(float f0, float f1, float &b0, flo
 // ==========================================================================================================
 // Torso pass (nerf/renderer.py:269-299, nerf/network.py:188-219) and final blend (renderer.py:306-311)
 //
-// Packed torso image: deform L0 (21 steps, freq(x) part) | deform L1 (32 steps) | deform L2 VALU [2][2][32]
-//                     | torso L0 (37 steps x 64: grid 16 + freq 21, 32 rows) | torso L1 (16 steps x 64)
-//                     | torso L2 VALU [4][2][16] | raw broadcast columns for the bias: def [64][54+ind], tor [32][54+ind]
+// The packed weight image and the constant columns are rn_torso_dev.h's; k_torso_fused reads the grid steps of torso L0 in
+// level order.
 #ifndef RN_TORSO_GROUP
 #define RN_TORSO_GROUP 2
 #endif
 constexpr int kTorsoGroup = RN_TORSO_GROUP;  // torso-grid levels gathered together (divides 16)
-constexpr int kTStep32 = 64;  // floats per MFMA step of a 32-row layer ([2 h][32 j])
-constexpr int TOFF_D0 = 0;
-constexpr int TOFF_D1 = TOFF_D0 + 21 * kStep;
-constexpr int TOFF_D2 = TOFF_D1 + 32 * kStep;
-constexpr int TOFF_T0 = TOFF_D2 + 128;
-constexpr int TOFF_T1 = TOFF_T0 + 37 * kTStep32;
-constexpr int TOFF_T2 = TOFF_T1 + 16 * kTStep32;
-constexpr int kTorsoPacked = TOFF_T2 + 128;  // 10320 floats
-constexpr int kTorsoBias = 96;               // deform 64 | torso 32
-
-struct RawT {
-    const float *def_w0, *def_w1, *def_w2, *tor_w0, *tor_w1, *tor_w2;
-    uint32_t ind_dim;
-};
-
-// k index of a 32-wide hidden vector held in one accumulator row tile
-__host__ __device__ constexpr int kmap32(int s, int h) { return rowmap(s & 15, h); }
 
 __global__ void __launch_bounds__(256) k_pack_torso(RawT w, float *__restrict__ packed) {
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= kTorsoPacked) return;
-    const int ldD0 = 96 + (int)w.ind_dim, ldT0 = 128 + (int)w.ind_dim;
-    float v;
-    if (e < TOFF_D1) {  // deform L0: k = 2s + h over freq(x) (42)
-        const int q = e - TOFF_D0, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
-        v = w.def_w0[(32 * rt + j) * ldD0 + 2 * s + h];
-    } else if (e < TOFF_D2) {
-        const int q = e - TOFF_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
-        v = w.def_w1[(32 * rt + j) * 64 + kmap(s, h)];
-    } else if (e < TOFF_T0) {
-        const int q0 = e - TOFF_D2, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
-        v = w.def_w2[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
-    } else if (e < TOFF_T1) {  // torso L0: steps 0..15 grid (cols 0..31), 16..36 freq(x) (cols 32..73)
-        const int q = e - TOFF_T0, s = q / kTStep32, rem = q % kTStep32, h = rem / 32, j = rem % 32;
-        v = w.tor_w0[j * ldT0 + 2 * s + h];
-    } else if (e < TOFF_T2) {
-        const int q = e - TOFF_T1, s = q / kTStep32, rem = q % kTStep32, h = rem / 32, j = rem % 32;
-        v = w.tor_w1[j * 32 + kmap32(s, h)];
-    } else {
-        const int q0 = e - TOFF_T2, o = q0 / 32, h = (q0 % 32) / 16, r = q0 % 16;
-        v = w.tor_w2[o * 32 + rowmap(r, h)];
-    }
-    packed[e] = v;
+    if (e < kTorsoPacked) packed[e] = torso_image_elem<false>(w, e);
 }
 
 struct BlendArgs {   // final blend folded into the torso pass (renderer.py:306-311; rn_torso_blend_frame)
@@ -156,31 +116,10 @@ __global__ void __launch_bounds__(kFusedThreads, 2) k_torso_fused(TorsoParams p)
 
     for (int i = threadIdx.x; i < kTorsoPacked / 4; i += kFusedThreads)
         reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.packed)[i];
-    // enc_pose = freq(poses6, deg 4) -> 54 values (network.py:197), same layout as k_freq_forward
-    if (threadIdx.x < 54) {
-        const int c = threadIdx.x;
-        float v;
-        if (c < 6) v = p.poses6[c];
-        else {
-            const int col = c / 6 - 1, d = c % 6, f = col / 2;
-            const float a = scalbnf(p.poses6[d], f);
-            v = (col & 1) ? sinf(a + 3.141592653589793f / 2) : sinf(a);
-        }
-        enc_pose[c] = v;
-    }
+    if (threadIdx.x < 54) enc_pose[threadIdx.x] = enc_pose_elem(p.poses6, threadIdx.x);
     __syncthreads();
-    // broadcast columns: deform [42 .. 96+ind), torso [74 .. 128+ind)  (network.py:201, 212)
-    if (threadIdx.x < 96) {
-        const int t = threadIdx.x;
-        const bool is_def = t < 64;
-        const int row = is_def ? t : t - 64;
-        const int ld = (is_def ? 96 : 128) + (int)p.w.ind_dim;
-        const float *r = (is_def ? p.w.def_w0 : p.w.tor_w0) + row * ld + (is_def ? 42 : 74);
-        float acc = 0.0f;
-        for (int k = 0; k < 54; k++) acc += r[k] * enc_pose[k];
-        for (uint32_t c = 0; c < p.w.ind_dim; c++) acc += r[54 + c] * p.ind_code[c];
-        (is_def ? bias_def : bias_tor)[row] = acc;
-    }
+    // the constant columns as biases: deform 64 | torso 32
+    if (threadIdx.x < kTorsoBias) bias_def[threadIdx.x] = torso_const_bias(p.w, enc_pose, p.ind_code, threadIdx.x);
     __syncthreads();
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -216,11 +155,11 @@ __global__ void __launch_bounds__(kFusedThreads, 2) k_torso_fused(TorsoParams p)
             fq[0] = x0; fq[1] = x1;
 #pragma unroll
             for (int f = 0; f < 10; f++) {
-                const float a0 = scalbnf(x0, f), a1 = scalbnf(x1, f);
-                fq[2 + 4 * f + 0] = on ? sinf(a0) : 0.0f;
-                fq[2 + 4 * f + 1] = on ? sinf(a1) : 0.0f;
-                fq[2 + 4 * f + 2] = on ? sinf(a0 + 3.141592653589793f / 2) : 0.0f;
-                fq[2 + 4 * f + 3] = on ? sinf(a1 + 3.141592653589793f / 2) : 0.0f;
+                const float a0 = freq_angle(x0, f), a1 = freq_angle(x1, f);
+                fq[2 + 4 * f + 0] = on ? freq_sin(a0) : 0.0f;
+                fq[2 + 4 * f + 1] = on ? freq_sin(a1) : 0.0f;
+                fq[2 + 4 * f + 2] = on ? freq_cos(a0) : 0.0f;
+                fq[2 + 4 * f + 3] = on ? freq_cos(a1) : 0.0f;
             }
             if (!on) { fq[0] = 0.0f; fq[1] = 0.0f; }
 #pragma unroll
@@ -282,19 +221,19 @@ __global__ void __launch_bounds__(kFusedThreads, 2) k_torso_fused(TorsoParams p)
         }
 #pragma unroll
         for (int s = 0; s < 16; s++) {
-            const float wv = lds[TOFF_T0 + s * kTStep32 + lane_off32];
+            const float wv = lds[TOFF_T0 + s * kS32 + lane_off32];
             t0[0] = mfma32(wv, bg_[0][s], t0[0]); t0[1] = mfma32(wv, bg_[1][s], t0[1]);
         }
 #pragma unroll
         for (int s = 0; s < 21; s++) {
-            const float wv = lds[TOFF_T0 + (16 + s) * kTStep32 + lane_off32];
+            const float wv = lds[TOFF_T0 + (16 + s) * kS32 + lane_off32];
             t0[0] = mfma32(wv, bq[0][s], t0[0]); t0[1] = mfma32(wv, bq[1][s], t0[1]);
         }
 #pragma unroll
         for (int r = 0; r < 16; r++) { t0[0][r] = fmaxf(t0[0][r], 0.0f); t0[1][r] = fmaxf(t0[1][r], 0.0f); t1[0][r] = 0.0f; t1[1][r] = 0.0f; }
 #pragma unroll
         for (int s = 0; s < 16; s++) {
-            const float wv = lds[TOFF_T1 + s * kTStep32 + lane_off32];
+            const float wv = lds[TOFF_T1 + s * kS32 + lane_off32];
             t1[0] = mfma32(wv, t0[0][s], t1[0]); t1[1] = mfma32(wv, t0[1][s], t1[1]);
         }
         float o4[4];
@@ -314,9 +253,9 @@ __global__ void __launch_bounds__(kFusedThreads, 2) k_torso_fused(TorsoParams p)
         if (in_range) {
             float alpha = 0.0f, col[3] = {0.0f, 0.0f, 0.0f};
             if (on) {
-                alpha = 1.0f / (1.0f + expf(-o4[0]));
+                alpha = sigmoid_out(o4[0]);
 #pragma unroll
-                for (int c = 0; c < 3; c++) col[c] = 1.0f / (1.0f + expf(-o4[1 + c]));
+                for (int c = 0; c < 3; c++) col[c] = sigmoid_out(o4[1 + c]);
             }
             // bg = torso_color * alpha + bg * (1 - alpha)  (renderer.py:299)
             float bgf[3];
@@ -351,17 +290,18 @@ k_blend(float *__restrict__ image, const float *__restrict__ weights_sum, const 
         uint8_t *__restrict__ u8) {
     const uint32_t n = blockIdx.x * 256 + threadIdx.x;
     if (n >= N) return;
-    const float w = 1 - weights_sum[n];
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const float b = bg ? bg[3 * (size_t)n + c] : 1.0f;
-        float v = image[3 * (size_t)n + c] + w * b;
-        v = fminf(fmaxf(v, 0.0f), 1.0f);
-        image[3 * (size_t)n + c] = v;
-        if (u8) u8[3 * (size_t)n + c] = (uint8_t)(v * 255.0f);
-    }
-    const float dd = depth[n] - nears[n];
-    depth[n] = fmaxf(dd, 0.0f) / (fars[n] - nears[n]);
+    float b[3] = {1.0f, 1.0f, 1.0f};
+    if (bg) { b[0] = bg[3 * (size_t)n]; b[1] = bg[3 * (size_t)n + 1]; b[2] = bg[3 * (size_t)n + 2]; }
+    blend_pixel(BlendArgs{image, weights_sum, depth, nears, fars, u8}, n, b);
+}
+
+// the launch behind rn_torso_fused and rn_torso_blend_frame: one 64-pixel tile per wave, at most two workgroups per CU
+template <bool BLEND>
+static int launch_torso(const TorsoParams &p, int table_dtype, rn_stream_t stream, const char *what) {
+    const dim3 grid(tile_blocks((p.N + 63u) >> 6, kWavesPerBlock, 2));
+    if (table_dtype == RN_F32) hipLaunchKernelGGL((k_torso_fused<float, BLEND>), grid, dim3(kFusedThreads), 0, as_stream(stream), p);
+    else hipLaunchKernelGGL((k_torso_fused<__half, BLEND>), grid, dim3(kFusedThreads), 0, as_stream(stream), p);
+    return check_launch(what);
 }
 
 }  // namespace rn
@@ -373,11 +313,9 @@ extern "C" {
 size_t rn_torso_packed_floats(void) { return (size_t)kTorsoPacked; }
 
 int rn_torso_pack_weights(const rn_torso_weights_t *w, float *packed, rn_stream_t stream) {
-    RN_REQUIRE(w && w->def_w0 && w->def_w1 && w->def_w2 && w->tor_w0 && w->tor_w1 && w->tor_w2 && packed,
-               "torso_pack_weights: null pointer");
-    RN_REQUIRE(((uintptr_t)packed & 15u) == 0, "torso_pack_weights: packed must be 16-byte aligned");
-    RawT r{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
-    hipLaunchKernelGGL(k_pack_torso, dim3(div_up(kTorsoPacked, 256)), dim3(256), 0, as_stream(stream), r, packed);
+    if (int rc = check_torso_weights(w, "torso_pack_weights")) return rc;
+    RN_REQUIRE(packed && ((uintptr_t)packed & 15u) == 0, "torso_pack_weights: packed must be 16-byte aligned");
+    hipLaunchKernelGGL(k_pack_torso, dim3(div_up(kTorsoPacked, 256)), dim3(256), 0, as_stream(stream), raw_t(w), packed);
     return check_launch("torso_pack_weights");
 }
 
@@ -390,15 +328,9 @@ int rn_torso_fused(const float *bg_coords, uint32_t N, const float *density_grid
     RN_REQUIRE(ind_code || w->ind_dim == 0, "torso_fused: ind_code required when ind_dim > 0");
     RN_REQUIRE(((uintptr_t)packed & 15u) == 0, "torso_fused: packed must be 16-byte aligned");
     if (int rc = check_fused_grid(grid_torso, 2, "torso_fused(torso grid)")) return rc;
-    RawT r{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
-    TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, r, packed,
+    TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, raw_t(w), packed,
                   grid_args(grid_torso), bg_in, bg_out, torso_alpha, deform, BlendArgs{}};
-    uint32_t blocks = div_up((N + 63u) >> 6, kWavesPerBlock);
-    const uint32_t cap = (uint32_t)num_cus() * 2;
-    if (blocks > cap) blocks = cap;
-    if (grid_torso->dtype == RN_F32) hipLaunchKernelGGL((k_torso_fused<float, false>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL((k_torso_fused<__half, false>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
-    return check_launch("torso_fused");
+    return launch_torso<false>(p, grid_torso->dtype, stream, "torso_fused");
 }
 
 int rn_torso_blend_frame(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,
@@ -412,15 +344,9 @@ int rn_torso_blend_frame(const float *bg_coords, uint32_t N, const float *densit
     RN_REQUIRE(ind_code || w->ind_dim == 0, "torso_blend_frame: ind_code required when ind_dim > 0");
     RN_REQUIRE(((uintptr_t)packed & 15u) == 0, "torso_blend_frame: packed must be 16-byte aligned");
     if (int rc = check_fused_grid(grid_torso, 2, "torso_blend_frame(torso grid)")) return rc;
-    RawT r{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
-    TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, r, packed,
+    TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, raw_t(w), packed,
                   grid_args(grid_torso), bg_in, bg_out, torso_alpha, nullptr, BlendArgs{image, weights_sum, depth, nears, fars, image_u8}};
-    uint32_t blocks = div_up((N + 63u) >> 6, kWavesPerBlock);
-    const uint32_t cap = (uint32_t)num_cus() * 2;
-    if (blocks > cap) blocks = cap;
-    if (grid_torso->dtype == RN_F32) hipLaunchKernelGGL((k_torso_fused<float, true>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL((k_torso_fused<__half, true>), dim3(blocks), dim3(kFusedThreads), 0, as_stream(stream), p);
-    return check_launch("torso_blend_frame");
+    return launch_torso<true>(p, grid_torso->dtype, stream, "torso_blend_frame");
 }
 
 int rn_torso_mask(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,

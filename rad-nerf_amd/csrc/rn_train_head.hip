@@ -611,16 +611,8 @@ __global__ void __launch_bounds__(wgrad::kThreads, 2) k_train_wgrad(WArgs p) {
     }
 }
 
-struct RArgs {
-    RJob job[kJobs];
-    const float *partial;
-    uint32_t parts;
-};
-__global__ void __launch_bounds__(256) k_train_wreduce(RArgs p) {
-    const RJob &job = p.job[blockIdx.y];
-    wgrad::wreduce(p.partial + (size_t)blockIdx.y * p.parts * wgrad::kPartial, p.parts, blockIdx.x * 256 + threadIdx.x, job.rows, job.cols,
-                   job.bias_col, job.out, job.ld, job.bias_out);
-}
+typedef wgrad::RArgs<kJobs> RArgs;
+__global__ void __launch_bounds__(256) k_train_wreduce(RArgs p) { wgrad::wreduce_jobs(p); }
 
 // The per-call constants enter the first layers as biases (k_train_pack).  With gb = the bias gradient [64]:
 //   d constant[a] = sum_u W0[u][c0 + a] gb[u]        d W0[u][c0 + a] = gb[u] constant[a]
@@ -738,11 +730,6 @@ static int check_w(const rn_nerf_weights_t *w) {
     RN_REQUIRE(w->has_eye <= 1, "train_head: has_eye must be 0 or 1");
     return RN_OK;
 }
-static int check_grid(const rn_grid_t *g, uint32_t D, const char *name) {
-    RN_REQUIRE(g && g->embeddings && g->offsets, "train_head: %s grid is null", name);
-    RN_REQUIRE(g->D == D && g->L == 16 && g->dtype == RN_F32, "train_head: %s grid must be D=%u, L=16, fp32 with C=2", name, D);
-    return RN_OK;
-}
 
 }  // namespace th
 }  // namespace rn
@@ -780,15 +767,12 @@ int rn_train_head_forward(const float *xyzs, const float *dirs, uint32_t M, cons
                           const rn_grid_t *grid_amb, const float *image, float bound, float *sigmas, float *rgbs,
                           float *ambient, float *ambient_abs, float *xn, float *wn, float *workspace, rn_stream_t stream) {
     if (M == 0) return RN_OK;
-    if (int rc = check_grid(grid_xyz, 3, "xyz")) return rc;
-    if (int rc = check_grid(grid_amb, 2, "ambient")) return rc;
+    if (int rc = check_train_grid(grid_xyz, 3, "train_head: xyz")) return rc;
+    if (int rc = check_train_grid(grid_amb, 2, "train_head: ambient")) return rc;
     RN_REQUIRE(xyzs && dirs && image && sigmas && rgbs && ambient && xn && wn && workspace, "train_head_forward: null pointer");
     RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_head_forward: image / workspace must be 16-byte aligned");
     FwdParams p{xyzs, dirs, M, m_dev, grid_args(grid_xyz), grid_args(grid_amb), image, bound, sigmas, rgbs, ambient, ambient_abs, xn, wn, workspace};
-    const uint32_t n_tiles = (M + 31u) >> 5;
-    uint32_t blocks = div_up(n_tiles, kWaves);
-    const uint32_t cap = (uint32_t)num_cus();
-    if (blocks > cap) blocks = cap;
+    const uint32_t blocks = tile_blocks((M + 31u) >> 5, kWaves, 1);
     static int groups = -1;
     if (groups < 0) { const char *e = getenv("RN_TRAIN_FWD_GROUPS"); groups = e ? atoi(e) : 11; }
     // measured at 62 k samples (tools/bench_train_head.py): <1,1> 82.5 us, <1,2> 82.4, <2,2> 84.5, <2,4> 85.9 -- with one tile per
@@ -806,11 +790,7 @@ int rn_train_head_backward(const float *grad_sigmas, const float *grad_rgbs, con
     RN_REQUIRE(grad_sigmas && grad_rgbs && rgbs && ambient && image && workspace && grad_enc_x && grad_enc_w, "train_head_backward: null pointer");
     RN_REQUIRE(((uintptr_t)grad_enc_x & 7u) == 0 && ((uintptr_t)grad_enc_w & 7u) == 0, "train_head_backward: feature gradients must be 8-byte aligned");
     BwdParams p{grad_sigmas, grad_rgbs, grad_ambient, grad_ambient_abs, rgbs, ambient, M, m_dev, image, workspace, grad_enc_x, grad_enc_w};
-    const uint32_t n_tiles = (M + 31u) >> 5;
-    uint32_t blocks = div_up(n_tiles, kWaves);
-    const uint32_t cap = (uint32_t)num_cus();
-    if (blocks > cap) blocks = cap;
-    hipLaunchKernelGGL(k_train_bwd, dim3(blocks), dim3(kThreads), 0, as_stream(stream), p);
+    hipLaunchKernelGGL(k_train_bwd, dim3(tile_blocks((M + 31u) >> 5, kWaves, 1)), dim3(kThreads), 0, as_stream(stream), p);
     return check_launch("train_head_backward");
 }
 
@@ -818,15 +798,14 @@ int rn_train_head_input_grads(const float *xn, const float *dirs, const float *g
                               const rn_grid_t *grid_xyz, const float *image, const float *workspace, float bound,
                               float *grad_xyzs, float *grad_dirs, rn_stream_t stream) {
     if (M == 0) return RN_OK;
-    if (int rc = check_grid(grid_xyz, 3, "xyz")) return rc;
+    if (int rc = check_train_grid(grid_xyz, 3, "train_head: xyz")) return rc;
     RN_REQUIRE(xn && dirs && grad_enc_x && image && workspace && grad_xyzs && grad_dirs, "train_head_input_grads: null pointer");
     RN_REQUIRE(((uintptr_t)grad_enc_x & 7u) == 0, "train_head_input_grads: feature gradients must be 8-byte aligned");
     RN_REQUIRE(bound > 0.0f, "train_head_input_grads: bound must be positive");
     IgParams p{xn, dirs, grad_enc_x, M, m_dev, grid_args(grid_xyz), image, const_cast<float *>(workspace), bound, grad_xyzs, grad_dirs};
-    const uint32_t n_tiles = (M + 31u) >> 5;   // of the capacity: the rows past the live count are zero-filled by the same launch
-    uint32_t blocks = div_up(n_tiles, kIgWaves);
-    const uint32_t cap = 4u * (uint32_t)num_cus();   // 110 VGPRs: 4 waves per SIMD = 4 workgroups of 4 waves per CU
-    if (blocks > cap) blocks = cap;
+    // tiles of the capacity: the rows past the live count are zero-filled by the same launch.  110 VGPRs: 4 waves per SIMD = 4
+    // workgroups of 4 waves per CU
+    const uint32_t blocks = tile_blocks((M + 31u) >> 5, kIgWaves, 4);
     hipLaunchKernelGGL((k_train_input_grads<2>), dim3(blocks), dim3(kIgThreads), 0, as_stream(stream), p);
     return check_launch("train_head_input_grads");
 }

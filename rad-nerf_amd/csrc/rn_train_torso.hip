@@ -15,7 +15,7 @@
 //    computed from xy while a tile is staged; the column of ones gives the bias gradients, from which the gradients of the
 //    constant columns (pose encoding, individual code) and of the code follow.
 // The table gradient is rn_grid_scatter_jobs (rn_grid_scatter.hip) with one D = 2 job.
-#include "rn_fused_dev.h"
+#include "rn_torso_dev.h"
 #include "rn_wgrad_dev.h"
 
 #include "../../include/radnerf_train.h"
@@ -23,35 +23,18 @@
 namespace rn {
 namespace tt {
 
-constexpr int kS32 = 64;   // floats per MFMA step of a 32-row layer: [2 h][32 j]
-constexpr float kHalfPi = 3.141592653589793f / 2;
-
-// ---- the weight image of a step: forward | transposed | constants ------------------------------------------------------------
-constexpr int F_D0 = 0;                    // deform L0, 21 steps over enc_x: k = 2 s + h
-constexpr int F_D1 = F_D0 + 21 * kStep;
-constexpr int F_D2 = F_D1 + 32 * kStep;    // VALU rows [2][2 h][32]
-constexpr int F_T0 = F_D2 + 128;           // torso L0, 37 steps x 64: 16 grid steps in gather order, 21 over enc_x
-constexpr int F_T1 = F_T0 + 37 * kS32;
-constexpr int F_T2 = F_T1 + 16 * kS32;     // VALU rows [4][2 h][16]
-constexpr int kFwd = F_T2 + 128;           // 10432 floats
+// ---- the weight image of a step: forward (rn_torso_dev.h, grid steps in gather order) | transposed | constants --------------
+constexpr int kFwd = kTorsoPacked;
 constexpr int B_T2 = 0;                    // (relative to the transposed image) the narrow rows again
 constexpr int B_T1 = B_T2 + 128;           // d h_t0 = W_tor1^T dZ_t1
 constexpr int B_T0 = B_T1 + 16 * kS32;     // d grid features = W_tor0[:, 0:32]^T dZ_t0, output rows in gather order
 constexpr int B_D2 = B_T0 + 16 * kS32;
 constexpr int B_D1 = B_D2 + 128;           // d h_d0 = W_def1^T dZ_d1
 constexpr int kBwd = B_D1 + 32 * kStep;    // 6400 floats
-constexpr int C_DEF = 0, C_TOR = 64, C_POSE = 96;   // first-layer biases of the constant columns, enc_pose [54]
+constexpr int C_DEF = 0, C_TOR = 64, C_POSE = kTorsoBias;   // first-layer biases of the constant columns, enc_pose [54]
 constexpr int kConst = 152;
 constexpr int kImage = kFwd + kBwd + kConst;
 constexpr int kPackBlocks = (kFwd + kBwd + 255) / 256;   // workgroups of k_train_torso_pack that write weights; one more: the constants
-
-struct RawT {
-    const float *def_w0, *def_w1, *def_w2, *tor_w0, *tor_w1, *tor_w2;
-    uint32_t ind_dim;
-};
-static inline RawT raw_t(const rn_torso_weights_t *w) {
-    return RawT{w->def_w0, w->def_w1, w->def_w2, w->tor_w0, w->tor_w1, w->tor_w2, w->ind_dim};
-}
 
 // Output row j of a 32-row tile sits in register r of lane half hh with rowmap(r, hh) == j; the grid features want register
 // 2 q + c of lane half hh to be (level 2 q + hh, channel c), the order the forward gathers in: feature 4 q + 2 hh + c.
@@ -60,77 +43,34 @@ __host__ __device__ constexpr int gather_feature(int j) {
     return 4 * (r >> 1) + 2 * hh + (r & 1);
 }
 
-// freq(poses6, 4) -> 54 values (network.py:197), the layout of k_freq_forward
-__device__ __forceinline__ float enc_pose_elem(const float *poses6, int c) {
-    if (c < 6) return poses6[c];
-    const int col = c / 6 - 1, d = c % 6, f = col / 2;
-    const float a = scalbnf(poses6[d], f);
-    return (col & 1) ? sinf(a + kHalfPi) : sinf(a);
+// Element t (< kBwd) of the transposed image: the narrow layers as the forward image has them, the MFMA layers transposed
+__device__ __forceinline__ float torso_bwd_image_elem(const RawT &w, int t) {
+    if (t < B_T1) return torso_image_elem<true>(w, TOFF_T2 + t - B_T2);
+    if (t >= B_D2 && t < B_D1) return torso_image_elem<true>(w, TOFF_D2 + t - B_D2);
+    if (t < B_D2) {   // 32 rows: [step][h][row j]
+        const int q = t < B_T0 ? t - B_T1 : t - B_T0, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
+        return t < B_T0 ? w.tor_w1[rowmap(s, h) * 32 + j] : w.tor_w0[rowmap(s, h) * (128 + (int)w.ind_dim) + gather_feature(j)];
+    }
+    const int q = t - B_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
+    return w.def_w1[kmap(s, h) * 64 + 32 * rt + j];
 }
 
 __global__ void __launch_bounds__(256) k_train_torso_pack(RawT w, const float *__restrict__ poses6, const float *__restrict__ ind_code,
                                                           float *__restrict__ image) {
-    const int ldD0 = 96 + (int)w.ind_dim, ldT0 = 128 + (int)w.ind_dim;
     if (blockIdx.x == kPackBlocks) {
-        // the last workgroup: enc_pose once, then the constant columns [enc_pose | c] folded into the first layers as biases
-        // (network.py:201, 212).  enc_pose stays in the image: the constants' gradients need it
+        // the last workgroup: enc_pose once, then the constant columns folded into the first layers as biases.  enc_pose stays in
+        // the image: the constants' gradients need it
         __shared__ float enc_pose[54];
         float *c = image + kFwd + kBwd;
         const int t = threadIdx.x;
         if (t < 54) enc_pose[t] = enc_pose_elem(poses6, t);
         __syncthreads();
-        if (t < C_POSE) {
-            const float *r = t < C_TOR ? w.def_w0 + (t - C_DEF) * ldD0 + 42 : w.tor_w0 + (t - C_TOR) * ldT0 + 74;
-            float acc = 0.0f;
-            for (int k = 0; k < 54; k++) acc += r[k] * enc_pose[k];
-            for (uint32_t k = 0; k < w.ind_dim; k++) acc += r[54 + k] * ind_code[k];
-            c[t] = acc;
-        } else if (t < kConst) {
-            c[t] = t < C_POSE + 54 ? enc_pose[t - C_POSE] : 0.0f;
-        }
+        if (t < C_POSE) c[t] = torso_const_bias(w, enc_pose, ind_code, t);
+        else if (t < kConst) c[t] = t < C_POSE + 54 ? enc_pose[t - C_POSE] : 0.0f;
         return;
     }
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= kFwd + kBwd) return;
-    float v = 0.0f;
-    if (e < F_D1) {
-        const int q = e - F_D0, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
-        v = w.def_w0[(32 * rt + j) * ldD0 + 2 * s + h];
-    } else if (e < F_D2) {
-        const int q = e - F_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
-        v = w.def_w1[(32 * rt + j) * 64 + kmap(s, h)];
-    } else if (e < F_T0) {
-        const int q0 = e - F_D2, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
-        v = w.def_w2[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
-    } else if (e < F_T1) {
-        const int q = e - F_T0, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
-        v = w.tor_w0[j * ldT0 + (s < 16 ? 4 * (s >> 1) + 2 * h + (s & 1) : 32 + 2 * (s - 16) + h)];
-    } else if (e < F_T2) {
-        const int q = e - F_T1, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
-        v = w.tor_w1[j * 32 + rowmap(s, h)];
-    } else if (e < kFwd) {
-        const int q0 = e - F_T2, o = q0 / 32, h = (q0 % 32) / 16, r = q0 % 16;
-        v = w.tor_w2[o * 32 + rowmap(r, h)];
-    } else {
-        const int t = e - kFwd;
-        if (t < B_T1) {
-            const int o = t / 32, h = (t % 32) / 16, r = t % 16;
-            v = w.tor_w2[o * 32 + rowmap(r, h)];
-        } else if (t < B_T0) {
-            const int q = t - B_T1, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
-            v = w.tor_w1[rowmap(s, h) * 32 + j];
-        } else if (t < B_D2) {
-            const int q = t - B_T0, s = q / kS32, rem = q % kS32, h = rem / 32, j = rem % 32;
-            v = w.tor_w0[rowmap(s, h) * ldT0 + gather_feature(j)];
-        } else if (t < B_D1) {
-            const int q0 = t - B_D2, o = q0 / 64, h = (q0 % 64) / 32, q = q0 % 32;
-            v = w.def_w2[o * 64 + 32 * (q >> 4) + rowmap(q & 15, h)];
-        } else {
-            const int q = t - B_D1, s = q / kStep, rem = q % kStep, h = rem / 64, j = (rem % 64) / 2, rt = rem % 2;
-            v = w.def_w1[kmap(s, h) * 64 + 32 * rt + j];
-        }
-    }
-    image[e] = v;
+    if (e < kFwd + kBwd) image[e] = e < kFwd ? torso_image_elem<true>(w, e) : torso_bwd_image_elem(w, e - kFwd);
 }
 
 // ---- workspace: native tiles ([registers][64 lanes] floats per 32-pixel tile) and per-pixel rows -------------------------------
@@ -164,25 +104,6 @@ __host__ __device__ inline Ws make_ws(float *base, uint32_t P) {
     w.ddx = p; p += nt * 64;
     w.dto = p; p += nt * 128;
     return w;
-}
-
-// 32-row layers: one row tile of 16 registers
-__device__ __forceinline__ void store16(float *__restrict__ dst, const f32x16 &a, int lane) {
-#pragma unroll
-    for (int r = 0; r < 16; r++) dst[r * 64 + lane] = a[r];
-}
-__device__ __forceinline__ void relu_mask16(f32x16 &g, const float *__restrict__ saved, int lane) {
-    float hv[16];
-#pragma unroll
-    for (int r = 0; r < 16; r++) hv[r] = saved[r * 64 + lane];
-#pragma unroll
-    for (int r = 0; r < 16; r++) g[r] = hv[r] > 0.0f ? g[r] : 0.0f;
-}
-__device__ __forceinline__ f32x16 zero16() {
-    f32x16 a;
-#pragma unroll
-    for (int r = 0; r < 16; r++) a[r] = 0.0f;
-    return a;
 }
 
 constexpr int kThreads = 256, kWaves = kThreads / kWave;   // a 4096-ray torso step is ~41 tiles: spread them over many CUs
@@ -232,24 +153,24 @@ __global__ void __launch_bounds__(kThreads) k_train_torso_fwd(FwdParams p) {
             fq[0] = xs;
 #pragma unroll
             for (int f = 0; f < 10; f++) {
-                const float a = scalbnf(xs, f);
-                fq[1 + 2 * f] = sinf(a);
-                fq[2 + 2 * f] = sinf(a + kHalfPi);
+                const float a = freq_angle(xs, f);
+                fq[1 + 2 * f] = freq_sin(a);
+                fq[2 + 2 * f] = freq_cos(a);
             }
         }
         // ---- deformation net: [enc_x | enc_pose | c] -> 64 -> 64 -> 2
         Acc32 a0, a1;
         acc_bias(a0, bias_def, h);
 #pragma unroll
-        for (int s = 0; s < 21; s++) step32(a0, lds + F_D0, s, lane_off, fq[s]);
+        for (int s = 0; s < 21; s++) step32(a0, lds + TOFF_D0, s, lane_off, fq[s]);
         acc_relu(a0);
         tile_store(ws.hd0 + (size_t)tile * kTile32, a0, lane);
         acc_zero(a1);
-        layer_from_acc(a1, a0, lds + F_D1, lane_off);
+        layer_from_acc(a1, a0, lds + TOFF_D1, lane_off);
         acc_relu(a1);
         tile_store(ws.hd1 + (size_t)tile * kTile32, a1, lane);
         float dxy[2];
-        valu_out<2>(a1, lds + F_D2, h, dxy);
+        valu_out<2>(a1, lds + TOFF_D2, h, dxy);
         // ---- x = clamp(x + dx, -1, 1); the torso grid (bound = 1) with d enc / d input
         f32x16 t0;
 #pragma unroll
@@ -284,8 +205,8 @@ __global__ void __launch_bounds__(kThreads) k_train_torso_fwd(FwdParams p) {
 #pragma unroll
                     for (int q = 0; q < 4; q++) g[q] = grads[q];
                 }
-                t0 = mfma32(lds[F_T0 + (2 * r) * kS32 + lane_off32], f0, t0);
-                t0 = mfma32(lds[F_T0 + (2 * r + 1) * kS32 + lane_off32], f1, t0);
+                t0 = mfma32(lds[TOFF_T0 + (2 * r) * kS32 + lane_off32], f0, t0);
+                t0 = mfma32(lds[TOFF_T0 + (2 * r + 1) * kS32 + lane_off32], f1, t0);
                 eg[(2 * r) * 64 + lane] = f0;
                 eg[(2 * r + 1) * 64 + lane] = f1;
 #pragma unroll
@@ -294,13 +215,13 @@ __global__ void __launch_bounds__(kThreads) k_train_torso_fwd(FwdParams p) {
         }
         // ---- torso net: [grid | enc_x | enc_pose | c] -> 32 -> 32 -> 4, sigmoid
 #pragma unroll
-        for (int s = 0; s < 21; s++) t0 = mfma32(lds[F_T0 + (16 + s) * kS32 + lane_off32], fq[s], t0);
+        for (int s = 0; s < 21; s++) t0 = mfma32(lds[TOFF_T0 + (16 + s) * kS32 + lane_off32], fq[s], t0);
 #pragma unroll
         for (int r = 0; r < 16; r++) t0[r] = relu_bits(t0[r]);
         store16(ws.ht0 + (size_t)tile * kTile16, t0, lane);
         f32x16 t1 = zero16();
 #pragma unroll
-        for (int s = 0; s < 16; s++) t1 = mfma32(lds[F_T1 + s * kS32 + lane_off32], t0[s], t1);
+        for (int s = 0; s < 16; s++) t1 = mfma32(lds[TOFF_T1 + s * kS32 + lane_off32], t0[s], t1);
 #pragma unroll
         for (int r = 0; r < 16; r++) t1[r] = relu_bits(t1[r]);
         store16(ws.ht1 + (size_t)tile * kTile16, t1, lane);
@@ -308,15 +229,15 @@ __global__ void __launch_bounds__(kThreads) k_train_torso_fwd(FwdParams p) {
 #pragma unroll
         for (int o = 0; o < 4; o++) {
             float s = 0.0f;
-            const float *wo = lds + F_T2 + (o * 2 + h) * 16;
+            const float *wo = lds + TOFF_T2 + (o * 2 + h) * 16;
 #pragma unroll
             for (int r = 0; r < 16; r++) s = __builtin_fmaf(t1[r], wo[r], s);
             o4[o] = s + __shfl_xor(s, 32, 64);
         }
         if (live && h == 0) {
-            p.alpha[px] = 1.0f / (1.0f + expf(-o4[0]));
+            p.alpha[px] = sigmoid_out(o4[0]);
 #pragma unroll
-            for (int c = 0; c < 3; c++) p.color[3 * (size_t)px + c] = 1.0f / (1.0f + expf(-o4[1 + c]));
+            for (int c = 0; c < 3; c++) p.color[3 * (size_t)px + c] = sigmoid_out(o4[1 + c]);
         }
     }
 }
@@ -470,16 +391,8 @@ __global__ void __launch_bounds__(wgrad::kThreads, 2) k_train_torso_wgrad(WArgs 
     }
 }
 
-struct RArgs {
-    RJob job[kJobs];
-    const float *partial;
-    uint32_t parts;
-};
-__global__ void __launch_bounds__(256) k_train_torso_wreduce(RArgs p) {
-    const RJob &job = p.job[blockIdx.y];
-    wgrad::wreduce(p.partial + (size_t)blockIdx.y * p.parts * wgrad::kPartial, p.parts, blockIdx.x * 256 + threadIdx.x, job.rows, job.cols,
-                   job.bias_col, job.out, job.ld, job.bias_out);
-}
+typedef wgrad::RArgs<kJobs> RArgs;
+__global__ void __launch_bounds__(256) k_train_torso_wreduce(RArgs p) { wgrad::wreduce_jobs(p); }
 
 // The constant columns [enc_pose | c] entered the first layers as biases (k_train_torso_pack).  With b_def [64] / b_tor [32] the
 // bias gradients:  gW_def0[:, 42:] = b_def (x) [enc_pose | c],  gW_tor0[:, 74:] = b_tor (x) [enc_pose | c],
@@ -515,11 +428,8 @@ constexpr uint32_t kWPartsMax = 128;
 constexpr uint32_t kBlocksMax = 1u << 16;
 // workgroups of the forward / backward launch: one per kWaves tiles, at most one round of two per CU; RN_TORSO_TRAIN_BLOCKS caps
 // it further (read at every launch: a test runs the grid-stride loop at a small P with it)
-static uint32_t tile_blocks(uint32_t P) {
-    const uint32_t n_tiles = (P + 31u) >> 5;
-    uint32_t blocks = div_up(n_tiles, kWaves);
-    const uint32_t cap = 2u * (uint32_t)num_cus();
-    if (blocks > cap) blocks = cap;
+static uint32_t launch_blocks(uint32_t P) {
+    const uint32_t blocks = tile_blocks((P + 31u) >> 5, kWaves, 2);
     const uint32_t knob = env_uint_clamped("RN_TORSO_TRAIN_BLOCKS", kBlocksMax, kBlocksMax);
     return blocks < knob ? blocks : knob;
 }
@@ -527,15 +437,6 @@ static uint32_t wparts(uint32_t P) {   // workgroups (= partial sums) per weight
     static const uint32_t n = env_uint_clamped("RN_TORSO_TRAIN_WPARTS", 64, kWPartsMax);
     const uint32_t n_tiles = (P + 31u) >> 5;
     return n < n_tiles ? n : n_tiles;
-}
-static int check_w(const rn_torso_weights_t *w, const char *what) {
-    RN_REQUIRE(w && w->def_w0 && w->def_w1 && w->def_w2 && w->tor_w0 && w->tor_w1 && w->tor_w2, "%s: null weight pointer", what);
-    return RN_OK;
-}
-static int check_grid(const rn_grid_t *g, const char *what) {
-    RN_REQUIRE(g && g->embeddings && g->offsets, "%s: torso grid is null", what);
-    RN_REQUIRE(g->D == 2 && g->L == 16 && g->dtype == RN_F32, "%s: torso grid must be D=2, L=16, fp32 with C=2", what);
-    return RN_OK;
 }
 
 }  // namespace tt
@@ -551,7 +452,7 @@ size_t rn_train_torso_workspace_floats(uint32_t P) { return (size_t)((P + 31u) >
 size_t rn_train_torso_wgrad_workspace(void) { return ((size_t)kJobs * kWPartsMax * wgrad::kPartial + 128) * sizeof(float); }
 
 int rn_train_torso_pack(const rn_torso_weights_t *w, const float *poses6, const float *ind_code, float *image, rn_stream_t stream) {
-    if (int rc = check_w(w, "train_torso_pack")) return rc;
+    if (int rc = check_torso_weights(w, "train_torso_pack")) return rc;
     RN_REQUIRE(poses6 && image, "train_torso_pack: null pointer");
     RN_REQUIRE(ind_code || w->ind_dim == 0, "train_torso_pack: null pointer (ind_code with ind_dim > 0)");
     RN_REQUIRE(((uintptr_t)image & 15u) == 0, "train_torso_pack: image must be 16-byte aligned");
@@ -563,13 +464,13 @@ int rn_train_torso_forward(const float *xy, uint32_t P, const int32_t *p_dev, fl
                            const float *image, float *alpha, float *color, float *dx, float *wn, float *workspace,
                            rn_stream_t stream) {
     if (P == 0) return RN_OK;
-    if (int rc = check_grid(grid_torso, "train_torso_forward")) return rc;
+    if (int rc = check_train_grid(grid_torso, 2, "train_torso_forward: torso")) return rc;
     RN_REQUIRE(xy && image && alpha && color && dx && wn && workspace, "train_torso_forward: null pointer");
     RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_torso_forward: image / workspace must be 16-byte aligned");
     RN_REQUIRE(((uintptr_t)grid_torso->embeddings & 7u) == 0, "train_torso_forward: the table must be 8-byte aligned");
     RN_REQUIRE(torso_shrink > 0.0f, "train_torso_forward: torso_shrink must be positive");
     FwdParams p{xy, P, p_dev, torso_shrink, grid_args(grid_torso), image, alpha, color, dx, wn, workspace};
-    hipLaunchKernelGGL(k_train_torso_fwd, dim3(tile_blocks(P)), dim3(kThreads), 0, as_stream(stream), p);
+    hipLaunchKernelGGL(k_train_torso_fwd, dim3(launch_blocks(P)), dim3(kThreads), 0, as_stream(stream), p);
     return check_launch("train_torso_forward");
 }
 
@@ -581,7 +482,7 @@ int rn_train_torso_backward(const float *grad_alpha, const float *grad_color, co
     RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_torso_backward: image / workspace must be 16-byte aligned");
     RN_REQUIRE(((uintptr_t)grad_feat & 7u) == 0, "train_torso_backward: feature gradients must be 8-byte aligned");
     BwdParams p{grad_alpha, grad_color, grad_dx, alpha, color, P, p_dev, image, workspace, grad_feat};
-    hipLaunchKernelGGL(k_train_torso_bwd, dim3(tile_blocks(P)), dim3(kThreads), 0, as_stream(stream), p);
+    hipLaunchKernelGGL(k_train_torso_bwd, dim3(launch_blocks(P)), dim3(kThreads), 0, as_stream(stream), p);
     return check_launch("train_torso_backward");
 }
 
@@ -589,7 +490,7 @@ int rn_train_torso_weight_grads(const rn_torso_weights_t *w, const float *xy, fl
                                 const int32_t *p_dev, const float *image, const float *workspace,
                                 const rn_train_torso_grads_t *g, void *wgrad_workspace, rn_stream_t stream) {
     if (P == 0) return RN_OK;
-    if (int rc = check_w(w, "train_torso_weight_grads")) return rc;
+    if (int rc = check_torso_weights(w, "train_torso_weight_grads")) return rc;
     RN_REQUIRE(xy && image && workspace && g && wgrad_workspace, "train_torso_weight_grads: null pointer");
     RN_REQUIRE(g->def_w0 && g->def_w1 && g->def_w2 && g->tor_w0 && g->tor_w1 && g->tor_w2, "train_torso_weight_grads: null gradient pointer");
     RN_REQUIRE(w->ind_dim == 0 || (ind_code && g->ind_code), "train_torso_weight_grads: null pointer (ind_code with ind_dim > 0)");

@@ -9,7 +9,8 @@
 // waves (<= 3 each), whose accumulators stay in registers over all tiles.  Tiles travel global -> registers two strides
 // ahead of their use (two register sets, alternating): the HBM latency of a tile that is read exactly once (~3 us) is
 // longer than the ~1 us of MFMA work per tile.  Per-workgroup partial sums [96 x 96] go to a workspace; wreduce() adds
-// them up, one thread per element, into the nn.Linear layout.
+// them up, one thread per element, into the nn.Linear layout (wreduce_jobs(): the body of the two fused reduce kernels,
+// one launch for all jobs of a step).
 //
 // How a tile gets from global memory into the staged tile is the operand's business.  An operand type provides
 //   Fetched                          the registers one thread holds of a tile in flight
@@ -18,9 +19,11 @@
 //   fetch(f, tile)                   global -> registers
 //   commit(t, f, tile, M)            registers -> staged tile t; M = live samples (rows past it stage as zeros)
 // The two families: OpT<...> below (layout known at compile time: the fused head, rn_train_head.hip, and the fused torso,
-// rn_train_torso.hip) and Op<NATIVE> of rn_mlp.hip (run-time native tile / row-major matrix).
+// rn_train_torso.hip, whose enc_x operand is computed with rn_freq_dev.h) and Op<NATIVE> of rn_mlp.hip (run-time native
+// tile / row-major matrix).
 #pragma once
 
+#include "rn_freq_dev.h"
 #include "rn_tile32_dev.h"
 
 namespace rn {
@@ -177,7 +180,7 @@ struct OpT {
                 t[c * kTS + (s & 1) * 16 + (s >> 1)] = f.rm;
             }
         }
-        if constexpr (FREQ) {   // the forward's arithmetic (k_torso_fused): scalbnf, sinf(a + pi / 2) for the cosine
+        if constexpr (FREQ) {   // the forward's arithmetic (rn_freq_dev.h)
             const int s = threadIdx.x & 31, c0 = threadIdx.x >> 5;
             const bool on = tile * 32 + s < M;
             float *dst = t + kFreq0 * kTS + (s & 1) * 16 + (s >> 1);
@@ -186,8 +189,8 @@ struct OpT {
                 if (c < 2) v = c ? f.x1 : f.x0;
                 else {
                     const int q = c - 2;
-                    const float a = scalbnf((q & 1) ? f.x1 : f.x0, q >> 2);
-                    v = (q & 2) ? sinf(a + 3.141592653589793f / 2) : sinf(a);
+                    const float a = freq_angle((q & 1) ? f.x1 : f.x0, q >> 2);
+                    v = (q & 2) ? freq_cos(a) : freq_sin(a);
                 }
                 dst[c * kTS] = on ? v : 0.0f;
             }
@@ -227,6 +230,21 @@ __device__ __forceinline__ void wreduce(const float *__restrict__ partial, uint3
     const float total = ((s[0] + s[1]) + (s[2] + s[3])) + ((s[4] + s[5]) + (s[6] + s[7]));
     if (bias) bias_out[row] = total;
     else out[row * ld + col] = total;
+}
+
+// A reduce launch of JOBS jobs whose partials follow each other in one workspace ([JOBS][parts][kPartial]): grid
+// (kPartial / 256, JOBS) x 256 threads.  The fused head (8 jobs) and the fused torso (6) wrap it in a kernel each.
+template <int JOBS>
+struct RArgs {
+    RJob job[JOBS];
+    const float *partial;
+    uint32_t parts;
+};
+template <int JOBS>
+__device__ __forceinline__ void wreduce_jobs(const RArgs<JOBS> &p) {
+    const RJob &job = p.job[blockIdx.y];
+    wreduce(p.partial + (size_t)blockIdx.y * p.parts * kPartial, p.parts, blockIdx.x * 256 + threadIdx.x, job.rows, job.cols, job.bias_col,
+            job.out, job.ld, job.bias_out);
 }
 
 }  // namespace wgrad

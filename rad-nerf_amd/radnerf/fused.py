@@ -50,6 +50,25 @@ def weights_desc(ws, audio_dim, has_eye, ind_dim):
     return nw
 
 
+def torso_weights(model):
+    """The six nn.Linear weights of the torso layer, in the order of rn_torso_weights_t."""
+    return [l.weight for l in model.torso_deform_net.net] + [l.weight for l in model.torso_net.net]
+
+
+def torso_weights_desc(ws, ind_dim):
+    assert tuple(ws[0].shape) == (64, 96 + ind_dim) and tuple(ws[3].shape) == (32, 128 + ind_dim)
+    tw = TorsoWeightsT()
+    (tw.def_w0, tw.def_w1, tw.def_w2, tw.tor_w0, tw.tor_w1, tw.tor_w2) = [w.data_ptr() for w in ws]
+    tw.ind_dim = ind_dim
+    return tw
+
+
+def torso_constants(poses, ind_code):
+    """The constant inputs of the torso layer as the kernels read them: (poses6 [6], individual code [ind_dim] or None)."""
+    return (poses.detach().reshape(-1).contiguous().float(),
+            ind_code.detach().reshape(-1).contiguous().float() if ind_code is not None else None)
+
+
 def supported(model):
     """True when the model has the shape the fused kernels are built for (else: use the 'ops' engine)."""
     try:
@@ -94,7 +113,7 @@ class FusedState:
         m = self.model
         ws = head_weights(m)
         if m.torso:
-            ws += [l.weight for l in m.torso_deform_net.net] + [l.weight for l in m.torso_net.net]
+            ws += torso_weights(m)
         return ws
 
     def refresh(self):
@@ -125,11 +144,7 @@ class FusedState:
                   RN_F32_SPLIT: "rn_nerf_pack_weights_split"}[mlp]
         hip.call(packer, C.byref(self.nw), hip.ptr(self.packed), hip.stream())
         if m.torso:
-            self.tw = TorsoWeightsT()
-            (self.tw.def_w0, self.tw.def_w1, self.tw.def_w2, self.tw.tor_w0, self.tw.tor_w1,
-             self.tw.tor_w2) = [w.data_ptr() for w in ws[8:14]]
-            self.tw.ind_dim = m.individual_dim_torso
-            assert tuple(ws[8].shape) == (64, 96 + m.individual_dim_torso) and tuple(ws[11].shape) == (32, 128 + m.individual_dim_torso)
+            self.tw = torso_weights_desc(ws[8:14], m.individual_dim_torso)
             hip.call("rn_torso_pack_weights", C.byref(self.tw), hip.ptr(self.tpacked), hip.stream())
         # tables: fp32 parameters are read in place; with opt.half_tables their persistent fp16 copies
         if half:
@@ -352,8 +367,7 @@ def torso_forward(model, bg_coords, poses6, ind_code_torso, thresh, bg_in=None, 
     N = bg_coords.shape[0]
     dev = bg_coords.device
     bg_coords = bg_coords.contiguous().float()
-    poses6 = poses6.reshape(-1).contiguous().float()
-    ict = ind_code_torso.detach().reshape(-1).contiguous().float() if ind_code_torso is not None else None
+    poses6, ict = torso_constants(poses6, ind_code_torso)
     if bg_out is None:
         bg_out = torch.empty(N, 3, dtype=torch.float32, device=dev)
     if alpha_out is None:
@@ -471,8 +485,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
         talpha = torch.empty(N, 1, dtype=torch.float32, device=dev) if keep else None
         bg_final = torch.empty(N, 3, dtype=torch.float32, device=dev) if keep else None
         coords = bg_coords.contiguous().float()
-        p6 = poses.reshape(-1).contiguous().float()
-        ict = ind_code_torso.detach().reshape(-1).contiguous().float() if ind_code_torso is not None else None
+        p6, ict = torso_constants(poses, ind_code_torso)
         hip.call("rn_torso_blend_frame", hip.ptr(coords), N, hip.ptr(model.density_grid_torso), int(model.grid_size), float(thresh),
                  hip.ptr(p6), hip.ptr(ict), float(model.opt.torso_shrink), C.byref(st.tw), hip.ptr(st.tpacked), C.byref(st.gt),
                  hip.ptr(bg_in), hip.ptr(bg_final), hip.ptr(talpha), hip.ptr(image), hip.ptr(weights_sum), hip.ptr(depth),

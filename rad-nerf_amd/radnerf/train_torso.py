@@ -15,17 +15,12 @@ import os
 import torch
 
 import radnerf_hip as hip
-from radnerf_hip.abi import TorsoGradsT, TorsoWeightsT
+from radnerf_hip.abi import TorsoGradsT
 
-from .fused import _grid_desc
+from .fused import _grid_desc, torso_constants, torso_weights, torso_weights_desc  # noqa: F401  (torso_weights: re-exported)
 from .train_head import grid_scatter
 
 _lib = hip._lib
-
-
-def torso_weights(model):
-    """The six nn.Linear weights of the torso layer, in the order of rn_torso_weights_t."""
-    return [l.weight for l in model.torso_deform_net.net] + [l.weight for l in model.torso_net.net]
 
 
 def supported(model):
@@ -47,13 +42,6 @@ def usable(model, x):
             and x.dtype == torch.float32 and not torch.is_autocast_enabled() and supported(model))
 
 
-def _weights_desc(ws, ind_dim):
-    tw = TorsoWeightsT()
-    (tw.def_w0, tw.def_w1, tw.def_w2, tw.tor_w0, tw.tor_w1, tw.tor_w2) = [w.data_ptr() for w in ws]
-    tw.ind_dim = ind_dim
-    return tw
-
-
 def _empty(dev):
     def alloc(*shape):
         return torch.empty(*shape, dtype=torch.float32, device=dev)
@@ -73,13 +61,11 @@ class _TorsoTrain(torch.autograd.Function):
         xy = xy.detach().contiguous()
         ws = [w.detach().contiguous() for w in ws]
         ind_dim = ws[0].shape[1] - 96
-        assert tuple(ws[0].shape) == (64, 96 + ind_dim) and tuple(ws[3].shape) == (32, 128 + ind_dim) and xy.shape[1] == 2
-        p6 = poses.detach().reshape(-1).contiguous().float()
-        assert p6.numel() == 6
-        code_c = code.detach().reshape(-1).contiguous().float() if ind_dim else None
-        assert code_c is None or code_c.numel() == ind_dim
+        assert xy.shape[1] == 2
+        p6, code_c = torso_constants(poses, code if ind_dim else None)
+        assert p6.numel() == 6 and (code_c is None or code_c.numel() == ind_dim)
         tab = hip.aligned(table.detach(), 64)
-        tw = _weights_desc(ws, ind_dim)
+        tw = torso_weights_desc(ws, ind_dim)
         gd = _grid_desc(enc, tab)
         s = hip.stream()
         alpha, color, dx, wn = alloc(P, 1), alloc(P, 3), alloc(P, 2), alloc(P, 2)
@@ -114,7 +100,7 @@ class _TorsoTrain(torch.autograd.Function):
             g_feat = alloc(16 * P, 2)
             hip.call("rn_train_torso_backward", hip.ptr(g_alpha), hip.ptr(g_color), hip.ptr(g_dx), hip.ptr(alpha), hip.ptr(color), P,
                      hip.ptr(p_dev), hip.ptr(image), hip.ptr(work), hip.ptr(g_feat), s)
-            tw = _weights_desc(ws, ind_dim)
+            tw = torso_weights_desc(ws, ind_dim)
             tg = TorsoGradsT()
             (tg.def_w0, tg.def_w1, tg.def_w2, tg.tor_w0, tg.tor_w1, tg.tor_w2) = [g.data_ptr() for g in grads]
             tg.ind_code = hip.ptr(g_code)
