@@ -209,6 +209,38 @@ int rn_train_torso_weight_grads(const rn_torso_weights_t *w, const float *xy, fl
                                 const int32_t *p_dev, const float *image, const float *workspace,
                                 const rn_train_torso_grads_t *grads, void *wgrad_workspace, rn_stream_t stream);
 
+/*
+ * A torso step that never tells the host how many pixels are covered (opt-in RN_TORSO_TRAIN=fused, radnerf/train_torso.py).  The
+ * launches of the torso part of such a step, forward + backward, ten in all:
+ *
+ *   rn_torso_select              covered pixels of the batch, compacted in ascending order, and their count            1 launch
+ *   rn_train_torso_pack / _forward   on the compact rows at capacity N with p_dev = the count                          2 launches
+ *   rn_train_torso_loss          scatter-back, blend over the background, MSE + entropy, their gradients               1 launch
+ *   rn_train_torso_backward, _weight_grads, a memset and rn_grid_scatter_jobs, all with the same p_dev               1 + 3 + 1 + 1
+ *
+ * Nothing in it depends on the count on the host side, so the step can be captured in a graph and replayed.
+ */
+/* Pixels the torso layer covers, as rn_torso_mask decides it (bilinear occupancy of density_grid_torso [G * G] at bg_coords [N,2]
+ * strictly above the threshold), compacted: covered [N] int32 receives their indices in ascending order, xy_c [N,2] their
+ * coordinates in the same order, count [1] how many there are; rows at or past the count of both are not written.  The
+ * threshold is min(density_thresh, *mean_density_dev), the device float read when the kernel runs (nerf/renderer.py:281:
+ * min(density_thresh_torso, mean_density_torso)); mean_density_dev == NULL: density_thresh alone.  One workgroup walks the pixels
+ * (a training batch: 4 096 .. 65 536); N == 0 sets *count = 0 and launches nothing. */
+int rn_torso_select(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float density_thresh,
+                    const float *mean_density_dev, int32_t *covered, float *xy_c, int32_t *count, rn_stream_t stream);
+
+/* Loss of a torso step (nerf/renderer.py:286-302, nerf/utils.py:749, 783-791) from the compact rows of the layer:
+ *   a[n] = alpha_c[i], c[n] = color_c[i] where covered[i] == n for an i < live count (p_dev clipped to P; NULL = P), a[n] = 0 elsewhere;
+ *   pred[n] = c[n] a[n] + bg[n] (1 - a[n])   (= bg[n] bit for bit on uncovered pixels);
+ *   loss = mean_n mean_c (pred - target)^2 + 1e-4 mean_n H(clamp(a[n], 1e-5, 1 - 1e-5)),  H the binary entropy in log2,
+ * uncovered pixels included in both means.  covered [P] must be ascending over its live rows (rn_torso_select's order).
+ * Outputs: loss [1], pred [N,3], alpha_full [N,1], and for live rows only grad_alpha_c [P,1], grad_color_c [P,3] = d loss / d
+ * (alpha_c, color_c).  No gradient for bg.  bg / target: [N,3] with row strides in floats (columns of one packed batch table).
+ * One launch, one workgroup, sums in double in a fixed order.  N == 0: nothing is launched. */
+int rn_train_torso_loss(const float *alpha_c, const float *color_c, const int32_t *covered, uint32_t P, const int32_t *p_dev,
+                        const float *bg, uint32_t bg_stride, const float *target, uint32_t target_stride, uint32_t N, float *loss,
+                        float *pred, float *alpha_full, float *grad_alpha_c, float *grad_color_c, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,6 +6,8 @@
 // per feature pair to build both B operands; the weights sit in LDS, the per-frame inputs enter as accumulator biases.
 #include "rn_torso_dev.h"
 
+#include "../../include/radnerf_train.h"   // rn_torso_select: the covered pixels of a training step
+
 namespace rn {
 
 // ---- 64-sample tiles (two column tiles per wave)
@@ -283,6 +285,50 @@ k_torso_mask(const float *__restrict__ bg_coords, uint32_t N, const float *__res
     mask[n] = sample_torso_grid(grid, G, bg_coords[2 * (size_t)n], bg_coords[2 * (size_t)n + 1]) > thresh ? 1 : 0;
 }
 
+// The same test as a stable compaction on the device: covered[0 .. count) = the covered pixel indices ascending (torch.nonzero's
+// order), xy_c their coordinates, for a training step that never tells the host how many there are.  The threshold is
+// min(thresh, *mean_dev), read here, so a captured launch follows an occupancy refresh.  ONE workgroup walks the pixels
+// kSelectThreads at a time: ballot + mbcnt rank inside a wave, the waves' counts through LDS (two buffers in turn: one barrier
+// per round), the running total in a register.  A training batch is 4 096 .. 65 536 pixels: 4 .. 64 rounds.
+constexpr int kSelectThreads = 1024;
+__global__ void __launch_bounds__(kSelectThreads)
+k_torso_select(const float *__restrict__ bg_coords, uint32_t N, const float *__restrict__ grid, uint32_t G, float thresh,
+               const float *__restrict__ mean_dev, int32_t *__restrict__ covered, float *__restrict__ xy_c,
+               int32_t *__restrict__ count) {
+    constexpr int kWaves = kSelectThreads / kWave;
+    __shared__ uint32_t wave_cnt[2][kWaves];
+    if (mean_dev) thresh = fminf(thresh, mean_dev[0]);
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t base = 0;
+    for (uint32_t n0 = 0, round = 0; n0 < N; n0 += kSelectThreads, round++) {
+        const uint32_t n = n0 + threadIdx.x;
+        float cx = 0.0f, cy = 0.0f;
+        bool on = false;
+        if (n < N) {
+            cx = bg_coords[2 * (size_t)n]; cy = bg_coords[2 * (size_t)n + 1];
+            on = sample_torso_grid(grid, G, cx, cy) > thresh;
+        }
+        const unsigned long long mask = __ballot(on);
+        uint32_t *cnt = wave_cnt[round & 1];
+        if ((threadIdx.x & 63) == 0) cnt[wave] = (uint32_t)__popcll(mask);
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < (uint32_t)kWaves; w++) {
+            const uint32_t cw = cnt[w];
+            before += (w < wave) ? cw : 0u;
+            total += cw;
+        }
+        if (on) {
+            const uint32_t row = base + before + ballot_prefix(mask);
+            covered[row] = (int32_t)n;
+            *reinterpret_cast<float2 *>(xy_c + 2 * (size_t)row) = make_float2(cx, cy);
+        }
+        base += total;
+    }
+    if (threadIdx.x == 0) count[0] = (int32_t)base;
+}
+
 // renderer.py:306-311
 __global__ void __launch_bounds__(256)
 k_blend(float *__restrict__ image, const float *__restrict__ weights_sum, const float *__restrict__ bg,
@@ -356,6 +402,19 @@ int rn_torso_mask(const float *bg_coords, uint32_t N, const float *density_grid_
     hipLaunchKernelGGL(k_torso_mask, dim3(div_up(N, 256)), dim3(256), 0, as_stream(stream), bg_coords, N, density_grid_torso, grid_size,
                        thresh, mask);
     return check_launch("torso_mask");
+}
+
+int rn_torso_select(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float density_thresh,
+                    const float *mean_density_dev, int32_t *covered, float *xy_c, int32_t *count, rn_stream_t stream) {
+    RN_REQUIRE(count, "torso_select: null pointer (count)");
+    if (N == 0) return hipMemsetAsync(count, 0, sizeof(int32_t), as_stream(stream)) == hipSuccess ? RN_OK : RN_ERR_LAUNCH;
+    RN_REQUIRE(bg_coords && density_grid_torso && covered && xy_c, "torso_select: null pointer");
+    RN_REQUIRE(grid_size >= 2, "torso_select: grid_size must be at least 2");
+    RN_REQUIRE(N <= (1u << 30), "torso_select: N = %u is more than 2^30 pixels (int32 indices)", N);
+    RN_REQUIRE(((uintptr_t)xy_c & 7u) == 0, "torso_select: xy_c must be 8-byte aligned");
+    hipLaunchKernelGGL(k_torso_select, dim3(1), dim3(kSelectThreads), 0, as_stream(stream), bg_coords, N, density_grid_torso, grid_size,
+                       density_thresh, mean_density_dev, covered, xy_c, count);
+    return check_launch("torso_select");
 }
 
 int rn_blend_frame(float *image, const float *weights_sum, const float *bg, float *depth, const float *nears,

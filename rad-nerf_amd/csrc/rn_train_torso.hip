@@ -424,6 +424,61 @@ __global__ void __launch_bounds__(256) k_train_torso_const(CArgs p) {
     }
 }
 
+// ---- loss of a torso step -------------------------------------------------------------------------------------------------
+// Scatter-back of the compact rows, blend over the background, MSE + entropy and their gradients (nerf/renderer.py:286-302,
+// nerf/utils.py:749, 783-791), one pass over the N pixels in k_train_head_loss's shape: one workgroup, a double accumulator, a
+// fixed summation order.  `covered` is ascending (rn_torso_select), so pixel n finds its compact row by bisection instead of
+// through a scattered index map that would have to be written and read back inside the launch; every output element has one
+// writer.  Uncovered pixels: alpha 0, pred = bg bit for bit, and their share of both means.
+constexpr int kLossThreads = 1024;
+__global__ void __launch_bounds__(kLossThreads)
+k_train_torso_loss(const float *__restrict__ alpha_c, const float *__restrict__ color_c, const int32_t *__restrict__ covered, uint32_t P,
+                   const int32_t *__restrict__ p_dev, const float *__restrict__ bg, uint32_t bg_stride, const float *__restrict__ target,
+                   uint32_t target_stride, uint32_t N, float *__restrict__ loss, float *__restrict__ pred, float *__restrict__ alpha_full,
+                   float *__restrict__ g_alpha_c, float *__restrict__ g_color_c) {
+    __shared__ double red[kLossThreads / kWave];
+    const uint32_t count = live_count(P, p_dev);
+    const float inv_n = 1.0f / (float)N;
+    double acc = 0.0;
+    for (uint32_t n = threadIdx.x; n < N; n += kLossThreads) {
+        uint32_t lo = 0, hi = count;                 // first row whose pixel index is >= n
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if ((uint32_t)covered[mid] < n) lo = mid + 1; else hi = mid;
+        }
+        const bool on = lo < count && (uint32_t)covered[lo] == n;
+        const float w = on ? alpha_c[lo] : 0.0f;
+        float mse = 0.0f, ga = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float b = bg[(size_t)n * bg_stride + c];
+            const float col = on ? color_c[3 * (size_t)lo + c] : 0.0f;
+            const float pr = on ? col * w + b * (1.0f - w) : b;      // renderer.py:299
+            pred[3 * (size_t)n + c] = pr;
+            const float d = pr - target[(size_t)n * target_stride + c];
+            mse += d * d;
+            const float gp = 2.0f * d * (inv_n / 3.0f);
+            if (on) g_color_c[3 * (size_t)lo + c] = w * gp;
+            ga += (col - b) * gp;
+        }
+        alpha_full[n] = w;
+        const float a = fminf(fmaxf(w, 1e-5f), 1.0f - 1e-5f);
+        const float la = log2f(a), lb = log2f(1.0f - a);
+        const float ent = -a * la - (1.0f - a) * lb;
+        const bool inside = w >= 1e-5f && w <= 1.0f - 1e-5f;         // clamp passes the gradient on [1e-5, 1 - 1e-5]
+        if (on) g_alpha_c[lo] = ga + (inside ? 1e-4f * inv_n * (lb - la) : 0.0f);
+        acc += (double)(mse / 3.0f) * inv_n + 1e-4 * (double)ent * inv_n;
+    }
+    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double t = 0.0;
+        for (int w = 0; w < kLossThreads / kWave; w++) t += red[w];
+        loss[0] = (float)t;
+    }
+}
+
 constexpr uint32_t kWPartsMax = 128;
 constexpr uint32_t kBlocksMax = 1u << 16;
 // workgroups of the forward / backward launch: one per kWaves tiles, at most one round of two per CU; RN_TORSO_TRAIN_BLOCKS caps
@@ -516,6 +571,18 @@ int rn_train_torso_weight_grads(const rn_torso_weights_t *w, const float *xy, fl
     CArgs c{raw_t(w), image + kFwd + kBwd + C_POSE, ind_code, gb, g->def_w0, g->tor_w0, w->ind_dim ? g->ind_code : nullptr};
     hipLaunchKernelGGL(k_train_torso_const, dim3(3), dim3(256), 0, s, c);
     return check_launch("train_torso_weight_grads");
+}
+
+int rn_train_torso_loss(const float *alpha_c, const float *color_c, const int32_t *covered, uint32_t P, const int32_t *p_dev,
+                        const float *bg, uint32_t bg_stride, const float *target, uint32_t target_stride, uint32_t N, float *loss,
+                        float *pred, float *alpha_full, float *grad_alpha_c, float *grad_color_c, rn_stream_t stream) {
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(bg && target && loss && pred && alpha_full, "train_torso_loss: null pointer");
+    RN_REQUIRE(P == 0 || (alpha_c && color_c && covered && grad_alpha_c && grad_color_c), "train_torso_loss: null pointer (compact rows with P > 0)");
+    RN_REQUIRE(bg_stride >= 3 && target_stride >= 3, "train_torso_loss: row strides of bg / target must be at least 3 floats");
+    hipLaunchKernelGGL(k_train_torso_loss, dim3(1), dim3(kLossThreads), 0, as_stream(stream), alpha_c, color_c, covered, P, p_dev, bg,
+                       bg_stride, target, target_stride, N, loss, pred, alpha_full, grad_alpha_c, grad_color_c);
+    return check_launch("train_torso_loss");
 }
 
 }  // extern "C"

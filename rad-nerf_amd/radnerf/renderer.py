@@ -11,7 +11,8 @@ How a frame is produced here:
     one host sync per iteration), torso layer through the fused torso kernel when the network has its shape;
   * training: march_rays_train -> network -> composite_rays_train with autograd through the HIP backward kernels; the torso
     layer gathers the covered pixels (index list from a HIP kernel), runs the PyTorch layers on them and copies the result
-    back by index.
+    back by index; opt-in (RN_TORSO_TRAIN=fused, from train_step): the covered pixels compacted on the device and the fused layer
+    on a device-side count, the blend left to the loss kernel (_torso_layer_deferred).
 Occupancy-grid maintenance (`update_extra_state`, `mark_untrained_grid`) is radnerf/occupancy.py: kernels over the cells
 in morton order, no Python block loops.
 """
@@ -251,6 +252,37 @@ class NeRFRenderer(nn.Module):
         return dict(weights_sum=weights_sum, ambient=ambient_sum, depth=depth, image=image, nears=nears, fars=fars)
 
     # ---------------------------------------------------------------------------------------------- torso layer
+    def _index_tensor(self, index, dev):
+        """The loader's frame index as an int64 device tensor: a tensor as it is, a Python list uploaded once per distinct value
+        (not once per step, and never inside a capture)."""
+        if torch.is_tensor(index):
+            return index
+        key = tuple(int(i) for i in index)
+        cache = self.__dict__.setdefault("_index_cache", {})
+        idx = cache.get(key)
+        if idx is None or idx.device != dev:
+            if len(cache) > 4096:
+                cache.clear()
+            idx = cache[key] = torch.as_tensor(key, dtype=torch.long, device=dev)
+        return idx
+
+    def _torso_layer_deferred(self, bg_coords, poses, index, background, results):
+        """The torso layer of a training step without a word to the host (opt-in, radnerf/train_torso.py): the covered pixels
+        compacted on the device, the fused layer on all N rows' capacity with the count as its live count.  Leaves the compact
+        pieces in `results`; the caller (radnerf/train.py) scatters back, blends and takes the loss in one kernel."""
+        from . import train_torso
+        code = None
+        if self.individual_dim_torso > 0:
+            table = self.individual_codes_torso
+            if isinstance(index, int):
+                code = table[index]
+            else:       # index_select: the row picked on the device, no list upload per step (run_cuda does the same for the head)
+                code = torch.index_select(table, 0, self._index_tensor(index, table.device).reshape(-1).long())
+        covered, xy_c, count = train_torso.select(self, bg_coords)
+        alpha_c, color_c, deform = train_torso.torso_forward(self, xy_c, poses, code, p_dev=count)
+        results.update(torso_alpha_c=alpha_c, torso_color_c=color_c, torso_covered=covered, torso_count=count, deform=deform,
+                       background=background)
+
     def _torso_layer(self, bg_coords, poses, enc_a, index, background, results):
         """Background with the 2-D torso layer blended over it (renderer.py:269-302); fills results[torso_*]."""
         n_px, dev = bg_coords.shape[0], bg_coords.device
@@ -338,17 +370,8 @@ class NeRFRenderer(nn.Module):
             if self.training and not isinstance(index, int):
                 # index_select = the same rows as individual_codes[index] (nerf/renderer.py:199); its backward is one index_add
                 # instead of index_put's sort + segmented scatter (5 launches for a one-element index)
-                if torch.is_tensor(index):
-                    idx = index
-                else:       # the loader's Python list: uploaded once per distinct value, not once per step
-                    key = tuple(int(i) for i in index)
-                    cache = self.__dict__.setdefault("_index_cache", {})
-                    idx = cache.get(key)
-                    if idx is None or idx.device != self.individual_codes.device:
-                        if len(cache) > 4096:
-                            cache.clear()
-                        idx = cache[key] = torch.as_tensor(key, dtype=torch.long, device=self.individual_codes.device)
-                idx = idx.reshape(-1)
+                # the loader's Python list: uploaded once per distinct value, not once per step
+                idx = self._index_tensor(index, self.individual_codes.device).reshape(-1)
                 if idx.numel() == 1 and idx.dtype == torch.int64 and idx.is_cuda and self._fused_head_expected(rays_o, auds):
                     ind_index = idx                 # the fused training kernels pick the row themselves (train_head.head_forward)
                 else:
@@ -370,6 +393,13 @@ class NeRFRenderer(nn.Module):
             # the caller blends, clamps and takes the loss in one kernel (radnerf/train.py: train_head.head_loss)
             results["head_image"], results["background"] = head["image"], background
             return results
+        if self.training and self.torso and kwargs.get("defer_blend") and torch.is_tensor(background):
+            from . import train_torso
+            bg_rows = background.reshape(-1, 3)
+            if bg_rows.shape[0] == bg_coords.shape[0] and train_torso.step_usable(self, bg_coords, bg_rows):
+                # opt-in: compact torso rows on a device-side count; the caller blends and takes the loss in one kernel
+                self._torso_layer_deferred(bg_coords, poses, index, bg_rows, results)
+                return results
         if self.torso:
             background = self._torso_layer(bg_coords, poses, enc_a, index, background, results)
         elif torch.is_tensor(background):

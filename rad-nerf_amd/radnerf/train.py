@@ -170,9 +170,20 @@ def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, am
     import os
     fused_loss = (not torso and rgb.is_cuda and rgb.dtype == torch.float32 and os.environ.get("RN_TRAIN_LOSS", "fused") == "fused"
                   and torch.is_tensor(data.get("bg_color")) and data["bg_color"].dtype == torch.float32)
+    # opt-in: a torso step that stays on the device (covered pixels compacted there, blend + loss in one kernel).  Asked for here
+    # when the target can feed the loss kernel; the renderer decides (train_torso.step_usable, once per step) and answers with
+    # the compact pieces, or with today's results
+    torso_direct = (torso and os.environ.get("RN_TORSO_TRAIN") == "fused" and rgb.is_cuda and rgb.dtype == torch.float32
+                    and torch.is_tensor(data.get("bg_color")))
     out = model.render(data["rays_o"], data["rays_d"], data["auds"], data["bg_coords"], data["poses"], eye=data["eye"],
                        index=data["index"], staged=False, bg_color=data["bg_color"], perturb=True, force_all_rays=False,
-                       dt_gamma=opt.dt_gamma, max_steps=opt.max_steps, defer_blend=fused_loss)
+                       dt_gamma=opt.dt_gamma, max_steps=opt.max_steps, defer_blend=fused_loss or torso_direct)
+    if "torso_alpha_c" in out:
+        from . import train_torso
+        loss, pred, alpha_full = train_torso.torso_loss(out["torso_alpha_c"], out["torso_color_c"], out["torso_covered"], out["torso_count"],
+                                                        out["background"], rgb)
+        out["torso_color"], out["torso_alpha"] = pred, alpha_full
+        return pred, rgb, loss
     if "head_image" in out:
         # blend over the background (nerf/renderer.py:306), clamp and the loss below with their gradients: ONE kernel
         from . import train_head
@@ -389,6 +400,9 @@ class GraphedTrainer(Trainer):
         n_rays = int(self._static["rays_o"].reshape(-1, 3).shape[0])
         if step_marcher_supported(n_rays, self._counter.device):
             step_marcher_prepare(n_rays, self._counter.device)       # persistent state: must not be born inside the capture
+        if self._torso_route():
+            from . import train_torso
+            train_torso.prepare(m, n_rays)                           # the same for the torso route: pinned mean density, workspaces
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)
@@ -410,6 +424,12 @@ class GraphedTrainer(Trainer):
         self.captures += 1
         self.capture_log.append((self.global_step, int(self._budget.item()), self._capacity))
 
+    def _torso_route(self):
+        """A torso step can be captured only on the device-resident route (opt-in RN_TORSO_TRAIN=fused, radnerf/train_torso.py):
+        the default one asks the host for the covered pixels."""
+        import os
+        return bool(self.opt.torso) and os.environ.get("RN_TORSO_TRAIN") == "fused" and os.environ.get("RN_TORSO_STEP", "device") == "device"
+
     def step(self, data):
         m = self.model
         m.train()
@@ -417,6 +437,9 @@ class GraphedTrainer(Trainer):
             with torch.no_grad():
                 m.update_extra_state()
         self.global_step += 1
+        if self._torso_route() and next(m.parameters()).is_cuda:
+            from . import train_torso
+            train_torso.pin_mean(m)          # a mean set from the host since the last step goes into the scalar the graph reads
         if m.mean_count <= 0 or not next(m.parameters()).is_cuda:        # first window / CPU: the eager step
             self.optimizer.zero_grad(set_to_none=True)
             with _join_in_optimizer(self.optimizer):

@@ -7,7 +7,14 @@ torch.autograd in Trainer.train_step.  One call of `torso_forward` is 2 launches
 frequency encodes, the grid operator, two MLP stacks of five launches each, pads, concatenations and the autograd of all of it.
 Differentiable in the six weight matrices, the torso table and the individual code; the pixel coordinates get no gradient.
 
-Opt-in: RN_TORSO_TRAIN=fused in the environment.  Eager, on the caller's stream.
+Opt-in: RN_TORSO_TRAIN=fused in the environment.  On the caller's stream.
+
+With the opt-in a training step (radnerf/train.py: train_step) keeps the whole torso part on the device: `select` compacts the
+covered pixels of the batch in ascending order and leaves their count in device memory (rn_torso_select, csrc/rn_torso.hip),
+`torso_forward` runs at the capacity of all N rows with that count as its live count, and `torso_loss` scatters back, blends over
+the background and takes MSE + entropy with their gradients in one launch (rn_train_torso_loss) -- no torch.nonzero, no .item(),
+no shape that depends on the data, so GraphedTrainer can capture the step.  RN_TORSO_STEP=host keeps the fused layer on the index
+list the host asks for (rn_torso_mask + torch.nonzero), for comparisons.
 """
 import ctypes as C
 import os
@@ -104,7 +111,7 @@ class _TorsoTrain(torch.autograd.Function):
             tg = TorsoGradsT()
             (tg.def_w0, tg.def_w1, tg.def_w2, tg.tor_w0, tg.tor_w1, tg.tor_w2) = [g.data_ptr() for g in grads]
             tg.ind_code = hip.ptr(g_code)
-            wsp = hip.workspace(int(_lib.rn_train_torso_wgrad_workspace()), dev)
+            wsp = _wgrad_workspace(dev)
             hip.call("rn_train_torso_weight_grads", C.byref(tw), hip.ptr(xy), shrink, hip.ptr(code_c), P, hip.ptr(p_dev), hip.ptr(image),
                      hip.ptr(work), C.byref(tg), hip.ptr(wsp), s)
             g_table = torch.zeros_like(tab)
@@ -116,6 +123,131 @@ class _TorsoTrain(torch.autograd.Function):
             if g_code is not None:
                 g_code.zero_()
         return (None, None, g_code.view(code_shape) if g_code is not None else None, None, None, g_table, *grads)
+
+
+def step_usable(model, bg_coords, background, target=None):
+    """May a training step take the device-resident route (select -> torso_forward on a live count -> torso_loss)?  Opted in, the
+    supported shape, fp32 CUDA tensors, no autocast, grad enabled, and a background that is a tensor without a gradient (the loss
+    kernel returns none for it)."""
+    tensors = [bg_coords, background] + ([target] if target is not None else [])
+    # RN_TORSO_STEP=host: the fused layer on the index list the host asks for (rn_torso_mask + torch.nonzero), for comparisons
+    return (os.environ.get("RN_TORSO_TRAIN") == "fused" and os.environ.get("RN_TORSO_STEP", "device") == "device"
+            and model.training and torch.is_grad_enabled()
+            and not torch.is_autocast_enabled() and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors)
+            and not background.requires_grad and supported(model))
+
+
+def pin_mean(model):
+    """The mean torso density as a device scalar at ONE fixed address, whatever set it last -- the occupancy refresh's own
+    `stats_torso`: the refresh leaves it there; a value set from the host (checkpoint, the setter) or held in another tensor is
+    written into that buffer.  Call outside a capture: a captured select reads the buffer at every replay."""
+    from . import occupancy
+    stats = occupancy._scratch(model).stats_torso
+    held = model._mean_density_torso_dev
+    if held is None:
+        stats.fill_(float(model._mean_density_torso))
+    elif held is not stats:
+        stats.copy_(held.reshape(-1)[:1])
+    model._mean_density_torso_dev = stats
+    return stats
+
+
+_WGRAD_WS = {}
+
+
+def _wgrad_workspace(dev):
+    """The weight-gradient scratch of the torso layer: its own buffer per device, of the one size the library asks for.  It never
+    grows and nothing else uses it, so a captured step can keep its address (the shared hip.workspace() buffer is replaced when a
+    larger request comes)."""
+    key = dev.index if dev.index is not None else torch.cuda.current_device()
+    buf = _WGRAD_WS.get(key)
+    if buf is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("train_torso: the weight-gradient workspace must exist before a step is captured (train_torso.prepare)")
+        buf = _WGRAD_WS[key] = torch.empty(int(_lib.rn_train_torso_wgrad_workspace()), dtype=torch.uint8, device=dev)
+    return buf
+
+
+def prepare(model, n_px):
+    """Everything persistent a captured torso step of `n_px` pixels touches, created before the capture: the pinned mean density,
+    the weight-gradient workspace, the host copy of the table's level offsets."""
+    dev = model.density_grid_torso.device
+    pin_mean(model)
+    _wgrad_workspace(dev)
+    hip.host_offsets(model.torso_encoder.offsets)
+
+
+def select(model, bg_coords, alloc=None):
+    """-> (covered int32 [N], xy_c [N,2], count int32 [1]): the pixels of bg_coords [N,2] the torso layer covers (ascending, the
+    order of occupancy.torso_pixels) and their coordinates, compacted on the device; rows at or past `count` are not written.
+    The threshold min(density_thresh_torso, mean_density_torso) takes the mean from device memory while the refresh's value is
+    still there, so nothing here waits for the GPU."""
+    N, dev = int(bg_coords.shape[0]), bg_coords.device
+    coords = bg_coords.contiguous()
+    mean = model._mean_density_torso_dev
+    thresh = float(model.density_thresh_torso) if mean is not None else min(model.density_thresh_torso, model._mean_density_torso)
+    if alloc is None:
+        covered = torch.empty(N, dtype=torch.int32, device=dev)
+        xy_c = torch.empty(N, 2, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+    else:
+        covered, xy_c, count = alloc(N, dtype=torch.int32), alloc(N, 2), alloc(1, dtype=torch.int32)
+    hip.call("rn_torso_select", hip.ptr(coords, torch.float32), N, hip.ptr(model.density_grid_torso), int(model.grid_size), float(thresh),
+             hip.ptr(mean), hip.ptr(covered), hip.ptr(xy_c), hip.ptr(count), hip.stream())
+    return covered, xy_c, count
+
+
+class _TorsoLoss(torch.autograd.Function):
+    """Scatter-back, blend, MSE + entropy of a torso step in one kernel; returns (loss, pred, alpha_full, gradients)."""
+
+    @staticmethod
+    def forward(ctx, alpha_c, color_c, covered, count, bg, target, alloc):
+        P, N, dev = alpha_c.shape[0], bg.shape[0], bg.device
+        alpha_c, color_c = alpha_c.contiguous(), color_c.contiguous()
+        if alloc is None:
+            out = torch.empty(4 * N + 4 * P + 1, dtype=torch.float32, device=dev)
+            pred, alpha_full = out[0:3 * N].view(N, 3), out[3 * N:4 * N].view(N, 1)
+            grads, loss = out[4 * N:4 * N + 4 * P], out[4 * N + 4 * P:]
+        else:
+            pred, alpha_full, grads, loss = alloc(N, 3), alloc(N, 1), alloc(4 * P), alloc(1)
+        g_alpha, g_color = grads[0:P].view(P, 1), grads[P:4 * P].view(P, 3)
+        hip.call("rn_train_torso_loss", hip.ptr(alpha_c), hip.ptr(color_c), hip.ptr(covered), P, hip.ptr(count), bg.data_ptr(), bg.stride(0),
+                 target.data_ptr(), target.stride(0), N, loss.data_ptr(), pred.data_ptr(), alpha_full.data_ptr(), g_alpha.data_ptr(),
+                 g_color.data_ptr(), hip.stream())
+        ctx.save_for_backward(grads)
+        ctx.P = P
+        ctx.mark_non_differentiable(pred, alpha_full, grads)
+        ctx.set_materialize_grads(False)
+        return loss.view(()), pred, alpha_full, grads
+
+    @staticmethod
+    def backward(ctx, g, *_unused):
+        (grads,) = ctx.saved_tensors
+        P = ctx.P
+        if g is None:
+            return (None,) * 7
+        scaled = grads * g                        # rows past the live count hold nothing; the layer's backward never reads them
+        return scaled[0:P].view(P, 1), scaled[P:4 * P].view(P, 3), None, None, None, None, None
+
+
+def torso_loss(alpha_c, color_c, covered, count, bg, target, alloc=None):
+    """The torso loss of Trainer.train_step from the compact rows of the layer: alpha_c [P,1], color_c [P,3] (rows below `count`
+    live), covered int32 [P] ascending, count int32 [1] on the device, bg / target [N,3] fp32 (rows may be strided views of one
+    batch table; bg gets no gradient).  -> (loss, pred [N,3] = results["torso_color"], alpha_full [N,1] = results["torso_alpha"])."""
+    def rows(t):
+        t = t.reshape(-1, 3)
+        return t if t.stride(1) == 1 and t.stride(0) >= 3 else t.contiguous()
+    if bg.requires_grad:
+        raise ValueError("torso_loss: the background gets no gradient from this kernel; take the per-operator path")
+    bg, target = rows(bg), rows(target)
+    if bg.shape[0] != target.shape[0] or alpha_c.shape[0] > bg.shape[0]:
+        raise ValueError(f"torso_loss: {bg.shape[0]} background rows, {target.shape[0]} target rows, {alpha_c.shape[0]} compact rows")
+    loss, pred, alpha_full, grads = _TorsoLoss.apply(alpha_c, color_c, covered, count, bg, target, alloc)
+    loss._rn_torso_alpha = alpha_full            # what results["torso_alpha"] holds; a captured step keeps it with its loss
+    # d loss / d (alpha_c, color_c) were written by the same kernel: train_head.backward(loss) hands them to autograd as they are
+    P = alpha_c.shape[0]
+    loss._rn_direct = ((alpha_c, color_c), (grads[0:P].view(P, 1), grads[P:4 * P].view(P, 3)))
+    return loss, pred, alpha_full
 
 
 def torso_forward(model, xy, poses, code, p_dev=None, alloc=None):

@@ -226,6 +226,8 @@ FUNCTIONS = {
     "rn_train_torso_backward": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "rn_train_torso_weight_grads": (_int, [_P(TorsoWeightsT), _ptr, _f32, _ptr, _u32, _ptr, _ptr, _ptr, _P(TorsoGradsT), _ptr,
                                            _ptr]),
+    "rn_torso_select": (_int, [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_torso_loss": (_int, [_ptr, _ptr, _ptr, _u32, _ptr, _ptr, _u32, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
 }
 
 
