@@ -91,4 +91,74 @@ __device__ __forceinline__ uint32_t ballot_prefix(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// uniform in [0,1) with 24 random bits from a 32-bit mix (public-domain "lowbias32" finaliser applied twice): the jitter of the
+// occupancy refresh and of the one-launch training marcher, identical on the CPU oracle
+__host__ __device__ inline uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+__host__ __device__ inline float hash_u01(uint32_t seed, uint32_t idx) {
+    return (float)(mix32(mix32(idx) ^ seed) >> 8) * (1.0f / 16777216.0f);
+}
+
+// A size the host passes as an upper bound and the device may know better: min(n_arg, *n_dev) (n_dev may be NULL).
+__device__ __forceinline__ uint32_t clamp_count(uint32_t n_arg, const int32_t *__restrict__ n_dev) {
+    if (!n_dev) return n_arg;
+    const uint32_t d = (uint32_t)*n_dev;
+    return d < n_arg ? d : n_arg;
+}
+
+// ---- workgroup primitives (THREADS = blockDim.x, a multiple of the wave; lds: THREADS / kWave words) ------------------
+// Lane 0 of every wave gets the wave's sum.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+// Sum over the workgroup, returned to every thread; the waves' sums are added in wave order.  Two barriers: the second one
+// frees `lds` for the next call, and between them every thread has passed a barrier after whatever it wrote to LDS before.
+template <typename T, int THREADS>
+__device__ __forceinline__ T block_sum(T v, T *lds) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = 0;
+    for (int w = 0; w < THREADS / kWave; w++) s += lds[w];
+    __syncthreads();
+    return s;
+}
+// The same sum for thread 0 alone (the others get 0) behind ONE barrier: the epilogue of a kernel that publishes one number.
+template <typename T, int THREADS>
+__device__ __forceinline__ T block_sum_first(T v, T *lds) {
+    v = wave_sum(v);
+    if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = v;
+    __syncthreads();
+    T s = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < THREADS / kWave; w++) s += lds[w];
+    return s;
+}
+// Exclusive prefix sum over the workgroup in thread order (wave scan by __shfl_up, wave totals in LDS); *total = the sum.
+// One barrier, after the write: the caller keeps `lds` free of readers of an earlier phase.
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t *lds, uint32_t *total = nullptr) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t incl = v;
+#pragma unroll
+    for (uint32_t d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) lds[wave] = incl;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < THREADS / kWave; w++) {
+        all += lds[w];
+        before += w < wave ? lds[w] : 0u;
+    }
+    if (total) *total = all;
+    return before + incl - v;
+}
+
 }  // namespace rn

@@ -1,5 +1,6 @@
-// rn_dda_dev.h -- the occupancy-grid DDA walk, shared by the marching kernels of rn_raymarching.hip and
-// the device-side inference loop of rn_head_loop.hip (identical samples from both).
+// rn_dda_dev.h -- the occupancy-grid DDA walk: ONE loop (Dda::walk) with a sink per use (count / emit / record), the jittered
+// start and the per-slot march of the inference loop.  Shared by the marching kernels of rn_raymarching.hip and the
+// device-side inference loop of rn_head_loop.hip (identical samples from both).
 #pragma once
 
 #include "rn_common.h"
@@ -91,13 +92,12 @@ struct Dda {
         return (uint32_t)((float)level * H3 + (float)morton3D((uint32_t)nx, (uint32_t)ny, (uint32_t)nz));
     }
 
-    // Walk from t, at most `limit` occupied steps.  EMIT writes samples to xyzs/dirs/deltas.
+    // Walk from t, at most `limit` occupied steps; sink(*this, step, t, x, y, z, dt) sees every sample (see the sinks below).
     // (Measured on MI355X: the walk is bound by its own arithmetic, ~100 VALU ops per lattice point, not by the
     // dependent bitfield loads -- fetching the occupancy of the next 4 / 8 / 16 lattice points together and replaying the
     // decisions on a bit mask made k_head_march 10-17 % slower, so the loop keeps the reference's shape.)
-    template <bool EMIT>
-    __device__ __forceinline__ uint32_t walk(float &t_io, uint32_t limit, float *xyzs, float *dirs,
-                                             float *deltas) const {
+    template <class Sink>
+    __device__ __forceinline__ uint32_t walk(float &t_io, uint32_t limit, Sink sink) const {
         float t = t_io;
         uint32_t step = 0;
         uint32_t guard = 0;  // not in the reference: bounds the walk on degenerate inputs (far = inf)
@@ -106,16 +106,8 @@ struct Dda {
             int nx, ny, nz;
             const uint32_t index = cell_of(t, x, y, z, dt, mip_bound, nx, ny, nz);
             if (grid[index >> 3] & (1u << (index & 7u))) {
-                if (EMIT) {
-                    xyzs[0] = x; xyzs[1] = y; xyzs[2] = z;
-                    dirs[0] = dx; dirs[1] = dy; dirs[2] = dz;
-                }
+                sink(*this, step, t, x, y, z, dt);
                 t += dt;
-                if (EMIT) {
-                    deltas[0] = dt;
-                    deltas[1] = t;
-                    xyzs += 3; dirs += 3; deltas += 2;
-                }
                 step++;
             } else if (one_step_skips) {
                 t += dt;                     // = t + clampf(t * dt_gamma, dt_min, dt_max), the loop's single pass
@@ -138,49 +130,45 @@ struct Dda {
         return step;
     }
 
-    // The same walk, remembering where each sample was taken instead of writing it: rec[k * stride] = t of sample k.
-    // emit() rebuilds the sample from that t with the expressions of cell_of() / walk<true>() -- same bits -- so a caller that
-    // must know every ray's count before it can place the samples (the training marcher) walks once, not twice.
-    __device__ __forceinline__ uint32_t walk_record(float &t_io, uint32_t limit, float *rec, uint32_t stride) const {
-        float t = t_io;
-        uint32_t step = 0;
-        uint32_t guard = 0;
-        while (t < far && step < limit && guard < (1u << 20)) {
-            float x, y, z, dt, mip_bound;
-            int nx, ny, nz;
-            const uint32_t index = cell_of(t, x, y, z, dt, mip_bound, nx, ny, nz);
-            if (grid[index >> 3] & (1u << (index & 7u))) {
-                rec[step * stride] = t;
-                t += dt;
-                step++;
-            } else if (one_step_skips) {
-                t += dt;                     // = t + clampf(t * dt_gamma, dt_min, dt_max), the loop's single pass
-                guard++;
-            } else {
-                const float sx = copysignf(1.0f, dx), sy = copysignf(1.0f, dy), sz = copysignf(1.0f, dz);
-                const float tx = ((((float)nx + 0.5f + 0.5f * sx) * rH * 2 - 1) * mip_bound - x) * rdx;
-                const float ty = ((((float)ny + 0.5f + 0.5f * sy) * rH * 2 - 1) * mip_bound - y) * rdy;
-                const float tz = ((((float)nz + 0.5f + 0.5f * sz) * rH * 2 - 1) * mip_bound - z) * rdz;
-                const float tt = fminf(t + fmaxf(0.0f, fminf(tx, fminf(ty, tz))), far);
-                do {
-                    t += clampf(t * dt_gamma, dt_min, dt_max);
-                    guard++;
-                } while (t < tt && guard < (1u << 20));
-            }
-            guard++;
+    // The sinks of walk().  CountSamples: the count is all the caller wants.
+    struct CountSamples {
+        __device__ __forceinline__ void operator()(const Dda &, uint32_t, float, float, float, float, float) {}
+    };
+    // EmitSamples: sample k goes to row k of xyzs / dirs / deltas; deltas = (dt, t of the next lattice point).
+    struct EmitSamples {
+        float *xyzs, *dirs, *deltas;
+        __device__ __forceinline__ void operator()(const Dda &s, uint32_t, float t, float x, float y, float z, float dt) {
+            xyzs[0] = x; xyzs[1] = y; xyzs[2] = z;
+            dirs[0] = s.dx; dirs[1] = s.dy; dirs[2] = s.dz;
+            deltas[0] = dt;
+            deltas[1] = t + dt;
+            xyzs += 3; dirs += 3; deltas += 2;
         }
-        t_io = t;
-        return step;
+    };
+    // RecordSamples: remember where each sample was taken instead of writing it, rec[k * stride] = t of sample k; emit()
+    // rebuilds the sample from that t -- same bits -- so a caller that must know every ray's count before it can place the
+    // samples (the training marcher) walks once, not twice.
+    struct RecordSamples {
+        float *rec;
+        uint32_t stride;
+        __device__ __forceinline__ void operator()(const Dda &, uint32_t step, float t, float, float, float, float) { rec[step * stride] = t; }
+    };
+
+    // the sample at parameter t, as walk() hands it to EmitSamples (the expressions of cell_of())
+    __device__ __forceinline__ void emit(float t, float *xyz, float *dir, float *delta) const {
+        EmitSamples{xyz, dir, delta}(*this, 0u, t, clampf(ox + t * dx, -bound, bound), clampf(oy + t * dy, -bound, bound),
+                                     clampf(oz + t * dz, -bound, bound), clampf(t * dt_gamma, dt_min, dt_max));
     }
 
-    __device__ __forceinline__ void emit(float t, float *xyz, float *dir, float *delta) const {
-        xyz[0] = clampf(ox + t * dx, -bound, bound);
-        xyz[1] = clampf(oy + t * dy, -bound, bound);
-        xyz[2] = clampf(oz + t * dz, -bound, bound);
-        dir[0] = dx; dir[1] = dy; dir[2] = dz;
-        const float dt = clampf(t * dt_gamma, dt_min, dt_max);
-        delta[0] = dt;
-        delta[1] = t + dt;
+    // the jittered start of a ray whose walk begins at t (raymarching.cu:392 == :873): u = a uniform number, 0 = no jitter
+    __device__ __forceinline__ float start(float t, float u) const { return t + clampf(t * dt_gamma, dt_min, dt_max) * u; }
+
+    // One ray's share of a loop iteration: at most n_step samples from t into rows base .. base + n_step - 1; the rows the walk
+    // did not reach get deltas = 0 (the network and the compositor skip them), so the sample buffers never need a memset.
+    __device__ __forceinline__ uint32_t march_slot(float t, uint32_t n_step, uint32_t base, float *xyzs, float *dirs, float *deltas) const {
+        const uint32_t emitted = walk(t, n_step, EmitSamples{xyzs + (size_t)base * 3, dirs + (size_t)base * 3, deltas + (size_t)base * 2});
+        for (uint32_t k = emitted; k < n_step; k++) { deltas[((size_t)base + k) * 2] = 0.0f; deltas[((size_t)base + k) * 2 + 1] = 0.0f; }
+        return emitted;
     }
 };
 

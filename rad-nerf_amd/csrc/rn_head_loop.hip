@@ -4,9 +4,10 @@
 // nerf/renderer.py:225-262 per frame.  The loop keeps n_alive / step / n_step in device memory (double-buffered state
 // words), so a frame is enqueued without a single host read-back; compaction is a stable ballot/mbcnt scatter.  The
 // per-sample network between march and composite is rn_fused.hip's kernel, launched through run_fused().
+// What happens to one ray (box test, list order, walk, compositor) is rn_ray_dev.h's / rn_dda_dev.h's, shared with the per-operator
+// kernels of rn_raymarching.hip; this file owns the loop: its state words, the live list, the compaction and the launches.
 #include "rn_fused_dev.h"
-
-#include <float.h>
+#include "rn_ray_dev.h"
 
 namespace rn {
 
@@ -39,26 +40,13 @@ __device__ __forceinline__ void next_state(int32_t *st, uint32_t N, uint32_t n_a
 // independent), a block-wide scan places each lane's entries.  Returns the workgroup's live-sample count.
 __device__ __forceinline__ uint32_t list_live_slots(uint32_t emitted, uint32_t base, int32_t *live_count,
                                                     int32_t *__restrict__ live_slots, uint32_t *sh /* [kLoopBlock / kWave + 1] */) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t incl = emitted;
-#pragma unroll
-    for (uint32_t d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
     __syncthreads();  // sh may still be read by the caller's previous phase
-    if (lane == 63) sh[wave] = incl;
-    __syncthreads();
-    uint32_t total = 0, before = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < kLoopBlock / kWave; w++) {
-        total += sh[w];
-        before += w < wave ? sh[w] : 0u;
-    }
+    uint32_t total;
+    const uint32_t before = block_exclusive_scan<kLoopBlock>(emitted, sh, &total);
     if (live_slots) {
         if (threadIdx.x == 0) sh[kLoopBlock / kWave] = total ? (uint32_t)atomicAdd(live_count, (int32_t)total) : 0u;
         __syncthreads();
-        const uint32_t at = sh[kLoopBlock / kWave] + before + incl - emitted;
+        const uint32_t at = sh[kLoopBlock / kWave] + before;
         for (uint32_t k = 0; k < emitted; k++) live_slots[at + k] = (int32_t)(base + k);
     }
     return total;
@@ -79,41 +67,9 @@ k_head_begin(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
         state[RN_HEAD_ST_HIST] = (int32_t)N;
     }
     if (n >= N) return;
-    const float ox = rays_o[n * 3], oy = rays_o[n * 3 + 1], oz = rays_o[n * 3 + 2];
-    const float dx = rays_d[n * 3], dy = rays_d[n * 3 + 1], dz = rays_d[n * 3 + 2];
-    const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
-    float near = (aabb[0] - ox) * rdx, far = (aabb[3] - ox) * rdx;
-    if (near > far) { float c = near; near = far; far = c; }
-    float near_y = (aabb[1] - oy) * rdy, far_y = (aabb[4] - oy) * rdy;
-    if (near_y > far_y) { float c = near_y; near_y = far_y; far_y = c; }
-    bool miss = (near > far_y || near_y > far);
-    if (!miss) {
-        if (near_y > near) near = near_y;
-        if (far_y < far) far = far_y;
-        float near_z = (aabb[2] - oz) * rdz, far_z = (aabb[5] - oz) * rdz;
-        if (near_z > far_z) { float c = near_z; near_z = far_z; far_z = c; }
-        miss = (near > far_z || near_z > far);
-        if (!miss) {
-            if (near_z > near) near = near_z;
-            if (far_z < far) far = far_z;
-            if (near < min_near) near = min_near;
-        }
-    }
-    near = miss ? FLT_MAX : near;
-    far = miss ? FLT_MAX : far;
-    nears[n] = near; fars[n] = far;
-    rays_t[n] = near;
-    // Slot n of the alive list: ray n, or (order_w = image width) the rays of 8 x 8 pixel blocks together, so that the 64
-    // samples of a wave and the tiles of a CU cover a compact patch of the image instead of a one-pixel-high strip --
-    // more of their grid rows coincide.  Rays are independent, so the order changes no pixel.
-    uint32_t ray = n;
-    if (order_w) {
-        const uint32_t t = n >> 6, within = n & 63u, tiles_x = order_w >> 3;
-        ray = ((t / tiles_x) * 8u + (within >> 3)) * order_w + (t % tiles_x) * 8u + (within & 7u);
-    }
-    rays_alive[n] = (int32_t)ray;
-    weights_sum[n] = 0.0f; depth[n] = 0.0f;
-    image[n * 3] = 0.0f; image[n * 3 + 1] = 0.0f; image[n * 3 + 2] = 0.0f;
+    float near, far;
+    begin_ray(n, rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, aabb, min_near, nears, fars, rays_t, weights_sum, depth, image, near, far);
+    rays_alive[n] = (int32_t)alive_order(n, order_w);
 }
 
 // raymarching.cu:827-929 with device-resident n_alive / n_step; every slot of a live ray is written
@@ -133,9 +89,7 @@ k_head_march(const int32_t *__restrict__ st, const int32_t *__restrict__ rays_al
         const int index = rays_alive[n];
         Dda s;
         s.init(rays_o + (size_t)index * 3, rays_d + (size_t)index * 3, bound, dt_gamma, max_steps, C, H, grid, fars[index]);
-        float t = rays_t[index];  // perturb is off at inference: no noise term (renderer.py:251)
-        emitted = s.walk<true>(t, n_step, xyzs + (size_t)base * 3, dirs + (size_t)base * 3, deltas + (size_t)base * 2);
-        for (uint32_t k = emitted; k < n_step; k++) { deltas[((size_t)base + k) * 2] = 0.0f; deltas[((size_t)base + k) * 2 + 1] = 0.0f; }
+        emitted = s.march_slot(rays_t[index], n_step, base, xyzs, dirs, deltas);  // perturb is off at inference: no noise term (renderer.py:251)
     }
     // live samples of this iteration: listed for the network kernel, and counted -- one partial sum per workgroup, added up by
     // the compaction kernel (a same-address atomic per wavefront for the statistic cost 38 us per frame)
@@ -174,60 +128,23 @@ k_frame_begin(RaySource rs, float *__restrict__ rays_o, float *__restrict__ rays
     }
     uint32_t emitted = 0;
     if (n < N) {
-        uint32_t ray = n;                                         // alive-list order (see k_head_begin)
-        if (order_w) {
-            const uint32_t t = n >> 6, within = n & 63u, tiles_x = order_w >> 3;
-            ray = ((t / tiles_x) * 8u + (within >> 3)) * order_w + (t % tiles_x) * 8u + (within & 7u);
-        }
+        const uint32_t ray = alive_order(n, order_w);
         float o[3], d[3];
-        if (rs.pose) {                                            // same expressions as k_get_rays
-            const uint32_t r = ray / rs.W, c = ray - r * rs.W;
-            const float x = ((float)c + 0.5f - rs.cx) / rs.fx, y = ((float)r + 0.5f - rs.cy) / rs.fy, z = 1.0f;
-            const float norm = sqrtf(x * x + y * y + z * z);
-            const float ux = x / norm, uy = y / norm, uz = z / norm;
+        if (rs.pose) {
+            pinhole_ray(ray, rs.W, rs.fx, rs.fy, rs.cx, rs.cy, rs.pose, o, d);
 #pragma unroll
-            for (int k = 0; k < 3; k++) {
-                d[k] = ux * rs.pose[k * 4] + uy * rs.pose[k * 4 + 1] + uz * rs.pose[k * 4 + 2];
-                o[k] = rs.pose[k * 4 + 3];
-                rays_d[(size_t)ray * 3 + k] = d[k];
-                rays_o[(size_t)ray * 3 + k] = o[k];
-            }
+            for (int k = 0; k < 3; k++) { rays_d[(size_t)ray * 3 + k] = d[k]; rays_o[(size_t)ray * 3 + k] = o[k]; }
         } else {
 #pragma unroll
             for (int k = 0; k < 3; k++) { o[k] = rays_o[(size_t)ray * 3 + k]; d[k] = rays_d[(size_t)ray * 3 + k]; }
         }
-        // raymarching.cu:91-145
-        const float rdx = 1 / d[0], rdy = 1 / d[1], rdz = 1 / d[2];
-        float near = (aabb[0] - o[0]) * rdx, far = (aabb[3] - o[0]) * rdx;
-        if (near > far) { float c = near; near = far; far = c; }
-        float near_y = (aabb[1] - o[1]) * rdy, far_y = (aabb[4] - o[1]) * rdy;
-        if (near_y > far_y) { float c = near_y; near_y = far_y; far_y = c; }
-        bool miss = (near > far_y || near_y > far);
-        if (!miss) {
-            if (near_y > near) near = near_y;
-            if (far_y < far) far = far_y;
-            float near_z = (aabb[2] - o[2]) * rdz, far_z = (aabb[5] - o[2]) * rdz;
-            if (near_z > far_z) { float c = near_z; near_z = far_z; far_z = c; }
-            miss = (near > far_z || near_z > far);
-            if (!miss) {
-                if (near_z > near) near = near_z;
-                if (far_z < far) far = far_z;
-                if (near < min_near) near = min_near;
-            }
-        }
-        near = miss ? FLT_MAX : near;
-        far = miss ? FLT_MAX : far;
-        nears[ray] = near; fars[ray] = far;
-        rays_t[ray] = near;
+        float near, far;
+        begin_ray(ray, o, d, aabb, min_near, nears, fars, rays_t, weights_sum, depth, image, near, far);
         rays_alive[n] = (int32_t)ray;
-        weights_sum[ray] = 0.0f; depth[ray] = 0.0f;
-        image[(size_t)ray * 3] = 0.0f; image[(size_t)ray * 3 + 1] = 0.0f; image[(size_t)ray * 3 + 2] = 0.0f;
         // iteration 0 (k_head_march with n_alive = N, n_step = 1): slot n
         Dda s;
         s.init(o, d, bound, dt_gamma, max_steps, C, H, grid, far);
-        float t = near;
-        emitted = s.walk<true>(t, 1u, xyzs + (size_t)n * 3, dirs + (size_t)n * 3, deltas + (size_t)n * 2);
-        if (!emitted) { deltas[(size_t)n * 2] = 0.0f; deltas[(size_t)n * 2 + 1] = 0.0f; }
+        emitted = s.march_slot(near, 1u, n, xyzs, dirs, deltas);
     }
     __shared__ uint32_t sh[kLoopBlock / kWave + 1];
     const uint32_t total = list_live_slots(emitted, n, state + 6, live_slots, sh);
@@ -251,36 +168,8 @@ __device__ __forceinline__ void composite_chunk(uint32_t c, uint32_t n_alive, ui
                                                 uint32_t tag = 0) {
     const uint32_t n = c * kLoopBlock + threadIdx.x;
     bool survive = false;
-    if (n < n_alive) {
-        const int index = rays_alive[n];
-        const float *sg = sigmas + (size_t)n * n_step;
-        const float *rg = rgbs + (size_t)n * n_step * 3;
-        const float *dl = deltas + (size_t)n * n_step * 2;
-        float t = rays_t[index];
-        float weight_sum = weights_sum[index];
-        float d = depth[index];
-        float r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
-        uint32_t step = 0;
-        while (step < n_step) {
-            if (dl[0] == 0) break;
-            const float alpha = 1.0f - __expf(-sg[0] * dl[0]);
-            const float T = 1 - weight_sum;
-            const float weight = alpha * T;
-            weight_sum += weight;
-            t = dl[1];
-            d += weight * t;
-            r += weight * rg[0]; g += weight * rg[1]; b += weight * rg[2];
-            if (T < T_thresh) break;
-            sg++; rg += 3; dl += 2;
-            step++;
-        }
-        survive = !(step < n_step);
-        if (survive) rays_t[index] = t;
-        else rays_alive[n] = -1;
-        weights_sum[index] = weight_sum;
-        depth[index] = d;
-        image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
-    }
+    if (n < n_alive)
+        survive = composite_ray(n, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image);
     const unsigned long long mask = __ballot(survive);
     if ((threadIdx.x & 63) == 0) wave_cnt[threadIdx.x >> 6] = (uint32_t)__popcll(mask);
     __syncthreads();
@@ -378,9 +267,7 @@ __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, con
         const uint32_t n_live = st[5] ? (uint32_t)st[5] : n_blocks;
         for (uint32_t b = threadIdx.x; b < n_live; b += kLoopBlock) live += block_live[b];
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        part += __shfl_down(part, off, 64); live += __shfl_down(live, off, 64); all += __shfl_down(all, off, 64);
-    }
+    part = wave_sum(part); live = wave_sum(live); all = wave_sum(all);   // three sums behind one barrier
     if ((threadIdx.x & 63) == 0) { red[threadIdx.x >> 6] = part; red_live[threadIdx.x >> 6] = live; red_all[threadIdx.x >> 6] = all; }
     __syncthreads();
     uint32_t offset = 0, n_next = 0;
@@ -425,9 +312,7 @@ __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, con
             Dda s;
             s.init(m.rays_o + (size_t)v * 3, m.rays_d + (size_t)v * 3, m.bound, m.dt_gamma, max_steps, m.cascade, m.grid_size, m.grid,
                    m.fars[v]);
-            float t = m.rays_t[v];
-            emitted = s.walk<true>(t, n_step_next, m.xyzs + (size_t)base * 3, m.dirs + (size_t)base * 3, m.deltas + (size_t)base * 2);
-            for (uint32_t k = emitted; k < n_step_next; k++) { m.deltas[((size_t)base + k) * 2] = 0.0f; m.deltas[((size_t)base + k) * 2 + 1] = 0.0f; }
+            emitted = s.march_slot(m.rays_t[v], n_step_next, base, m.xyzs, m.dirs, m.deltas);
         }
         __shared__ uint32_t sh[kLoopBlock / kWave + 1];
         const uint32_t total = list_live_slots(emitted, base, st_next + 6, m.live_slots, sh);
@@ -527,8 +412,7 @@ static int check_head(const rn_head_t *h) {
 
 int rn_head_begin(const rn_head_t *h, rn_stream_t stream) {
     if (int rc = check_head(h)) return rc;
-    uint32_t order_w = h->order_w;
-    if (order_w && (order_w % 8u || h->N % order_w || (h->N / order_w) % 8u)) order_w = 0;
+    const uint32_t order_w = usable_order_w(h->order_w, h->N);
     hipLaunchKernelGGL(k_head_begin, dim3(div_up(h->N, kLoopBlock)), dim3(kLoopBlock), 0, as_stream(stream), h->rays_o,
                        h->rays_d, h->aabb, h->N, h->min_near, h->max_steps, h->nears, h->fars, h->weights_sum, h->depth,
                        h->image, h->rays_alive_a, h->rays_t, h->state, order_w);
@@ -612,8 +496,7 @@ int rn_head_iterate(const rn_head_t *h, const rn_grid_t *grid_xyz, const rn_grid
 int rn_frame_begin(const rn_head_t *h, const float *pose, float fx, float fy, float cx, float cy, uint32_t W, rn_stream_t stream) {
     if (int rc = check_head(h)) return rc;
     RN_REQUIRE(!pose || (fx != 0.0f && fy != 0.0f && W >= 1 && h->N % W == 0), "frame_begin: bad intrinsics / image width");
-    uint32_t order_w = h->order_w;
-    if (order_w && (order_w % 8u || h->N % order_w || (h->N / order_w) % 8u)) order_w = 0;
+    const uint32_t order_w = usable_order_w(h->order_w, h->N);
     const uint32_t nb = div_up(h->N, kLoopBlock) + 1;
     const RaySource rs{pose, fx, fy, cx, cy, W ? W : 1u};
     hipLaunchKernelGGL(k_frame_begin, dim3(div_up(h->N, kLoopBlock)), dim3(kLoopBlock), 0, as_stream(stream), rs,

@@ -17,7 +17,8 @@
 // (5 x 5 max pool with -inf padding, decayed running max, mean; one workgroup, the whole grid staged in LDS).
 //
 // Jitter: either the caller's uniform numbers (noise != NULL; torch.rand_like in the reference) or a counter-based hash of
-// (seed, element index) -- stateless, identical on the CPU oracle, so refreshes are reproducible bit for bit.
+// (seed, element index), hash_u01() of rn_common.h -- stateless, identical on the CPU oracle, so refreshes are reproducible bit
+// for bit.
 #include "rn_common.h"
 
 #include "../../include/radnerf_fused.h"
@@ -27,15 +28,6 @@
 namespace rn {
 
 constexpr int kOccBlock = 256;
-
-// uniform in [0,1) with 24 random bits from a 32-bit mix (public-domain "lowbias32" finaliser applied twice)
-__host__ __device__ inline uint32_t mix32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__host__ __device__ inline float hash_u01(uint32_t seed, uint32_t idx) {
-    return (float)(mix32(mix32(idx) ^ seed) >> 8) * (1.0f / 16777216.0f);
-}
 
 struct CascadeConsts {        // per cascade, computed on the host in double exactly as the Python expressions are
     float scale[16];          // (float)(bound_c - bound_c / H)          renderer.py:427-428
@@ -89,15 +81,8 @@ k_occ_update(const float *__restrict__ sigmas, float density_scale, float *__res
         clamped = v > 0.0f ? v : 0.0f;       // density_grid.clamp(min=0)
     }
     // sum in double: 2^21 floats add up exactly enough for the mean to round to the same float in any order
-    double s = (double)clamped;
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double b = 0.0;
-        for (int w = 0; w < kOccBlock / kWave; w++) b += red[w];
-        partial[blockIdx.x] = b;
-    }
+    const double b = block_sum_first<double, kOccBlock>((double)clamped, red);
+    if (threadIdx.x == 0) partial[blockIdx.x] = b;
 }
 
 // The partial sums added up in index order -> mean and threshold.  A launch of its own (one workgroup): the "last workgroup to
@@ -108,12 +93,8 @@ k_occ_mean(const double *__restrict__ partial, uint32_t blocks, uint32_t total, 
     __shared__ double red[kOccBlock / kWave];
     double acc = 0.0;
     for (uint32_t b = threadIdx.x; b < blocks; b += kOccBlock) acc += partial[b];
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
+    const double sum = block_sum_first<double, kOccBlock>(acc, red);
     if (threadIdx.x == 0) {
-        double sum = 0.0;
-        for (int w = 0; w < kOccBlock / kWave; w++) sum += red[w];
         const float mean = (float)(sum / (double)total);
         stats[0] = mean;
         stats[1] = fminf(mean, density_thresh);                     // density_thresh = min(mean_density, self.density_thresh)
@@ -225,14 +206,8 @@ k_torso_update(const float *__restrict__ alphas, float *__restrict__ grid, uint3
         grid[i] = v;
         s += (double)v;
     }
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double sum = 0.0;
-        for (int w = 0; w < kTorsoUpdThreads / kWave; w++) sum += red[w];
-        stats[0] = (float)(sum / (double)n);
-    }
+    const double sum = block_sum_first<double, kTorsoUpdThreads>(s, red);
+    if (threadIdx.x == 0) stats[0] = (float)(sum / (double)n);
 }
 
 static CascadeConsts cascade_consts(uint32_t C, uint32_t H, double bound) {

@@ -5,9 +5,9 @@
 // MI355X-first: 64-wide waves, one ray per lane, deterministic scan-based slice
 // reservation instead of per-ray atomics, ballot/mbcnt stable compaction, device-side
 // live-ray counts so the inference loop never has to read a size back on the host.
-#include "rn_dda_dev.h"
-
-#include <float.h>
+// The per-ray arithmetic (box test, DDA walk and its sinks, jittered start, compositor) is rn_ray_dev.h's / rn_dda_dev.h's, shared
+// with the device-resident loop of rn_head_loop.hip; workgroup sums and scans are rn_common.h's.
+#include "rn_ray_dev.h"
 
 namespace rn {
 
@@ -17,34 +17,6 @@ constexpr float kRPi = 0.3183098861837907f;
 
 // ------------------------------------------------------------------------------------------------
 // near / far  (raymarching.cu:91-145)
-__device__ __forceinline__ void near_far_of(const float *__restrict__ o, const float *__restrict__ d, const float *__restrict__ aabb,
-                                            float min_near, float &near_out, float &far_out) {
-    const float ox = o[0], oy = o[1], oz = o[2];
-    const float dx = d[0], dy = d[1], dz = d[2];
-    const float rdx = 1 / dx, rdy = 1 / dy, rdz = 1 / dz;
-
-    float near = (aabb[0] - ox) * rdx, far = (aabb[3] - ox) * rdx;
-    if (near > far) { float c = near; near = far; far = c; }
-    float near_y = (aabb[1] - oy) * rdy, far_y = (aabb[4] - oy) * rdy;
-    if (near_y > far_y) { float c = near_y; near_y = far_y; far_y = c; }
-
-    bool miss = (near > far_y || near_y > far);
-    if (!miss) {
-        if (near_y > near) near = near_y;
-        if (far_y < far) far = far_y;
-        float near_z = (aabb[2] - oz) * rdz, far_z = (aabb[5] - oz) * rdz;
-        if (near_z > far_z) { float c = near_z; near_z = far_z; far_z = c; }
-        miss = (near > far_z || near_z > far);
-        if (!miss) {
-            if (near_z > near) near = near_z;
-            if (far_z < far) far = far_z;
-            if (near < min_near) near = min_near;
-        }
-    }
-    near_out = miss ? FLT_MAX : near;
-    far_out = miss ? FLT_MAX : far;
-}
-
 __global__ void __launch_bounds__(kBlock)
 k_near_far(const float *__restrict__ rays_o, const float *__restrict__ rays_d,
            const float *__restrict__ aabb, uint32_t N, float min_near,
@@ -141,8 +113,7 @@ k_march_rays(uint32_t n_alive_arg, uint32_t n_step, const int32_t *__restrict__ 
              uint32_t C, uint32_t H, const uint8_t *__restrict__ grid, const float *__restrict__ fars,
              float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas,
              const float *__restrict__ noises, const int32_t *__restrict__ n_alive_dev) {
-    uint32_t n_alive = n_alive_arg;
-    if (n_alive_dev) { const uint32_t d = (uint32_t)*n_alive_dev; n_alive = d < n_alive ? d : n_alive; }
+    const uint32_t n_alive = clamp_count(n_alive_arg, n_alive_dev);
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= n_alive) return;
 
@@ -151,10 +122,9 @@ k_march_rays(uint32_t n_alive_arg, uint32_t n_step, const int32_t *__restrict__ 
     Dda s;
     s.init(rays_o + (size_t)index * 3, rays_d + (size_t)index * 3, bound, dt_gamma, max_steps, C, H, grid,
            fars[index]);
-    float t = rays_t[index];
-    t += clampf(t * dt_gamma, s.dt_min, s.dt_max) * noise;  // :873
+    float t = s.start(rays_t[index], noise);  // :873
     const size_t base = (size_t)n * n_step;
-    s.walk<true>(t, n_step, xyzs + base * 3, dirs + base * 3, deltas + base * 2);
+    s.walk(t, n_step, Dda::EmitSamples{xyzs + base * 3, dirs + base * 3, deltas + base * 2});
 }
 
 // Inference compositor  (raymarching.cu:942-1029)
@@ -164,41 +134,10 @@ k_composite_rays(uint32_t n_alive_arg, uint32_t n_step, float T_thresh, int32_t 
                  const float *__restrict__ rgbs, const float *__restrict__ deltas,
                  float *__restrict__ weights_sum, float *__restrict__ depth, float *__restrict__ image,
                  const int32_t *__restrict__ n_alive_dev) {
-    uint32_t n_alive = n_alive_arg;
-    if (n_alive_dev) { const uint32_t d = (uint32_t)*n_alive_dev; n_alive = d < n_alive ? d : n_alive; }
+    const uint32_t n_alive = clamp_count(n_alive_arg, n_alive_dev);
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     if (n >= n_alive) return;
-
-    const int index = rays_alive[n];
-    const float *sg = sigmas + (size_t)n * n_step;
-    const float *rg = rgbs + (size_t)n * n_step * 3;
-    const float *dl = deltas + (size_t)n * n_step * 2;
-
-    float t = rays_t[index];
-    float weight_sum = weights_sum[index];
-    float d = depth[index];
-    float r = image[index * 3], g = image[index * 3 + 1], b = image[index * 3 + 2];
-
-    uint32_t step = 0;
-    while (step < n_step) {
-        if (dl[0] == 0) break;
-        const float alpha = 1.0f - __expf(-sg[0] * dl[0]);
-        const float T = 1 - weight_sum;
-        const float weight = alpha * T;
-        weight_sum += weight;
-        t = dl[1];
-        d += weight * t;
-        r += weight * rg[0]; g += weight * rg[1]; b += weight * rg[2];
-        if (T < T_thresh) break;
-        sg++; rg += 3; dl += 2;
-        step++;
-    }
-    if (step < n_step) rays_alive[n] = -1;
-    else rays_t[index] = t;
-
-    weights_sum[index] = weight_sum;
-    depth[index] = d;
-    image[index * 3] = r; image[index * 3 + 1] = g; image[index * 3 + 2] = b;
+    composite_ray(n, n_step, T_thresh, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -206,30 +145,18 @@ k_composite_rays(uint32_t n_alive_arg, uint32_t n_step, float T_thresh, int32_t 
 // sums the counts of the blocks before it, and scatters with a ballot/mbcnt prefix per wavefront.
 constexpr int kCompactItems = 1024;  // elements per workgroup (4 per lane)
 
-__device__ __forceinline__ uint32_t block_reduce_sum(uint32_t v, uint32_t *lds) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) lds[wave] = v;
-    __syncthreads();
-    uint32_t s = 0;
-    for (uint32_t w = 0; w < kBlock / kWave; w++) s += lds[w];
-    __syncthreads();
-    return s;
-}
-
 __global__ void __launch_bounds__(kBlock)
 k_compact_count(const int32_t *__restrict__ in, uint32_t n_arg, const int32_t *__restrict__ n_dev,
                 uint32_t *__restrict__ block_counts) {
     __shared__ uint32_t lds[kBlock / kWave];
-    uint32_t n = n_arg;
-    if (n_dev) { const uint32_t d = (uint32_t)*n_dev; n = d < n ? d : n; }
+    const uint32_t n = clamp_count(n_arg, n_dev);
     const uint32_t base = blockIdx.x * kCompactItems;
     uint32_t c = 0;
     for (int i = 0; i < kCompactItems / kBlock; i++) {
         const uint32_t idx = base + i * kBlock + threadIdx.x;
         c += (idx < n && in[idx] >= 0) ? 1u : 0u;
     }
-    const uint32_t s = block_reduce_sum(c, lds);
+    const uint32_t s = block_sum<uint32_t, kBlock>(c, lds);
     if (threadIdx.x == 0) block_counts[blockIdx.x] = s;
 }
 
@@ -239,13 +166,12 @@ k_compact_scatter(const int32_t *__restrict__ in, uint32_t n_arg, const int32_t 
                   int32_t *__restrict__ n_out) {
     __shared__ uint32_t lds[kBlock / kWave];
     __shared__ uint32_t wave_off[kBlock / kWave];
-    uint32_t n = n_arg;
-    if (n_dev) { const uint32_t d = (uint32_t)*n_dev; n = d < n ? d : n; }
+    const uint32_t n = clamp_count(n_arg, n_dev);
 
     // exclusive prefix of the blocks before this one (and the grand total in the last block)
     uint32_t part = 0;
     for (uint32_t b = threadIdx.x; b < blockIdx.x; b += kBlock) part += block_counts[b];
-    uint32_t offset = block_reduce_sum(part, lds);
+    uint32_t offset = block_sum<uint32_t, kBlock>(part, lds);
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_out = (int32_t)(offset + block_counts[blockIdx.x]);
 
     const uint32_t base = blockIdx.x * kCompactItems;
@@ -285,12 +211,11 @@ k_march_train_count(const float *__restrict__ rays_o, const float *__restrict__ 
     if (n < N) {
         Dda s;
         s.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, bound, dt_gamma, max_steps, C, H, grid, fars[n]);
-        float t = nears[n];
-        t += clampf(t * dt_gamma, s.dt_min, s.dt_max) * noises[n];  // :392
-        num_steps = s.walk<false>(t, max_steps, nullptr, nullptr, nullptr);
+        float t = s.start(nears[n], noises[n]);  // :392
+        num_steps = s.walk(t, max_steps, Dda::CountSamples{});
         rays[n * 3 + 2] = (int32_t)num_steps;
     }
-    const uint32_t sum = block_reduce_sum(num_steps, lds);
+    const uint32_t sum = block_sum<uint32_t, kBlock>(num_steps, lds);
     if (threadIdx.x == 0) block_sums[blockIdx.x] = sum;
 }
 
@@ -305,28 +230,17 @@ k_march_train_write(const float *__restrict__ rays_o, const float *__restrict__ 
     __shared__ uint32_t lds[kBlock / kWave];
     __shared__ uint32_t wave_tot[kBlock / kWave];
     // M_dev (rn_march_rays_train_budget): the sample budget lives on the device and M is only the capacity of the buffers
-    if (M_dev) { const uint32_t b = (uint32_t)*M_dev; M = b < M ? b : M; }
+    M = clamp_count(M, M_dev);
     // samples reserved by all earlier blocks, on top of what the counter already holds (:446)
     uint32_t part = 0;
     for (uint32_t b = threadIdx.x; b < blockIdx.x; b += kBlock) part += block_sums[b];
-    const uint32_t block_off = block_reduce_sum(part, lds);
+    const uint32_t block_off = block_sum<uint32_t, kBlock>(part, lds);
     const uint32_t counter0 = (uint32_t)counter[0], counter1 = (uint32_t)counter[1];
 
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t num_steps = (n < N) ? (uint32_t)rays[n * 3 + 2] : 0u;
 
-    // exclusive scan of num_steps inside the block: wave scan (dpp shuffles) + wave totals
-    uint32_t incl = num_steps;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if ((int)(threadIdx.x & 63) >= off) incl += o;
-    }
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; w++) before += wave_tot[w];
-    const uint32_t point_index = counter0 + block_off + before + (incl - num_steps);
+    const uint32_t point_index = counter0 + block_off + block_exclusive_scan<kBlock>(num_steps, wave_tot);
 
     if (n < N) {
         const uint32_t ray_index = counter1 + n;
@@ -339,10 +253,9 @@ k_march_train_write(const float *__restrict__ rays_o, const float *__restrict__ 
         if (num_steps != 0 && fits) {
             Dda s;
             s.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, bound, dt_gamma, max_steps, C, H, grid, fars[n]);
-            float t = nears[n];
-            t += clampf(t * dt_gamma, s.dt_min, s.dt_max) * noises[n];
-            s.walk<true>(t, num_steps, xyzs + (size_t)point_index * 3, dirs + (size_t)point_index * 3,
-                         deltas + (size_t)point_index * 2);
+            float t = s.start(nears[n], noises[n]);
+            s.walk(t, num_steps, Dda::EmitSamples{xyzs + (size_t)point_index * 3, dirs + (size_t)point_index * 3,
+                                                  deltas + (size_t)point_index * 2});
         }
     }
     // last block publishes the new counter values once every block has read the old ones:
@@ -353,7 +266,7 @@ __global__ void k_march_train_counter(int32_t *counter, const uint32_t *block_su
     __shared__ uint32_t lds[kBlock / kWave];
     uint32_t part = 0;
     for (uint32_t b = threadIdx.x; b < n_blocks; b += kBlock) part += block_sums[b];
-    const uint32_t total = block_reduce_sum(part, lds);
+    const uint32_t total = block_sum<uint32_t, kBlock>(part, lds);
     if (threadIdx.x == 0) {
         counter[0] += (int32_t)total;
         counter[1] += (int32_t)N;
@@ -380,11 +293,6 @@ __global__ void k_march_train_counter(int32_t *counter, const uint32_t *block_su
 constexpr uint32_t kStepPolls = 1u << 20;
 constexpr uint32_t kRecSteps = 32;
 
-__device__ __forceinline__ uint32_t mix32(uint32_t x) {   // "lowbias32" finaliser (as rn_occupancy.hip's jitter)
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-
 template <bool RECORD>
 __global__ void __launch_bounds__(kBlock)
 k_march_train_step(const float *__restrict__ rays_o, const float *__restrict__ rays_d, const uint8_t *__restrict__ grid,
@@ -400,8 +308,7 @@ k_march_train_step(const float *__restrict__ rays_o, const float *__restrict__ r
     const uint32_t n_blocks = gridDim.x;
     const uint32_t tag = __hip_atomic_load(&state[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
     if (threadIdx.x == 0) stalled = 0u;
-    uint32_t budget = M;                                       // M: rows the buffers hold; *M_dev: this step's sample budget
-    if (M_dev) { const uint32_t b = (uint32_t)*M_dev; budget = b < M ? b : M; }
+    const uint32_t budget = clamp_count(M, M_dev);             // M: rows the buffers hold; *M_dev: this step's sample budget
 
     const uint32_t n = blockIdx.x * kBlock + threadIdx.x;
     uint32_t num_steps = 0;
@@ -412,18 +319,17 @@ k_march_train_step(const float *__restrict__ rays_o, const float *__restrict__ r
         fars[n] = far;
         Dda s;
         s.init(rays_o + (size_t)n * 3, rays_d + (size_t)n * 3, bound, dt_gamma, max_steps, C, H, grid, far);
-        t0 = near;
         // :392 -- the jitter: the caller's uniform numbers (torch.rand in the reference), or (jitter_seed != 0) 24 random bits
         // of a counter-based hash of (seed, launch epoch, ray): a launch less per step, a new draw per launch even when replayed
         float u = 0.0f;
         if (noises) u = noises[n];
-        else if (jitter_seed) u = (float)(mix32(mix32(n) ^ mix32(jitter_seed + tag)) >> 8) * (1.0f / 16777216.0f);
-        t0 += clampf(t0 * dt_gamma, s.dt_min, s.dt_max) * u;
+        else if (jitter_seed) u = hash_u01(mix32(jitter_seed + tag), n);
+        t0 = s.start(near, u);
         float t = t0;
-        if constexpr (RECORD) num_steps = s.walk_record(t, max_steps, t_rec + threadIdx.x, kBlock);
-        else num_steps = s.walk<false>(t, max_steps, nullptr, nullptr, nullptr);
+        if constexpr (RECORD) num_steps = s.walk(t, max_steps, Dda::RecordSamples{t_rec + threadIdx.x, kBlock});
+        else num_steps = s.walk(t, max_steps, Dda::CountSamples{});
     }
-    const uint32_t sum = block_reduce_sum(num_steps, lds);
+    const uint32_t sum = block_sum<uint32_t, kBlock>(num_steps, lds);
     if (threadIdx.x == 0)
         __hip_atomic_store(&words[blockIdx.x], ((unsigned long long)tag << 32) | sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
@@ -441,22 +347,11 @@ k_march_train_step(const float *__restrict__ rays_o, const float *__restrict__ r
         all += cnt;
         part += b < blockIdx.x ? cnt : 0u;
     }
-    const uint32_t block_off = block_reduce_sum(part, lds);
-    const uint32_t total = block_reduce_sum(all, lds);         // (the reductions' barriers also publish `stalled`)
+    const uint32_t block_off = block_sum<uint32_t, kBlock>(part, lds);
+    const uint32_t total = block_sum<uint32_t, kBlock>(all, lds);         // (the reductions' barriers also publish `stalled`)
     const bool bad = stalled != 0u;
-
-    // exclusive scan of num_steps inside the workgroup (as k_march_train_write)
-    uint32_t incl = num_steps;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(incl, off, 64);
-        if ((int)(threadIdx.x & 63) >= off) incl += o;
-    }
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 63) wave_tot[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; w++) before += wave_tot[w];
-    const uint32_t point_index = block_off + before + (incl - num_steps);
+    // the ray's slice: after those of the earlier workgroups and of the earlier rays of this one
+    const uint32_t point_index = block_off + block_exclusive_scan<kBlock>(num_steps, wave_tot);
 
     if (n < N) {
         rays[n * 3] = (int32_t)n;
@@ -473,7 +368,7 @@ k_march_train_step(const float *__restrict__ rays_o, const float *__restrict__ r
                 }
             } else {
                 float t = t0;
-                s.walk<true>(t, num_steps, xyzs + (size_t)point_index * 3, dirs + (size_t)point_index * 3, deltas + (size_t)point_index * 2);
+                s.walk(t, num_steps, Dda::EmitSamples{xyzs + (size_t)point_index * 3, dirs + (size_t)point_index * 3, deltas + (size_t)point_index * 2});
             }
         } else if (num_steps != 0 && !bad) {
             // The slice of a ray that does not fit is cleared (up to the buffers' capacity): the network pass visits rows

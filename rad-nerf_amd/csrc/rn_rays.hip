@@ -1,6 +1,7 @@
 // rn_rays.hip -- full-image ray generation on the device (C ABI: include/radnerf_fused.h, "ray generation").
-// What is computed: get_rays, nerf/utils.py:249-333 (N = -1): the step immediately before the render path.
-#include "rn_common.h"
+// What is computed: get_rays, nerf/utils.py:249-333 (N = -1): the step immediately before the render path.  The ray of a pixel
+// is pinhole_ray() of rn_ray_dev.h, which the one-launch frame prologue (rn_head_loop.hip) builds its rays with as well.
+#include "rn_ray_dev.h"
 
 #include "../../include/radnerf_fused.h"
 
@@ -11,16 +12,10 @@ k_get_rays(const float *__restrict__ pose, float fx, float fy, float cx, float c
            float *__restrict__ rays_o, float *__restrict__ rays_d) {
     const uint32_t n = blockIdx.x * 256 + threadIdx.x;
     if (n >= H * W) return;
-    const uint32_t r = n / W, c = n - r * W;
-    // i = col + 0.5, j = row + 0.5 (:268-270); xs = (i - cx) / fx * zs, ys = (j - cy) / fy * zs, zs = 1 (:320-322)
-    const float x = ((float)c + 0.5f - cx) / fx, y = ((float)r + 0.5f - cy) / fy, z = 1.0f;
-    const float norm = sqrtf(x * x + y * y + z * z);  // :324
-    const float dx = x / norm, dy = y / norm, dz = z / norm;
+    float o[3], d[3];
+    pinhole_ray(n, W, fx, fy, cx, cy, pose, o, d);
 #pragma unroll
-    for (int k = 0; k < 3; k++) {  // rays_d = directions @ R^T (:325): row k of R
-        rays_d[(size_t)n * 3 + k] = dx * pose[k * 4] + dy * pose[k * 4 + 1] + dz * pose[k * 4 + 2];
-        rays_o[(size_t)n * 3 + k] = pose[k * 4 + 3];  // :327
-    }
+    for (int k = 0; k < 3; k++) { rays_d[(size_t)n * 3 + k] = d[k]; rays_o[(size_t)n * 3 + k] = o[k]; }
 }
 
 // get_bg_coords (nerf/utils.py:240-245): [H*W, 2] in [-1, 1], component 0 along the rows -- arange / (n - 1) * 2 - 1 in fp32

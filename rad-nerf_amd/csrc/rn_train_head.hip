@@ -691,14 +691,8 @@ __global__ void __launch_bounds__(kLossThreads) k_train_head_loss(const float *_
         g_amb[n] = wa * inv_n * keep;
         acc += (double)(mse / 3.0f) * inv_n + 1e-4 * (double)ent * inv_n + (double)wa * (double)(ambient[n] * keep) * inv_n;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kLossThreads / kWave; w++) t += red[w];
-        loss[0] = (float)t;
-    }
+    const double t = block_sum_first<double, kLossThreads>(acc, red);
+    if (threadIdx.x == 0) loss[0] = (float)t;
 }
 
 // ---- batch gather ---------------------------------------------------------------------------------------------------------

@@ -469,14 +469,8 @@ k_train_torso_loss(const float *__restrict__ alpha_c, const float *__restrict__ 
         if (on) g_alpha_c[lo] = ga + (inside ? 1e-4f * inv_n * (lb - la) : 0.0f);
         acc += (double)(mse / 3.0f) * inv_n + 1e-4 * (double)ent * inv_n;
     }
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double t = 0.0;
-        for (int w = 0; w < kLossThreads / kWave; w++) t += red[w];
-        loss[0] = (float)t;
-    }
+    const double t = block_sum_first<double, kLossThreads>(acc, red);
+    if (threadIdx.x == 0) loss[0] = (float)t;
 }
 
 constexpr uint32_t kWPartsMax = 128;

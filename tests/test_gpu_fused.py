@@ -511,3 +511,41 @@ def test_two_frames_in_flight_render_the_same_frames(hiplib):
     torch.cuda.synchronize()
     for s, (g, w) in enumerate(zip(got, want)):
         assert torch.equal(g, w), s
+
+
+@pytest.mark.parametrize("H,W", [(24, 40), (37, 53)])
+def test_loop_with_a_partial_last_chunk(hiplib, H, W):
+    """Frames whose ray count is no multiple of the loop's 256-ray chunk: 24 x 40 = 960 rays (block order usable, last chunk of
+    192 lanes) and 37 x 53 = 1 961 rays (block order refused, last chunk of 169 lanes = two full waves + 41).  The loop's
+    variants -- merged / separate prologue, one-launch / split step, block / plain ray order -- must agree on image, depth and
+    the loop statistics bit for bit over two frames, no workgroup may give up at the barrier, and the frames must be those of
+    the per-operator engine on the same rays (the bar of test_fused_equals_ops_engine)."""
+    from radnerf import fused
+    from radnerf.scene import SyntheticScene, default_opt
+
+    def frames(order_w=W, engine="fused", **kw):
+        scene = SyntheticScene(H=H, W=W, n_frames=8, device="cuda", opt=default_opt(engine=engine, **kw))
+        scene.model.ray_order_width = order_w
+        outs = []
+        for i in range(2):
+            with torch.no_grad():
+                out = scene.render(i)
+            outs.append((out["image"].clone(), torch.nan_to_num(out["depth"], nan=-1.0).clone(), dict(scene.model.last_stats)))
+        if engine == "fused":
+            assert fused.stalled_workgroups(scene.model) == 0 and fused.unfinished_frames(scene.model) == 0
+        return outs
+
+    assert H * W % 256 != 0
+    base = frames()
+    variants = {"separate prologue": frames(frame_kernels="separate"), "one-launch step": frames(loop_launch="coop"),
+                "plain ray order": frames(order_w=0)}
+    for name, outs in variants.items():
+        for i, (got, want) in enumerate(zip(outs, base)):
+            assert torch.equal(got[0], want[0]), (name, i, "image")
+            assert torch.equal(got[1], want[1]), (name, i, "depth")
+            assert got[2] == want[2], (name, i, got[2], want[2])
+    same_rays, ops = frames(ray_engine="torch"), frames(engine="ops")
+    for i in range(2):
+        diff = (same_rays[i][0] - ops[i][0]).abs().max().item()
+        print(f"{H}x{W} frame {i}: max |fused - ops| = {diff:.3e}")
+        assert diff <= 1e-4
