@@ -241,6 +241,42 @@ int rn_train_torso_loss(const float *alpha_c, const float *color_c, const int32_
                         const float *bg, uint32_t bg_stride, const float *target, uint32_t target_stride, uint32_t N, float *loss,
                         float *pred, float *alpha_full, float *grad_alpha_c, float *grad_color_c, rn_stream_t stream);
 
+/*
+ * The training step's input stage for a data set that already lives in device memory: the loader's batch of one frame
+ * (NeRFDataset.collate, nerf/provider.py:625-714, with get_rays / get_audio_features / convert_poses of nerf/utils.py) in ONE
+ * launch that touches only the n picked pixels.  The arrays stay as decoded: uint8 images, 7 bytes per pixel and frame.
+ *
+ *   images [F,H,W,3] u8, torso [F,H,W,4] u8 (RGBA, 4-byte aligned), bg [H,W,3] u8, poses [F,4,4] f32 cam2world,
+ *   face_rect [F,4] i32 (xmin, xmax, ymin, ymax; x indexes ROWS, provider.py:657-658), eye [F] f32 (nullable),
+ *   auds [Fa,C,16] f32; att 0 / 1 / 2 = get_audio_features' mode; torso_mode = opt.torso.
+ */
+typedef struct {
+    const uint8_t *images, *torso, *bg;
+    const float *poses;
+    const int32_t *face_rect;
+    const float *eye, *auds;
+    float fx, fy, cx, cy;
+    uint32_t H, W, F, Fa, C, att, torso_mode;
+} rn_train_set_t;
+
+/* One training batch of `n` pixels of frame `frame` (audio window around `aud_frame`).  inds: int64 [n] pixel indices r * W + c;
+ * a value outside [0, H*W) is clamped into it and counted in *bad (device word, added to, never reset here).  inds == NULL: the
+ * kernel draws them, n independent uniform integers from a counter-based generator keyed by (seed, draw, k) -- duplicates
+ * allowed, no state in device memory, the same (seed, draw) gives the same batch.  inds_out (nullable) receives the pixels used.
+ * packed: rays_o [n,3] | rays_d [n,3] | bg_coords [n,2] | bg_color [n,3] | target [n,3] | face [n], each section contiguous, 15 n
+ * floats.  Decoded values are float(u8) / 255 correctly rounded; blend = t_rgb * a + bg * (1 - a), every operation rounded on its
+ * own.  Head mode: bg_color = blend, target = images.  Torso mode: bg_color = bg, target = blend.  face = 1 inside the frame's
+ * rect, else 0.  Per call: poses6 [6] (rn_convert_poses), pose_matrix [16], eye [1] = set->eye[frame] (both nullable together
+ * with set->eye), auds_out = the audio window ([1,C,16] for att 0; [8,C,16]: frames [i-8, i) for att 1, [i-4, i+4) for att 2, rows
+ * outside [0, Fa) zero).  n == 0: RN_OK, nothing launched. */
+int rn_train_set_batch(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, const int64_t *inds, uint32_t n,
+                       uint32_t seed, uint32_t draw, float *packed, int64_t *inds_out, float *poses6, float *pose_matrix,
+                       float *eye, float *auds_out, uint32_t *bad, rn_stream_t stream);
+/* The loader's evaluation form (training = False): every pixel in order, no face section, target = images in both modes.
+ * packed: rays_o | rays_d | bg_coords | bg_color | images over H*W pixels, 14 H W floats.  Same kernel, same per-call outputs. */
+int rn_train_set_frame(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, float *packed, float *poses6,
+                       float *pose_matrix, float *eye, float *auds_out, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

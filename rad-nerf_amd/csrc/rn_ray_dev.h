@@ -1,5 +1,5 @@
 // rn_ray_dev.h -- what the ray loop does per ray around the DDA walk (rn_dda_dev.h), each piece written once: the pinhole ray of a
-// pixel, the ray/box test, the order of the alive list, the reset of a ray's accumulators, the inference compositor.  Used by
+// pixel, its background coordinate, the pose 6-vector, the ray/box test, the order of the alive list, the reset of a ray's accumulators, the inference compositor.  Used by
 // rn_rays.hip, rn_raymarching.hip (the per-operator kernels) and rn_head_loop.hip (the device-resident loop): the two engines
 // produce the same bits because they run the same expressions.  -ffp-contract=off: the expressions round as written.
 #pragma once
@@ -23,6 +23,23 @@ __device__ __forceinline__ void pinhole_ray(uint32_t ray, uint32_t W, float fx, 
         d[k] = ux * pose[k * 4] + uy * pose[k * 4 + 1] + uz * pose[k * 4 + 2];
         o[k] = pose[k * 4 + 3];  // :327
     }
+}
+
+// get_bg_coords (nerf/utils.py:240-245) for pixel (row r, column c): [-1, 1], component 0 along the rows -- arange / (n - 1) * 2 - 1
+__device__ __forceinline__ void bg_coord_of(uint32_t r, uint32_t c, uint32_t H, uint32_t W, float &x, float &y) {
+    x = (float)r / (float)(H - 1u) * 2.0f - 1.0f;
+    y = (float)c / (float)(W - 1u) * 2.0f - 1.0f;
+}
+
+// convert_poses (nerf/utils.py:231-237) of one cam2world matrix m [4,4]: (XYZ euler angles of the rotation, translation);
+// matrix_to_euler_angles(R, 'XYZ') (:130-169) = (atan2(-R12, R22), asin(R02), atan2(-R01, R00))
+__device__ __forceinline__ void pose6_of(const float *__restrict__ m, float *__restrict__ o) {
+    o[0] = atan2f(-m[1 * 4 + 2], m[2 * 4 + 2]);
+    o[1] = asinf(m[0 * 4 + 2]);
+    o[2] = atan2f(-m[0 * 4 + 1], m[0 * 4 + 0]);
+    o[3] = m[3];
+    o[4] = m[7];
+    o[5] = m[11];
 }
 
 // near / far of a ray against the box  (raymarching.cu:91-145); FLT_MAX for both when the ray misses

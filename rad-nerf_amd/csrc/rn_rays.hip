@@ -18,28 +18,19 @@ k_get_rays(const float *__restrict__ pose, float fx, float fy, float cx, float c
     for (int k = 0; k < 3; k++) { rays_d[(size_t)n * 3 + k] = d[k]; rays_o[(size_t)n * 3 + k] = o[k]; }
 }
 
-// get_bg_coords (nerf/utils.py:240-245): [H*W, 2] in [-1, 1], component 0 along the rows -- arange / (n - 1) * 2 - 1 in fp32
+// get_bg_coords (nerf/utils.py:240-245): [H*W, 2] in [-1, 1], component 0 along the rows
 __global__ void __launch_bounds__(256) k_bg_coords(uint32_t H, uint32_t W, float *__restrict__ out) {
     const uint32_t n = blockIdx.x * 256 + threadIdx.x;
     if (n >= H * W) return;
     const uint32_t r = n / W, c = n - r * W;
-    out[2 * (size_t)n] = (float)r / (float)(H - 1u) * 2.0f - 1.0f;
-    out[2 * (size_t)n + 1] = (float)c / (float)(W - 1u) * 2.0f - 1.0f;
+    bg_coord_of(r, c, H, W, out[2 * (size_t)n], out[2 * (size_t)n + 1]);
 }
 
-// convert_poses (nerf/utils.py:231-237): cam2world [n, 4, 4] -> (XYZ euler angles of the rotation, translation) [n, 6];
-// matrix_to_euler_angles(R, 'XYZ') (:130-169) = (atan2(-R12, R22), asin(R02), atan2(-R01, R00))
+// convert_poses (nerf/utils.py:231-237): cam2world [n, 4, 4] -> (XYZ euler angles of the rotation, translation) [n, 6]
 __global__ void __launch_bounds__(64) k_convert_poses(const float *__restrict__ poses, uint32_t n, float *__restrict__ out) {
     const uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    const float *m = poses + (size_t)i * 16;
-    float *o = out + (size_t)i * 6;
-    o[0] = atan2f(-m[1 * 4 + 2], m[2 * 4 + 2]);
-    o[1] = asinf(m[0 * 4 + 2]);
-    o[2] = atan2f(-m[0 * 4 + 1], m[0 * 4 + 0]);
-    o[3] = m[3];
-    o[4] = m[7];
-    o[5] = m[11];
+    pose6_of(poses + (size_t)i * 16, out + (size_t)i * 6);
 }
 
 }  // namespace rn

@@ -474,7 +474,10 @@ class GraphedTrainer(Trainer):
                     self._static[k].copy_(v)
         v = data.get("index")
         if isinstance(v, (list, tuple)) and list(v) != self._static_index:
-            self._static["index"].copy_(torch.tensor(v, dtype=torch.long))
+            # a feed whose frame changes every step brings the index as a device tensor too (DeviceTrainSet): a copy on the
+            # stream instead of an upload from pageable memory, which the host waits for
+            src = data.get("_index_dev")
+            self._static["index"].copy_(src if src is not None else torch.tensor(v, dtype=torch.long))
             self._static_index = list(v)
         w_amb = min(self.global_step / self.iters, 1.0) * self.lambda_amb
         if w_amb != getattr(self, "_amb_value", None):                   # constant once the ramp is over

@@ -89,6 +89,13 @@ class TorsoGradsT(C.Structure):
     _fields_ = [(n, _ptr) for n in ("def_w0", "def_w1", "def_w2", "tor_w0", "tor_w1", "tor_w2", "ind_code")]
 
 
+class TrainSetT(C.Structure):
+    c_name = "rn_train_set_t"
+    _fields_ = [("images", _ptr), ("torso", _ptr), ("bg", _ptr), ("poses", _ptr), ("face_rect", _ptr), ("eye", _ptr),
+                ("auds", _ptr), ("fx", _f32), ("fy", _f32), ("cx", _f32), ("cy", _f32), ("H", _u32), ("W", _u32), ("F", _u32),
+                ("Fa", _u32), ("C", _u32), ("att", _u32), ("torso_mode", _u32)]
+
+
 # name -> (restype, argtypes).  rn_stream_t and pointers to device or host buffers are void *; pointers to the structs above
 # are typed, as are the few host arrays the callers hand over as ctypes objects.
 FUNCTIONS = {
@@ -228,6 +235,9 @@ FUNCTIONS = {
                                            _ptr]),
     "rn_torso_select": (_int, [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "rn_train_torso_loss": (_int, [_ptr, _ptr, _ptr, _u32, _ptr, _ptr, _u32, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_set_batch": (_int, [_P(TrainSetT), _u32, _u32, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                  _ptr]),
+    "rn_train_set_frame": (_int, [_P(TrainSetT), _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
 }
 
 
