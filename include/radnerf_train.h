@@ -156,6 +156,33 @@ int rn_train_batch_gather(const float *table, uint32_t row_floats, const int64_t
                           uint32_t sections, float *out, rn_stream_t stream);
 
 /*
+ * The pose code of --train_camera (nerf/renderer.py:170-174) around the step: the frame's row of camera_dT [n_rows,3] added to
+ * the ray origins, the ray directions turned by R = Rx(a0) Ry(a1) Rz(a2) (euler_angles_to_matrix, nerf/utils.py:172-227) with
+ * a[k] = camera_dR[row][k] / 180 * pi + 1e-8 -- and the gradients of both tables.  Opt-in (RN_TRAIN_CAMERA=fused,
+ * radnerf/train_camera.py); one launch forward, two backward, where autograd over the torch operators takes ~30 each way.
+ *
+ * index: int64 device scalar, the frame's row.  A negative value wraps once (row + n_rows).  A row outside the tables reads and
+ * writes nothing outside them: the forward copies the rays unchanged, the backward writes zeros everywhere.
+ */
+/* out_rays_o[n] = rays_o[n] + camera_dT[row];  out_rays_d[n][j] = d[n][0] R[0][j] + d[n][1] R[1][j] + d[n][2] R[2][j].  All of it
+ * fp32, every operation rounded on its own, sums from left to right (csrc/rn_camera_dev.h).  rays / outputs: [N,3].  N == 0:
+ * nothing is launched. */
+int rn_camera_rays_forward(const float *rays_o, const float *rays_d, const float *camera_dT, const float *camera_dR,
+                           const int64_t *index, uint32_t n_rows, uint32_t N, float *out_rays_o, float *out_rays_d,
+                           rn_stream_t stream);
+/* Bytes of the backward's workspace for N rays (12 partial sums per 256 rays; opaque, needs no initialisation). */
+size_t rn_camera_rays_workspace(uint32_t N);
+/* grad_rays_o / grad_rays_d [N,3]: the gradients of the forward's outputs (what rn_march_rays_train_backward wrote); rays_d: the
+ * forward's UNTRANSFORMED directions.  grad_dT [n_rows,3] and grad_dR [n_rows,3] are written whole:
+ *   grad_dT[row] = sum_n g_o[n];   grad_dR[row][k] = pi / 180 * sum_ij G[i][j] dR[i][j] / da_k,  G[i][j] = sum_n d[n][i] g_d[n][j],
+ * zeros in every other row -- the dense gradient index_put's backward builds with a memset and a scatter.  The sums run over a
+ * shuffle tree per wave, the waves of a workgroup in order, the workgroups' partials in double in a fixed order: no float
+ * atomics, two calls give the same bits.  N == 0: both tables are written as zeros. */
+int rn_camera_rays_backward(const float *grad_rays_o, const float *grad_rays_d, const float *rays_d, const float *camera_dR,
+                            const int64_t *index, uint32_t n_rows, uint32_t N, float *grad_dT, float *grad_dR, void *workspace,
+                            rn_stream_t stream);
+
+/*
  * The torso layer under autograd: NeRFNetwork.forward_torso (nerf/network.py:188-219) per covered pixel -- two frequency
  * encodings, the deformation net (104 + ind -> 64 -> 64 -> 2), x = clamp(x + dx, -1, 1), the 2-D grid (L = 16, C = 2, fp32,
  * bound 1) with dy_dx, the torso net (136 + ind -> 32 -> 32 -> 4), sigmoid -- and the gradients of the six weight matrices, the

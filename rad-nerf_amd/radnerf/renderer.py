@@ -17,6 +17,7 @@ Occupancy-grid maintenance (`update_extra_state`, `mark_untrained_grid`) is radn
 in morton order, no Python block loops.
 """
 import math
+import os
 import random
 
 import numpy as np
@@ -323,9 +324,16 @@ class NeRFRenderer(nn.Module):
         rays_o, rays_d = rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
         bg_coords = bg_coords.contiguous().view(-1, 2)
         if self.train_camera and (self.training or self.test_train):
-            from .rays import euler_angles_to_matrix
-            rays_o = rays_o + self.camera_dT[index]
-            rays_d = rays_d @ euler_angles_to_matrix(self.camera_dR[index] / 180 * np.pi + 1e-8).squeeze(0)
+            train_camera = None
+            if rays_o.is_cuda and os.environ.get("RN_TRAIN_CAMERA") == "fused":
+                from . import train_camera
+            if train_camera is not None and train_camera.usable(self, rays_o, rays_d, index):
+                # opt-in: the row lookups, the rotation and their autograd as one forward and one backward call
+                rays_o, rays_d = train_camera.camera_rays(self, rays_o, rays_d, index)
+            else:
+                from .rays import euler_angles_to_matrix
+                rays_o = rays_o + self.camera_dT[index]
+                rays_d = rays_d @ euler_angles_to_matrix(self.camera_dR[index] / 180 * np.pi + 1e-8).squeeze(0)
 
         if not self.training and self.engine == "fused" and not perturb:
             from . import fused

@@ -10,7 +10,7 @@ value and the individual code -- and, when they require grad (--train_camera: th
 camera_dT, nerf/renderer.py:104-107, 170-174), in the sample positions and directions: one more launch in the backward
 (rn_train_head_input_grads) gathers the corners of the xyz grid again for d/d xyzs and takes d/d dirs through the SH Jacobian;
 it is not made, and nothing is allocated for it, when neither input needs a gradient.  While a stream is capturing, a call whose
-positions require grad keeps the per-operator path (usable()).
+positions require grad keeps the per-operator path (usable()), except on the opt-in camera route (RN_TRAIN_CAMERA=fused).
 """
 import ctypes as C
 
@@ -321,11 +321,13 @@ def head_forward(model, xyzs, dirs, enc_a, ind_code, eye, m_dev=None, ind_index=
 
 def usable(model, x, enc_a):
     """Training call of the supported shape on the GPU in fp32 (autocast keeps the per-operator path; so does a call whose
-    positions require grad while a stream is capturing: a captured --train_camera step replays the operator chain)."""
+    positions require grad while a stream is capturing: a captured --train_camera step replays the operator chain -- unless the
+    pose code runs through the camera kernels, RN_TRAIN_CAMERA=fused (radnerf/train_camera.py): then the captured step keeps the
+    fused head and replays its input-gradient launch)."""
     import os
     return (os.environ.get("RN_TRAIN_HEAD", "fused") == "fused" and x.is_cuda and torch.is_grad_enabled() and x.dim() == 2
             and x.dtype == torch.float32 and not torch.is_autocast_enabled() and enc_a is not None
-            and not (x.requires_grad and torch.cuda.is_current_stream_capturing())
+            and not (x.requires_grad and torch.cuda.is_current_stream_capturing() and os.environ.get("RN_TRAIN_CAMERA") != "fused")
             and getattr(model, "_train_head_ok", None) is not False and _check(model))
 
 

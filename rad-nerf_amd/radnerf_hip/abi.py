@@ -225,6 +225,9 @@ FUNCTIONS = {
     "rn_train_head_loss": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _ptr, _ptr, _ptr,
                                   _ptr, _ptr]),
     "rn_train_batch_gather": (_int, [_ptr, _u32, _ptr, _u32, C.POINTER(_u32), _u32, _ptr, _ptr]),
+    "rn_camera_rays_forward": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr]),
+    "rn_camera_rays_workspace": (_sz, [_u32]),
+    "rn_camera_rays_backward": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr]),
     "rn_train_torso_image_floats": (_sz, []),
     "rn_train_torso_workspace_floats": (_sz, [_u32]),
     "rn_train_torso_wgrad_workspace": (_sz, []),

@@ -10,6 +10,12 @@ cycle; the sample count of every step stays on the device until the end.  Report
 spread, and ms per step of the cycles grouped by their samples per step (the budget moves with the refresh, so a run has a phase
 of large steps and a phase of small ones).  The JSON goes to DIR/train_camera.json (default DIR: profiles).
 
+    python tools/bench_train_camera.py --compare-pose [--parent DIR] [--repeats 5]
+the pose code of the step instead of its head: RN_TRAIN_CAMERA = torch | fused (radnerf/train_camera.py), each eager and under
+GraphedTrainer (--graph), as alternating child processes (`--one fused --pose P [--graph]`); --parent DIR adds the eager run of
+another checkout's copy of this tool (the parent commit, built in DIR) to the rotation.  Written under the key "pose" of the
+same JSON, with the launches per step of tools/train_step_launches.py --train-camera for both pose codes.
+
     python tools/bench_train_camera.py --kernel-stats KERNEL_TRACE.csv [--samples 62000]
 folds the kernel-trace CSV of `rocprofv3 --kernel-trace --stats -- python tools/bench_train_camera.py --one fused` into the JSON: the
 new kernel's average time over the launches of the large-step phase and its rate on algorithmic bytes (1 024 B gathered + 128 B feature gradients + 24 B written per sample).
@@ -30,17 +36,18 @@ KERNEL = "k_train_input_grads"
 BYTES_PER_SAMPLE = 1024 + 128 + 24
 
 
-def one(head, cycles, rays, size, train_camera=True):
+def one(head, cycles, rays, size, train_camera=True, pose="torch", graph=False):
     os.environ["RN_TRAIN_HEAD"] = head
     os.environ["RN_TRAIN_LOSS"] = "fused" if head == "fused" else "torch"
+    os.environ["RN_TRAIN_CAMERA"] = pose
     import torch
     from bench import GRIDS
     from radnerf.scene import SyntheticScene, default_opt
-    from radnerf.train import SyntheticTrainStream, Trainer
+    from radnerf.train import GraphedTrainer, SyntheticTrainStream, Trainer
     scene = SyntheticScene(H=size, W=size, n_frames=8, device="cuda",
                            opt=default_opt(engine="ops", torso=False, smooth_lips=False, train_camera=train_camera, **GRIDS["hash19"]))
     stream = SyntheticTrainStream(scene, n_rays=rays)
-    trainer = Trainer(scene.model, scene.opt)
+    trainer = (GraphedTrainer if graph else Trainer)(scene.model, scene.opt)
     m = scene.model
     for _ in range(33 + (16 - 33 % 16) % 16):          # warm-up ends on a cycle boundary: every timed cycle starts with a refresh
         trainer.step(stream.batch())
@@ -58,7 +65,8 @@ def one(head, cycles, rays, size, train_camera=True):
     elapsed = time.perf_counter() - t0
     per_cycle = counts.double().mean(1).tolist()
     cam = float(m.camera_dT[stream.frame].abs().max()) if train_camera else None
-    return dict(head=head, train_camera=train_camera, steps=16 * cycles, steps_per_s=16 * cycles / elapsed, ms_per_step=elapsed / (16 * cycles) * 1e3,
+    extra = dict(captures=trainer.captures, replays=trainer.replays) if graph else {}
+    return dict(head=head, pose=pose, graph=graph, **extra, train_camera=train_camera, steps=16 * cycles, steps_per_s=16 * cycles / elapsed, ms_per_step=elapsed / (16 * cycles) * 1e3,
                 cycle_ms_per_step=cycle_ms, cycle_samples_per_step=per_cycle, camera_dT_moved=cam)
 
 
@@ -92,10 +100,56 @@ def kernel_stats(path, samples):
                              "streamed gradients and outputs per sample")
 
 
+def _child(cmd, cwd=None, last_line=True):
+    """The JSON a child process printed (its last line, or all of its output)."""
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=cwd)
+    if r.returncode != 0:                              # a failed run ends the measurement: nothing more is started on the device
+        sys.stderr.write(r.stdout + r.stderr)
+        sys.exit(r.returncode or 1)
+    return json.loads(r.stdout.strip().splitlines()[-1] if last_line else r.stdout)
+
+
+def compare_pose(args, path):
+    """Alternating runs of the step with each pose code, eager and graphed (and the parent checkout's eager step)."""
+    me, size = os.path.abspath(__file__), ["--cycles", str(args.cycles), "--rays", str(args.rays), "--size", str(args.size)]
+    variants = {f"{pose}_{'graph' if graph else 'eager'}": ([sys.executable, me, "--one", "fused", "--pose", pose] + (["--graph"] if graph else []) + size, None)
+                for graph in (False, True) for pose in ("torch", "fused")}
+    if args.parent:
+        variants = {"parent_eager": ([sys.executable, os.path.join(os.path.abspath(args.parent), "tools", "bench_train_camera.py"), "--one", "fused"] + size,
+                                     os.path.abspath(args.parent)), **variants}
+    runs = {k: [] for k in variants}
+    for rep in range(args.repeats):
+        for name, (cmd, cwd) in variants.items():
+            runs[name].append(_child(cmd, cwd))
+            print(f"repeat {rep} {name}: {runs[name][-1]['steps_per_s']:.1f} steps/s", flush=True)
+    rec = json.load(open(path)) if os.path.exists(path) else {}
+    out = {"workload": f"config 2 with --train_camera, fused head: {args.rays} rays of a {args.size}x{args.size} frame, hash grid T=2^19, "
+                       f"{16 * args.cycles} timed steps per run after warm-up, occupancy refresh every 16 steps inside the timed region",
+           "repeats": args.repeats}
+    for name, rs in runs.items():
+        v = [r["steps_per_s"] for r in rs]
+        out[name] = dict(steps_per_s=v, mean=sum(v) / len(v), ms_per_step=[r["ms_per_step"] for r in rs], phases=phases(rs),
+                         camera_dT_moved=[r["camera_dT_moved"] for r in rs])
+        if rs[0].get("graph"):
+            out[name]["captures"] = [r["captures"] for r in rs]
+    launches = os.path.join(ROOT, "tools", "train_step_launches.py")
+    for pose in ("torch", "fused"):
+        os.environ["RN_TRAIN_CAMERA"] = pose
+        step = _child([sys.executable, launches, "--train-camera", "--rays", str(args.rays), "--size", str(args.size)], last_line=False)
+        out[f"{pose}_eager"]["launches_per_step"] = dict(launches=step["launches"], kernels=step["kernels"], gpu_us=step["gpu_us"], samples=step["samples"])
+    rec["pose"] = out
+    json.dump(rec, open(path, "w"), indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--one", choices=["fused", "ops"])
     ap.add_argument("--no-camera", action="store_true", help="--one: the same step without --train_camera")
+    ap.add_argument("--pose", choices=["torch", "fused"], default="torch", help="--one: the pose code (RN_TRAIN_CAMERA)")
+    ap.add_argument("--graph", action="store_true", help="--one: the step under GraphedTrainer")
+    ap.add_argument("--compare-pose", action="store_true")
+    ap.add_argument("--parent", help="--compare-pose: a built checkout of the parent commit")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--cycles", type=int, default=16, help="timed 16-step refresh cycles per run (16 = 256 steps)")
     ap.add_argument("--rays", type=int, default=4096)
@@ -107,7 +161,10 @@ def main():
     os.makedirs(args.out, exist_ok=True)
     path = os.path.join(args.out, "train_camera.json")
     if args.one:
-        print(json.dumps(one(args.one, args.cycles, args.rays, args.size, not args.no_camera)))
+        print(json.dumps(one(args.one, args.cycles, args.rays, args.size, not args.no_camera, args.pose, args.graph)))
+        return
+    if args.compare_pose:
+        compare_pose(args, path)
         return
     if args.kernel_stats:
         rec = json.load(open(path)) if os.path.exists(path) else {}
@@ -136,6 +193,8 @@ def main():
     f, o = rec["fused"], rec["ops"]
     rec["speedup"] = f["mean"] / o["mean"]
     rec["faster_by_more_than_the_spread"] = min(f["steps_per_s"]) > max(o["steps_per_s"])
+    if os.path.exists(path) and "pose" in (kept := json.load(open(path))):
+        rec["pose"] = kept["pose"]                    # --compare-pose's record lives in the same file
     json.dump(rec, open(path, "w"), indent=1)
     print(json.dumps(rec))
 

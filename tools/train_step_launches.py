@@ -1,6 +1,8 @@
 """The kernel launches of ONE eager training step, in order (torch.profiler device activities), with their durations.
 
-    python tools/train_step_launches.py [--rays 4096] [--size 512] [--grid hash19]
+    python tools/train_step_launches.py [--rays 4096] [--size 512] [--grid hash19] [--train-camera]
+
+--train-camera: the step with the camera pose trained (RN_TRAIN_CAMERA in the environment picks the pose code).
 """
 import argparse
 import json
@@ -19,11 +21,12 @@ def main():
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--grid", default="hash19")
+    ap.add_argument("--train-camera", action="store_true")
     args = ap.parse_args()
     from bench import GRIDS
     from radnerf.scene import SyntheticScene, default_opt
     from radnerf.train import SyntheticTrainStream, Trainer
-    scene = SyntheticScene(H=args.size, W=args.size, n_frames=8, device="cuda", opt=default_opt(engine="ops", torso=False, smooth_lips=False, **GRIDS[args.grid]))
+    scene = SyntheticScene(H=args.size, W=args.size, n_frames=8, device="cuda", opt=default_opt(engine="ops", torso=False, smooth_lips=False, train_camera=args.train_camera, **GRIDS[args.grid]))
     stream = SyntheticTrainStream(scene, n_rays=args.rays)
     trainer = Trainer(scene.model, scene.opt)
     for _ in range(35):
