@@ -15,11 +15,11 @@ On CPU tensors, or with RN_TRAIN_SET=torch (or kernel="torch"), the same class r
 the N picked pixels: the oracle of the kernel's tests, itself pinned to the reference by tests/golden/reference_batch.npz.
 """
 import ctypes
-import os
 
 import numpy as np
 import torch
 
+from . import switches
 from .rays import convert_poses, get_audio_features
 
 _MASK32 = 0xFFFFFFFF
@@ -95,7 +95,7 @@ class DeviceTrainSet:
             raise ValueError("DeviceTrainSet: opt.exp_eye needs eye_area")
         self.num_rays, self.seed, self._draw = int(num_rays), int(seed), 0
         if kernel is None:
-            kernel = os.environ.get("RN_TRAIN_SET", "hip") if dev.type == "cuda" else "torch"
+            kernel = switches.get("RN_TRAIN_SET") if dev.type == "cuda" else "torch"
         if kernel not in ("hip", "torch") or (kernel == "hip" and dev.type != "cuda"):
             raise ValueError(f"DeviceTrainSet: kernel={kernel!r} on {dev}: the kernel needs a GPU, the other path is 'torch'")
         self.kernel = kernel

@@ -13,7 +13,9 @@ import torch.nn.functional as F
 from activation import trunc_exp
 from encoding import get_encoder
 
+from . import switches
 from .renderer import NeRFRenderer
+from .route import kernels, training_call
 
 
 class AudioAttNet(nn.Module):
@@ -88,67 +90,34 @@ class _SkinnyLinear(torch.autograd.Function):
         return gx, gw
 
 
-_MLP_KERNELS = []
-_AUDIO_KERNELS = []
-_TRAIN_GLUE = []
-_TRAIN_HEAD = []
-_TRAIN_TORSO = []
-
-
 def _train_head():
     """radnerf.train_head (the whole per-sample network as one forward + one backward kernel; needs the HIP library and a GPU),
     or None on the CPU."""
-    if not torch.cuda.is_available():
-        return None
-    if not _TRAIN_HEAD:
-        from . import train_head
-        _TRAIN_HEAD.append(train_head)
-    return _TRAIN_HEAD[0]
+    return kernels("train_head") if torch.cuda.is_available() else None
 
 
 def _train_torso():
     """radnerf.train_torso when RN_TORSO_TRAIN=fused asks for it (the torso layer as one forward + one backward kernel; needs the
     HIP library and a GPU), else None: the default path imports nothing."""
-    import os
-    if os.environ.get("RN_TORSO_TRAIN") != "fused" or not torch.cuda.is_available():
-        return None
-    if not _TRAIN_TORSO:
-        from . import train_torso
-        _TRAIN_TORSO.append(train_torso)
-    return _TRAIN_TORSO[0]
+    return kernels("train_torso") if switches.get("RN_TORSO_TRAIN") == "fused" and torch.cuda.is_available() else None
 
 
 def _train_glue():
     """radnerf.train_glue (needs the HIP library and a GPU), or None on the CPU."""
-    if not torch.cuda.is_available():
-        return None
-    if not _TRAIN_GLUE:
-        from . import train_glue
-        _TRAIN_GLUE.append(train_glue)
-    return _TRAIN_GLUE[0]
+    return kernels("train_glue") if torch.cuda.is_available() else None
 
 
 def _audio_kernels(model, need_grad=True):
     """radnerf.audio when its kernels cover the model's audio nets, or None (RN_AUDIO_TRAIN=torch: the nn.Module path)."""
-    import os
-    if os.environ.get("RN_AUDIO_TRAIN", "hip") == "torch":
+    if switches.get("RN_AUDIO_TRAIN") == "torch":
         return None
-    if not _AUDIO_KERNELS:
-        from . import audio
-        _AUDIO_KERNELS.append(audio)
-    a = _AUDIO_KERNELS[0]
+    a = kernels("audio")
     return a if a.supported(model) and (not need_grad or any(p.requires_grad for p in model.audio_net.parameters())) else None
 
 
 def _mlp_kernels():
     """radnerf.mlp_train (needs the HIP library), or None when RN_MLP_TRAIN=torch selects the nn.Linear path."""
-    import os
-    if os.environ.get("RN_MLP_TRAIN", "hip") == "torch":
-        return None
-    if not _MLP_KERNELS:
-        from . import mlp_train
-        _MLP_KERNELS.append(mlp_train)
-    return _MLP_KERNELS[0]
+    return None if switches.get("RN_MLP_TRAIN") == "torch" else kernels("mlp_train")
 
 
 class MLP(nn.Module):
@@ -168,16 +137,13 @@ class MLP(nn.Module):
         consts = [c.reshape(1, -1) for c in constants if c is not None]
         if not consts:
             return self.forward(x)
-        training_shape = x.is_cuda and torch.is_grad_enabled() and x.dim() == 2 and x.dtype == torch.float32 and \
-            not torch.is_autocast_enabled()
-        if training_shape and x.shape[0] >= 1024 and _mlp_kernels() is not None and x.shape[1] <= 92 and \
+        if training_call(x) and x.dim() == 2 and x.shape[0] >= 1024 and _mlp_kernels() is not None and x.shape[1] <= 92 and \
                 _mlp_kernels().supported(x.shape[1], self.dim_out, self.dim_hidden, self.num_layers):
             return _mlp_kernels().fused_mlp(x, [layer.weight for layer in self.net], torch.cat(consts, dim=1))
         return self.forward(torch.cat([x] + [c.to(x.dtype).repeat(x.shape[0], 1) for c in consts], dim=-1))
 
     def forward(self, x):
-        training_shape = x.is_cuda and torch.is_grad_enabled() and x.dim() == 2 and x.dtype == torch.float32 and \
-            not torch.is_autocast_enabled()
+        training_shape = training_call(x) and x.dim() == 2
         # training on the GPU: hand-written forward / backward kernels for the whole stack (radnerf/mlp_train.py), unless
         # RN_MLP_TRAIN=torch asks for the nn.Linear path (the parity tests compare the two)
         if training_shape and x.shape[0] >= 1024 and _mlp_kernels() is not None and \

@@ -17,8 +17,8 @@ Occupancy-grid maintenance (`update_extra_state`, `mark_untrained_grid`) is radn
 in morton order, no Python block loops.
 """
 import math
-import os
 import random
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -26,8 +26,9 @@ import torch.nn as nn
 
 import raymarching
 
-from . import occupancy
+from . import occupancy, switches
 from .rays import convert_poses, get_audio_features
+from .route import kernels, training_call
 
 _LIP_SMOOTHING = 0.35     # weight of the previous frame's audio code (nerf/renderer.py:192)
 
@@ -35,6 +36,17 @@ _LIP_SMOOTHING = 0.35     # weight of the previous frame's audio code (nerf/rend
 def _n_step_policy(n_rays, n_alive):
     """Samples per live ray of one loop iteration: the fewer rays are left, the more steps each takes (renderer.py:249)."""
     return max(1, min(8, n_rays // n_alive))
+
+
+class HeadRoute(NamedTuple):
+    """How one training call goes through the head (NeRFRenderer._route_head decides, _head_training / _head_network follow)."""
+    marcher: str                # "step": the one-launch marcher | "budget": a device-side budget | "reference": march_rays_train
+    fused_head: bool            # the fused training kernels (radnerf/train_head.py) instead of the operator chain
+    ind_on_device: bool         # they also pick the individual code's row, from the frame index on the device
+    audio_side: object          # the side stream the audio nets run on, or None
+
+
+_NO_ROUTE = HeadRoute("reference", False, False, None)       # nothing decided: the operator chain, everything on the caller's stream
 
 
 class NeRFRenderer(nn.Module):
@@ -175,73 +187,76 @@ class NeRFRenderer(nn.Module):
             self.last_stats["live_samples"] = int(live.item())
         return acc
 
-    def _step_marcher_ok(self, rays_o, force_all_rays):
-        """The one-launch marcher of a budgeted training step: a device-side budget is set, the rays fit one workgroup per CU."""
-        import os
-        if getattr(self, "_sample_budget", None) is None or force_all_rays or self.mean_count <= 0 or not rays_o.is_cuda:
-            return False
-        if os.environ.get("RN_TRAIN_MARCH", "step") != "step" or not torch.is_grad_enabled() or torch.is_autocast_enabled():
-            return False
-        from raymarching.ops import step_marcher_supported
-        return step_marcher_supported(rays_o.shape[0], rays_o.device)
-
-    def _fused_head_expected(self, rays_o, auds):
-        """Will _head_network take the fused training kernels for this call?  (What train_head.usable() will say once the samples
-        exist: they inherit device and dtype from the rays.)"""
+    def _route_head(self, rays_o, rays_d, auds, idx, force_all_rays):
+        """The route of one training call through the head, decided here once, after the pose code has run.  The samples inherit
+        device and dtype from the rays and a gradient from either of them, so what train_head.usable() would say of the samples
+        is asked of the rays.  idx: the frame index as a device tensor, or None (a Python int, or no individual code)."""
         from .network import _train_head
         th = _train_head()
-        return th is not None and auds is not None and th.usable(self, rays_o, auds)
+        marcher = "reference"
+        if getattr(self, "_sample_budget", None) is not None and not force_all_rays and self.mean_count > 0:
+            # a device-side budget is set (radnerf/train.py); in one launch when the rays fit one workgroup per CU
+            from raymarching.ops import step_marcher_supported
+            one = (switches.get("RN_TRAIN_MARCH") == "step" and training_call(rays_o)
+                   and step_marcher_supported(rays_o.shape[0], rays_o.device))
+            marcher = "step" if one else "budget"
+        fused_head = (th is not None and auds is not None
+                      and th.usable(self, rays_o, auds, requires_grad=rays_o.requires_grad or rays_d.requires_grad))
+        # the audio nets (four latency-bound launches) go to a side stream beside near/far and the marcher, which need nothing
+        # of them; the stream that owns the step waits just before the network kernel reads the code (_head_network)
+        audio_side = None
+        if th is not None and rays_o.is_cuda and torch.is_grad_enabled() and auds is not None and auds.is_cuda and th.overlap_enabled():
+            audio_side = th.side_stream(rays_o.device, 1)
+        on_device = fused_head and idx is not None and idx.numel() == 1 and idx.dtype == torch.int64 and idx.is_cuda
+        return HeadRoute(marcher, fused_head, on_device, audio_side)
 
-    def _head_training(self, rays_o, rays_d, nears, fars, enc_a, ind_code, eye, perturb, force_all_rays, dt_gamma, max_steps, wait_for=None,
-                       box=None, ind_index=None):
+    def _head_training(self, rays_o, rays_d, nears, fars, enc_a, ind, eye, perturb, force_all_rays, dt_gamma, max_steps, route, box=None):
         """Train branch (renderer.py:206-223): every sample of every ray, packed; one sample counter per step (ring of 16)."""
         counter = getattr(self, "_static_counter", None)           # a captured training step counts into a fixed pair
         if counter is None:
             counter = self.step_counter[self.local_step % 16]
         budget = getattr(self, "_sample_budget", None)             # (device int32 budget, row capacity): see radnerf/train.py
-        from .network import _train_glue, _train_head
-        th = _train_head()
-        if nears is None:
+        self.local_step += 1
+        if route.marcher == "step":
             # one launch: near / far, count, slices, samples, counters (set, not added to).  The fused network pass stops at the
             # counter, below which the launch has written every row -- no memset of the sample buffers for it.
             from raymarching.ops import march_rays_train_step
-            self.local_step += 1
-            fused_head = th is not None and th.usable(self, rays_o, enc_a)
-            import os
-            jitter = "hash" if (perturb and os.environ.get("RN_TRAIN_NOISE", "hash") == "hash") else perturb
+            jitter = "hash" if (perturb and switches.get("RN_TRAIN_NOISE") == "hash") else perturb
             nears, fars, xyzs, dirs, deltas, rays = march_rays_train_step(rays_o, rays_d, box, self.min_near, self.bound, self.density_bitfield,
                                                                           self.cascade, self.grid_size, counter, budget[0], budget[1], jitter,
-                                                                          dt_gamma, max_steps, not fused_head)
-            return self._head_network(xyzs, dirs, deltas, rays, nears, fars, enc_a, ind_code, eye, counter, wait_for, ind_index)
-        counter.zero_()
-        self.local_step += 1
-        if budget is not None and not force_all_rays and self.mean_count > 0:
+                                                                          dt_gamma, max_steps, not route.fused_head)
+        elif route.marcher == "budget":
             from raymarching.ops import march_rays_train_budget
+            counter.zero_()
             xyzs, dirs, deltas, rays = march_rays_train_budget(rays_o, rays_d, self.bound, self.density_bitfield, self.cascade,
                                                                self.grid_size, nears, fars, counter, budget[0], budget[1], perturb,
                                                                dt_gamma, max_steps)
         else:
+            counter.zero_()
             xyzs, dirs, deltas, rays = raymarching.march_rays_train(rays_o, rays_d, self.bound, self.density_bitfield, self.cascade,
                                                                     self.grid_size, nears, fars, counter, self.mean_count, perturb, 128,
                                                                     force_all_rays, dt_gamma, max_steps)
-        return self._head_network(xyzs, dirs, deltas, rays, nears, fars, enc_a, ind_code, eye, counter, wait_for, ind_index)
+        return self._head_network(xyzs, dirs, deltas, rays, nears, fars, enc_a, ind, eye, counter, route)
 
-    def _head_network(self, xyzs, dirs, deltas, rays, nears, fars, enc_a, ind_code, eye, counter, wait_for, ind_index=None):
-        """The network over a step's samples + the training compositor (renderer.py:213-223)."""
-        if wait_for is not None:                 # the audio code was computed on a side stream (run_cuda)
-            main = torch.cuda.current_stream(xyzs.device)
-            main.wait_stream(wait_for)
-            if torch.is_tensor(enc_a):
-                enc_a.record_stream(main)
+    def _head_network(self, xyzs, dirs, deltas, rays, nears, fars, enc_a, ind, eye, counter, route=None):
+        """The network over a step's samples + the training compositor (renderer.py:213-223).  ind: the individual code, or the
+        row's index when route.ind_on_device.  Without a route (a caller with samples of its own) the head is chosen on the
+        samples, as NeRFNetwork.forward chooses it."""
         from .network import _train_glue, _train_head
         th = _train_head()
-        if th is not None and th.usable(self, xyzs, enc_a):
+        if route is None:
+            route = _NO_ROUTE._replace(fused_head=th is not None and th.usable(self, xyzs, enc_a))
+        if route.audio_side is not None:         # the audio code was computed on a side stream (run_cuda)
+            main = torch.cuda.current_stream(xyzs.device)
+            main.wait_stream(route.audio_side)
+            if torch.is_tensor(enc_a):
+                enc_a.record_stream(main)
+        if route.fused_head:
             # one forward kernel for the network (+ |ambient| sum); the marcher's counter bounds the rows it visits
-            sigmas, rgbs, ambient, ambient_abs = th.head_forward(self, xyzs, dirs, enc_a, ind_code, eye, m_dev=counter, ind_index=ind_index)
+            code, row = (None, ind) if route.ind_on_device else (ind, None)
+            sigmas, rgbs, ambient, ambient_abs = th.head_forward(self, xyzs, dirs, enc_a, code, eye, m_dev=counter, ind_index=row)
         else:
-            if ind_index is not None:       # expected the fused kernels, got the operator chain after all: pick the row here
-                ind_code = torch.index_select(self.individual_codes, 0, ind_index)
-            sigmas, rgbs, ambient = self(xyzs, dirs, enc_a, ind_code, eye)
+            sigmas, rgbs, ambient = self(xyzs, dirs, enc_a, ind, eye)
             glue = _train_glue()
             if glue is not None and ambient.dim() == 2 and ambient.shape[1] == 2 and glue.enabled(ambient):
                 ambient_abs = glue.abs_sum2(ambient)
@@ -324,12 +339,9 @@ class NeRFRenderer(nn.Module):
         rays_o, rays_d = rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3)
         bg_coords = bg_coords.contiguous().view(-1, 2)
         if self.train_camera and (self.training or self.test_train):
-            train_camera = None
-            if rays_o.is_cuda and os.environ.get("RN_TRAIN_CAMERA") == "fused":
-                from . import train_camera
-            if train_camera is not None and train_camera.usable(self, rays_o, rays_d, index):
-                # opt-in: the row lookups, the rotation and their autograd as one forward and one backward call
-                rays_o, rays_d = train_camera.camera_rays(self, rays_o, rays_d, index)
+            if rays_o.is_cuda and kernels("train_camera").usable(self, rays_o, rays_d, index):
+                # opt-in (RN_TRAIN_CAMERA=fused): the row lookups, the rotation and their autograd as one forward and one backward call
+                rays_o, rays_d = kernels("train_camera").camera_rays(self, rays_o, rays_d, index)
             else:
                 from .rays import euler_angles_to_matrix
                 rays_o = rays_o + self.camera_dT[index]
@@ -351,50 +363,40 @@ class NeRFRenderer(nn.Module):
             return results
 
         box = self.aabb_train if self.training else self.aabb_infer
-        # training on the GPU: the audio nets (four latency-bound launches) run on a side stream beside near/far and the marcher,
-        # which need nothing of them; the stream that owns the step waits just before the network kernel reads the code
-        audio_side = None
-        if self.training and rays_o.is_cuda and torch.is_grad_enabled() and auds is not None and auds.is_cuda:
-            from .network import _train_head
-            th = _train_head()
-            if th is not None and th.overlap_enabled():
-                audio_side = th.side_stream(rays_o.device, 1)
-        # a step with a device-side sample budget (radnerf/train.py) marches in ONE launch that also intersects the rays with the
-        # box and sets the step's counters (raymarching.ops.march_rays_train_step): no near/far launch here then
-        one_launch = self.training and self._step_marcher_ok(rays_o, force_all_rays)
-        if audio_side is not None:
-            main = torch.cuda.current_stream(rays_o.device)
-            audio_side.wait_stream(main)
-            with torch.cuda.stream(audio_side):
-                enc_a = self._audio_code(auds)
-            nears, fars = (None, None) if one_launch else (
-                t.detach() for t in raymarching.near_far_from_aabb(rays_o, rays_d, box, self.min_near))
-        else:
-            nears, fars = (None, None) if one_launch else (
-                t.detach() for t in raymarching.near_far_from_aabb(rays_o, rays_d, box, self.min_near))
-            enc_a = self._audio_code(auds)
-        ind_code = ind_index = None
-        if self.individual_dim > 0:
-            if self.training and not isinstance(index, int):
-                # index_select = the same rows as individual_codes[index] (nerf/renderer.py:199); its backward is one index_add
-                # instead of index_put's sort + segmented scatter (5 launches for a one-element index)
+        idx, route = None, _NO_ROUTE
+        if self.training:
+            if self.individual_dim > 0 and not isinstance(index, int):
                 # the loader's Python list: uploaded once per distinct value, not once per step
                 idx = self._index_tensor(index, self.individual_codes.device).reshape(-1)
-                if idx.numel() == 1 and idx.dtype == torch.int64 and idx.is_cuda and self._fused_head_expected(rays_o, auds):
-                    ind_index = idx                 # the fused training kernels pick the row themselves (train_head.head_forward)
-                else:
-                    ind_code = torch.index_select(self.individual_codes, 0, idx.long())
+            route = self._route_head(rays_o, rays_d, auds, idx, force_all_rays)
+        # a step with a device-side sample budget (radnerf/train.py) marches in ONE launch that also intersects the rays with the
+        # box and sets the step's counters (raymarching.ops.march_rays_train_step): no near/far launch here then
+        if route.audio_side is not None:
+            route.audio_side.wait_stream(torch.cuda.current_stream(rays_o.device))
+            with torch.cuda.stream(route.audio_side):
+                enc_a = self._audio_code(auds)
+        nears, fars = (None, None) if route.marcher == "step" else (
+            t.detach() for t in raymarching.near_far_from_aabb(rays_o, rays_d, box, self.min_near))
+        if route.audio_side is None:
+            enc_a = self._audio_code(auds)
+        ind = None
+        if self.individual_dim > 0:
+            if idx is None:
+                ind = self.individual_codes[index if self.training else 0]
+            elif route.ind_on_device:
+                ind = idx                           # the fused training kernels pick the row themselves (train_head.head_forward)
             else:
-                ind_code = self.individual_codes[index if self.training else 0]
+                # index_select = the same rows as individual_codes[index] (nerf/renderer.py:199); its backward is one index_add
+                # instead of index_put's sort + segmented scatter (5 launches for a one-element index)
+                ind = torch.index_select(self.individual_codes, 0, idx.long())
 
         results = {}
         if self.training:
-            head = self._head_training(rays_o, rays_d, nears, fars, enc_a, ind_code, eye, perturb, force_all_rays, dt_gamma, max_steps,
-                                       wait_for=audio_side, box=box, ind_index=ind_index)
+            head = self._head_training(rays_o, rays_d, nears, fars, enc_a, ind, eye, perturb, force_all_rays, dt_gamma, max_steps, route, box)
             nears, fars = head["nears"], head["fars"]
             results["weights_sum"], results["ambient"] = head["weights_sum"], head["ambient"]
         else:
-            head = self._head_inference_ops(rays_o, rays_d, nears, fars, enc_a, ind_code, eye, perturb, dt_gamma, max_steps, T_thresh)
+            head = self._head_inference_ops(rays_o, rays_d, nears, fars, enc_a, ind, eye, perturb, dt_gamma, max_steps, T_thresh)
 
         background = 1 if bg_color is None else bg_color
         if self.training and kwargs.get("defer_blend") and not self.torso and torch.is_tensor(background):

@@ -1,0 +1,52 @@
+"""The RN_* environment switches of the Python side, in one table; `get` / `on` are their only readers.
+
+A switch is read when it is asked for (nothing is cached: tests and tools flip them between calls), a value outside its accepted
+ones is a ValueError, and `python -m radnerf.switches` prints the table as the "Switches" section of INTEGRATION.md.  The tuning
+knobs the C library reads for itself (csrc/) are not listed here."""
+import os
+
+# (name, default, accepted values, what the switch selects)
+TABLE = (
+    ("RN_ADAM", "hip", ("hip", "torch"), "optimizer of `make_optimizer` on the GPU: `HipAdam` (one update kernel for all tensors) or torch's fused Adam"),
+    ("RN_AUDIO_TRAIN", "hip", ("hip", "torch"), "`encode_audio` on the GPU: the audio kernels (`radnerf/audio.py`) or the `nn.Module` path"),
+    ("RN_LIVE_LIST", "1", ("1", "0"), "fused inference engine: hand the loop the list of live sample slots (`0`: every launch scans all slots)"),
+    ("RN_MLP_TRAIN", "hip", ("hip", "torch"), "the per-operator MLP stacks under autograd: `rn_mlp64_*` (`radnerf/mlp_train.py`) or `nn.Linear`"),
+    ("RN_SCATTER", "lbc", ("lbc", "binned"), "table-gradient scatter: the line merge for every level, or hashed levels of the first grid summed by table region"),
+    ("RN_TORSO_STEP", "device", ("device", "host"), "with `RN_TORSO_TRAIN=fused`: the whole torso step on a device-side count, or the fused layer on the index list the host asks for"),
+    ("RN_TORSO_TRAIN", "ops", ("ops", "fused"), "torso layer of a training call: the per-operator layers, or the fused kernels of `radnerf/train_torso.py` (opt-in)"),
+    ("RN_TRAIN_CAMERA", "torch", ("torch", "fused"), "pose code of `--train_camera`: torch's expressions, or `rn_camera_rays_*` (`radnerf/train_camera.py`, opt-in; lets a captured camera step keep the fused head)"),
+    ("RN_TRAIN_GLUE", "hip", ("hip", "torch"), "elementwise glue of the per-operator step: single kernels (`radnerf/train_glue.py`) or the PyTorch expressions"),
+    ("RN_TRAIN_HEAD", "fused", ("fused", "ops"), "`NeRFNetwork.forward` of a training call: one forward and one backward kernel (`radnerf/train_head.py`) or the per-operator path"),
+    ("RN_TRAIN_HEAD_ZERO", "0", ("0", "1"), "`1`: the fused head zero-fills its output rows past the live count (for tools that look at all rows)"),
+    ("RN_TRAIN_LOSS", "fused", ("fused", "torch"), "head loss of `train_step`: blend, clamp and loss in one kernel, or the PyTorch expression"),
+    ("RN_TRAIN_MARCH", "step", ("step", "ops"), "marcher of a budgeted step: one launch with near / far and the counters, or `near_far_from_aabb` + `rn_march_rays_train_budget`"),
+    ("RN_TRAIN_NOISE", "hash", ("hash", "torch"), "jitter of the one-launch marcher: the launch's own hash, or `torch.rand` as the reference draws it (the test suite pins this)"),
+    ("RN_TRAIN_OVERLAP", "1", ("1", "0"), "table-gradient scatter and audio nets on side streams beside the step (`0`: everything on one stream)"),
+    ("RN_TRAIN_PACKED", "1", ("1", "0"), "`SyntheticTrainStream.batch`: one gather kernel into one flat buffer (`0`: separate tensors, as a generic loader hands over)"),
+    ("RN_TRAIN_SET", "hip", ("hip", "torch"), "`DeviceTrainSet.batch` on the GPU: one launch, or the plain-torch restatement of `collate`"),
+)
+_ROWS = {row[0]: row for row in TABLE}
+
+
+def get(name):
+    """The switch's value in the environment now, or its default; ValueError for a value it does not accept."""
+    _, default, accepted, _ = _ROWS[name]
+    value = os.environ.get(name, default)
+    if value not in accepted:
+        raise ValueError(f"{name}={value!r} is not one of its accepted values: {' | '.join(accepted)}")
+    return value
+
+
+def on(name):
+    """get() of a `0 | 1` switch as a bool."""
+    return get(name) == "1"
+
+
+def markdown():
+    rows = ["| switch | default | accepted | selects |", "|---|---|---|---|"]
+    rows += ["| `%s` | `%s` | %s | %s |" % (name, default, " \\| ".join("`%s`" % v for v in accepted), doc) for name, default, accepted, doc in TABLE]
+    return "\n".join(rows)
+
+
+if __name__ == "__main__":
+    print(markdown())

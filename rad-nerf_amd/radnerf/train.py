@@ -8,17 +8,20 @@ the order zero_grad -> step -> backward -> optimizer and the `update_extra_state
 NeRFNetwork.get_params(lr, lr_net) (nerf/network.py:328-357).  The data loader, LPIPS, EMA, GradScaler and the
 learning-rate schedule are outside the path (out of scope) and are not rebuilt.
 """
+import contextlib
+
 import torch
+
+from radnerf import route, switches      # by the package's name: this file is also loaded on its own (tests/test_train_host.py)
 
 
 def make_optimizer(model, lr=5e-3, lr_net=5e-4, fused=None, capturable=False, kernel=None):
     """main.py:204; lr for the grid tables, lr_net for the MLPs / audio nets / individual codes.  On the GPU the update runs
     as ONE kernel over all tensors (HipAdam; `kernel="torch"` or RN_ADAM=torch: torch's fused Adam, one launch per parameter
     group) -- the 49 MB table is read and written once per step either way; same arithmetic as the default implementation."""
-    import os
     on_gpu = next(model.parameters()).is_cuda
     if kernel is None:
-        kernel = os.environ.get("RN_ADAM", "hip") if on_gpu else "torch"
+        kernel = switches.get("RN_ADAM") if on_gpu else "torch"
     if kernel == "hip" and on_gpu:
         return HipAdam(model.get_params(lr, lr_net))
     if fused is None:
@@ -86,19 +89,16 @@ class HipAdam:
 
     @torch.no_grad()
     def step(self):
-        import sys
-        th = sys.modules.get("radnerf.train_head")
-        if th is not None:                       # table-gradient scatters still running on the side stream (train_head.deferred_join)
-            pending = th.take_pending_events()
-            if pending:
-                held = {p.grad.data_ptr() for g in self.param_groups for p in g["params"] if p.grad is not None}
-                for ev, *ptrs in pending:
-                    torch.cuda.current_stream().wait_event(ev)
-                    if not all(q in held for q in ptrs):
-                        # autograd copied a table gradient instead of keeping the buffer the scatter writes (a parameter that
-                        # already had a .grad): that copy raced with the side stream
-                        raise RuntimeError("HipAdam: a table gradient was copied before its scatter had finished; use "
-                                           "zero_grad(set_to_none=True) or RN_TRAIN_OVERLAP=0")
+        pending = route.take_pending_events()    # table-gradient scatters still running on the side stream (route.deferred_join)
+        if pending:
+            held = {p.grad.data_ptr() for g in self.param_groups for p in g["params"] if p.grad is not None}
+            for ev, *ptrs in pending:
+                torch.cuda.current_stream().wait_event(ev)
+                if not all(q in held for q in ptrs):
+                    # autograd copied a table gradient instead of keeping the buffer the scatter writes (a parameter that
+                    # already had a .grad): that copy raced with the side stream
+                    raise RuntimeError("HipAdam: a table gradient was copied before its scatter had finished; use "
+                                       "zero_grad(set_to_none=True) or RN_TRAIN_OVERLAP=0")
         entries, keep, written, groups = [], [], [], []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
@@ -167,14 +167,13 @@ def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, am
     eye [B,1], auds, index, bg_color [B,N,3], images (head) or bg_torso_color (torso) [B,N,3]."""
     torso = bool(opt.torso)
     rgb = data["bg_torso_color"] if torso else data["images"]
-    import os
-    fused_loss = (not torso and rgb.is_cuda and rgb.dtype == torch.float32 and os.environ.get("RN_TRAIN_LOSS", "fused") == "fused"
+    fused_loss = (not torso and rgb.is_cuda and rgb.dtype == torch.float32 and switches.get("RN_TRAIN_LOSS") == "fused"
                   and torch.is_tensor(data.get("bg_color")) and data["bg_color"].dtype == torch.float32)
     # opt-in: a torso step that stays on the device (covered pixels compacted there, blend + loss in one kernel).  Asked for here
     # when the target can feed the loss kernel; the renderer decides (train_torso.step_usable, once per step) and answers with
     # the compact pieces, or with today's results
-    torso_direct = (torso and os.environ.get("RN_TORSO_TRAIN") == "fused" and rgb.is_cuda and rgb.dtype == torch.float32
-                    and torch.is_tensor(data.get("bg_color")))
+    torso_direct = (torso and rgb.is_cuda and rgb.dtype == torch.float32 and torch.is_tensor(data.get("bg_color"))
+                    and route.kernels("train_torso").step_enabled())
     out = model.render(data["rays_o"], data["rays_d"], data["auds"], data["bg_coords"], data["poses"], eye=data["eye"],
                        index=data["index"], staged=False, bg_color=data["bg_color"], perturb=True, force_all_rays=False,
                        dt_gamma=opt.dt_gamma, max_steps=opt.max_steps, defer_blend=fused_loss or torso_direct)
@@ -255,8 +254,8 @@ class SyntheticTrainStream:
             cols = [f["rays_o"][0], f["rays_d"][0], f["bg_coords"][0], f["bg_color"][0], self.target[0], self.face_mask[0].float().unsqueeze(-1)]
             self._table = torch.cat([c.reshape(n_px, -1).float() for c in cols], dim=1).contiguous()
         idx = torch.randint(0, n_px, (self.n_rays,), device=self.target.device, generator=self.gen)
-        import os
-        if self._table.is_cuda and os.environ.get("RN_TRAIN_PACKED", "1") != "0":
+        packed = switches.on("RN_TRAIN_PACKED")
+        if self._table.is_cuda and packed:
             # one kernel: the picked rows, every column section written as its own contiguous array of one flat buffer
             from . import train_head
             flat, _ = train_head.batch_gather(self._table, idx, self._WIDTHS)
@@ -264,7 +263,7 @@ class SyntheticTrainStream:
         rows = self._table.index_select(0, idx)
         flat = torch.cat([rows[:, a:a + w].reshape(-1) for a, w in zip(self._COL0, self._WIDTHS)])
         out = self.unpack(flat)
-        if os.environ.get("RN_TRAIN_PACKED", "1") == "0":       # experiment switch: separate tensors, as a generic loader would hand over
+        if not packed:                                          # experiment switch: separate tensors, as a generic loader would hand over
             out = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in out.items() if not k.startswith("_")}
         return out
 
@@ -302,23 +301,34 @@ class Trainer:
         self.update_extra_interval, self.iters, self.lambda_amb = update_extra_interval, iters, lambda_amb
         self.global_step = 0
 
-    def step(self, data):
+    def _begin_step(self):
+        """What comes before every step: train mode, the occupancy refresh on its cadence, the step count."""
         m = self.model
         m.train()
         if self.update_extra_interval and self.global_step % self.update_extra_interval == 0:
             with torch.no_grad():
                 m.update_extra_state()
         self.global_step += 1
+        return m
+
+    def _forward_backward_update(self, data, budget, amb_weight=None):
+        """zero_grad -> train_step -> backward -> optimizer.step with `budget` as the renderer's sample budget (device int32 budget,
+        row capacity; None: the marcher of the first window); returns the loss with its graph."""
+        m = self.model
         self.optimizer.zero_grad(set_to_none=True)
-        m._sample_budget = self._device_budget(m)
+        m._sample_budget = budget
         try:
             with _join_in_optimizer(self.optimizer):
-                _, _, loss = train_step(m, data, self.opt, self.global_step, self.iters, self.lambda_amb)
+                _, _, loss = train_step(m, data, self.opt, self.global_step, self.iters, self.lambda_amb, amb_weight)
                 _backward(loss)
                 self.optimizer.step()
         finally:
             m._sample_budget = None
-        return loss.detach()
+        return loss
+
+    def step(self, data):
+        m = self._begin_step()
+        return self._forward_backward_update(data, self._device_budget(m)).detach()
 
     def _device_budget(self, m):
         """(device int32 budget, row capacity) for the renderer's one-launch marcher, or None (first window, CPU).  The budget is
@@ -326,8 +336,7 @@ class Trainer:
         dev = next(m.parameters()).device
         if m.mean_count <= 0 or dev.type != "cuda":
             return None
-        budget = int(m.mean_count)
-        budget += 128 - budget % 128
+        budget = _aligned_budget(m.mean_count)
         held = getattr(self, "_budget_held", None)
         if held is None or held[0] != budget or held[1].device != dev:
             t = held[1] if held is not None and held[1].device == dev else torch.zeros(1, dtype=torch.int32, device=dev)
@@ -336,23 +345,16 @@ class Trainer:
         return held[1], budget
 
 
-class _join_in_optimizer:
-    """HipAdam.step waits for the table-gradient scatter the backward pass left on a side stream (train_head.deferred_join); any
-    other optimizer gets gradients that are complete when backward() returns."""
+def _aligned_budget(mean_count):
+    """raymarching.py:226-229: the running average of the sample count, rounded up past the next multiple of 128."""
+    budget = int(mean_count)
+    return budget + 128 - budget % 128
 
-    def __init__(self, optimizer):
-        self.ctx = None
-        if isinstance(optimizer, HipAdam) and torch.cuda.is_available():
-            from . import train_head
-            self.ctx = train_head.deferred_join()
 
-    def __enter__(self):
-        if self.ctx is not None:
-            self.ctx.__enter__()
-
-    def __exit__(self, *exc):
-        if self.ctx is not None:
-            self.ctx.__exit__(*exc)
+def _join_in_optimizer(optimizer):
+    """HipAdam.step waits for the table-gradient scatter the backward pass left on a side stream (route.deferred_join); any other
+    optimizer gets gradients that are complete when backward() returns."""
+    return route.deferred_join() if isinstance(optimizer, HipAdam) and torch.cuda.is_available() else contextlib.nullcontext()
 
 
 class GraphedTrainer(Trainer):
@@ -401,21 +403,16 @@ class GraphedTrainer(Trainer):
         if step_marcher_supported(n_rays, self._counter.device):
             step_marcher_prepare(n_rays, self._counter.device)       # persistent state: must not be born inside the capture
         if self._torso_route():
-            from . import train_torso
-            train_torso.prepare(m, n_rays)                           # the same for the torso route: pinned mean density, workspaces
+            route.kernels("train_torso").prepare(m, n_rays)          # the same for the torso route: pinned mean density, workspaces
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
-        self.optimizer.zero_grad(set_to_none=True)
+        self.optimizer.zero_grad(set_to_none=True)            # gradients of earlier steps go before the capture begins
         m._static_counter = self._counter                     # renderer._head_training counts into this pair while captured
-        m._sample_budget = (self._budget, self._capacity)
         try:
-            with torch.cuda.graph(g), _join_in_optimizer(self.optimizer):   # a private memory pool per graph: cached graphs never alias each other
-                _, _, loss = train_step(m, self._static, self.opt, amb_weight=self._amb_weight)
-                _backward(loss)
-                self.optimizer.step()
+            with torch.cuda.graph(g):                         # a private memory pool per graph: cached graphs never alias each other
+                loss = self._forward_backward_update(self._static, (self._budget, self._capacity), self._amb_weight)
         finally:
             m._static_counter = None
-            m._sample_budget = None
         m.local_step -= 1                                     # the capture pass went through the Python bookkeeping once
         self._graph, self._loss, self._key = g, loss, key
         self._graphs[key] = (g, loss)
@@ -427,28 +424,15 @@ class GraphedTrainer(Trainer):
     def _torso_route(self):
         """A torso step can be captured only on the device-resident route (opt-in RN_TORSO_TRAIN=fused, radnerf/train_torso.py):
         the default one asks the host for the covered pixels."""
-        import os
-        return bool(self.opt.torso) and os.environ.get("RN_TORSO_TRAIN") == "fused" and os.environ.get("RN_TORSO_STEP", "device") == "device"
+        return bool(self.opt.torso) and next(self.model.parameters()).is_cuda and route.kernels("train_torso").step_enabled()
 
     def step(self, data):
-        m = self.model
-        m.train()
-        if self.update_extra_interval and self.global_step % self.update_extra_interval == 0:
-            with torch.no_grad():
-                m.update_extra_state()
-        self.global_step += 1
-        if self._torso_route() and next(m.parameters()).is_cuda:
-            from . import train_torso
-            train_torso.pin_mean(m)          # a mean set from the host since the last step goes into the scalar the graph reads
+        m = self._begin_step()
+        if self._torso_route():
+            route.kernels("train_torso").pin_mean(m)   # a mean set from the host since the last step goes into the scalar the graph reads
         if m.mean_count <= 0 or not next(m.parameters()).is_cuda:        # first window / CPU: the eager step
-            self.optimizer.zero_grad(set_to_none=True)
-            with _join_in_optimizer(self.optimizer):
-                _, _, loss = train_step(m, data, self.opt, self.global_step, self.iters, self.lambda_amb)
-                _backward(loss)
-                self.optimizer.step()
-            return loss.detach()
-        budget = int(m.mean_count)
-        budget += 128 - budget % 128                                     # raymarching.py:226-229 (align = 128)
+            return self._forward_backward_update(data, None).detach()
+        budget = _aligned_budget(m.mean_count)
         step = self.capacity_step
         if not (budget <= self._capacity <= budget + 2 * step):         # keep the capacity while the budget stays inside its window
             self._capacity = -(-(budget + step // 4) // step) * step

@@ -9,26 +9,25 @@ The frame's row is an int64 scalar on the device, so nothing depends on the host
 launches for whatever frame the feed wrote there.  Nothing persistent is allocated here; the backward's workspace (12 floats per
 256 rays) is a temporary of the caching allocator like every other buffer of the step.
 """
-import os
-
 import torch
 
 import radnerf_hip as hip
+
+from . import switches
+from .route import training_call
 
 _lib = hip._lib
 
 
 def enabled():
-    return os.environ.get("RN_TRAIN_CAMERA", "torch") == "fused"
+    return switches.get("RN_TRAIN_CAMERA") == "fused"
 
 
 def usable(model, rays_o, rays_d, index):
     """RN_TRAIN_CAMERA=fused, CUDA fp32 rays and tables, grad on, autocast off, rays that carry no gradient themselves (the
     backward returns none for them), one frame index."""
-    if not enabled() or not torch.is_grad_enabled() or torch.is_autocast_enabled():
-        return False
     dT, dR = model.camera_dT, model.camera_dR
-    if not all(t.is_cuda and t.dtype == torch.float32 for t in (rays_o, rays_d, dT, dR)):
+    if not enabled() or not training_call(rays_o, rays_d, dT, dR):
         return False
     if rays_o.requires_grad or rays_d.requires_grad or dT.shape != dR.shape or dT.dim() != 2 or dT.shape[1] != 3:
         return False

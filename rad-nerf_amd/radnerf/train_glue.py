@@ -3,17 +3,17 @@
 The expressions are the reference's (nerf/network.py:266-276, nerf/renderer.py:216, nerf/utils.py:772-803); PyTorch evaluates
 each as 3 - 15 kernels per direction, which at 2 - 5 us apiece is a third of a 1.5 ms training step.  RN_TRAIN_GLUE=torch keeps
 the PyTorch expressions (the parity tests compare the two)."""
-import os
-
 import torch
 
 import radnerf_hip as hip
 
+from . import switches
+from .route import training_call
+
 
 def enabled(*tensors):
     """The kernels apply to CUDA fp32 tensors under autograd, outside autocast."""
-    return os.environ.get("RN_TRAIN_GLUE", "hip") != "torch" and torch.is_grad_enabled() and not torch.is_autocast_enabled() and \
-        all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
+    return switches.get("RN_TRAIN_GLUE") == "hip" and training_call(*tensors)
 
 
 class _HeadMid(torch.autograd.Function):

@@ -19,6 +19,7 @@ import torch
 import radnerf_hip as hip
 from radnerf_hip.abi import HeadGradsT, ScatterJobT
 
+from . import route, switches
 from .fused import _grid_desc, head_weights, weights_desc
 
 _lib = hip._lib
@@ -63,8 +64,7 @@ class _HeadTrain(torch.autograd.Function):
         work = torch.empty(int(_lib.rn_train_head_workspace_floats(M)), dtype=torch.float32, device=dev)
         # one block for the outputs.  Rows past the live count are not written: they belong to no ray, so the compositor never
         # reads them and the backward kernel skips them (RN_TRAIN_HEAD_ZERO=1 zero-fills the block, for tools that look at all rows)
-        import os
-        out = (torch.zeros if (m_dev is not None and os.environ.get("RN_TRAIN_HEAD_ZERO") == "1") else torch.empty)(
+        out = (torch.zeros if (m_dev is not None and switches.on("RN_TRAIN_HEAD_ZERO")) else torch.empty)(
             M, 12, dtype=torch.float32, device=dev)
         flat = out.view(-1)
         sigmas, amb_abs = flat[0:M], flat[M:2 * M]
@@ -121,8 +121,8 @@ class _HeadTrain(torch.autograd.Function):
             # The table gradients need only the feature gradients the kernel above has written; the weight gradients, the
             # constants' gradients and whatever autograd runs after this function (the audio nets' backward) need nothing of the
             # tables.  RN_TRAIN_OVERLAP=1: the scatter launches go to a side stream and the optimizer waits for them
-            # (take_pending_events), so they run beside those kernels instead of in front of them.
-            side = _side_stream(dev) if overlap_enabled() else None
+            # (route.take_pending_events), so they run beside those kernels instead of in front of them.
+            side = side_stream(dev, 0) if overlap_enabled() else None
             joined = None
             if side is not None:
                 main = torch.cuda.current_stream(dev)
@@ -137,8 +137,8 @@ class _HeadTrain(torch.autograd.Function):
                     t.record_stream(side)
                 g_tx.record_stream(main)
                 g_tw.record_stream(main)
-                if DEFER_JOIN:
-                    _PENDING.append((ev, g_tx.data_ptr(), g_tw.data_ptr()))
+                if route.DEFER_JOIN:           # the optimizer joins (route.take_pending_events)
+                    route._PENDING.append((ev, g_tx.data_ptr(), g_tw.data_ptr()))
                 else:
                     joined = ev
             if need_in:
@@ -181,22 +181,16 @@ class _HeadTrain(torch.autograd.Function):
                 g_ind.view(ind_shape) if g_ind is not None else None, None, None, g_tx, g_tw, *grads)
 
 
-_SCATTER_WS = {}
 _SIDE = {}
-_PENDING = []
-
-
-DEFER_JOIN = False      # set by a caller whose optimizer waits for take_pending_events() (radnerf.train.Trainer with HipAdam)
 
 
 def overlap_enabled():
     """RN_TRAIN_OVERLAP (default on): the table-gradient scatter of the backward pass runs on a side stream beside the weight
-    gradients (and, when the caller's optimizer takes over the join -- DEFER_JOIN -- beside everything autograd runs after this
+    gradients (and, when the caller's optimizer takes over the join -- route.deferred_join -- beside everything autograd runs after this
     function: the audio nets' backward).  Measured on config 2: 1266 -> 1351 steps/s.  (Round 2 had found the same overlap
     slower, 1.35 -> 1.45 ms per step: the scatter was then 6.4 M memory-side atomic requests, which slowed whatever ran beside it;
     it is now mostly bucket sums in LDS.)"""
-    import os
-    return os.environ.get("RN_TRAIN_OVERLAP", "1") == "1"
+    return switches.on("RN_TRAIN_OVERLAP")
 
 
 def side_stream(dev, which=0):
@@ -209,37 +203,12 @@ def side_stream(dev, which=0):
     return st
 
 
-def _side_stream(dev):
-    return side_stream(dev, 0)
-
-
-def take_pending_events():
-    """Events of table-gradient scatters still running on the side stream (RN_TRAIN_OVERLAP=1): whoever reads the table gradients
-    next (the optimizer) makes its stream wait for them."""
-    evs = list(_PENDING)
-    _PENDING.clear()
-    return evs
-
-
-class deferred_join:
-    """with deferred_join(): ... loss.backward(); optimizer.step() -- the optimizer (HipAdam.step) joins the side stream."""
-
-    def __enter__(self):
-        global DEFER_JOIN
-        self.prev, DEFER_JOIN = DEFER_JOIN, True
-
-    def __exit__(self, *exc):
-        global DEFER_JOIN
-        DEFER_JOIN = self.prev
-
-
 def binning_active():
     """RN_SCATTER=binned: the hashed levels of the first grid are summed by table region (no global atomics on them: 0.4 -- 1.2 M
     atomic requests per xyz launch instead of 3.0 -- 4.1 M).  Default: the per-workgroup line merge for every level -- measured
     FASTER end to end (1 380 against 1 340 steps/s on config 2): the bucket passes are bound by the LDS float-atomic rate, cost two
     more launches, and compete with the kernels the scatter overlaps with, while the line merge mostly waits for its atomics."""
-    import os
-    return os.environ.get("RN_SCATTER", "lbc") == "binned"
+    return switches.get("RN_SCATTER") == "binned"
 
 
 def zero_table_gradient(enc, table):
@@ -274,7 +243,6 @@ def grid_scatter(jobs, M, m_dev):
     enough are summed by table region (two launches, no global atomics: the T = 2^19 xyz table), every other level of both grids
     goes through the per-workgroup line merge in ONE launch (rn_grid_scatter_jobs) -- with RN_SCATTER=binned; by default every
     level of both grids takes the line merge (one launch; see binning_active)."""
-    import os
     s = hip.stream()
     grad0, _, enc0, gd0, table0 = jobs[0]
     arr = (ScatterJobT * len(jobs))()
@@ -290,15 +258,9 @@ def grid_scatter(jobs, M, m_dev):
         if int(_lib.rn_grid_scatter_workspace(M, C.byref(gd0), off_host)) > 256:
             # bucket workspace: per device and grid, sized for a multiple of 65 536 rows (a step's changing sample budget does not
             # re-allocate), zeroed once -- the bucket cursors at its start are left zero by every call
-            dev = table0.device
             need = int(_lib.rn_grid_scatter_workspace(-(-M // 65536) * 65536, C.byref(gd0), off_host))
-            key = (dev.index if dev.index is not None else torch.cuda.current_device(), enc0.offsets.data_ptr(), int(enc0.offsets[-1]) if False else 0)
-            buf = _SCATTER_WS.get(key)
-            if buf is None or buf.numel() < need:
-                if torch.cuda.is_current_stream_capturing():
-                    raise RuntimeError("grid_scatter: the bucket workspace must exist before a step is captured (take one eager step first)")
-                buf = _SCATTER_WS[key] = torch.zeros(need, dtype=torch.uint8, device=dev)
-            ws, ws_bytes = buf, buf.numel()
+            ws = hip.persistent_buffer(("grid_scatter", enc0.offsets.data_ptr()), need, table0.device, zero=True)
+            ws_bytes = ws.numel()
             arr[0].offsets_host = C.cast(off_host, C.c_void_p)
     hip.call("rn_grid_scatter_jobs", arr, len(jobs), M, hip.ptr(m_dev), hip.ptr(ws), ws_bytes, s)
 
@@ -319,15 +281,15 @@ def head_forward(model, xyzs, dirs, enc_a, ind_code, eye, m_dev=None, ind_index=
                             model.encoder.embeddings, model.encoder_ambient.embeddings, *ws)
 
 
-def usable(model, x, enc_a):
-    """Training call of the supported shape on the GPU in fp32 (autocast keeps the per-operator path; so does a call whose
+def usable(model, x, enc_a, requires_grad=None):
+    """Training call of the supported shape on the GPU in fp32 on samples `x` -- or on the rays the samples will come from, with
+    `requires_grad` saying whether they will carry a gradient (autocast keeps the per-operator path; so does a call whose
     positions require grad while a stream is capturing: a captured --train_camera step replays the operator chain -- unless the
     pose code runs through the camera kernels, RN_TRAIN_CAMERA=fused (radnerf/train_camera.py): then the captured step keeps the
     fused head and replays its input-gradient launch)."""
-    import os
-    return (os.environ.get("RN_TRAIN_HEAD", "fused") == "fused" and x.is_cuda and torch.is_grad_enabled() and x.dim() == 2
-            and x.dtype == torch.float32 and not torch.is_autocast_enabled() and enc_a is not None
-            and not (x.requires_grad and torch.cuda.is_current_stream_capturing() and os.environ.get("RN_TRAIN_CAMERA") != "fused")
+    needs_grad = x.requires_grad if requires_grad is None else requires_grad
+    return (switches.get("RN_TRAIN_HEAD") == "fused" and route.training_call(x) and x.dim() == 2 and enc_a is not None
+            and not (needs_grad and torch.cuda.is_current_stream_capturing() and switches.get("RN_TRAIN_CAMERA") != "fused")
             and getattr(model, "_train_head_ok", None) is not False and _check(model))
 
 

@@ -17,14 +17,15 @@ no shape that depends on the data, so GraphedTrainer can capture the step.  RN_T
 list the host asks for (rn_torso_mask + torch.nonzero), for comparisons.
 """
 import ctypes as C
-import os
 
 import torch
 
 import radnerf_hip as hip
 from radnerf_hip.abi import TorsoGradsT
 
+from . import switches
 from .fused import _grid_desc, torso_constants, torso_weights, torso_weights_desc  # noqa: F401  (torso_weights: re-exported)
+from .route import training_call
 from .train_head import grid_scatter
 
 _lib = hip._lib
@@ -45,8 +46,7 @@ def supported(model):
 def usable(model, x):
     """Opted in (RN_TORSO_TRAIN=fused) and a training call of the supported shape on the GPU in fp32; autocast, no_grad and
     anything else keep the per-operator path."""
-    return (os.environ.get("RN_TORSO_TRAIN") == "fused" and x.is_cuda and torch.is_grad_enabled() and x.dim() == 2
-            and x.dtype == torch.float32 and not torch.is_autocast_enabled() and supported(model))
+    return switches.get("RN_TORSO_TRAIN") == "fused" and training_call(x) and x.dim() == 2 and supported(model)
 
 
 def _empty(dev):
@@ -125,15 +125,18 @@ class _TorsoTrain(torch.autograd.Function):
         return (None, None, g_code.view(code_shape) if g_code is not None else None, None, None, g_table, *grads)
 
 
+def step_enabled():
+    """Is the device-resident torso step switched on?  RN_TORSO_TRAIN=fused, and not RN_TORSO_STEP=host: the fused layer on the
+    index list the host asks for (rn_torso_mask + torch.nonzero), for comparisons."""
+    return switches.get("RN_TORSO_TRAIN") == "fused" and switches.get("RN_TORSO_STEP") == "device"
+
+
 def step_usable(model, bg_coords, background, target=None):
     """May a training step take the device-resident route (select -> torso_forward on a live count -> torso_loss)?  Opted in, the
     supported shape, fp32 CUDA tensors, no autocast, grad enabled, and a background that is a tensor without a gradient (the loss
     kernel returns none for it)."""
     tensors = [bg_coords, background] + ([target] if target is not None else [])
-    # RN_TORSO_STEP=host: the fused layer on the index list the host asks for (rn_torso_mask + torch.nonzero), for comparisons
-    return (os.environ.get("RN_TORSO_TRAIN") == "fused" and os.environ.get("RN_TORSO_STEP", "device") == "device"
-            and model.training and torch.is_grad_enabled()
-            and not torch.is_autocast_enabled() and all(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 for t in tensors)
+    return (step_enabled() and model.training and all(torch.is_tensor(t) for t in tensors) and training_call(*tensors)
             and not background.requires_grad and supported(model))
 
 
@@ -152,20 +155,11 @@ def pin_mean(model):
     return stats
 
 
-_WGRAD_WS = {}
-
-
 def _wgrad_workspace(dev):
     """The weight-gradient scratch of the torso layer: its own buffer per device, of the one size the library asks for.  It never
     grows and nothing else uses it, so a captured step can keep its address (the shared hip.workspace() buffer is replaced when a
-    larger request comes)."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    buf = _WGRAD_WS.get(key)
-    if buf is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("train_torso: the weight-gradient workspace must exist before a step is captured (train_torso.prepare)")
-        buf = _WGRAD_WS[key] = torch.empty(int(_lib.rn_train_torso_wgrad_workspace()), dtype=torch.uint8, device=dev)
-    return buf
+    larger request comes); prepare() creates it before a capture."""
+    return hip.persistent_buffer("train_torso.wgrad", int(_lib.rn_train_torso_wgrad_workspace()), dev)
 
 
 def prepare(model, n_px):

@@ -192,6 +192,23 @@ def aligned(t, nbytes=16):
 _WS = {}
 
 
+def persistent_buffer(key, nbytes, device, zero=False):
+    """uint8 buffer of at least `nbytes` that belongs to `key` on `device`: created on the first request (zero-filled if asked)
+    and kept at its address from then on -- only a larger request replaces it.  A captured step replays that address, so the
+    buffer must exist, at its final size, before the capture."""
+    key = (device.index if device.index is not None else torch.cuda.current_device(), key)
+    buf = _PERSISTENT.get(key)
+    if buf is None or buf.numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"radnerf_hip: the buffer {key[1]!r} ({nbytes} bytes) must exist before a step is captured "
+                               "(take one eager step, or call the route's prepare(), first)")
+        buf = _PERSISTENT[key] = (torch.zeros if zero else torch.empty)(int(nbytes), dtype=torch.uint8, device=device)
+    return buf
+
+
+_PERSISTENT = {}
+
+
 def workspace(nbytes, device):
     """Small per-device scratch buffer, grown on demand, reused across calls on one stream."""
     key = (device.index if device.index is not None else torch.cuda.current_device())
