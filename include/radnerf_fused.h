@@ -296,6 +296,16 @@ int rn_audio_encode_windows_train(const rn_audio_weights_t *w, const float *auds
 int rn_audio_encode_windows_backward_acts(const rn_audio_weights_t *w, const float *auds, uint32_t n, const float *codes,
                                           const float *grad_enc, const rn_audio_grads_t *grads, float *grad_codes,
                                           const float *acts, rn_stream_t stream);
+/* The same backward without a float atomic (opt-in, RN_TRAIN_DETERMINISTIC=1): every workgroup STORES its contributions to the
+ * parameter gradients into its own slice of `partials` (rn_audio_backward_partials_floats(n, has_att) floats, sized for dim_in
+ * = dim_aud = 64; needs no initialisation), and one reduction launch computes per element acc = p[0]; acc = acc + p[k] in
+ * ascending workgroup order -- (window, frame) row-major for AudioNet, window for AudioAttNet -- and then grads[e] = grads[e] +
+ * acc: like the entries above it ADDS to `grads`.  The per-workgroup arithmetic is that of the entries above; two calls give
+ * the same bits. */
+size_t rn_audio_backward_partials_floats(uint32_t n, int has_att);
+int rn_audio_encode_windows_backward_ordered(const rn_audio_weights_t *w, const float *auds, uint32_t n, const float *codes,
+                                             const float *grad_enc, const rn_audio_grads_t *grads, float *grad_codes,
+                                             const float *acts, float *partials, rn_stream_t stream);
 /* The same for n consecutive frames (first + i) mod T of a feature stream feats [T, dim_in, 16]: the windows are cut on
  * the device exactly as get_audio_features(att_mode=2) does (nerf/utils.py:56-72: frames index-4 .. index+3, zero rows
  * outside the stream).  Needs T >= 8 and has_att. */

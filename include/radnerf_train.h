@@ -138,6 +138,21 @@ int rn_grid_scatter_jobs(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t
 int rn_grid_scatter_binned(const float *grad, const float *inputs, uint32_t M, const int32_t *m_dev, const rn_grid_t *grid,
                            const int32_t *offsets_host, float *grad_table, void *workspace, size_t workspace_bytes, rn_stream_t stream);
 
+/* The same gradient summed in ONE fixed order, without a float atomic (csrc/rn_grid_scatter_ordered.hip; opt-in,
+ * RN_TRAIN_DETERMINISTIC=1).  Same jobs, M, m_dev and zeroed grad_table as rn_grid_scatter_jobs.  Every row of grad_table starts
+ * at +0.0f and receives its contributions level by level, samples ascending, corners ascending, with sequential fp32 adds; a
+ * contribution is w * g with w = 1; w *= (bit d of the corner ? pos[d] : 1 - pos[d]) for d = 0 .. D-1, every operation rounded
+ * on its own -- the order and the arithmetic of the CPU oracle's loops, so the result equals orc_grid_encode_backward's bit for
+ * bit, and two calls give the same bits.  A sample with a coordinate outside [0, 1] contributes nothing; rows of `grad` and
+ * `inputs` at or past the live count are not read; table rows nothing contributes to are not written.  Per job: one launch that
+ * writes a key (the table row) per (level, sample, corner), a stable radix sort of (key, item), one launch that walks every
+ * row's run.  The jobs run one after the other and share the workspace: rn_grid_scatter_ordered_workspace() bytes (0: a job is
+ * out of range), 256-byte aligned, needs no initialisation; it is sized from the capacity M alone, never from the device count.
+ * offsets_host (nullable) lets the sort stop at the table's top row bit instead of bit 31.  L * M * 2^D must stay below 2^31. */
+size_t rn_grid_scatter_ordered_workspace(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t M);
+int rn_grid_scatter_ordered(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t M, const int32_t *m_dev, void *workspace,
+                            size_t workspace_bytes, rn_stream_t stream);
+
 /* Head loss of the training step on the composited rays (nerf/renderer.py:306 + nerf/utils.py:772-803):
  *   pred = clamp(image + (1 - weights_sum) * bg, 0, 1);
  *   loss = mean_n mean_c (pred - target)^2 + 1e-4 mean_n H(clamp(ws, 1e-5, 1 - 1e-5)) + *w_amb mean_n (ambient_n (1 - face_n))

@@ -244,11 +244,21 @@ __global__ void k_audio_smooth(const float *__restrict__ enc, uint32_t n, uint32
 // the same two-kernel shape as the forward.  Each workgroup recomputes its forward with every layer's output kept in LDS,
 // then walks the layers backwards; weight and bias gradients are ADDED to the caller's buffers with atomics (8 frames
 // share AudioNet's weights).  ~50 torch / MIOpen launches (naive conv kernels of 7 - 20 us each) become two.
+// ORDERED (rn_audio_encode_windows_backward_ordered, RN_TRAIN_DETERMINISTIC=1): the same kernels' bodies STORE every parameter
+// gradient into the workgroup's own slice of a partials buffer instead, and k_audio_reduce_partials adds the slices in
+// ascending workgroup order -- no float atomic, two calls give the same bits.
 struct AudioG {
     float *conv_w[4], *conv_b[4], *fc_w[2], *fc_b[2], *att_conv_w[5], *att_conv_b[5], *att_fc_w, *att_fc_b;
 };
 
 __device__ __forceinline__ float leaky_grad(float y) { return y > 0.0f ? 1.0f : 0.02f; }  // y = leaky(z) has the sign of z
+
+// where a workgroup's parameter-gradient contribution goes: added to the shared buffer, or stored into the workgroup's slice
+template <bool ORDERED>
+__device__ __forceinline__ void grad_out(float *p, float v) {
+    if constexpr (ORDERED) *p = v;
+    else atomicAdd(p, v);
+}
 
 __device__ __forceinline__ void stage_weights(float *dst, const float *__restrict__ src, int n) {
     for (int i = threadIdx.x; i < n; i += kAudioThreads) dst[i] = src[i];
@@ -256,6 +266,7 @@ __device__ __forceinline__ void stage_weights(float *dst, const float *__restric
 
 // Backward of conv3 (+ LeakyReLU): x [cin][len_in] -> y [cout][len_out].  dy is turned into dz in place; gw / gb receive
 // atomicAdds; dx (nullable) [cin][len_in] is written.  Ends with a barrier.
+template <bool ORDERED = false>
 __device__ __forceinline__ void conv3_bwd(const float *x, const float *y, float *dy, const float *w, float *__restrict__ gw,
                                           float *__restrict__ gb, float *dx, int cin, int cout, int len_in, int stride) {
     const int len_out = (len_in - 1) / stride + 1;
@@ -268,12 +279,12 @@ __device__ __forceinline__ void conv3_bwd(const float *x, const float *y, float 
             const int p = pos * stride - 1 + k;
             if (p >= 0 && p < len_in) acc += dy[co * len_out + pos] * x[ci * len_in + p];
         }
-        atomicAdd(gw + e, acc);
+        grad_out<ORDERED>(gw + e, acc);
     }
     for (int co = threadIdx.x; co < cout; co += kAudioThreads) {
         float acc = 0.0f;
         for (int pos = 0; pos < len_out; pos++) acc += dy[co * len_out + pos];
-        atomicAdd(gb + co, acc);
+        grad_out<ORDERED>(gb + co, acc);
     }
     if (dx) {
         for (int e = threadIdx.x; e < cin * len_in; e += kAudioThreads) {
@@ -294,14 +305,15 @@ __device__ __forceinline__ void conv3_bwd(const float *x, const float *y, float 
 }
 
 // Backward of linear(): y [dout] = act(W x + b).  dy -> dz in place (act), gw/gb atomics, dx written.  Ends with a barrier.
+template <bool ORDERED = false>
 __device__ __forceinline__ void linear_bwd(const float *x, const float *y, float *dy, const float *w, float *__restrict__ gw,
                                            float *__restrict__ gb, float *dx, int din, int dout, bool act) {
     if (act) {
         for (int o = threadIdx.x; o < dout; o += kAudioThreads) dy[o] *= leaky_grad(y[o]);
         __syncthreads();
     }
-    for (int e = threadIdx.x; e < dout * din; e += kAudioThreads) atomicAdd(gw + e, dy[e / din] * x[e % din]);
-    for (int o = threadIdx.x; o < dout; o += kAudioThreads) atomicAdd(gb + o, dy[o]);
+    for (int e = threadIdx.x; e < dout * din; e += kAudioThreads) grad_out<ORDERED>(gw + e, dy[e / din] * x[e % din]);
+    for (int o = threadIdx.x; o < dout; o += kAudioThreads) grad_out<ORDERED>(gb + o, dy[o]);
     if (dx) {
         for (int k = threadIdx.x; k < din; k += kAudioThreads) {
             float acc = 0.0f;
@@ -313,8 +325,9 @@ __device__ __forceinline__ void linear_bwd(const float *x, const float *y, float
 }
 
 // AudioAttNet backward, one window per workgroup: grad_enc [n][A] + codes [n][8][A] -> grad_codes [n][8][A]
-__global__ void __launch_bounds__(kAudioThreads) k_audio_attend_bwd(AudioW w, AudioG g, const float *__restrict__ codes_all,
-                                                                    const float *__restrict__ grad_enc, float *__restrict__ grad_codes) {
+template <bool ORDERED>
+__device__ __forceinline__ void audio_attend_bwd(const AudioW &w, const AudioG &g, const float *__restrict__ codes_all,
+                                                 const float *__restrict__ grad_enc, float *__restrict__ grad_codes) {
     __shared__ float wts[64 * 16 * 3 + 16 * 8 * 3 + 8 * 4 * 3 + 4 * 2 * 3 + 2 * 1 * 3];
     __shared__ float act[(64 + 16 + 8 + 4 + 2 + 1) * kSeq];   // a0 (= codes^T) .. a5 (scores)
     __shared__ float grad[2][64 * kSeq];
@@ -366,16 +379,16 @@ __global__ void __launch_bounds__(kAudioThreads) k_audio_attend_bwd(AudioW w, Au
     __syncthreads();
     // attentionNet Linear(8, 8): logits = W score + b
     float *ga = grad[0], *gb_ = grad[1];
-    if (threadIdx.x < kSeq * kSeq) atomicAdd(g.att_fc_w + threadIdx.x, logit_g[threadIdx.x / kSeq] * score[threadIdx.x % kSeq]);
+    if (threadIdx.x < kSeq * kSeq) grad_out<ORDERED>(g.att_fc_w + threadIdx.x, logit_g[threadIdx.x / kSeq] * score[threadIdx.x % kSeq]);
     if (threadIdx.x < kSeq) {
-        atomicAdd(g.att_fc_b + threadIdx.x, logit_g[threadIdx.x]);
+        grad_out<ORDERED>(g.att_fc_b + threadIdx.x, logit_g[threadIdx.x]);
         float acc = 0.0f;
         for (int t = 0; t < kSeq; t++) acc += w.att_fc_w[t * kSeq + threadIdx.x] * logit_g[t];
         ga[threadIdx.x] = acc;    // d score
     }
     __syncthreads();
     for (int l = 4; l >= 0; l--) {
-        conv3_bwd(act + aoff[l], act + aoff[l + 1], ga, wts + woff[l], g.att_conv_w[l], g.att_conv_b[l], gb_, chans[l], chans[l + 1],
+        conv3_bwd<ORDERED>(act + aoff[l], act + aoff[l + 1], ga, wts + woff[l], g.att_conv_w[l], g.att_conv_b[l], gb_, chans[l], chans[l + 1],
                   kSeq, 1);
         float *t = ga; ga = gb_; gb_ = t;
     }
@@ -386,9 +399,15 @@ __global__ void __launch_bounds__(kAudioThreads) k_audio_attend_bwd(AudioW w, Au
     }
 }
 
+__global__ void __launch_bounds__(kAudioThreads) k_audio_attend_bwd(AudioW w, AudioG g, const float *__restrict__ codes_all,
+                                                                    const float *__restrict__ grad_enc, float *__restrict__ grad_codes) {
+    audio_attend_bwd<false>(w, g, codes_all, grad_enc, grad_codes);
+}
+
 // AudioNet backward, one frame per workgroup: grad_codes [n * frames][A] -> weight gradients
-__global__ void __launch_bounds__(kAudioThreads) k_audio_frames_bwd(AudioW w, AudioG g, Source src, const float *__restrict__ grad_codes,
-                                                                    const float *__restrict__ acts) {
+template <bool ORDERED>
+__device__ __forceinline__ void audio_frames_bwd(const AudioW &w, const AudioG &g, const Source &src, const float *__restrict__ grad_codes,
+                                                 const float *__restrict__ acts) {
     __shared__ float wts[kMaxWeights];
     __shared__ float x0[kMaxDimIn * kWin], y1[32 * 8], y2[32 * 4], y3[64 * 2], y4[64], y5[64];
     __shared__ float ga[32 * 8], gb_[32 * 8];
@@ -433,16 +452,97 @@ __global__ void __launch_bounds__(kAudioThreads) k_audio_frames_bwd(AudioW w, Au
     // backward
     for (int i = threadIdx.x; i < A; i += kAudioThreads) ga[i] = grad_codes[(size_t)blockIdx.x * A + i];
     stage_weights(wts, w.fc_w[1], A * 64); __syncthreads();
-    linear_bwd(y5, nullptr, ga, wts, g.fc_w[1], g.fc_b[1], gb_, 64, A, false);
+    linear_bwd<ORDERED>(y5, nullptr, ga, wts, g.fc_w[1], g.fc_b[1], gb_, 64, A, false);
     stage_weights(wts, w.fc_w[0], 64 * 64); __syncthreads();
-    linear_bwd(y4, y5, gb_, wts, g.fc_w[0], g.fc_b[0], ga, 64, 64, true);
+    linear_bwd<ORDERED>(y4, y5, gb_, wts, g.fc_w[0], g.fc_b[0], ga, 64, 64, true);
     stage_weights(wts, w.conv_w[3], 64 * 64 * 3); __syncthreads();
-    conv3_bwd(y3, y4, ga, wts, g.conv_w[3], g.conv_b[3], gb_, 64, 64, 2, 2);
+    conv3_bwd<ORDERED>(y3, y4, ga, wts, g.conv_w[3], g.conv_b[3], gb_, 64, 64, 2, 2);
     stage_weights(wts, w.conv_w[2], 64 * 32 * 3); __syncthreads();
-    conv3_bwd(y2, y3, gb_, wts, g.conv_w[2], g.conv_b[2], ga, 32, 64, 4, 2);
+    conv3_bwd<ORDERED>(y2, y3, gb_, wts, g.conv_w[2], g.conv_b[2], ga, 32, 64, 4, 2);
     stage_weights(wts, w.conv_w[1], 32 * 32 * 3); __syncthreads();
-    conv3_bwd(y1, y2, ga, wts, g.conv_w[1], g.conv_b[1], gb_, 32, 32, 8, 2);
-    conv3_bwd(x0, y1, gb_, wts, g.conv_w[0], g.conv_b[0], nullptr, cin0, 32, 16, 2);   // no dx: weights not needed
+    conv3_bwd<ORDERED>(y1, y2, ga, wts, g.conv_w[1], g.conv_b[1], gb_, 32, 32, 8, 2);
+    conv3_bwd<ORDERED>(x0, y1, gb_, wts, g.conv_w[0], g.conv_b[0], nullptr, cin0, 32, 16, 2);   // no dx: weights not needed
+}
+
+__global__ void __launch_bounds__(kAudioThreads) k_audio_frames_bwd(AudioW w, AudioG g, Source src, const float *__restrict__ grad_codes,
+                                                                    const float *__restrict__ acts) {
+    audio_frames_bwd<false>(w, g, src, grad_codes, acts);
+}
+
+// ---- ordered form: per-workgroup slices + one reduction ------------------------------------------------------------------------
+// A slice holds the tensors back to back in the order of rn_audio_grads_t, at their real sizes; slices are kSliceNet / kSliceAtt
+// floats apart, the sizes at dim_in = dim_aud = 64 (rn_audio_backward_partials_floats knows neither).  partials = AudioNet slices
+// [n * frames] (row-major (window, frame)) | AudioAttNet slices [n].
+constexpr int kSliceNet = 32 * kMaxDimIn * 3 + 32 * 32 * 3 + 64 * 32 * 3 + 64 * 64 * 3 + (32 + 32 + 64 + 64) + 64 * 64 + 64 * 64 + 64 + 64;
+constexpr int kSliceAtt = 64 * 16 * 3 + 16 * 8 * 3 + 8 * 4 * 3 + 4 * 2 * 3 + 2 * 1 * 3 + (16 + 8 + 4 + 2 + 1) + kSeq * kSeq + kSeq;
+constexpr int kNetTensors = 12, kAttTensors = 12;
+
+struct AudioSizes {
+    int net[kNetTensors], att[kAttTensors];      // floats of conv_w[4], conv_b[4], fc_w[2], fc_b[2] | att_conv_w[5], att_conv_b[5], att_fc_w, att_fc_b
+};
+__host__ __device__ inline AudioSizes audio_sizes(int cin0, int A) {
+    AudioSizes s{};
+    const int cw[4] = {32 * cin0 * 3, 32 * 32 * 3, 64 * 32 * 3, 64 * 64 * 3}, cb[4] = {32, 32, 64, 64};
+    for (int l = 0; l < 4; l++) { s.net[l] = cw[l]; s.net[4 + l] = cb[l]; }
+    s.net[8] = 64 * 64; s.net[9] = A * 64; s.net[10] = 64; s.net[11] = A;
+    const int chans[6] = {A, 16, 8, 4, 2, 1};
+    for (int l = 0; l < 5; l++) { s.att[l] = chans[l + 1] * chans[l] * 3; s.att[5 + l] = chans[l + 1]; }
+    s.att[10] = kSeq * kSeq; s.att[11] = kSeq;
+    return s;
+}
+// the gradient pointers of one workgroup's slices
+__device__ __forceinline__ AudioG slice_net(float *p, const AudioSizes &s) {
+    AudioG g{};
+    for (int l = 0; l < 4; l++) { g.conv_w[l] = p; p += s.net[l]; }
+    for (int l = 0; l < 4; l++) { g.conv_b[l] = p; p += s.net[4 + l]; }
+    for (int l = 0; l < 2; l++) { g.fc_w[l] = p; p += s.net[8 + l]; }
+    for (int l = 0; l < 2; l++) { g.fc_b[l] = p; p += s.net[10 + l]; }
+    return g;
+}
+__device__ __forceinline__ AudioG slice_att(float *p, const AudioSizes &s) {
+    AudioG g{};
+    for (int l = 0; l < 5; l++) { g.att_conv_w[l] = p; p += s.att[l]; }
+    for (int l = 0; l < 5; l++) { g.att_conv_b[l] = p; p += s.att[5 + l]; }
+    g.att_fc_w = p; p += s.att[10];
+    g.att_fc_b = p;
+    return g;
+}
+
+__global__ void __launch_bounds__(kAudioThreads) k_audio_attend_bwd_ordered(AudioW w, float *__restrict__ partials_att,
+                                                                            const float *__restrict__ codes_all,
+                                                                            const float *__restrict__ grad_enc, float *__restrict__ grad_codes) {
+    const AudioG g = slice_att(partials_att + (size_t)blockIdx.x * kSliceAtt, audio_sizes((int)w.dim_in, (int)w.dim_aud));
+    audio_attend_bwd<true>(w, g, codes_all, grad_enc, grad_codes);
+}
+
+__global__ void __launch_bounds__(kAudioThreads) k_audio_frames_bwd_ordered(AudioW w, float *__restrict__ partials_net, Source src,
+                                                                            const float *__restrict__ grad_codes, const float *__restrict__ acts) {
+    const AudioG g = slice_net(partials_net + (size_t)blockIdx.x * kSliceNet, audio_sizes((int)w.dim_in, (int)w.dim_aud));
+    audio_frames_bwd<true>(w, g, src, grad_codes, acts);
+}
+
+// grads[e] = grads[e] + (((p[0][e] + p[1][e]) + p[2][e]) + ...): blockIdx.y = the tensor, one thread per element, the slices in
+// ascending workgroup order.  Tensors 0 .. 11: AudioNet over n_net slices; 12 .. 23: AudioAttNet over n_att slices.
+__global__ void __launch_bounds__(kAudioThreads) k_audio_reduce_partials(AudioG g, uint32_t dim_in, uint32_t dim_aud, const float *__restrict__ partials,
+                                                                         uint32_t n_net, uint32_t n_att) {
+    const AudioSizes s = audio_sizes((int)dim_in, (int)dim_aud);
+    const uint32_t tensor = blockIdx.y, e = blockIdx.x * kAudioThreads + threadIdx.x;
+    const bool att = tensor >= (uint32_t)kNetTensors;
+    const uint32_t ti = att ? tensor - kNetTensors : tensor;
+    int at = 0, size = 0;
+    float *dst = nullptr;
+    for (uint32_t i = 0; i <= ti; i++) {
+        at += size;
+        size = att ? s.att[i] : s.net[i];
+    }
+    if (!att) dst = ti < 4 ? g.conv_w[ti] : (ti < 8 ? g.conv_b[ti - 4] : (ti < 10 ? g.fc_w[ti - 8] : g.fc_b[ti - 10]));
+    else dst = ti < 5 ? g.att_conv_w[ti] : (ti < 10 ? g.att_conv_b[ti - 5] : (ti == 10 ? g.att_fc_w : g.att_fc_b));
+    if (e >= (uint32_t)size) return;
+    const float *p = att ? partials + (size_t)n_net * kSliceNet : partials;
+    const uint32_t n = att ? n_att : n_net, stride = att ? (uint32_t)kSliceAtt : (uint32_t)kSliceNet;
+    float acc = p[at + e];
+    for (uint32_t k = 1; k < n; k++) acc = acc + p[(size_t)k * stride + at + e];
+    dst[e] = dst[e] + acc;
 }
 
 static int check_audio(const rn_audio_weights_t *w) {
@@ -551,6 +651,38 @@ static int audio_backward(const rn_audio_weights_t *w, const float *auds, uint32
     hipLaunchKernelGGL(k_audio_attend_bwd, dim3(n), dim3(kAudioThreads), 0, s, a, g, codes, grad_enc, grad_codes);
     hipLaunchKernelGGL(k_audio_frames_bwd, dim3(n * kSeq), dim3(kAudioThreads), 0, s, a, g, src, grad_codes, acts);
     return check_launch("audio_encode_windows_backward");
+}
+
+size_t rn_audio_backward_partials_floats(uint32_t n, int has_att) {
+    return (size_t)n * (has_att ? kSeq : 1) * kSliceNet + (has_att ? (size_t)n * kSliceAtt : 0u);
+}
+
+int rn_audio_encode_windows_backward_ordered(const rn_audio_weights_t *w, const float *auds, uint32_t n, const float *codes,
+                                             const float *grad_enc, const rn_audio_grads_t *grads, float *grad_codes, const float *acts,
+                                             float *partials, rn_stream_t stream) {
+    if (n == 0) return RN_OK;
+    if (int rc = check_audio(w)) return rc;
+    RN_REQUIRE(auds && grad_enc && grads && acts && partials, "audio_encode_windows_backward_ordered: null pointer");
+    AudioG g{};
+    for (int l = 0; l < 4; l++) { g.conv_w[l] = grads->conv_w[l]; g.conv_b[l] = grads->conv_b[l]; RN_REQUIRE(g.conv_w[l] && g.conv_b[l], "audio backward: null AudioNet gradient buffer"); }
+    for (int l = 0; l < 2; l++) { g.fc_w[l] = grads->fc_w[l]; g.fc_b[l] = grads->fc_b[l]; RN_REQUIRE(g.fc_w[l] && g.fc_b[l], "audio backward: null AudioNet gradient buffer"); }
+    const AudioW a = audio_w(w);
+    const Source src{auds, 0u, 0u, 0};
+    hipStream_t s = as_stream(stream);
+    const uint32_t n_net = n * (a.has_att ? (uint32_t)kSeq : 1u), n_att = a.has_att ? n : 0u;
+    float *partials_att = partials + (size_t)n_net * kSliceNet;
+    if (a.has_att) {
+        RN_REQUIRE(codes && grad_codes, "audio_encode_windows_backward_ordered: the forward's per-frame codes and n * 8 * dim_aud floats of scratch are required");
+        for (int l = 0; l < 5; l++) { g.att_conv_w[l] = grads->att_conv_w[l]; g.att_conv_b[l] = grads->att_conv_b[l]; RN_REQUIRE(g.att_conv_w[l] && g.att_conv_b[l], "audio backward: null AudioAttNet gradient buffer"); }
+        g.att_fc_w = grads->att_fc_w; g.att_fc_b = grads->att_fc_b;
+        RN_REQUIRE(g.att_fc_w && g.att_fc_b, "audio backward: null AudioAttNet gradient buffer");
+        hipLaunchKernelGGL(k_audio_attend_bwd_ordered, dim3(n), dim3(kAudioThreads), 0, s, a, partials_att, codes, grad_enc, grad_codes);
+    }
+    hipLaunchKernelGGL(k_audio_frames_bwd_ordered, dim3(n_net), dim3(kAudioThreads), 0, s, a, partials, src, a.has_att ? grad_codes : grad_enc, acts);
+    // the largest tensor (conv 64 -> 64, k = 3) sets the grid's width; the others' extra workgroups leave at once
+    hipLaunchKernelGGL(k_audio_reduce_partials, dim3(div_up(kMaxWeights, kAudioThreads), a.has_att ? kNetTensors + kAttTensors : kNetTensors),
+                       dim3(kAudioThreads), 0, s, g, a.dim_in, a.dim_aud, partials, n_net, n_att);
+    return check_launch("audio_encode_windows_backward_ordered");
 }
 
 int rn_audio_smooth(const float *enc, uint32_t n, uint32_t dim, float lambda, float *state, int state_valid,

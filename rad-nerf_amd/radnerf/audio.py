@@ -11,6 +11,8 @@ import torch
 import radnerf_hip as hip
 from radnerf_hip.abi import AudioGradsT, AudioWeightsT
 
+from . import switches
+
 _lib = hip._lib
 
 
@@ -127,6 +129,14 @@ class _EncodeWindows(torch.autograd.Function):
         w, keep = _weights(model)
         ge = grad_enc.contiguous().float()
         scratch = torch.empty_like(codes)
+        if switches.on("RN_TRAIN_DETERMINISTIC"):
+            # no float atomic: every workgroup stores into its slice of `partials`, one launch adds the slices in a fixed order
+            n = auds.shape[0]
+            partials = torch.empty(int(_lib.rn_audio_backward_partials_floats(n, 1 if model.att > 0 else 0)), dtype=torch.float32,
+                                   device=auds.device)
+            hip.call("rn_audio_encode_windows_backward_ordered", C.byref(w), hip.ptr(auds), n, hip.ptr(codes), hip.ptr(ge), C.byref(g),
+                     hip.ptr(scratch), hip.ptr(acts), hip.ptr(partials), hip.stream())
+            return (None, None, *views)
         hip.call("rn_audio_encode_windows_backward_acts", C.byref(w), hip.ptr(auds), auds.shape[0], hip.ptr(codes), hip.ptr(ge), C.byref(g),
                  hip.ptr(scratch), hip.ptr(acts), hip.stream())
         return (None, None, *views)

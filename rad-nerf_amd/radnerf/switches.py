@@ -15,6 +15,7 @@ TABLE = (
     ("RN_TORSO_STEP", "device", ("device", "host"), "with `RN_TORSO_TRAIN=fused`: the whole torso step on a device-side count, or the fused layer on the index list the host asks for"),
     ("RN_TORSO_TRAIN", "ops", ("ops", "fused"), "torso layer of a training call: the per-operator layers, or the fused kernels of `radnerf/train_torso.py` (opt-in)"),
     ("RN_TRAIN_CAMERA", "torch", ("torch", "fused"), "pose code of `--train_camera`: torch's expressions, or `rn_camera_rays_*` (`radnerf/train_camera.py`, opt-in; lets a captured camera step keep the fused head)"),
+    ("RN_TRAIN_DETERMINISTIC", "0", ("0", "1"), "`1`: a step on the fused routes (head, `RN_TRAIN_CAMERA=fused`, `RN_TORSO_TRAIN=fused`) runs no float atomic, eager or captured: the table gradients are summed in one fixed order (`rn_grid_scatter_ordered`; takes precedence over `RN_SCATTER`) and the audio nets' parameter gradients through per-workgroup partials -- two runs from the same seeds give the same bits (opt-in: slower)"),
     ("RN_TRAIN_GLUE", "hip", ("hip", "torch"), "elementwise glue of the per-operator step: single kernels (`radnerf/train_glue.py`) or the PyTorch expressions"),
     ("RN_TRAIN_HEAD", "fused", ("fused", "ops"), "`NeRFNetwork.forward` of a training call: one forward and one backward kernel (`radnerf/train_head.py`) or the per-operator path"),
     ("RN_TRAIN_HEAD_ZERO", "0", ("0", "1"), "`1`: the fused head zero-fills its output rows past the live count (for tools that look at all rows)"),

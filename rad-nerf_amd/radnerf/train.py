@@ -404,6 +404,9 @@ class GraphedTrainer(Trainer):
             step_marcher_prepare(n_rays, self._counter.device)       # persistent state: must not be born inside the capture
         if self._torso_route():
             route.kernels("train_torso").prepare(m, n_rays)          # the same for the torso route: pinned mean density, workspaces
+        elif not self.opt.torso and route.kernels("train_head").supported(m):
+            # RN_TRAIN_DETERMINISTIC=1: the ordered table scatter's workspace at this graph's row capacity
+            route.kernels("train_head").prepare_scatter((m.encoder, m.encoder_ambient), self._capacity, self._counter.device)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)            # gradients of earlier steps go before the capture begins

@@ -211,12 +211,21 @@ def binning_active():
     return switches.get("RN_SCATTER") == "binned"
 
 
+def deterministic():
+    """RN_TRAIN_DETERMINISTIC=1 (opt-in): the table gradients are summed in one fixed order (rn_grid_scatter_ordered: keys, a stable
+    sort, one walk per table row) and the audio nets' parameter gradients through per-workgroup partials (radnerf/audio.py) -- no
+    float atomic in a step of the fused routes, so two runs from the same seeds give the same bits.  Takes precedence over
+    RN_SCATTER."""
+    return switches.on("RN_TRAIN_DETERMINISTIC")
+
+
 def zero_table_gradient(enc, table):
     """A gradient buffer for `table` ready for grid_scatter as its FIRST job: the rows of binned levels are written by the scatter
     (every one of them, by the workgroup that owns its region), so only the other levels are cleared -- for the T = 2^19 xyz table
     2.8 MB instead of 49 MB."""
     gd = _grid_desc(enc, table)
-    mask = int(_lib.rn_grid_scatter_binned_levels(C.byref(gd), hip.host_offsets(enc.offsets))) if binning_active() else 0
+    mask = (int(_lib.rn_grid_scatter_binned_levels(C.byref(gd), hip.host_offsets(enc.offsets)))
+            if binning_active() and not deterministic() else 0)
     if not mask:
         return torch.zeros_like(table)
     g = torch.empty_like(table)
@@ -238,11 +247,14 @@ def zero_table_gradient(enc, table):
 
 
 def grid_scatter(jobs, M, m_dev):
-    """grad_table += the table gradient, for one or two grids: jobs = [(grad_lbc [L, M, 2] level-major feature gradients, inputs
+    """grad_table (zeroed by the caller) receives the table gradient, for one or two grids: jobs = [(grad_lbc [L, M, 2] level-major feature gradients, inputs
     [M, D] normalised coordinates, GridEncoder, its descriptor, grad_table), ...].  The first grid's hashed levels that are large
     enough are summed by table region (two launches, no global atomics: the T = 2^19 xyz table), every other level of both grids
     goes through the per-workgroup line merge in ONE launch (rn_grid_scatter_jobs) -- with RN_SCATTER=binned; by default every
-    level of both grids takes the line merge (one launch; see binning_active)."""
+    level of both grids takes the line merge (one launch; see binning_active).  RN_TRAIN_DETERMINISTIC=1 comes first: every level
+    of both grids through the ordered sum (see deterministic).  The table must be zero on entry on every route: the atomic routes
+    add to it (the binned levels are written), the ordered sum STORES each touched row's whole sum and leaves the other rows as
+    they are -- none of them accumulates onto earlier contents in a way a caller may rely on."""
     s = hip.stream()
     grad0, _, enc0, gd0, table0 = jobs[0]
     arr = (ScatterJobT * len(jobs))()
@@ -253,6 +265,10 @@ def grid_scatter(jobs, M, m_dev):
         arr[i].offsets_host = C.cast(off, C.c_void_p)
         keep += [gd, off]
     ws, ws_bytes = None, 0
+    if deterministic():
+        ws = _ordered_workspace(arr, len(jobs), M, enc0, table0.device)
+        hip.call("rn_grid_scatter_ordered", arr, len(jobs), M, hip.ptr(m_dev), hip.ptr(ws), ws.numel(), s)
+        return
     if binning_active():
         off_host = hip.host_offsets(enc0.offsets)
         if int(_lib.rn_grid_scatter_workspace(M, C.byref(gd0), off_host)) > 256:
@@ -263,6 +279,36 @@ def grid_scatter(jobs, M, m_dev):
             ws_bytes = ws.numel()
             arr[0].offsets_host = C.cast(off_host, C.c_void_p)
     hip.call("rn_grid_scatter_jobs", arr, len(jobs), M, hip.ptr(m_dev), hip.ptr(ws), ws_bytes, s)
+
+
+def _ordered_workspace(arr, n_jobs, M, enc0, device):
+    """The ordered scatter's keys, sorted pairs and sort storage: per device and first grid, sized for the capacity rounded up to
+    65 536 rows (a step's changing sample budget does not re-allocate), no initialisation needed.  Created on the first request;
+    a captured step replays its address, so prepare_scatter() makes it before the capture.  When a larger capacity replaces it,
+    the old buffer is kept (persistent_buffer's keep_replaced): GraphedTrainer replays graphs it captured at earlier capacities,
+    and launches on the side stream may still be using it -- one buffer per 65 536-row step up stays behind."""
+    need = max(int(_lib.rn_grid_scatter_ordered_workspace(arr, n_jobs, m)) for m in (M, -(-M // 65536) * 65536))
+    if need == 0:
+        raise RuntimeError(f"rn_grid_scatter_ordered_workspace: {M} rows are out of range ({hip.last_error()})")
+    return hip.persistent_buffer(("grid_scatter_ordered", enc0.offsets.data_ptr()), need, device, keep_replaced=True)
+
+
+def prepare_scatter(encoders, M, device):
+    """What the table scatter of a step at row capacity M keeps between calls, created now -- before a capture begins: with
+    RN_TRAIN_DETERMINISTIC=1 the ordered sum's workspace for `encoders` (the step's GridEncoders in job order), which only needs
+    the grids' shapes.  Nothing to do on the default route (the binned route's buffer is born in its first eager step)."""
+    if not deterministic() or M <= 0:
+        return
+    arr = (ScatterJobT * len(encoders))()
+    keep = []
+    for i, enc in enumerate(encoders):
+        gd = _grid_desc(enc, enc.embeddings.detach())
+        off = hip.host_offsets(enc.offsets)
+        # the sizes depend on the grid's shape and its host offsets only; the data pointers just have to pass the null check
+        arr[i].grad = arr[i].inputs = arr[i].grad_table = enc.embeddings.data_ptr()
+        arr[i].grid, arr[i].offsets_host = C.pointer(gd), C.cast(off, C.c_void_p)
+        keep += [gd, off]
+    _ordered_workspace(arr, len(encoders), int(M), encoders[0], device)
 
 
 def head_forward(model, xyzs, dirs, enc_a, ind_code, eye, m_dev=None, ind_index=None):

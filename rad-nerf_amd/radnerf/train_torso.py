@@ -26,7 +26,7 @@ from radnerf_hip.abi import TorsoGradsT
 from . import switches
 from .fused import _grid_desc, torso_constants, torso_weights, torso_weights_desc  # noqa: F401  (torso_weights: re-exported)
 from .route import training_call
-from .train_head import grid_scatter
+from .train_head import grid_scatter, prepare_scatter
 
 _lib = hip._lib
 
@@ -164,11 +164,13 @@ def _wgrad_workspace(dev):
 
 def prepare(model, n_px):
     """Everything persistent a captured torso step of `n_px` pixels touches, created before the capture: the pinned mean density,
-    the weight-gradient workspace, the host copy of the table's level offsets."""
+    the weight-gradient workspace, the host copy of the table's level offsets, and with RN_TRAIN_DETERMINISTIC=1 the ordered table
+    scatter's workspace (the layer runs at the capacity of all n_px rows)."""
     dev = model.density_grid_torso.device
     pin_mean(model)
     _wgrad_workspace(dev)
     hip.host_offsets(model.torso_encoder.offsets)
+    prepare_scatter((model.torso_encoder,), n_px, dev)
 
 
 def select(model, bg_coords, alloc=None):

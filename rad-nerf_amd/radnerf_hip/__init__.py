@@ -192,21 +192,26 @@ def aligned(t, nbytes=16):
 _WS = {}
 
 
-def persistent_buffer(key, nbytes, device, zero=False):
+def persistent_buffer(key, nbytes, device, zero=False, keep_replaced=False):
     """uint8 buffer of at least `nbytes` that belongs to `key` on `device`: created on the first request (zero-filled if asked)
     and kept at its address from then on -- only a larger request replaces it.  A captured step replays that address, so the
-    buffer must exist, at its final size, before the capture."""
+    buffer must exist, at its final size, before the capture.  keep_replaced: a buffer that a larger one replaces is never
+    freed -- for a buffer whose address graphs captured EARLIER keep replaying after it has grown (GraphedTrainer caches its
+    graphs per capacity): they go on using the old one, which only has to exist, not to hold anything between launches."""
     key = (device.index if device.index is not None else torch.cuda.current_device(), key)
     buf = _PERSISTENT.get(key)
     if buf is None or buf.numel() < nbytes:
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"radnerf_hip: the buffer {key[1]!r} ({nbytes} bytes) must exist before a step is captured "
                                "(take one eager step, or call the route's prepare(), first)")
+        if buf is not None and keep_replaced:
+            _REPLACED.append(buf)
         buf = _PERSISTENT[key] = (torch.zeros if zero else torch.empty)(int(nbytes), dtype=torch.uint8, device=device)
     return buf
 
 
 _PERSISTENT = {}
+_REPLACED = []      # superseded keep_replaced buffers: alive for as long as the process, a captured graph may hold their address
 
 
 def workspace(nbytes, device):

@@ -183,6 +183,9 @@ FUNCTIONS = {
     "rn_audio_encode_windows_train": (_int, [_P(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _ptr, _ptr]),
     "rn_audio_encode_windows_backward_acts": (_int, [_P(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _P(AudioGradsT), _ptr, _ptr,
                                                      _ptr]),
+    "rn_audio_backward_partials_floats": (_sz, [_u32, _int]),
+    "rn_audio_encode_windows_backward_ordered": (_int, [_P(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _P(AudioGradsT), _ptr, _ptr,
+                                                        _ptr, _ptr]),
     "rn_audio_encode_stream": (_int, [_P(AudioWeightsT), _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr]),
     "rn_audio_smooth": (_int, [_ptr, _u32, _u32, _f32, _ptr, _int, _ptr]),
     "rn_audio_smooth_seq": (_int, [_ptr, _u32, _u32, _f32, _ptr, _int, _ptr, _ptr]),
@@ -222,6 +225,8 @@ FUNCTIONS = {
     "rn_grid_scatter_binned_levels": (_u32, [_P(GridT), _ptr]),
     "rn_grid_scatter_jobs": (_int, [_P(ScatterJobT), _u32, _u32, _ptr, _ptr, _sz, _ptr]),
     "rn_grid_scatter_binned": (_int, [_ptr, _ptr, _u32, _ptr, _P(GridT), _ptr, _ptr, _ptr, _sz, _ptr]),
+    "rn_grid_scatter_ordered_workspace": (_sz, [_P(ScatterJobT), _u32, _u32]),
+    "rn_grid_scatter_ordered": (_int, [_P(ScatterJobT), _u32, _u32, _ptr, _ptr, _sz, _ptr]),
     "rn_train_head_loss": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _ptr, _ptr, _ptr,
                                   _ptr, _ptr]),
     "rn_train_batch_gather": (_int, [_ptr, _u32, _ptr, _u32, C.POINTER(_u32), _u32, _ptr, _ptr]),
