@@ -5,11 +5,11 @@ orc_grid_encode_backward adds every row's contributions level by level, samples 
 (hundreds of contributions per coarse row, gradients over 24 binades): a precondition, asserted on the CPU, shows that the oracle
 itself gives other bits when it sees the same samples in reversed order.  Rows past the live count are NaN: reading one would show.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
+
+from scatter_ref import _bits, _contributions, _inputs, _jobs, _oracle, accumulate  # noqa: F401  (shared with test_gpu_scatter_atomic.py)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,32 +27,6 @@ def _encoder(name):
     return GridEncoder(num_levels=16, level_dim=2, base_resolution=16, desired_resolution=2048, **GRIDS[name]).cuda()
 
 
-def _inputs(D, cap, live, seed=7):
-    """(inputs [cap, D], grad [16, cap, 2]) as numpy fp32: the recipe of the module docstring."""
-    r = np.random.default_rng(seed)
-    x = r.random((cap, D), dtype=np.float32)
-    n_cell = min(300, live)
-    x[:n_cell] = (r.random((1, D), dtype=np.float32) * 0.9 + 0.01 * r.random((n_cell, D), dtype=np.float32)).astype(np.float32)
-    if live > 402:
-        x[400, 0] = 1.5
-        x[401, D - 1] = -0.1
-    k = r.integers(-20, 4, size=(16, cap, 1))
-    g = (r.standard_normal((16, cap, 2)) * np.exp2(k)).astype(np.float32)
-    x[live:] = np.nan
-    g[:, live:] = np.nan
-    return x, g
-
-
-def _oracle(po, enc, x, g, live):
-    """The oracle's table gradient of the first `live` samples, [rows, 2] fp32."""
-    off = enc.offsets.cpu().numpy().astype(np.int32)
-    D = enc.input_dim
-    emb = np.zeros((int(off[-1]), 2), np.float32)
-    out, _ = po.grid_encode_backward(np.ascontiguousarray(g[:, :live]), np.ascontiguousarray(x[:live]), emb, off, live, D, 2, 16,
-                                     float(np.float32(np.log2(enc.per_level_scale))), 16, None, enc.gridtype_id, False, 0)
-    return out
-
-
 def _case(po, name):
     """One grid's inputs, oracle result and device tensors, computed once and shared (nobody writes to them)."""
     if name not in _CACHE:
@@ -61,20 +35,6 @@ def _case(po, name):
         _CACHE[name] = dict(enc=enc, x=x, g=g, want=_oracle(po, enc, x, g, LIVE), xd=torch.from_numpy(x).cuda(), gd=torch.from_numpy(g).cuda(),
                             cnt=torch.tensor([LIVE], dtype=torch.int32, device="cuda"))
     return _CACHE[name]
-
-
-def _jobs(entries):
-    """ScatterJobT array for [(grad, inputs, enc, grad_table), ...] + what must stay alive."""
-    import radnerf_hip as hip
-    from radnerf.fused import _grid_desc
-    from radnerf_hip.abi import ScatterJobT
-    arr, keep = (ScatterJobT * len(entries))(), []
-    for i, (grad, inputs, enc, table) in enumerate(entries):
-        gd, off = _grid_desc(enc, table), hip.host_offsets(enc.offsets)
-        arr[i].grad, arr[i].inputs, arr[i].grid, arr[i].grad_table = grad.data_ptr(), inputs.data_ptr(), C.pointer(gd), table.data_ptr()
-        arr[i].offsets_host = C.cast(off, C.c_void_p)
-        keep += [gd, off]
-    return arr, keep
 
 
 def _ordered(entries, M, cnt, short=0):
@@ -87,10 +47,6 @@ def _ordered(entries, M, cnt, short=0):
     rc = hip._lib.rn_grid_scatter_ordered(arr, len(entries), M, None if cnt is None else cnt.data_ptr(), ws.data_ptr(), need - short, hip.stream())
     torch.cuda.synchronize()
     return rc
-
-
-def _bits(t):
-    return (t.detach().cpu().numpy() if torch.is_tensor(t) else t).view(np.uint32)
 
 
 def _run(case, M=CAP, cnt="case"):
@@ -168,41 +124,6 @@ def test_two_calls_and_a_side_stream_give_the_same_bits(po, hiplib):
     assert np.array_equal(first, _bits(case["want"]))
 
 
-def _contributions(enc, x, g, live):
-    """(global row, w * g [.., 2]) of every (level, sample, corner) the oracle adds, restated in numpy fp32 (orc_grid.c:212-256)."""
-    off = enc.offsets.cpu().numpy().astype(np.int64)
-    D, S = enc.input_dim, np.float32(np.log2(enc.per_level_scale))
-    primes = np.array([1, 2654435761, 805459861], dtype=np.uint32)
-    exp2f = C.CDLL("libm.so.6").exp2f
-    exp2f.restype, exp2f.argtypes = C.c_float, [C.c_float]
-    xs, rows, vals = x[:live], [], []
-    inside = ~((xs < 0) | (xs > 1)).any(axis=1)
-    for level in range(16):
-        size = np.uint32(off[level + 1] - off[level])
-        scale = np.float32(np.float32(exp2f(np.float32(level) * S)) * np.float32(16) - np.float32(1))     # libm's exp2f, as the oracle's
-        res = np.uint32(np.ceil(scale)) + np.uint32(1)
-        pos = (xs[inside] * scale + np.float32(0.5)).astype(np.float32)
-        pg = np.floor(pos).astype(np.uint32)
-        pos = (pos - pg.astype(np.float32)).astype(np.float32)
-        for corner in range(1 << D):
-            w = np.ones(pos.shape[0], np.float32)
-            stride, index, dense = np.uint64(1), np.zeros(pos.shape[0], np.uint32), True
-            h = np.zeros(pos.shape[0], np.uint32)
-            for d in range(D):
-                bit = (corner >> d) & 1
-                w = (w * (pos[:, d] if bit else (np.float32(1) - pos[:, d]))).astype(np.float32)
-                p = pg[:, d] + np.uint32(bit)
-                h ^= p * primes[d]
-                if stride <= size:
-                    index = index + p * np.uint32(stride)
-                    stride = np.uint64(np.uint32(stride * np.uint64(res + 1)))       # uint32 arithmetic, as the oracle's
-            if enc.gridtype_id == 0 and stride > size:
-                index = h
-            rows.append(off[level] + (index % size).astype(np.int64))
-            vals.append((w[:, None] * g[level, :live][inside]).astype(np.float32))
-    return np.concatenate(rows), np.concatenate(vals)
-
-
 @pytest.mark.parametrize("name", ["hash3", "tiled2"])
 def test_within_the_two_sum_bound_of_the_atomic_scatter(po, hiplib, name):
     """|ordered - rn_grid_scatter_jobs| <= 2 (n - 1) 2^-24 sum |v_i| per element: two fp32 sums of the same n terms each lie within
@@ -210,12 +131,7 @@ def test_within_the_two_sum_bound_of_the_atomic_scatter(po, hiplib, name):
     import radnerf_hip as hip
     case = _case(po, name)
     rows, vals = _contributions(case["enc"], case["x"], case["g"], LIVE)
-    shape = case["want"].shape
-    n, mag, exact = np.zeros(shape[0]), np.zeros(shape, np.float64), np.zeros(shape, np.float64)
-    with np.errstate(over="ignore"):
-        np.add.at(n, rows, 1.0)
-        np.add.at(mag, rows, np.abs(vals.astype(np.float64)))
-        np.add.at(exact, rows, vals.astype(np.float64))
+    n, mag, exact = accumulate(rows, vals, case["want"].shape[0])
     bound = 2.0 * np.maximum(n - 1.0, 0.0)[:, None] * 2.0 ** -24 * mag
     # the restatement is the oracle's: same rows touched, and the oracle's fp32 sum within half that bound of the float64 one
     assert not (case["want"][n == 0] != 0).any()

@@ -190,7 +190,8 @@ def test_individual_code_row_picked_on_the_device(hiplib):
 @pytest.mark.parametrize("points", ["rays", "coincident"])
 @pytest.mark.parametrize("D", [2, 3])
 def test_line_keyed_scatter_matches_the_operator_scatter(hiplib, monkeypatch, D, points):
-    """rn_grid_scatter_lbc == rn_grid_encode_backward's table gradient (kernel_grid_backward, gridencoder.cu:247-339)."""
+    """rn_grid_scatter_lbc == rn_grid_encode_backward's table gradient (kernel_grid_backward, gridencoder.cu:247-339), in the table's
+    max norm; the bounds per row, against a float64 sum, are in tests/test_gpu_scatter_atomic.py."""
     import ctypes as C
     import radnerf_hip as hip
     from gridencoder import GridEncoder
