@@ -4,6 +4,7 @@ CPU oracle on the same seeded inputs.
 Bars: integer / index / byte outputs bit-exact; float outputs bit-exact where the op order is the same
 on both sides (-ffp-contract=off: DDA, grid interpolation in fp32 and fp16), otherwise a stated tolerance
 (fast exp in compositing, sinf in the frequency encoder, atomics order in the grid backward).
+The marchers here only see the +y camera of make_rays; everything off it (diagonals, cascades, variable dt) is tests/test_gpu_walk.py.
 """
 import numpy as np
 import pytest
