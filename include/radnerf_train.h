@@ -101,6 +101,40 @@ int rn_train_head_weight_grads_row(const rn_nerf_weights_t *w, const float *enc_
                                    const int64_t *ind_index, uint32_t ind_rows, uint32_t M, const int32_t *m_dev, const float *workspace,
                                    const rn_train_head_grads_t *g, void *wgrad_workspace, rn_stream_t stream);
 
+/* ---- 16-bit matrix products (opt-in; csrc/rn_train_head_f16.hip) ----------------------------------------------------------
+ * The arithmetic of the reference's `-O` runs for its eight nn.Linear layers (nerf/utils.py:1168-1172): 16-bit operands, fp32
+ * sums.  Same arguments, same outputs, same workspace (rn_train_head_workspace_floats) as the fp32 namesakes; only the image
+ * is longer.  rn_train_head_input_grads, rn_train_head_weight_grads(_row) and the table scatters are called as they are:
+ * they read the fp32 part of the image and the fp32 workspace.
+ *   rounded to half (nearest even), once, by the pack kernel: the weights of every 64-row contraction -- W_amb0[:, 0:32],
+ *     W_amb1, W_sig0[:, 0:64], W_sig1, W_sig2[1:65], W_col0[:, 0:80] -- and their transposes;
+ *   rounded to half where it enters a contraction: a layer's input (grid features, SH basis, the previous layer's fp32
+ *     accumulators after the activation) in the forward, and dY in the backward after the per-tile scaling below;
+ *   products are exact, sums are fp32 (v_mfma_f32_32x32x8f16);
+ *   per-tile scaling: for each 32-sample tile and each product dX = W^T dY, dY is multiplied by the power of two that
+ *     brings its largest magnitude in the tile into [2^14, 2^15) before it is rounded, and the fp32 sums by the inverse
+ *     power; a tile whose dY is all zero skips the products (its dX is zero).  No state, nothing to tune: a gradient 2^-20
+ *     times smaller gives 2^-20 times the same bits;
+ *   fp32 throughout: grid gathers and interpolation, d enc_w / d ambient, SH, tanh / trunc_exp / sigmoid and their
+ *     derivatives, the narrow layers (W_amb2, W_sig2[0], W_col1), the first-layer biases of the per-call constants, every
+ *     saved tile and pre-activation gradient of the workspace (so dW = dZ X^T sees unrounded X and dZ), the level-major
+ *     feature gradients.
+ * No float atomics: two calls on the same inputs give the same bits. */
+/* Floats of the image rn_train_head_pack_h16 writes: the fp32 image of rn_train_head_pack | 16-bit forward image | 16-bit
+ * transposed image. */
+size_t rn_train_head_image_floats_h16(void);
+int rn_train_head_pack_h16(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_code, float *image,
+                           rn_stream_t stream);
+int rn_train_head_pack_row_h16(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_table,
+                               const int64_t *ind_index, float *image, rn_stream_t stream);
+int rn_train_head_forward_h16(const float *xyzs, const float *dirs, uint32_t M, const int32_t *m_dev, const rn_grid_t *grid_xyz,
+                              const rn_grid_t *grid_amb, const float *image, float bound, float *sigmas, float *rgbs,
+                              float *ambient, float *ambient_abs, float *xn, float *wn, float *workspace, rn_stream_t stream);
+int rn_train_head_backward_h16(const float *grad_sigmas, const float *grad_rgbs, const float *grad_ambient,
+                               const float *grad_ambient_abs, const float *rgbs, const float *ambient, uint32_t M,
+                               const int32_t *m_dev, const float *image, float *workspace, float *grad_enc_x, float *grad_enc_w,
+                               rn_stream_t stream);
+
 /* Table gradient of one grid from level-major feature gradients: grad_table[row(l, corner)] += w_corner * grad[l, b, :]
  * (kernel_grid_backward, gridencoder.cu:247-339) for b < live count; inputs [M, D] normalised coordinates (rows outside
  * [0, 1] contribute nothing, gridencoder.cu:275-280).  grad_table [rows, 2] fp32 must be zeroed by the caller.  D = 2 / 3,

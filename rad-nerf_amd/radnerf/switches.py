@@ -21,6 +21,7 @@ TABLE = (
     ("RN_TRAIN_HEAD_ZERO", "0", ("0", "1"), "`1`: the fused head zero-fills its output rows past the live count (for tools that look at all rows)"),
     ("RN_TRAIN_LOSS", "fused", ("fused", "torch"), "head loss of `train_step`: blend, clamp and loss in one kernel, or the PyTorch expression"),
     ("RN_TRAIN_MARCH", "step", ("step", "ops"), "marcher of a budgeted step: one launch with near / far and the counters, or `near_far_from_aabb` + `rn_march_rays_train_budget`"),
+    ("RN_TRAIN_MLP", "f32", ("f32", "f16"), "matrix products of the fused head (`RN_TRAIN_HEAD=fused`): fp32 matrix cores, or 16-bit operands with fp32 sums (`rn_train_head_*_h16`, opt-in: the arithmetic of the reference's `-O` runs for its `nn.Linear` layers; saved tiles, tables and gradients stay fp32)"),
     ("RN_TRAIN_NOISE", "hash", ("hash", "torch"), "jitter of the one-launch marcher: the launch's own hash, or `torch.rand` as the reference draws it (the test suite pins this)"),
     ("RN_TRAIN_OVERLAP", "1", ("1", "0"), "table-gradient scatter and audio nets on side streams beside the step (`0`: everything on one stream)"),
     ("RN_TRAIN_PACKED", "1", ("1", "0"), "`SyntheticTrainStream.batch`: one gather kernel into one flat buffer (`0`: separate tensors, as a generic loader hands over)"),

@@ -56,11 +56,14 @@ class _HeadTrain(torch.autograd.Function):
         nw = weights_desc(ws, audio_dim, has_eye, ind_dim)
         gx, gw = _grid_desc(enc_x, tx), _grid_desc(enc_w, tw)
         s = hip.stream()
-        image = torch.empty(int(_lib.rn_train_head_image_floats()), dtype=torch.float32, device=dev)
+        # RN_TRAIN_MLP=f16: the pack / forward / backward entries with 16-bit matrix products; the image grows by the 16-bit
+        # weight images, everything else (workspace, weight gradients, input gradients, scatters) is the fp32 route's
+        sfx = ctx.sfx = "_h16" if switches.get("RN_TRAIN_MLP") == "f16" else ""
+        image = torch.empty(int(getattr(_lib, "rn_train_head_image_floats" + sfx)()), dtype=torch.float32, device=dev)
         if ind_index is not None:
-            hip.call("rn_train_head_pack_row", C.byref(nw), hip.ptr(enc_a_c), hip.ptr(eye_c), hip.ptr(ind_c), hip.ptr(ind_index), hip.ptr(image), s)
+            hip.call("rn_train_head_pack_row" + sfx, C.byref(nw), hip.ptr(enc_a_c), hip.ptr(eye_c), hip.ptr(ind_c), hip.ptr(ind_index), hip.ptr(image), s)
         else:
-            hip.call("rn_train_head_pack", C.byref(nw), hip.ptr(enc_a_c), hip.ptr(eye_c), hip.ptr(ind_c), hip.ptr(image), s)
+            hip.call("rn_train_head_pack" + sfx, C.byref(nw), hip.ptr(enc_a_c), hip.ptr(eye_c), hip.ptr(ind_c), hip.ptr(image), s)
         work = torch.empty(int(_lib.rn_train_head_workspace_floats(M)), dtype=torch.float32, device=dev)
         # one block for the outputs.  Rows past the live count are not written: they belong to no ray, so the compositor never
         # reads them and the backward kernel skips them (RN_TRAIN_HEAD_ZERO=1 zero-fills the block, for tools that look at all rows)
@@ -71,7 +74,7 @@ class _HeadTrain(torch.autograd.Function):
         rgbs, ambient = flat[2 * M:5 * M].view(M, 3), flat[5 * M:7 * M].view(M, 2)
         xn, wn = flat[7 * M:10 * M].view(M, 3), flat[10 * M:12 * M].view(M, 2)
         if M:
-            hip.call("rn_train_head_forward", hip.ptr(xyzs), hip.ptr(dirs), M, hip.ptr(m_dev), C.byref(gx), C.byref(gw), hip.ptr(image),
+            hip.call("rn_train_head_forward" + sfx, hip.ptr(xyzs), hip.ptr(dirs), M, hip.ptr(m_dev), C.byref(gx), C.byref(gw), hip.ptr(image),
                      float(bound), sigmas.data_ptr(), rgbs.data_ptr(), ambient.data_ptr(), amb_abs.data_ptr(), xn.data_ptr(), wn.data_ptr(),
                      hip.ptr(work), s)
         ctx.set_materialize_grads(False)      # an output nobody differentiates (ambient) costs no [M, 2] memset
@@ -116,7 +119,7 @@ class _HeadTrain(torch.autograd.Function):
             g_ind = torch.empty(ind_dim, dtype=torch.float32, device=dev) if ind_dim else None
         if M:
             g_feat = torch.empty(2, 16, M, 2, dtype=torch.float32, device=dev)
-            hip.call("rn_train_head_backward", hip.ptr(g_sigma), hip.ptr(g_rgb), hip.ptr(g_ambient), hip.ptr(g_amb_abs), rgbs.data_ptr(),
+            hip.call("rn_train_head_backward" + ctx.sfx, hip.ptr(g_sigma), hip.ptr(g_rgb), hip.ptr(g_ambient), hip.ptr(g_amb_abs), rgbs.data_ptr(),
                      ambient.data_ptr(), M, hip.ptr(m_dev), hip.ptr(image), hip.ptr(work), g_feat[0].data_ptr(), g_feat[1].data_ptr(), s)
             # The table gradients need only the feature gradients the kernel above has written; the weight gradients, the
             # constants' gradients and whatever autograd runs after this function (the audio nets' backward) need nothing of the

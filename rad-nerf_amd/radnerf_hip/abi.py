@@ -220,6 +220,12 @@ FUNCTIONS = {
     "rn_train_head_weight_grads": (_int, [_P(NerfWeightsT), _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _P(HeadGradsT), _ptr, _ptr]),
     "rn_train_head_weight_grads_row": (_int, [_P(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _P(HeadGradsT),
                                               _ptr, _ptr]),
+    "rn_train_head_image_floats_h16": (_sz, []),
+    "rn_train_head_pack_h16": (_int, [_P(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_head_pack_row_h16": (_int, [_P(NerfWeightsT), _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_head_forward_h16": (_int, [_ptr, _ptr, _u32, _ptr, _P(GridT), _P(GridT), _ptr, _f32, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                         _ptr, _ptr, _ptr]),
+    "rn_train_head_backward_h16": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "rn_grid_scatter_lbc": (_int, [_ptr, _ptr, _u32, _ptr, _P(GridT), _ptr, _ptr]),
     "rn_grid_scatter_workspace": (_sz, [_u32, _P(GridT), _ptr]),
     "rn_grid_scatter_binned_levels": (_u32, [_P(GridT), _ptr]),

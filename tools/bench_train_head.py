@@ -1,7 +1,7 @@
 """Isolated timing of the fused training pass of the per-sample network (include/radnerf_train.h) at a training step's size:
 HIP events around each C-ABI call (pack, forward, backward, weight gradients, table scatter).
 
-    python tools/bench_train_head.py [--M 62000] [--grid hash19] [--rounds 20]
+    python tools/bench_train_head.py [--M 62000] [--grid hash19] [--rounds 20] [--mlp f32,f16]
 """
 import argparse
 import json
@@ -20,6 +20,7 @@ def main():
     ap.add_argument("--M", type=int, default=62000)
     ap.add_argument("--grid", default="hash19")
     ap.add_argument("--rounds", type=int, default=20)
+    ap.add_argument("--mlp", default="f32", help="RN_TRAIN_MLP of the timed steps; a comma-separated list rotates (f32,f16)")
     args = ap.parse_args()
     os.environ["RN_TRAIN_OVERLAP"] = "0"           # every call on one stream: durations are the kernels' own
     import radnerf_hip as hip
@@ -47,16 +48,29 @@ def main():
             p.grad = None
         s, c, a, aa = train_head.head_forward(m, xyzs, dirs, enc_a, ind, eye)
         ((s * up[0]).sum() + (c * up[1]).sum() + (aa * up[2]).sum()).backward()
+    # --mlp f32,f16: both arithmetics of the network kernels in ONE rotation (f32 step, f16 step, f32 step, ...), so that clocks
+    # and cache state drift under both alike; the *_h16 entries are timed under their own names
+    mlps = args.mlp.split(",")
     for _ in range(3):
-        step()
+        for mlp in mlps:
+            os.environ["RN_TRAIN_MLP"] = mlp
+            step()
     hip.set_timer(timer)
     for _ in range(args.rounds):
-        step()
+        for mlp in mlps:
+            os.environ["RN_TRAIN_MLP"] = mlp
+            step()
     hip.set_timer(None)
     res = timer.results()
     out = {k: round(v["avg_ms"] * 1e3, 1) for k, v in sorted(res.items())}
-    out["sum_us"] = round(sum(out.values()), 1)
-    out.update(M=M, grid=args.grid, fwd_groups=os.environ.get("RN_TRAIN_FWD_GROUPS", "11"), wparts=os.environ.get("RN_TRAIN_WPARTS", "96"),
+    if len(mlps) == 1:
+        out["sum_us"] = round(sum(out.values()), 1)
+    # median and spread (min .. max) of the two network kernels per arithmetic, in microseconds
+    for key, evs in sorted(timer.events.items()):
+        if key.split("_h16")[0].endswith(("head_forward", "head_backward")):
+            us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
+            out[key + "_median_min_max_us"] = [round(us[len(us) // 2], 1), round(us[0], 1), round(us[-1], 1)]
+    out.update(M=M, grid=args.grid, mlp=args.mlp, fwd_groups=os.environ.get("RN_TRAIN_FWD_GROUPS", "11"), wparts=os.environ.get("RN_TRAIN_WPARTS", "96"),
                scatter=os.environ.get("RN_SCATTER", "lbc"))
     print(json.dumps(out))
 
