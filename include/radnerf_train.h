@@ -196,6 +196,13 @@ int rn_train_head_loss(const float *image, const float *weights_sum, const float
                        const float *target, uint32_t target_stride, const float *face, uint32_t face_stride, const float *w_amb,
                        uint32_t N, float *loss, float *pred, float *grad_image, float *grad_weights_sum, float *grad_ambient,
                        rn_stream_t stream);
+/* A further term on pred that the caller computed (the patch / lips term of nerf/utils.py:757-781) joins that loss: g_pred [N,3] =
+ * d term / d pred goes back through the clamp and the blend, in one launch with one thread per ray.  Per channel c = 0, 1, 2:
+ * raw = image + (1 - ws) * bg as above, pass = raw in [0, 1], grad_image += pass ? g_pred : 0, grad_weights_sum -= (pass ? g_pred
+ * : 0) * bg; and loss[0] += term[0].  grad_image / grad_weights_sum / loss: what rn_train_head_loss wrote, updated in place. */
+int rn_train_head_loss_chain(const float *image, const float *weights_sum, const float *bg, uint32_t bg_stride, const float *g_pred,
+                             uint32_t N, const float *term, float *loss, float *grad_image, float *grad_weights_sum,
+                             rn_stream_t stream);
 
 /* A training batch from a per-pixel table: out = [n, widths[0]] | [n, widths[1]] | ... (each section contiguous), section s
  * holding columns (widths[0] + .. + widths[s-1]) .. of the rows table[idx[i], :] (idx: int64 device array, row_floats = sum of
@@ -352,6 +359,22 @@ int rn_train_set_batch(const rn_train_set_t *set, uint32_t frame, uint32_t aud_f
  * packed: rays_o | rays_d | bg_coords | bg_color | images over H*W pixels, 14 H W floats.  Same kernel, same per-call outputs. */
 int rn_train_set_frame(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, float *packed, float *poses6,
                        float *pose_matrix, float *eye, float *auds_out, rn_stream_t stream);
+/* The two samplings of lip fine-tuning (nerf/utils.py:277-303) as further instantiations of the same kernel: only "which pixel
+ * is ray k" differs, every output is written as rn_train_set_batch writes it.
+ * _rect: the n = (xmax - xmin) * (ymax - ymin) pixels of a rect in ascending order (torch.where of its mask, :297-303): ray k is
+ * pixel (xmin + k / w) * W + (ymin + k % w), w = ymax - ymin, x along the ROWS.  0 <= xmin < xmax <= H and 0 <= ymin < ymax <= W
+ * are required (the reference's slice would clamp silently).
+ * _patch: n = P * patch^2 rays; ray k is offset o = k % patch^2 of patch q = k / patch^2, pixel (x0 + o / patch) * W + (y0 + o %
+ * patch) (:281-292, an 'ij' meshgrid).  corners: int32 [P,2] = (x0, y0) on the device; a corner outside [0, H - patch) x [0, W -
+ * patch) is clamped into it and counted once in *bad.  corners == NULL: drawn from (seed, draw) as rn_train_set_batch draws
+ * pixels, x0 from element 2q onto [0, H - patch), y0 from element 2q + 1 onto [0, W - patch) -- randint's exclusive upper end
+ * (:282-283), so the last row and column of start positions are never drawn.  2 <= patch < min(H, W), P >= 1, n < 2^31. */
+int rn_train_set_batch_rect(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, int32_t xmin, int32_t xmax, int32_t ymin,
+                            int32_t ymax, float *packed, int64_t *inds_out, float *poses6, float *pose_matrix, float *eye,
+                            float *auds_out, rn_stream_t stream);
+int rn_train_set_batch_patch(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, const int32_t *corners, uint32_t P,
+                             uint32_t patch, uint32_t seed, uint32_t draw, float *packed, int64_t *inds_out, float *poses6,
+                             float *pose_matrix, float *eye, float *auds_out, uint32_t *bad, rn_stream_t stream);
 
 #ifdef __cplusplus
 }

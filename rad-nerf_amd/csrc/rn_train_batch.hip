@@ -6,7 +6,9 @@
 // prologue, rn_get_rays, rn_get_bg_coords and rn_convert_poses run, so the batch and a rendered frame agree bit for bit.
 //
 // Layout: one thread per picked pixel; its 3- and 2-float rows go out as one 12- / 8-byte store per lane, lane k at row k of the
-// section, so a wave writes one contiguous span per section.  The reads are a coalesced int64 index, uniform (scalar) loads of the
+// section, so a wave writes one contiguous span per section.  Which pixel a ray is comes from an index list, the kernel's own draw,
+// a rect or a set of square patches (rn_train_set_batch / _rect / _patch: lip fine-tuning samples the last two,
+// nerf/utils.py:277-303); everything after that is one body.  The reads are a coalesced int64 index, uniform (scalar) loads of the
 // pose / rect, and three byte gathers of 3, 4 and 3 bytes per pixel, which the data layout makes inherent.  One extra workgroup
 // writes the per-call outputs.  No LDS, no scratch, nothing that depends on the wave's width.
 #include "rn_ray_dev.h"
@@ -59,12 +61,43 @@ __device__ __forceinline__ void per_call(const rn_train_set_t &s, uint32_t frame
     }
 }
 
-// FRAME: the evaluation form -- pixel k is ray k, no face section, target = images in both modes (provider.py:681-702 with
-// training = False).
-template <bool FRAME>
+// Which pixel is ray k: the four instantiations of the kernel differ in nothing else.
+//   kBatch  inds[k], or the draw above (get_rays' randint, nerf/utils.py:306)
+//   kFrame  the evaluation form -- pixel k is ray k, no face section, target = images in both modes (provider.py:681-702 with
+//           training = False)
+//   kRect   every pixel of a rect in ascending order (torch.where of the rect's mask, nerf/utils.py:297-303)
+//   kPatch  P square patches, each in meshgrid 'ij' order (nerf/utils.py:281-292)
+enum Mode { kBatch = 0, kFrame = 1, kRect = 2, kPatch = 3 };
+struct NoPick {};
+struct RectPick { uint32_t xmin, ymin, w; };                        // x along the ROWS; w = ymax - ymin
+struct PatchPick { const int32_t *corners; uint32_t patch, area; };  // corners [P,2] = (x0, y0) or null: drawn; area = patch^2
+template <int MODE> struct PickOf { typedef NoPick type; };
+template <> struct PickOf<kRect> { typedef RectPick type; };
+template <> struct PickOf<kPatch> { typedef PatchPick type; };
+
+// Top-left corner of patch q: explicit (clamped into the range the draw covers, counted in *bad by the patch's first ray), or
+// drawn like a pixel -- x0 from element 2q, y0 from element 2q + 1 of (seed, draw).  The ranges are randint's of
+// nerf/utils.py:282-283, [0, H - patch) and [0, W - patch): the last row and column of start positions are never drawn.
+__device__ __forceinline__ void patch_corner(const PatchPick &pk, const rn_train_set_t &s, uint32_t q, bool first, uint32_t seed,
+                                             uint32_t draw, uint32_t *bad, uint32_t &x0, uint32_t &y0) {
+    const uint32_t nx = s.H - pk.patch, ny = s.W - pk.patch;
+    if (pk.corners) {
+        const int32_t x = pk.corners[2 * (size_t)q], y = pk.corners[2 * (size_t)q + 1];
+        const bool out = x < 0 || x >= (int32_t)nx || y < 0 || y >= (int32_t)ny;
+        if (out && first) atomicAdd(bad, 1u);
+        x0 = x < 0 ? 0u : x >= (int32_t)nx ? nx - 1 : (uint32_t)x;
+        y0 = y < 0 ? 0u : y >= (int32_t)ny ? ny - 1 : (uint32_t)y;
+    } else {
+        x0 = drawn_pixel(seed, draw, 2 * q, nx);
+        y0 = drawn_pixel(seed, draw, 2 * q + 1, ny);
+    }
+}
+
+template <int MODE>
 __global__ void __launch_bounds__(256)
 k_train_set(rn_train_set_t s, uint32_t frame, uint32_t aud_frame, const int64_t *__restrict__ inds, uint32_t n, uint32_t seed,
-            uint32_t draw, Out o) {
+            uint32_t draw, Out o, typename PickOf<MODE>::type pick) {
+    constexpr bool FRAME = MODE == kFrame;
     if (blockIdx.x == gridDim.x - 1) {   // the workgroup past the rays
         per_call(s, frame, aud_frame, o);
         return;
@@ -75,6 +108,16 @@ k_train_set(rn_train_set_t s, uint32_t frame, uint32_t aud_frame, const int64_t 
     uint32_t p;
     if (FRAME) {
         p = k;
+    } else if constexpr (MODE == kRect) {
+        const uint32_t i = k / pick.w;
+        p = (pick.xmin + i) * s.W + pick.ymin + (k - i * pick.w);
+        if (o.inds_out) o.inds_out[k] = (int64_t)p;
+    } else if constexpr (MODE == kPatch) {
+        const uint32_t q = k / pick.area, off = k - q * pick.area, i = off / pick.patch;
+        uint32_t x0, y0;
+        patch_corner(pick, s, q, off == 0, seed, draw, o.bad, x0, y0);
+        p = (x0 + i) * s.W + y0 + (off - i * pick.patch);
+        if (o.inds_out) o.inds_out[k] = (int64_t)p;
     } else {
         if (inds) {
             int64_t v = inds[k];
@@ -150,9 +193,43 @@ extern "C" int rn_train_set_batch(const rn_train_set_t *set, uint32_t frame, uin
     RN_REQUIRE(((uintptr_t)packed & 7u) == 0, "train_set_batch: packed must be 8-byte aligned");
     RN_REQUIRE(n < (1u << 31), "train_set_batch: n must be below 2^31");
     const Out o{packed, inds_out, poses6, pose_matrix, eye, auds_out, bad};
-    hipLaunchKernelGGL(k_train_set<false>, dim3(div_up(n, 256) + 1), dim3(256), 0, as_stream(stream), *set, frame, aud_frame, inds, n,
-                       seed, draw, o);
+    hipLaunchKernelGGL(k_train_set<kBatch>, dim3(div_up(n, 256) + 1), dim3(256), 0, as_stream(stream), *set, frame, aud_frame, inds, n,
+                       seed, draw, o, NoPick{});
     return check_launch("train_set_batch");
+}
+
+extern "C" int rn_train_set_batch_rect(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, int32_t xmin, int32_t xmax,
+                                       int32_t ymin, int32_t ymax, float *packed, int64_t *inds_out, float *poses6,
+                                       float *pose_matrix, float *eye, float *auds_out, rn_stream_t stream) {
+    if (int rc = check_set(set, frame, aud_frame)) return rc;
+    RN_REQUIRE(0 <= xmin && xmin < xmax && xmax <= (int32_t)set->H && 0 <= ymin && ymin < ymax && ymax <= (int32_t)set->W,
+               "train_set_batch_rect: rect (%d, %d, %d, %d) is empty or outside the %u x %u image (0 <= xmin < xmax <= H and "
+               "0 <= ymin < ymax <= W are required)", xmin, xmax, ymin, ymax, set->H, set->W);
+    RN_REQUIRE(packed && poses6 && pose_matrix && auds_out, "train_set_batch_rect: null pointer");
+    RN_REQUIRE(((uintptr_t)packed & 7u) == 0, "train_set_batch_rect: packed must be 8-byte aligned");
+    const uint32_t w = (uint32_t)(ymax - ymin), n = (uint32_t)(xmax - xmin) * w;   // <= H * W < 2^31 (check_set)
+    const Out o{packed, inds_out, poses6, pose_matrix, eye, auds_out, nullptr};
+    hipLaunchKernelGGL(k_train_set<kRect>, dim3(div_up(n, 256) + 1), dim3(256), 0, as_stream(stream), *set, frame, aud_frame,
+                       (const int64_t *)nullptr, n, 0u, 0u, o, RectPick{(uint32_t)xmin, (uint32_t)ymin, w});
+    return check_launch("train_set_batch_rect");
+}
+
+extern "C" int rn_train_set_batch_patch(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, const int32_t *corners,
+                                        uint32_t P, uint32_t patch, uint32_t seed, uint32_t draw, float *packed, int64_t *inds_out,
+                                        float *poses6, float *pose_matrix, float *eye, float *auds_out, uint32_t *bad,
+                                        rn_stream_t stream) {
+    if (int rc = check_set(set, frame, aud_frame)) return rc;
+    RN_REQUIRE(patch >= 2 && patch < set->H && patch < set->W, "train_set_batch_patch: patch = %u; 2 <= patch < H and patch < W are required "
+               "(H = %u, W = %u)", patch, set->H, set->W);
+    RN_REQUIRE(P >= 1, "train_set_batch_patch: P >= 1 patches are required");
+    RN_REQUIRE((uint64_t)P * patch * patch < (1ull << 31), "train_set_batch_patch: P * patch^2 must be below 2^31");
+    RN_REQUIRE(packed && poses6 && pose_matrix && auds_out && bad, "train_set_batch_patch: null pointer");
+    RN_REQUIRE(((uintptr_t)packed & 7u) == 0, "train_set_batch_patch: packed must be 8-byte aligned");
+    const uint32_t area = patch * patch, n = P * area;
+    const Out o{packed, inds_out, poses6, pose_matrix, eye, auds_out, bad};
+    hipLaunchKernelGGL(k_train_set<kPatch>, dim3(div_up(n, 256) + 1), dim3(256), 0, as_stream(stream), *set, frame, aud_frame,
+                       (const int64_t *)nullptr, n, seed, draw, o, PatchPick{corners, patch, area});
+    return check_launch("train_set_batch_patch");
 }
 
 extern "C" int rn_train_set_frame(const rn_train_set_t *set, uint32_t frame, uint32_t aud_frame, float *packed, float *poses6,
@@ -162,7 +239,7 @@ extern "C" int rn_train_set_frame(const rn_train_set_t *set, uint32_t frame, uin
     RN_REQUIRE(((uintptr_t)packed & 7u) == 0, "train_set_frame: packed must be 8-byte aligned");
     const uint32_t n = set->H * set->W;
     const Out o{packed, nullptr, poses6, pose_matrix, eye, auds_out, nullptr};
-    hipLaunchKernelGGL(k_train_set<true>, dim3(div_up(n, 256) + 1), dim3(256), 0, as_stream(stream), *set, frame, aud_frame,
-                       (const int64_t *)nullptr, n, 0u, 0u, o);
+    hipLaunchKernelGGL(k_train_set<kFrame>, dim3(div_up(n, 256) + 1), dim3(256), 0, as_stream(stream), *set, frame, aud_frame,
+                       (const int64_t *)nullptr, n, 0u, 0u, o, NoPick{});
     return check_launch("train_set_frame");
 }

@@ -583,6 +583,30 @@ __global__ void __launch_bounds__(kLossThreads) k_train_head_loss(const float *_
     if (threadIdx.x == 0) loss[0] = (float)t;
 }
 
+// A term on `pred` that the caller computed (the patch / lips term of nerf/utils.py:757-781) joins the loss above: its gradient
+// g_pred = d term / d pred goes back through the clamp and the blend into the gradients k_train_head_loss wrote.  One thread per
+// ray; `raw` is recomputed by the expression above, so `pass` is the clamp decision the loss kernel took.
+__global__ void __launch_bounds__(256) k_train_head_loss_chain(const float *__restrict__ image, const float *__restrict__ ws,
+                                                               const float *__restrict__ bg, uint32_t bg_stride,
+                                                               const float *__restrict__ g_pred, uint32_t N, const float *__restrict__ term,
+                                                               float *__restrict__ loss, float *__restrict__ g_image,
+                                                               float *__restrict__ g_ws) {
+    const uint32_t n = blockIdx.x * 256 + threadIdx.x;
+    if (n == 0) loss[0] += term[0];
+    if (n >= N) return;
+    const float tr = 1.0f - ws[n];
+    float gws = g_ws[n];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float b = bg[(size_t)n * bg_stride + c];
+        const float raw = image[n * 3 + c] + tr * b;
+        const float gp = (raw >= 0.0f && raw <= 1.0f) ? g_pred[n * 3 + c] : 0.0f;
+        g_image[n * 3 + c] += gp;
+        gws -= gp * b;
+    }
+    g_ws[n] = gws;
+}
+
 // ---- batch gather ---------------------------------------------------------------------------------------------------------
 // A training batch = n rows picked from a per-pixel table [n_px, row_floats] whose columns are up to 8 sections (rays_o | rays_d |
 // bg_coords | bg_color | target | face ...): ONE kernel writes every section as its own contiguous [n, width] array (the
@@ -766,6 +790,16 @@ int rn_train_head_loss(const float *image, const float *weights_sum, const float
     hipLaunchKernelGGL(k_train_head_loss, dim3(1), dim3(kLossThreads), 0, as_stream(stream), image, weights_sum, ambient, bg, bg_stride, target,
                        target_stride, face, face_stride, w_amb, N, loss, pred, grad_image, grad_weights_sum, grad_ambient);
     return check_launch("train_head_loss");
+}
+
+int rn_train_head_loss_chain(const float *image, const float *weights_sum, const float *bg, uint32_t bg_stride, const float *g_pred,
+                             uint32_t N, const float *term, float *loss, float *grad_image, float *grad_weights_sum,
+                             rn_stream_t stream) {
+    RN_REQUIRE(N > 0 && N <= (1u << 30), "train_head_loss_chain: N must be in [1, 2^30]");
+    RN_REQUIRE(image && weights_sum && bg && g_pred && term && loss && grad_image && grad_weights_sum, "train_head_loss_chain: null pointer");
+    hipLaunchKernelGGL(k_train_head_loss_chain, dim3(div_up(N, 256)), dim3(256), 0, as_stream(stream), image, weights_sum, bg, bg_stride,
+                       g_pred, N, term, loss, grad_image, grad_weights_sum);
+    return check_launch("train_head_loss_chain");
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 """The training step's input stage for a data set that already lives in device memory: the loader's batch of one frame, built
-by ONE kernel launch over the N picked pixels (C ABI rn_train_set_batch / rn_train_set_frame, csrc/rn_train_batch.hip).
+by ONE kernel launch over the N picked pixels (C ABI rn_train_set_batch / _batch_rect / _batch_patch / rn_train_set_frame,
+csrc/rn_train_batch.hip).
 
 Reference: NeRFDataset.collate (nerf/provider.py:625-714) with mirror_index (:615-622), get_rays (nerf/utils.py:249-333),
 get_audio_features (:42-72), convert_poses (:231-237) and the dataloader's shuffle (provider.py:729).  With the data preloaded
@@ -8,8 +9,12 @@ step; here the decoded arrays stay uint8 (7 bytes per pixel and frame) and only 
 
 Values are the reference's float32 loader arithmetic (`--preload 0` / `1`: `astype(np.float32) / 255`, float32 blend).  Its
 `--preload 2` keeps fp16 copies of the images; that rounding is NOT reproduced.  Decoding files (cv2, json, the audio
-features' .npy) is not part of this module: a loader hands over arrays.  Sampling by `patch_size` or `rect`
-(nerf/utils.py:277-303) is not built either; a caller who wants such pixels passes `inds`.
+features' .npy) is not part of this module: a loader hands over arrays.
+
+The two samplings of lip fine-tuning (nerf/utils.py:277-303) are further instantiations of the same kernel: batch_rect() takes
+every pixel of a rect -- by default the frame's lips rect (provider.py:488-502, lips_rect_from_landmarks) -- and batch_patch()
+`num_rays // patch_size^2` square patches whose corners the kernel draws.  Their ray count follows the rect, so such a batch
+feeds the eager trainer only (radnerf/train.py: train_step's patch_criterion, lips_schedule).
 
 On CPU tensors, or with RN_TRAIN_SET=torch (or kernel="torch"), the same class runs a plain-torch path that restates collate on
 the N picked pixels: the oracle of the kernel's tests, itself pinned to the reference by tests/golden/reference_batch.npz.
@@ -47,16 +52,41 @@ def drawn_pixels(seed, draw, n, n_px, device):
     return (h * int(n_px)) >> 32
 
 
+def drawn_corners(seed, draw, P, H, W, patch, device):
+    """The kernel's own draw of P patch corners (csrc/rn_train_batch.hip patch_corner): int64 [P,2] = (x0, y0), x0 from element
+    2q of draw `draw` of stream `seed` onto [0, H - patch), y0 from element 2q + 1 onto [0, W - patch) -- randint's exclusive
+    upper end (nerf/utils.py:282-283)."""
+    e = torch.arange(2 * int(P), dtype=torch.int64, device=device)
+    h = _mix32(_mix32(_mix32(e) ^ (int(draw) & _MASK32)) ^ (int(seed) & _MASK32))
+    return torch.stack(((h[0::2] * (int(H) - int(patch))) >> 32, (h[1::2] * (int(W) - int(patch))) >> 32), dim=-1)
+
+
+def lips_rect_from_landmarks(lms, H, W):
+    """provider.py:488-502: the lips rect (xmin, xmax, ymin, ymax; x along the ROWS) of one frame's 68 face landmarks [68,2] =
+    (column, row) -- the bounding box of landmarks 48..59, padded to a square around its centre and clipped to the image.
+    [F,68,2] gives a list of F rects."""
+    lms = np.asarray(lms)
+    if lms.ndim == 3:
+        return [lips_rect_from_landmarks(one, H, W) for one in lms]
+    lips = lms[48:60]
+    xmin, xmax = int(lips[:, 1].min()), int(lips[:, 1].max())
+    ymin, ymax = int(lips[:, 0].min()), int(lips[:, 0].max())
+    cx, cy = (xmin + xmax) // 2, (ymin + ymax) // 2
+    half = max(xmax - xmin, ymax - ymin) // 2
+    return [max(0, cx - half), min(int(H), cx + half), max(0, cy - half), min(int(W), cy + half)]
+
+
 class DeviceTrainSet:
     """images [F,H,W,3], torso [F,H,W,4] (RGBA), bg [H,W,3]: uint8 (numpy or torch), kept uint8 on the device.  poses [F,4,4]
     cam2world, intrinsics (fx, fy, cx, cy), auds [Fa,C,16], face_rect [F,4] = (xmin, xmax, ymin, ymax) with x along the ROWS
-    (provider.py:657-658), eye_area [F] or [F,1] (needed with opt.exp_eye).  `opt` supplies att, torso and exp_eye."""
+    (provider.py:657-658), eye_area [F] or [F,1] (needed with opt.exp_eye).  `opt` supplies att, torso and exp_eye.  lips_rect
+    [F,4] (optional, same convention): what batch_rect() samples by default (provider.py:488-502)."""
 
     _WIDTHS = (3, 3, 2, 3, 3, 1)          # rays_o | rays_d | bg_coords | bg_color | target | face: SyntheticTrainStream's sections
     _FRAME_WIDTHS = (3, 3, 2, 3, 3)       # the evaluation form has no face section
 
     def __init__(self, images, torso, bg, poses, intrinsics, auds, face_rect, eye_area=None, opt=None, num_rays=4096, seed=0,
-                 device="cuda", kernel=None):
+                 device="cuda", kernel=None, lips_rect=None):
         dev = self.device = torch.device(device)
         if dev.type == "cuda" and dev.index is None:
             dev = self.device = torch.device("cuda", torch.cuda.current_device())
@@ -83,6 +113,14 @@ class DeviceTrainSet:
             raise ValueError("DeviceTrainSet: at least 8 audio frames are required (the window's padding below that is not restated)")
         self._rect_host = rect.tolist()
         self.face_rect = rect.to(dev).contiguous()
+        self._lips_host = None
+        if lips_rect is not None:
+            lips = torch.as_tensor(lips_rect).to(torch.int32).cpu()
+            if lips.shape != (F, 4):
+                raise ValueError("DeviceTrainSet: expected lips_rect [F,4]")
+            self._lips_host = lips.tolist()
+            for r in self._lips_host:
+                self._checked_rect(r)
         self.intrinsics = np.asarray(intrinsics, dtype=np.float32).reshape(4)
         self.opt = opt
         self.att, self.torso, self.exp_eye = int(opt.att), bool(opt.torso), bool(opt.exp_eye)
@@ -107,6 +145,7 @@ class DeviceTrainSet:
         self._auds = torch.zeros(rows, C, 16, device=dev)
         self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
         self._bufs, self._frame_buf, self._index, self._last = {}, None, [0], None
+        self._rect_buf = None             # batch_rect's outputs: ONE buffer at the largest lips rect, whatever the frame's size
         self._frame_ids = torch.arange(self.F, dtype=torch.int64, device=dev)     # `index` as a device tensor: a view of this, no upload
         if kernel == "hip":
             import radnerf_hip as hip
@@ -152,25 +191,28 @@ class DeviceTrainSet:
         torch path next to the kernel."""
         return type(self)(self.images, self.torso_img, self.bg_img, self.poses, self.intrinsics, self.auds, self.face_rect,
                           eye_area=self.eye_area, opt=self.opt, num_rays=self.num_rays if num_rays is None else num_rays,
-                          seed=self.seed if seed is None else seed, device=self.device, kernel=kernel)
+                          seed=self.seed if seed is None else seed, device=self.device, kernel=kernel, lips_rect=self._lips_host)
+
+    @property
+    def lips_rect(self):
+        """[F][4] host integers (xmin, xmax, ymin, ymax), or None."""
+        return self._lips_host
 
     def check(self):
-        """Raises when an explicit `inds` held pixels outside the image since the last check (they were clamped, never read
-        out of bounds).  Reads one device word back: call it where the host waits for the device anyway."""
+        """Raises when an explicit `inds` held pixels outside the image -- or explicit patch corners start positions outside
+        the range the draw covers -- since the last check (they were clamped, never read out of bounds).  Reads one device word back: call it where the host waits for the device anyway."""
         bad = int(self._bad.item())
         if bad:
             self._bad.zero_()
-            raise IndexError(f"DeviceTrainSet: {bad} pixel indices were outside [0, {self.H * self.W}) and were clamped")
+            raise IndexError(f"DeviceTrainSet: {bad} pixel indices were outside [0, {self.H * self.W}), or patch corners outside "
+                             "[0, H - patch) x [0, W - patch), and were clamped")
 
     def batch(self, index, inds=None):
         """The loader's training batch of frame index[0] (a Python list, as the reference's collate takes it): the dict
         SyntheticTrainStream.unpack returns -- per-ray entries are views of one `_packed` buffer that is rewritten in place by
         every call -- plus poses_matrix, H, W.  inds: explicit pixel indices (int64); None: `num_rays` pixels drawn on the device
         from (seed, draw counter), the counter advanced on the host.  One launch, nothing read back."""
-        aud_frame = int(index[0])                                   # audio uses the original index (provider.py:632-635)
-        frame = self.mirror_index(aud_frame)
-        if not 0 <= aud_frame < self.auds.shape[0]:
-            raise IndexError(f"DeviceTrainSet: audio frame {aud_frame} is outside the {self.auds.shape[0]} audio frames")
+        aud_frame, frame = self._frames(index)
         if inds is not None:
             inds = torch.as_tensor(inds).to(self.device, torch.int64).reshape(-1).contiguous()
         n = self.num_rays if inds is None else int(inds.numel())
@@ -193,6 +235,82 @@ class DeviceTrainSet:
             self._draw += 1
         self._index, self._last = [frame], picked
         return self.unpack(packed)
+
+    def batch_rect(self, index, rect=None):
+        """The batch of lip fine-tuning (provider.py:642-645, get_rays with `rect`, nerf/utils.py:297-303): EVERY pixel of `rect` =
+        (xmin, xmax, ymin, ymax), x along the rows, in ascending order -- the frame's lips rect unless given.  The dict of batch()
+        plus `rect`; the ray count is the rect's, so the views are laid out for this call inside one buffer sized for the
+        largest lips rect of the set (a larger explicit rect replaces it once).  An empty rect, or one that leaves the image, is
+        an error (the reference's slice would clamp silently).  One launch, nothing read back."""
+        aud_frame, frame = self._frames(index)
+        if rect is None:
+            if self._lips_host is None:
+                raise ValueError("DeviceTrainSet.batch_rect: the set has no lips_rect; pass rect=(xmin, xmax, ymin, ymax)")
+            rect = self._lips_host[frame]
+        xmin, xmax, ymin, ymax = rect = self._checked_rect(rect)
+        w = ymax - ymin
+        n = (xmax - xmin) * w
+        packed, picked = self._rect_views(n)
+        if self.kernel == "hip":
+            hip = self._hip
+            hip.call("rn_train_set_batch_rect", ctypes.byref(self._desc), frame, aud_frame, xmin, xmax, ymin, ymax, hip.ptr(packed),
+                     hip.ptr(picked), hip.ptr(self._poses6), hip.ptr(self._pose_matrix), hip.ptr(self._eye), hip.ptr(self._auds),
+                     hip.stream())
+        else:
+            k = torch.arange(n, dtype=torch.int64, device=self.device)
+            i = torch.div(k, w, rounding_mode="floor")
+            pix = (xmin + i) * self.W + ymin + (k - i * w)
+            picked.copy_(pix)
+            self._torch_fill(frame, aud_frame, pix, packed, training=True)
+        self._index, self._last = [frame], picked
+        out = self.unpack(packed)
+        out["rect"] = rect
+        return out
+
+    def batch_patch(self, index, patch_size, corners=None):
+        """The patch batch (`--patch_size`, get_rays nerf/utils.py:277-294): P = num_rays // patch_size^2 square patches, each in
+        meshgrid 'ij' order.  corners: explicit top-left corners, int [P,2] = (x0, y0) with x along the rows (P is then theirs);
+        one outside [0, H - patch_size) x [0, W - patch_size) is clamped and reported by check().  None: drawn on the device from
+        (seed, draw counter) over exactly those ranges (drawn_corners).  The dict of batch() plus `patch_size`."""
+        aud_frame, frame = self._frames(index)
+        ps = int(patch_size)
+        if not (2 <= ps < self.H and ps < self.W):
+            raise ValueError(f"DeviceTrainSet.batch_patch: 2 <= patch_size < min(H, W) is required, got {ps} on {self.H} x {self.W}")
+        if corners is None:
+            if self.num_rays % (ps * ps) != 0 or self.num_rays < ps * ps:      # main.py:125
+                raise ValueError(f"DeviceTrainSet.batch_patch: num_rays = {self.num_rays} is not a positive multiple of patch_size^2 = {ps * ps}")
+            P = self.num_rays // (ps * ps)
+        else:
+            corners = torch.as_tensor(corners).to(self.device, torch.int32).reshape(-1, 2).contiguous()
+            P = int(corners.shape[0])
+            if P < 1:
+                raise ValueError("DeviceTrainSet.batch_patch: at least one corner is required")
+        n = P * ps * ps
+        packed, picked = self._buf(n)
+        if self.kernel == "hip":
+            hip = self._hip
+            hip.call("rn_train_set_batch_patch", ctypes.byref(self._desc), frame, aud_frame, hip.ptr(corners), P, ps, self.seed & _MASK32,
+                     self._draw & _MASK32, hip.ptr(packed), hip.ptr(picked), hip.ptr(self._poses6), hip.ptr(self._pose_matrix),
+                     hip.ptr(self._eye), hip.ptr(self._auds), hip.ptr(self._bad), hip.stream())
+        else:
+            nx, ny = self.H - ps, self.W - ps
+            if corners is None:
+                c = drawn_corners(self.seed, self._draw, P, self.H, self.W, ps, self.device)
+            else:
+                c = corners.to(torch.int64)
+                self._bad += ((c[:, 0] < 0) | (c[:, 0] >= nx) | (c[:, 1] < 0) | (c[:, 1] >= ny)).sum().to(torch.int32)
+                c = torch.stack((c[:, 0].clamp(0, nx - 1), c[:, 1].clamp(0, ny - 1)), dim=-1)
+            o = torch.arange(ps * ps, dtype=torch.int64, device=self.device)
+            i = torch.div(o, ps, rounding_mode="floor")
+            pix = ((c[:, 0:1] + i) * self.W + c[:, 1:2] + (o - i * ps)).reshape(-1)       # nerf/utils.py:287-292
+            picked.copy_(pix)
+            self._torch_fill(frame, aud_frame, pix, packed, training=True)
+        if corners is None:
+            self._draw += 1
+        self._index, self._last = [frame], picked
+        out = self.unpack(packed)
+        out["patch_size"] = ps
+        return out
 
     def frame(self, index, aud_index=None):
         """The loader's evaluation form (training = False) of frame `index`: every pixel in order, no face mask.  The index is
@@ -234,6 +352,30 @@ class DeviceTrainSet:
             sec.append(flat[at:at + n * w].view(1, n, w))
             at += n * w
         return sec
+
+    def _frames(self, index):
+        """(audio frame, mirrored frame) of a loader index list: the audio uses the original index (provider.py:632-640)."""
+        aud_frame = int(index[0])
+        if not 0 <= aud_frame < self.auds.shape[0]:
+            raise IndexError(f"DeviceTrainSet: audio frame {aud_frame} is outside the {self.auds.shape[0]} audio frames")
+        return aud_frame, self.mirror_index(aud_frame)
+
+    def _checked_rect(self, rect):
+        xmin, xmax, ymin, ymax = (int(v) for v in rect)
+        if not (0 <= xmin < xmax <= self.H and 0 <= ymin < ymax <= self.W):
+            raise ValueError(f"DeviceTrainSet: rect {(xmin, xmax, ymin, ymax)} is empty or outside the {self.H} x {self.W} image "
+                             "(0 <= xmin < xmax <= H and 0 <= ymin < ymax <= W are required)")
+        return xmin, xmax, ymin, ymax
+
+    def _rect_views(self, n):
+        """(packed [15 n], picked [n]) for a rect of n pixels: the head of ONE flat buffer allocated at the largest lips rect of
+        the set -- rect sizes differ per frame, and a buffer per size would grow with every new one."""
+        if self._rect_buf is None or self._rect_buf[1].numel() < n:
+            cap = max([n] + [(r[1] - r[0]) * (r[3] - r[2]) for r in (self._lips_host or [])])
+            self._rect_buf = (torch.zeros(cap * sum(self._WIDTHS), device=self.device),
+                              torch.zeros(cap, dtype=torch.int64, device=self.device))
+        flat, picked = self._rect_buf
+        return flat[:n * sum(self._WIDTHS)], picked[:n]
 
     def _buf(self, n):
         if n not in self._bufs:       # allocated once per batch size, rewritten in place afterwards
@@ -287,7 +429,8 @@ class DeviceTrainSet:
         gradient background, and as ground truth `n_frames` frames of a SyntheticScene rendered once OVER THAT BLEND and quantised
         to uint8 -- the scene's own frozen render as target, as SyntheticTrainStream has it, so a head step sees a target its
         model can already produce.  The face rect is the bounding box of the pixels the head layer changed; poses and audio
-        features are the scene's, the eye value is constant."""
+        features are the scene's, the eye value is constant.  The lips rect of every frame: the square of half the face rect's
+        shorter side, centred in the face rect and clipped as provider.py:492-500 clips."""
         if not 8 <= n_frames <= scene.n_frames:
             raise ValueError("from_scene: 8 <= n_frames <= scene.n_frames is required")
         H, W, m = scene.H, scene.W, scene.model
@@ -323,6 +466,11 @@ class DeviceTrainSet:
         finally:
             scene.bg_color = white
             m.train(was_training)
+        lips = []
+        for xmin, xmax, ymin, ymax in rects:
+            cx, cy, half = (xmin + xmax) // 2, (ymin + ymax) // 2, max(min(xmax - xmin, ymax - ymin) // 4, 1)
+            lips.append([max(0, cx - half), min(H, cx + half), max(0, cy - half), min(W, cy + half)])
         eye = np.full((n_frames,), 0.25, dtype=np.float32)
         return cls(torch.stack(images), torso, bg, scene.poses[:n_frames], scene.intrinsics, scene.aud_features[:n_frames], rects,
-                   eye_area=eye, opt=scene.opt, num_rays=num_rays, seed=seed, device=scene.device, kernel=kernel)
+                   eye_area=eye, opt=scene.opt, num_rays=num_rays, seed=seed, device=scene.device, kernel=kernel,
+                   lips_rect=lips)

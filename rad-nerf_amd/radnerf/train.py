@@ -161,21 +161,60 @@ def entropy_of(alphas):
     return -a * torch.log2(a) - (1 - a) * torch.log2(1 - a)
 
 
-def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, amb_weight=None):
+def _patch_views(data, n):
+    """(weight, (P, h, w), force_all_rays) of a lip fine-tuning batch, or None for a plain one: a `rect` batch is ONE h x w image
+    at weight 0.01 (nerf/utils.py:757-766), a `patch_size` > 1 batch P = n / patch_size^2 square patches at weight 0.001
+    (:773-781) -- and only the latter marches all rays (:741)."""
+    rect, ps = data.get("rect"), int(data.get("patch_size") or 1)
+    if rect is not None and ps > 1:
+        raise ValueError("train_step: a batch is sampled by `rect` or by `patch_size`, not both")
+    if rect is not None:
+        xmin, xmax, ymin, ymax = rect
+        if (xmax - xmin) * (ymax - ymin) != n:
+            raise ValueError(f"train_step: rect {tuple(rect)} does not hold the batch's {n} rays")
+        return 0.01, (1, xmax - xmin, ymax - ymin), False
+    if ps > 1:
+        if n % (ps * ps):
+            raise ValueError(f"train_step: {n} rays are no multiple of patch_size^2 = {ps * ps}")
+        return 0.001, (n // (ps * ps), ps, ps), True
+    return None
+
+
+def _patch_term(criterion, weight, shape, pred, rgb):
+    """weight * criterion(pred patches, target patches).mean() with both as [P,3,h,w] (nerf/utils.py:759-760, 774-775)."""
+    P, h, w = shape
+    nchw = lambda t: t.reshape(P, h, w, 3).permute(0, 3, 1, 2).contiguous()
+    return weight * criterion(nchw(pred), nchw(rgb)).mean()
+
+
+def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, amb_weight=None, patch_criterion=None):
     """-> (pred_rgb, target_rgb, loss); `data` has the keys of the reference's loader batch
     (nerf/provider.py:588-690): rays_o, rays_d [B,N,3], bg_coords [1,N,2], poses [B,6], face_mask [B,N],
-    eye [B,1], auds, index, bg_color [B,N,3], images (head) or bg_torso_color (torso) [B,N,3]."""
+    eye [B,1], auds, index, bg_color [B,N,3], images (head) or bg_torso_color (torso) [B,N,3].
+
+    Lip fine-tuning (DeviceTrainSet.batch_rect / batch_patch): a batch with `rect`, or with `patch_size` > 1, adds
+    weight * patch_criterion(pred, target).mean() on [P,3,h,w] views -- weight 0.01 and one h x w view for a rect, 0.001 and
+    [P,3,ps,ps] for patches (which also march all rays).  patch_criterion is the caller's perceptual function (the reference's
+    LPIPS); it returns [P,1,1,1], or anything `.mean()` reduces.  The value is nerf/utils.py:757-783's: there the [P,1,1,1] term
+    is broadcast onto the [B,N] squared errors before the mean, which is mean(mse) + weight * mean(term).  Without a criterion
+    such a batch trains as a plain one.  On the fused loss route the term's gradient reaches the ready-made gradients through
+    train_head.head_loss_chain."""
     torso = bool(opt.torso)
     rgb = data["bg_torso_color"] if torso else data["images"]
+    views = _patch_views(data, int(rgb.reshape(-1, 3).shape[0]))
+    force_all = views is not None and views[2]
+    term_of = None
+    if views is not None and patch_criterion is not None:
+        term_of = lambda pred: _patch_term(patch_criterion, views[0], views[1], pred, rgb)
     fused_loss = (not torso and rgb.is_cuda and rgb.dtype == torch.float32 and switches.get("RN_TRAIN_LOSS") == "fused"
                   and torch.is_tensor(data.get("bg_color")) and data["bg_color"].dtype == torch.float32)
     # opt-in: a torso step that stays on the device (covered pixels compacted there, blend + loss in one kernel).  Asked for here
     # when the target can feed the loss kernel; the renderer decides (train_torso.step_usable, once per step) and answers with
     # the compact pieces, or with today's results
-    torso_direct = (torso and rgb.is_cuda and rgb.dtype == torch.float32 and torch.is_tensor(data.get("bg_color"))
+    torso_direct = (torso and term_of is None and rgb.is_cuda and rgb.dtype == torch.float32 and torch.is_tensor(data.get("bg_color"))
                     and route.kernels("train_torso").step_enabled())
     out = model.render(data["rays_o"], data["rays_d"], data["auds"], data["bg_coords"], data["poses"], eye=data["eye"],
-                       index=data["index"], staged=False, bg_color=data["bg_color"], perturb=True, force_all_rays=False,
+                       index=data["index"], staged=False, bg_color=data["bg_color"], perturb=True, force_all_rays=force_all,
                        dt_gamma=opt.dt_gamma, max_steps=opt.max_steps, defer_blend=fused_loss or torso_direct)
     if "torso_alpha_c" in out:
         from . import train_torso
@@ -190,6 +229,9 @@ def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, am
         face = face if face.dtype == torch.float32 else face.float()
         w = amb_weight if amb_weight is not None else torch.full((1,), min(global_step / iters, 1.0) * lambda_amb, device=rgb.device)
         loss, pred = train_head.head_loss(out["head_image"], out["weights_sum"], out["ambient"], out["background"], rgb, face, w)
+        if term_of is not None:
+            own = list(patch_criterion.parameters()) if isinstance(patch_criterion, torch.nn.Module) else []
+            loss = train_head.head_loss_chain(loss, pred, out["background"], term_of, own)
         return pred.view(rgb.shape), rgb, loss
     pred = out["torso_color"] if torso else out["image"]
     if not torso and pred.is_cuda:
@@ -198,7 +240,7 @@ def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, am
         if train_glue.enabled(pred, rgb, out["weights_sum"], out["ambient"]):
             w = amb_weight if amb_weight is not None else torch.full((1,), min(global_step / iters, 1.0) * lambda_amb, device=pred.device)
             loss = train_glue.train_loss(pred, rgb, out["weights_sum"], out["ambient"], face if face.dtype == torch.float32 else face.float(), w)
-            return pred, rgb, loss
+            return pred, rgb, loss if term_of is None else loss + term_of(pred)
     # the torso prediction is [n, 3], its target [1, n, 3]: the same values without the broadcast (and its warning); a target
     # of another size is an error (reshape raises), not something to broadcast
     target = rgb.reshape(pred.shape) if torso else rgb
@@ -212,7 +254,15 @@ def train_step(model, data, opt, global_step=0, iters=200000, lambda_amb=0.1, am
         loss_amb = (out["ambient"] * ((~face) if face.dtype == torch.bool else (1.0 - face))).mean()   # a 0/1 float mask is the same product
         # amb_weight: the same factor as a device scalar (a captured step reads it instead of baking the Python float in)
         loss = loss + (amb_weight if amb_weight is not None else min(global_step / iters, 1.0) * lambda_amb) * loss_amb
+    if term_of is not None:
+        loss = loss + term_of(pred)
     return pred, rgb, loss
+
+
+def lips_schedule(train_set, index, step):
+    """The batch of step `step` of lip fine-tuning: the frame's lips rect on even steps, a plain batch of random pixels on odd
+    ones -- the `flip_finetune_lips` alternation of nerf/utils.py:769-770, which starts on the rect."""
+    return train_set.batch_rect(index) if step % 2 == 0 else train_set.batch(index)
 
 
 def _backward(loss):
@@ -289,8 +339,12 @@ class Trainer:
     """zero_grad -> train_step -> backward -> Adam, with the occupancy grid refreshed every
     `update_extra_interval` steps as the reference's loop does under --cuda_ray (nerf/utils.py:1015-1018)."""
 
+    # the perceptual term of a lip fine-tuning batch (train_step).  A class default, so that a trainer assembled without
+    # __init__ around another trainer's state (bench.py's eager probe) steps as it did before the term existed
+    patch_criterion = None
+
     def __init__(self, model, opt, lr=5e-3, lr_net=5e-4, update_extra_interval=16, iters=200000, lambda_amb=0.1,
-                 prefer_rocblas=True, capturable=False):
+                 prefer_rocblas=True, capturable=False, patch_criterion=None):
         # The weight gradients of the 64-wide MLPs are [64 x ~40 000] x [~40 000 x 96] products: all reduction, almost
         # no output.  On this stack hipBLASLt runs them without a K split (132 us each, measured), rocBLAS in 37 us;
         # eight of them per step make that the largest single item of the step.
@@ -299,6 +353,7 @@ class Trainer:
         self.model, self.opt = model, opt
         self.optimizer = make_optimizer(model, lr, lr_net, capturable=capturable)
         self.update_extra_interval, self.iters, self.lambda_amb = update_extra_interval, iters, lambda_amb
+        self.patch_criterion = patch_criterion
         self.global_step = 0
 
     def _begin_step(self):
@@ -319,7 +374,8 @@ class Trainer:
         m._sample_budget = budget
         try:
             with _join_in_optimizer(self.optimizer):
-                _, _, loss = train_step(m, data, self.opt, self.global_step, self.iters, self.lambda_amb, amb_weight)
+                _, _, loss = train_step(m, data, self.opt, self.global_step, self.iters, self.lambda_amb, amb_weight,
+                                        self.patch_criterion)
                 _backward(loss)
                 self.optimizer.step()
         finally:
@@ -430,6 +486,9 @@ class GraphedTrainer(Trainer):
         return bool(self.opt.torso) and next(self.model.parameters()).is_cuda and route.kernels("train_torso").step_enabled()
 
     def step(self, data):
+        if data.get("rect") is not None or int(data.get("patch_size") or 1) > 1:
+            raise ValueError("GraphedTrainer: a lip fine-tuning batch (`rect` / `patch_size`) cannot be replayed from a captured "
+                             "step -- its ray count follows the frame's rect; take such steps with Trainer")
         m = self._begin_step()
         if self._torso_route():
             route.kernels("train_torso").pin_mean(m)   # a mean set from the host since the last step goes into the scalar the graph reads

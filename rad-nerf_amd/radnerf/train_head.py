@@ -384,20 +384,49 @@ def loss_usable(*tensors):
     return all(t.is_cuda and t.dtype == torch.float32 for t in tensors)
 
 
+def _rows(t, width):
+    t = t.reshape(-1, width) if width > 1 else t.reshape(-1)
+    if t.dim() == 2 and t.stride(1) != 1:
+        t = t.contiguous()
+    return t
+
+
 def head_loss(image, weights_sum, ambient, bg, target, face, w_amb):
     """image [N,3], weights_sum [N], ambient [N] (composited), bg / target [N,3] and face [N] (0/1 floats; rows may be strided
     views of one batch table), w_amb: device scalar.  -> (loss, pred [N,3])."""
-    def rows(t, width):
-        t = t.reshape(-1, width) if width > 1 else t.reshape(-1)
-        if t.dim() == 2 and t.stride(1) != 1:
-            t = t.contiguous()
-        return t
-    loss, pred, grads = _HeadLoss.apply(image, weights_sum, ambient, rows(bg, 3), rows(target, 3), rows(face, 1), w_amb.reshape(1))
+    loss, pred, grads = _HeadLoss.apply(image, weights_sum, ambient, _rows(bg, 3), _rows(target, 3), _rows(face, 1), w_amb.reshape(1))
     # d loss / d (image, weights_sum, ambient) were written by the same kernel: backward(loss) below hands them to autograd as
     # they are instead of going through `ones_like(loss)` and a multiplication by it (two launches)
     N = image.shape[0]
     loss._rn_direct = ((image, weights_sum, ambient), (grads[0:3 * N].view(N, 3), grads[3 * N:4 * N], grads[4 * N:5 * N]))
     return loss, pred
+
+
+def head_loss_chain(loss, pred, bg, term_of, params=()):
+    """A term on `pred` joins a loss of head_loss() -- the patch / lips term of nerf/utils.py:757-781, which the ready-made
+    gradients of that loss would otherwise silently drop.  term_of(pred) -> the weighted scalar term; it runs under autograd on
+    a detached copy of pred, and ONE launch (rn_train_head_loss_chain) takes d term / d pred back through the clamp and the blend
+    into the gradient arrays the loss kernel wrote, and adds the term to the loss, all in place.  params: parameters of the
+    term's own (a criterion network's); their gradients come from the same autograd.grad call and reach .grad with the others in
+    backward(loss).  -> loss (the same tensor)."""
+    (image, weights_sum, ambient), (g_image, g_ws, g_amb) = loss._rn_direct
+    N = image.shape[0]
+    leaf = pred.detach().requires_grad_()
+    with torch.enable_grad():
+        term = term_of(leaf).reshape(())
+    params = [p for p in params if p.requires_grad]
+    if term.requires_grad:
+        grads = torch.autograd.grad(term, [leaf] + params, allow_unused=True)
+    else:                                        # a term that does not depend on pred: only its value joins the loss
+        grads = [None] * (1 + len(params))
+    g_pred = torch.zeros_like(leaf) if grads[0] is None else grads[0].contiguous()
+    image, weights_sum, bg = image.contiguous(), weights_sum.contiguous(), _rows(bg, 3)
+    value = term.detach().to(torch.float32).reshape(1)
+    hip.call("rn_train_head_loss_chain", hip.ptr(image), hip.ptr(weights_sum), bg.data_ptr(), bg.stride(0), hip.ptr(g_pred), N,
+             hip.ptr(value), loss.data_ptr(), g_image.data_ptr(), g_ws.data_ptr(), hip.stream())
+    own = [(p, g) for p, g in zip(params, grads[1:]) if g is not None]
+    loss._rn_direct = (loss._rn_direct[0] + tuple(p for p, _ in own), loss._rn_direct[1] + tuple(g for _, g in own))
+    return loss
 
 
 def backward(loss):

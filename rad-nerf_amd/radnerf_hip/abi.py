@@ -235,6 +235,7 @@ FUNCTIONS = {
     "rn_grid_scatter_ordered": (_int, [_P(ScatterJobT), _u32, _u32, _ptr, _ptr, _sz, _ptr]),
     "rn_train_head_loss": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _u32, _ptr, _ptr, _ptr, _ptr,
                                   _ptr, _ptr]),
+    "rn_train_head_loss_chain": (_int, [_ptr, _ptr, _ptr, _u32, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "rn_train_batch_gather": (_int, [_ptr, _u32, _ptr, _u32, C.POINTER(_u32), _u32, _ptr, _ptr]),
     "rn_camera_rays_forward": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr]),
     "rn_camera_rays_workspace": (_sz, [_u32]),
@@ -252,6 +253,10 @@ FUNCTIONS = {
     "rn_train_set_batch": (_int, [_P(TrainSetT), _u32, _u32, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                   _ptr]),
     "rn_train_set_frame": (_int, [_P(TrainSetT), _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_train_set_batch_rect": (_int, [_P(TrainSetT), _u32, _u32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ptr, _ptr, _ptr, _ptr,
+                                       _ptr, _ptr, _ptr]),
+    "rn_train_set_batch_patch": (_int, [_P(TrainSetT), _u32, _u32, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                        _ptr, _ptr]),
 }
 
 

@@ -1,6 +1,7 @@
 """What the device-resident training set costs (radnerf/dataset.py, csrc/rn_train_batch.hip), on one GPU.
 
     python tools/bench_train_set.py [--size 512] [--rays 4096] [--frames 64] [--out profiles/train_set_bench.json]
+    python tools/bench_train_set.py --mode rect [--rect 96]       (or --mode patch [--patch 16]): the lip fine-tuning batches
 
 1. Microseconds per DeviceTrainSet.batch(): the one-launch kernel against the class's own torch path on the device (the parent
    has no data-set path to compare with), same arrays, same run, alternating, `--repeats` windows of `--calls` calls each after a
@@ -10,6 +11,10 @@
    SyntheticTrainStream (one frame, float table), same process, alternating windows of `--steps` steps after both are past their
    first grid refreshes.  Host clock around each window, ending in a synchronise.  `--feeds` picks the feeds (one alone for a
    profiler run of its own: rocprofv3 --kernel-trace --stats -- python tools/bench_train_set.py --skip-batch --feeds device_train_set).
+
+--mode rect / patch time DeviceTrainSet.batch_rect() on a centred `--rect` x `--rect` square and batch_patch() with `--rays`
+rays in `--patch` x `--patch` patches the same way (part 1 only: a captured step does not take these batches), and count the
+device launches of one call of either path with the profiler.
 
 Prints one JSON object (and writes it to --out).  Needs a GPU: there is no CPU timing worth reporting.
 """
@@ -44,15 +49,37 @@ def time_calls(fn, calls):
     return a.elapsed_time(b) * 1e3 / calls, (t1 - t0) * 1e6 / calls
 
 
+def count_launches(fn):
+    """Device activities (kernels, copies, fills) of one call, counted with the profiler's device events."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    return sum(1 for e in prof.events() if e.device_type is not None and "cuda" in str(e.device_type).lower())
+
+
 def bench_batch(ds, args):
     oracle = ds.clone(kernel="torch")
     frames = list(range(ds.F))
     state = {"k": 0}
 
+    if args.mode == "rect":
+        lo_r, lo_c = (ds.H - args.rect) // 2, (ds.W - args.rect) // 2
+        rect = (lo_r, lo_r + args.rect, lo_c, lo_c + args.rect)
+        one = lambda s, index: s.batch_rect(index, rect=rect)
+        n = args.rect * args.rect
+    elif args.mode == "patch":
+        one = lambda s, index: s.batch_patch(index, args.patch)
+        n = ds.num_rays
+    else:
+        one = lambda s, index: s.batch(index)
+        n = ds.num_rays
+
     def call(s):
         def fn():
             state["k"] += 1
-            s.batch([frames[state["k"] % len(frames)]])
+            one(s, [frames[state["k"] % len(frames)]])
         return fn
     paths = {"kernel": call(ds), "torch": call(oracle)}
     for fn in paths.values():
@@ -69,7 +96,9 @@ def bench_batch(ds, args):
     out["torch_over_kernel_event"] = out["torch"]["event_us"]["median"] / out["kernel"]["event_us"]["median"]
     out["torch_over_kernel_host"] = out["torch"]["host_us"]["median"] / out["kernel"]["host_us"]["median"]
     out["calls_per_window"], out["windows"] = args.calls, args.repeats
-    n = ds.num_rays
+    out["mode"], out["rays_per_call"] = args.mode, n
+    if args.mode != "batch":
+        out["launches_per_call"] = {name: count_launches(fn) for name, fn in paths.items()}
     out["bytes_per_call"] = dict(written=n * 15 * 4 + n * 8, gathered=n * 10)    # packed + inds_out; 3 + 4 + 3 image bytes per pixel
     return out
 
@@ -128,6 +157,9 @@ def bench_trainers(ds, scene_ds, args):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=("batch", "rect", "patch"), default="batch")
+    ap.add_argument("--rect", type=int, default=96, help="--mode rect: side of the centred square")
+    ap.add_argument("--patch", type=int, default=16, help="--mode patch: patch_size (--rays must be a multiple of its square)")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--rays", type=int, default=4096)
     ap.add_argument("--frames", type=int, default=64)
@@ -152,7 +184,7 @@ def main():
            "set_bytes": int(ds.images.numel() + ds.torso_img.numel() + ds.bg_img.numel())}
     if not args.skip_batch:
         rec["batch"] = bench_batch(ds, args)
-    if not args.skip_trainers:
+    if not args.skip_trainers and args.mode == "batch":
         rec["graphed_trainer"] = bench_trainers(ds, scene, args)
     text = json.dumps(rec, indent=1)
     print(text)
