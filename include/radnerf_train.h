@@ -376,6 +376,48 @@ int rn_train_set_batch_patch(const rn_train_set_t *set, uint32_t frame, uint32_t
                              uint32_t patch, uint32_t seed, uint32_t draw, float *packed, int64_t *inds_out, float *poses6,
                              float *pose_matrix, float *eye, float *auds_out, uint32_t *bad, rn_stream_t stream);
 
+/*
+ * What the reference wraps around the training step (main.py:204-224, nerf/utils.py:1018, :1220-1300), keyed on the optimizer's
+ * device-side step counter: the learning-rate schedule and the EMA of the weights inside the Adam launches, a swap of weights and
+ * shadows, and the squared error of a rendered frame.  The arithmetic of the schedule and of the decay is csrc/rn_optim_dev.h.
+ */
+/* One tensor of rn_adam_step_sched: rn_adam_tensor_t with the shadow (EMA) array (nullable: no average is kept) and lr0, the rate
+ * before any decay.  grad == NULL: a tensor the optimizer holds that has no gradient this step -- no Adam update (exp_avg /
+ * exp_avg_sq are then not touched and may be NULL), but its shadow is averaged on update steps. */
+typedef struct {
+    float *param;
+    const float *grad;
+    float *exp_avg, *exp_avg_sq, *shadow;
+    uint32_t numel;
+    float lr0;
+} rn_sched_tensor_t;
+/* rn_adam_step_lr's update with the schedule and the EMA inside the same launches.  With s = *step after this call's increment:
+ *   lr_dev[t] = (float)((double)lr0_t * pow(gamma, (double)(s - 1) / (double)iters))   -- LambdaLR as Trainer.train_one_epoch drives
+ *     it (main.py:219, scheduler_update_every_step): step s uses the rate after s - 1 scheduler steps.  gamma == 1: lr0_t.  Written
+ *     by the begin kernel (one per 48 tensors), read by the update kernel, and left in lr_dev [count] for the caller to read back.
+ *   EMA (decay > 0): on steps with s % interval == 0 the begin kernel does *num_updates += 1 and
+ *     omd = (float)(1.0 - min(decay, (1.0 + *num_updates) / (10.0 + *num_updates))), in double; every tensor with a shadow then does
+ *     tmp = shadow - p_new; tmp *= omd; shadow -= tmp -- three separately rounded fp32 operations on the value this step wrote
+ *     (torch_ema's update with use_num_updates).  On every other step no shadow is read or written.
+ * corr: 4 floats of scratch (bias corrections, omd, the update flag).  num_updates: device int32, nullable when decay == 0.
+ * Enqueue-only, capturable.  Refused before any launch: decay > 0 with interval == 0, decay outside [0, 1], gamma != 1 with
+ * iters == 0, gamma <= 0, null pointers. */
+int rn_adam_step_sched(const rn_sched_tensor_t *tensors, uint32_t count, float beta1, float beta2, float eps, double gamma,
+                       uint32_t iters, double decay, uint32_t interval, int32_t *step, float *corr, float *lr_dev,
+                       int32_t *num_updates, rn_stream_t stream);
+/* Exchange a[i][0 .. numel[i]) with b[i][0 .. numel[i]) for `count` tensors (a, b, numel: HOST arrays) in one launch per 48:
+ * weights <-> shadows is torch_ema's store() + copy_to(), the same call again its restore().  float4 accesses where both
+ * pointers are 16-byte aligned, scalar ones elsewhere.  a[i] and b[i] must not overlap. */
+int rn_param_swap(float *const *a, float *const *b, const uint32_t *numel, uint32_t count, rn_stream_t stream);
+/* Squared error of one frame: pred, target [H*W, 3] fp32.  out [4] doubles: sum over all values of ((double)(pred - target))^2 with
+ * the difference taken in fp32 | the same sum over the pixels inside rect | the number of values | the number inside rect.
+ * rect: device int32 [4] = (xmin, xmax, ymin, ymax), xmin <= row < xmax, ymin <= col < ymax (rn_train_set_t's face_rect), NULL =
+ * no rect (both rect entries 0).  Per-workgroup partials in `workspace` (rn_image_error_workspace(H, W) bytes, 8-byte aligned, no
+ * initialisation), then one ordered pass: no float atomics, the same bits on every run.  H * W <= 2^30. */
+size_t rn_image_error_workspace(uint32_t H, uint32_t W);
+int rn_image_error(const float *pred, const float *target, uint32_t H, uint32_t W, const int32_t *rect, void *workspace,
+                   double *out, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,8 +6,9 @@
 // arrays written once (7 x 49 MB, the step's largest HBM stream), the ~35 small tensors ride along in the same grid.
 // PyTorch's fused Adam takes one multi-tensor launch per parameter group plus the step-counter updates (~18 launches).
 #include "rn_common.h"
+#include "rn_optim_dev.h"
 
-#include "../../include/radnerf_fused.h"
+#include "../../include/radnerf_train.h"
 
 namespace rn {
 
@@ -43,7 +44,46 @@ __device__ __forceinline__ void adam_one(float &p, float g, float &m, float &v, 
     p = p - step_size * (m / denom);
 }
 
-__global__ void __launch_bounds__(kAdamBlock) k_adam(AdamArgs a, float beta1, float beta2, float eps, const float *__restrict__ corr,
+// rn_adam_step_sched's arguments: the same block plus the shadow (EMA) pointers.  A separate type, so that the instantiation
+// rn_adam_step / rn_adam_step_lr launch keeps the kernel arguments it always had.
+struct SchedArgs : AdamArgs {
+    float *sh[kAdamMaxTensors];
+};
+struct SchedRates {
+    float lr0[kAdamMaxTensors];
+    uint32_t count;
+};
+
+// The begin kernel of rn_adam_step_sched, one launch per 48 tensors: thread k writes tensor k's rate of this step; in the first
+// launch thread 0 also does what k_adam_begin does and decides whether this step averages the weights (csrc/rn_optim_dev.h).
+// corr[2] = 1 - decay, corr[3] = the update flag as an integer word.
+__global__ void __launch_bounds__(kWave) k_adam_begin_sched(int32_t *step, float *corr, float beta1, float beta2, SchedRates r, double gamma,
+                                                            uint32_t iters, double decay, uint32_t interval, int32_t *num_updates,
+                                                            float *__restrict__ lr_dev, int first) {
+    const int32_t s = step[0] + (first ? 1 : 0);        // later launches of the call see the counter already advanced
+    __syncthreads();
+    if (threadIdx.x < r.count) lr_dev[threadIdx.x] = optim::sched_lr(r.lr0[threadIdx.x], gamma, s, iters);
+    if (threadIdx.x != 0 || !first) return;
+    step[0] = s;
+    corr[0] = (float)(1.0 - pow((double)beta1, (double)s));
+    corr[1] = (float)sqrt(1.0 - pow((double)beta2, (double)s));
+    float omd = 0.0f;
+    uint32_t update = 0;
+    if (decay > 0.0 && s % (int32_t)interval == 0) {      // nerf/utils.py:1018: global_step % ema_update_interval == 0
+        const int32_t n = num_updates[0] + 1;
+        num_updates[0] = n;
+        omd = optim::ema_one_minus_decay(decay, n);
+        update = 1;
+    }
+    corr[2] = omd;
+    reinterpret_cast<uint32_t *>(corr)[3] = update;
+}
+
+// SCHED = false: the update of rn_adam_step / rn_adam_step_lr, as it always was.  SCHED = true (Args = SchedArgs): rates always from
+// lr_dev, a tensor without a gradient is left alone, and on an update step (a wave-uniform flag) every tensor with a shadow folds
+// the value just written into it -- on any other step no shadow is touched.
+template <bool SCHED, typename Args>
+__global__ void __launch_bounds__(kAdamBlock) k_adam(Args a, float beta1, float beta2, float eps, const float *__restrict__ corr,
                                                      const float *__restrict__ lr_dev) {
     // which tensor does this workgroup belong to?  (<= 48 entries: a scan in scalar registers)
     uint32_t t = 0;
@@ -57,20 +97,49 @@ __global__ void __launch_bounds__(kAdamBlock) k_adam(AdamArgs a, float beta1, fl
     const float step_size = (lr_dev ? lr_dev[t] : a.lr[t]) / bc1;
     float *p = a.p[t] + base, *m = a.m[t] + base, *v = a.v[t] + base;
     const float *g = a.g[t] + base;
-    if (base + 4 <= n && ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
-                           reinterpret_cast<uintptr_t>(v)) & 15u) == 0) {
-        float4 P = *reinterpret_cast<float4 *>(p), M = *reinterpret_cast<float4 *>(m), V = *reinterpret_cast<float4 *>(v);
-        const float4 G = *reinterpret_cast<const float4 *>(g);
-        adam_one(P.x, G.x, M.x, V.x, beta1, beta2, eps, step_size, bc2_sqrt);
-        adam_one(P.y, G.y, M.y, V.y, beta1, beta2, eps, step_size, bc2_sqrt);
-        adam_one(P.z, G.z, M.z, V.z, beta1, beta2, eps, step_size, bc2_sqrt);
-        adam_one(P.w, G.w, M.w, V.w, beta1, beta2, eps, step_size, bc2_sqrt);
-        *reinterpret_cast<float4 *>(p) = P; *reinterpret_cast<float4 *>(m) = M; *reinterpret_cast<float4 *>(v) = V;
+    uintptr_t align = reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) |
+                      reinterpret_cast<uintptr_t>(v);
+    bool adam = true;
+    float *sh = nullptr;
+    float omd = 0.0f;
+    if constexpr (SCHED) {
+        adam = a.g[t] != nullptr;
+        if (reinterpret_cast<const uint32_t *>(corr)[3] != 0 && a.sh[t]) sh = a.sh[t] + base;
+        if (!adam && !sh) return;
+        omd = corr[2];
+        if (!adam) align = reinterpret_cast<uintptr_t>(p);
+        align |= reinterpret_cast<uintptr_t>(sh);
+    }
+    if (base + 4 <= n && (align & 15u) == 0) {
+        float4 P = *reinterpret_cast<float4 *>(p);
+        if (adam) {
+            float4 M = *reinterpret_cast<float4 *>(m), V = *reinterpret_cast<float4 *>(v);
+            const float4 G = *reinterpret_cast<const float4 *>(g);
+            adam_one(P.x, G.x, M.x, V.x, beta1, beta2, eps, step_size, bc2_sqrt);
+            adam_one(P.y, G.y, M.y, V.y, beta1, beta2, eps, step_size, bc2_sqrt);
+            adam_one(P.z, G.z, M.z, V.z, beta1, beta2, eps, step_size, bc2_sqrt);
+            adam_one(P.w, G.w, M.w, V.w, beta1, beta2, eps, step_size, bc2_sqrt);
+            *reinterpret_cast<float4 *>(p) = P; *reinterpret_cast<float4 *>(m) = M; *reinterpret_cast<float4 *>(v) = V;
+        }
+        if constexpr (SCHED) {
+            if (sh) {
+                float4 S = *reinterpret_cast<float4 *>(sh);
+                S.x = optim::ema_one(S.x, P.x, omd); S.y = optim::ema_one(S.y, P.y, omd);
+                S.z = optim::ema_one(S.z, P.z, omd); S.w = optim::ema_one(S.w, P.w, omd);
+                *reinterpret_cast<float4 *>(sh) = S;
+            }
+        }
     } else {
         for (uint32_t i = 0; i < 4 && base + i < n; i++) {
-            float P = p[i], M = m[i], V = v[i];
-            adam_one(P, g[i], M, V, beta1, beta2, eps, step_size, bc2_sqrt);
-            p[i] = P; m[i] = M; v[i] = V;
+            float P = p[i];
+            if (adam) {
+                float M = m[i], V = v[i];
+                adam_one(P, g[i], M, V, beta1, beta2, eps, step_size, bc2_sqrt);
+                p[i] = P; m[i] = M; v[i] = V;
+            }
+            if constexpr (SCHED) {
+                if (sh) sh[i] = optim::ema_one(sh[i], P, omd);
+            }
         }
     }
 }
@@ -224,9 +293,45 @@ int rn_adam_step_lr(const rn_adam_tensor_t *tensors, uint32_t count, float beta1
         }
         a.first_block[k] = blocks;
         a.count = k;
-        if (blocks) hipLaunchKernelGGL(k_adam, dim3(blocks), dim3(kAdamBlock), 0, s, a, beta1, beta2, eps, corr, lr_dev ? lr_dev + at : nullptr);
+        if (blocks) hipLaunchKernelGGL((k_adam<false, AdamArgs>), dim3(blocks), dim3(kAdamBlock), 0, s, a, beta1, beta2, eps, corr, lr_dev ? lr_dev + at : nullptr);
     }
     return check_launch("adam_step");
+}
+
+int rn_adam_step_sched(const rn_sched_tensor_t *tensors, uint32_t count, float beta1, float beta2, float eps, double gamma,
+                       uint32_t iters, double decay, uint32_t interval, int32_t *step, float *corr, float *lr_dev,
+                       int32_t *num_updates, rn_stream_t stream) {
+    RN_REQUIRE(tensors || count == 0, "adam_step_sched: null tensor list");
+    RN_REQUIRE(step && corr && lr_dev, "adam_step_sched: null pointer (step counter (int32), a 4-float scratch and lr_dev are required)");
+    RN_REQUIRE(gamma > 0.0, "adam_step_sched: gamma must be positive");
+    RN_REQUIRE(gamma == 1.0 || iters > 0, "adam_step_sched: a decaying rate (gamma != 1) needs iters > 0");
+    RN_REQUIRE(decay >= 0.0 && decay <= 1.0, "adam_step_sched: decay must lie in [0, 1]");
+    RN_REQUIRE(!(decay > 0.0) || interval > 0, "adam_step_sched: an EMA (decay > 0) needs interval > 0");
+    RN_REQUIRE(!(decay > 0.0) || num_updates, "adam_step_sched: null pointer (an EMA needs the num_updates counter)");
+    for (uint32_t i = 0; i < count; i++) {          // everything is checked before the first launch
+        const rn_sched_tensor_t &t = tensors[i];
+        RN_REQUIRE(t.param && (!t.grad || (t.exp_avg && t.exp_avg_sq)), "adam_step_sched: null pointer in tensor %u", i);
+    }
+    hipStream_t s = as_stream(stream);
+    for (uint32_t at = 0; at < count || at == 0; at += kAdamMaxTensors) {
+        SchedArgs a{};
+        SchedRates r{};
+        uint32_t blocks = 0, k = 0;
+        for (; k < (uint32_t)kAdamMaxTensors && at + k < count; k++) {
+            const rn_sched_tensor_t &t = tensors[at + k];
+            a.p[k] = t.param; a.g[k] = t.grad; a.m[k] = t.exp_avg; a.v[k] = t.exp_avg_sq;
+            a.sh[k] = decay > 0.0 ? t.shadow : nullptr;
+            a.n[k] = t.numel; a.lr[k] = r.lr0[k] = t.lr0;
+            a.first_block[k] = blocks;
+            if (t.grad || a.sh[k]) blocks += div_up(t.numel, kAdamChunk);
+        }
+        a.first_block[k] = blocks;
+        a.count = r.count = k;
+        hipLaunchKernelGGL(k_adam_begin_sched, dim3(1), dim3(kWave), 0, s, step, corr, beta1, beta2, r, gamma, iters, decay, interval,
+                           num_updates, lr_dev + at, at == 0 ? 1 : 0);
+        if (blocks) hipLaunchKernelGGL((k_adam<true, SchedArgs>), dim3(blocks), dim3(kAdamBlock), 0, s, a, beta1, beta2, eps, corr, lr_dev + at);
+    }
+    return check_launch("adam_step_sched");
 }
 
 }  // extern "C"

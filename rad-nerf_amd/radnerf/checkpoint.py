@@ -14,8 +14,12 @@ def model_state(model):
             "mean_density_torso": model.mean_density_torso}
 
 
-def save_checkpoint(model, path, best=False, **extra):
+def save_checkpoint(model, path, best=False, ema=None, **extra):
+    """ema: a radnerf.ema.ParamEma; its state_dict() becomes the `ema` entry, as the reference writes torch_ema's
+    (nerf/utils.py:1327-1328)."""
     state = model_state(model)
+    if ema is not None:
+        state["ema"] = ema.state_dict()
     if best and "density_grid" in state["model"]:
         state["model"] = {k: v for k, v in state["model"].items() if k != "density_grid"}
     state.update(extra)
@@ -23,7 +27,7 @@ def save_checkpoint(model, path, best=False, **extra):
     return path
 
 
-def load_checkpoint(model, checkpoint, map_location=None, optimizer=None, half_tables=False):
+def load_checkpoint(model, checkpoint, map_location=None, optimizer=None, half_tables=False, ema=None):
     """Load a reference checkpoint (path or already-loaded dict).  Returns (missing_keys, unexpected_keys), as
     `load_state_dict(strict=False)` reports them for the model part (nerf/utils.py:1376-1396).
 
@@ -32,6 +36,8 @@ def load_checkpoint(model, checkpoint, map_location=None, optimizer=None, half_t
     half_tables: build the persistent fp16 copies of the three grid tables now (GridEncoder.half_table) and make the fused
     inference engine read them (model.opt.half_tables) -- what the reference's `-O` mode re-creates by casting every table on
     every call (gridencoder/grid.py:43-44).  The copies follow the parameters: they are re-cast when a table's version changes.
+    ema: a radnerf.ema.ParamEma over this model's parameters; restored from the `ema` entry (:1388-1389).  A checkpoint without
+    the entry leaves the shadows at the loaded weights.
     `model.checkpoint_meta` receives epoch / global_step / stats when the file has them."""
     if not isinstance(checkpoint, dict):
         checkpoint = torch.load(checkpoint, map_location=map_location, weights_only=False)
@@ -50,6 +56,12 @@ def load_checkpoint(model, checkpoint, map_location=None, optimizer=None, half_t
                 model.checkpoint_meta["optimizer_loaded"] = True
             except (ValueError, KeyError, RuntimeError):
                 model.checkpoint_meta["optimizer_loaded"] = False
+    if ema is not None:
+        if isinstance(checkpoint, dict) and checkpoint.get("ema") is not None and "model" in checkpoint:
+            ema.load_state_dict(checkpoint["ema"])
+        else:
+            ema.reset_to_weights()
+            ema.num_updates = 0
     if getattr(model, "enc_a", None) is not None:
         model.enc_a = None  # the lip-smoothing state belongs to a stream, not to the weights
     if half_tables:

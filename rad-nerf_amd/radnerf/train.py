@@ -5,8 +5,11 @@ backward kernels), the reference's loss and its Adam parameter groups.
 Reference: Trainer.train_step (nerf/utils.py:718-806) for the loss, Trainer.train_one_epoch (:1003-1040) for
 the order zero_grad -> step -> backward -> optimizer and the `update_extra_state` cadence
 (`--update_extra_interval 16`, main.py:31), main.py:204 for Adam(betas=(0.9, 0.99), eps=1e-15) over
-NeRFNetwork.get_params(lr, lr_net) (nerf/network.py:328-357).  The data loader, LPIPS, EMA, GradScaler and the
-learning-rate schedule are outside the path (out of scope) and are not rebuilt.
+NeRFNetwork.get_params(lr, lr_net) (nerf/network.py:328-357).  The data loader, LPIPS and GradScaler are outside the path
+(out of scope) and are not rebuilt.  What main.py:204-224 wraps around the step is opt-in by argument: the LambdaLR
+decay (lr_gamma), the EMA of the weights (ema_decay, ema_update_interval; radnerf/ema.py) -- on the GPU both inside the Adam
+launches, keyed on the optimizer's device-side step counter (rn_adam_step_sched) -- and Trainer.evaluate, the validation loss and
+PSNR of nerf/utils.py:1220-1300 under the averaged weights with one read-back.
 """
 import contextlib
 
@@ -15,15 +18,17 @@ import torch
 from radnerf import route, switches      # by the package's name: this file is also loaded on its own (tests/test_train_host.py)
 
 
-def make_optimizer(model, lr=5e-3, lr_net=5e-4, fused=None, capturable=False, kernel=None):
+def make_optimizer(model, lr=5e-3, lr_net=5e-4, fused=None, capturable=False, kernel=None, schedule=None, ema=None):
     """main.py:204; lr for the grid tables, lr_net for the MLPs / audio nets / individual codes.  On the GPU the update runs
     as ONE kernel over all tensors (HipAdam; `kernel="torch"` or RN_ADAM=torch: torch's fused Adam, one launch per parameter
-    group) -- the 49 MB table is read and written once per step either way; same arithmetic as the default implementation."""
+    group) -- the 49 MB table is read and written once per step either way; same arithmetic as the default implementation.
+    schedule = (gamma, iters) / ema = ParamEma: HipAdam carries them inside its launches; any other optimizer ignores them here
+    (Trainer then applies both from the host after each step)."""
     on_gpu = next(model.parameters()).is_cuda
     if kernel is None:
         kernel = switches.get("RN_ADAM") if on_gpu else "torch"
     if kernel == "hip" and on_gpu:
-        return HipAdam(model.get_params(lr, lr_net))
+        return HipAdam(model.get_params(lr, lr_net), schedule=schedule, ema=ema)
     if fused is None:
         fused = on_gpu
     return torch.optim.Adam(model.get_params(lr, lr_net), betas=(0.9, 0.99), eps=1e-15, fused=bool(fused),
@@ -35,14 +40,20 @@ class HipAdam:
     tensors (C ABI rn_adam_step, csrc/rn_train.hip) -- the table, its moments and its gradient stream through HBM once.
     Same interface as far as Trainer needs it (param_groups, zero_grad, step, state_dict / load_state_dict in
     torch.optim.Adam's format, so reference checkpoints carry over); the step counter lives on the device, so a step is
-    capturable in a hipGraph."""
+    capturable in a hipGraph.
+
+    schedule = (gamma, iters) and / or ema = ParamEma select rn_adam_step_sched: every tensor's rate is lr0 * gamma ** ((s - 1) / iters)
+    at step s (LambdaLR as the reference drives it, main.py:219), computed by the begin kernel from the device-side step counter,
+    and on steps with s % ema.update_interval == 0 the same launches fold the new weights into the shadows (which stay in the
+    ParamEma; its update counter moves to the device).  Nothing is uploaded per step on that route: refresh_lr() is a no-op,
+    current_lr() is a host mirror for logging, and param_groups[i]["lr"] is only rewritten by state_dict()."""
 
     # what torch.optim.Adam keeps in every param_group (torch/optim/adam.py): a state dict written here loads into the
     # reference's torch.optim.Adam (nerf/utils.py:1302-1426 saves / restores optimizer.state_dict())
     _TORCH_ADAM_DEFAULTS = dict(weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False,
                                 fused=None, decoupled_weight_decay=False)
 
-    def __init__(self, params, betas=(0.9, 0.99), eps=1e-15):
+    def __init__(self, params, betas=(0.9, 0.99), eps=1e-15, schedule=None, ema=None):
         import radnerf_hip as hip
         self._hip = hip
         self.param_groups = []
@@ -70,6 +81,29 @@ class HipAdam:
         # them at run time, so a schedule that rewrites param_groups[i]["lr"] is followed by every replay (refresh_lr())
         self._lr_dev = torch.zeros(max(n, 1), dtype=torch.float32, device=dev)
         self._lr_groups, self._lr_sent, self._written = [], None, []
+        self._sched = schedule is not None or ema is not None
+        self.ema, self._host_step, self.uploads = ema, 0, 0       # uploads: host -> device copies refresh_lr() made
+        self.gamma, self.sched_iters = (float(schedule[0]), int(schedule[1])) if schedule is not None else (1.0, 0)
+        if self._sched:
+            if not self.gamma > 0 or (self.gamma != 1.0 and self.sched_iters <= 0):
+                raise ValueError("HipAdam: schedule=(gamma, iters) needs gamma > 0, and iters > 0 unless gamma == 1")
+            self._corr = torch.zeros(4, dtype=torch.float32, device=dev)
+            if ema is not None:
+                ema.restrict([p for g in self.param_groups for p in g["params"]])
+                if ema.device_num_updates is None:
+                    ema.device_num_updates = torch.full((1,), ema._num_updates, dtype=torch.int32, device=dev)
+
+    def current_lr(self):
+        """Per group, the rate the NEXT step uses -- what param_groups[i]["lr"] shows in the reference once its scheduler has
+        stepped.  A host mirror (initial_lr, gamma and the number of steps taken); nothing is read from the device."""
+        if not self._sched:
+            return [float(g["lr"]) for g in self.param_groups]
+        f = 1.0 if self.gamma == 1.0 else self.gamma ** (self._host_step / self.sched_iters)
+        return [float(g["initial_lr"]) * f for g in self.param_groups]
+
+    def note_replayed(self, n=1):
+        """A captured step was replayed n times: the device-side counter advanced, the host mirror follows."""
+        self._host_step += int(n)
 
     def zero_grad(self, set_to_none=True):
         for g in self.param_groups:
@@ -81,11 +115,14 @@ class HipAdam:
 
     def refresh_lr(self):
         """Upload the groups' current learning rates when they changed since the last upload (call outside a capture; a
-        GraphedTrainer does so before every replay)."""
+        GraphedTrainer does so before every replay).  With a device-side schedule there is nothing to upload."""
+        if self._sched:
+            return
         lrs = [float(self.param_groups[gi]["lr"]) for gi in self._lr_groups]
         if lrs and lrs != self._lr_sent:
             self._lr_dev[:len(lrs)].copy_(torch.tensor(lrs, dtype=torch.float32))
             self._lr_sent = lrs
+            self.uploads += 1
 
     @torch.no_grad()
     def step(self):
@@ -99,6 +136,8 @@ class HipAdam:
                     # already had a .grad): that copy raced with the side stream
                     raise RuntimeError("HipAdam: a table gradient was copied before its scatter had finished; use "
                                        "zero_grad(set_to_none=True) or RN_TRAIN_OVERLAP=0")
+        if self._sched:
+            return self._step_sched()
         entries, keep, written, groups = [], [], [], []
         for gi, g in enumerate(self.param_groups):
             for p in g["params"]:
@@ -126,8 +165,48 @@ class HipAdam:
         self._written = written
         self._hip.mark_written(written)      # the kernel wrote through raw pointers: caches keyed on tensor versions must see it
 
+    def _step_sched(self):
+        """The same update through rn_adam_step_sched: rates and the EMA decision come from the device-side step counter.  A
+        parameter without a gradient this step still rides along when it has a shadow (torch_ema averages every parameter)."""
+        hip, ema = self._hip, self.ema
+        entries, keep, written = [], [], []
+        for g in self.param_groups:
+            for p in g["params"]:
+                shadow = ema.shadow_of(p) if ema is not None else None
+                if p.grad is None and shadow is None:
+                    continue
+                if not p.is_contiguous() or p.dtype != torch.float32:
+                    raise RuntimeError("HipAdam: parameters and gradients must be contiguous fp32")
+                grad = None
+                if p.grad is not None:
+                    grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
+                    if grad.dtype != torch.float32:
+                        raise RuntimeError("HipAdam: parameters and gradients must be contiguous fp32")
+                    keep.append(grad)
+                    written.append(p)
+                st = self.state[p]
+                entries.append((p.data_ptr(), hip.ptr(grad), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), hip.ptr(shadow),
+                                p.numel(), float(g["initial_lr"])))
+        arr = (hip.abi.SchedTensorT * max(len(entries), 1))()
+        for i, e in enumerate(entries):
+            arr[i].param, arr[i].grad, arr[i].exp_avg, arr[i].exp_avg_sq, arr[i].shadow, arr[i].numel, arr[i].lr0 = e
+        if len(entries) > self._lr_dev.numel():
+            raise RuntimeError("HipAdam: more tensors than learning-rate slots")
+        decay, interval = (ema.decay, ema.update_interval) if ema is not None else (0.0, 0)
+        hip.call("rn_adam_step_sched", arr, len(entries), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.gamma,
+                 self.sched_iters, float(decay), int(interval), hip.ptr(self._step), hip.ptr(self._corr), hip.ptr(self._lr_dev),
+                 hip.ptr(ema.device_num_updates) if ema is not None else None, hip.stream())
+        if not torch.cuda.is_current_stream_capturing():
+            self._host_step += 1
+        self._written = written
+        hip.mark_written(written)
+
     def state_dict(self):
-        """torch.optim.Adam's layout: state by running parameter index, one `step` per tensor."""
+        """torch.optim.Adam's layout: state by running parameter index, one `step` per tensor.  With a device-side schedule the
+        groups' `lr` is the rate the next step uses, as the reference's scheduler leaves it."""
+        if self._sched:
+            for g, lr in zip(self.param_groups, self.current_lr()):
+                g["lr"] = lr
         step = self._step.to(torch.float32).reshape(()).clone()
         state, groups, at = {}, [], 0
         for g in self.param_groups:
@@ -151,6 +230,7 @@ class HipAdam:
             steps.append(int(st["step"]))
         if steps:
             self._step.fill_(max(steps))
+            self._host_step = max(steps)
         for g, sg in zip(self.param_groups, sd["param_groups"]):
             g["lr"] = sg.get("lr", g["lr"])
 
@@ -342,19 +422,136 @@ class Trainer:
     # the perceptual term of a lip fine-tuning batch (train_step).  A class default, so that a trainer assembled without
     # __init__ around another trainer's state (bench.py's eager probe) steps as it did before the term existed
     patch_criterion = None
+    # the same for the schedule around the step: such a trainer has no EMA and a constant rate
+    ema = lr_gamma = None
+    _device_schedule = False
 
     def __init__(self, model, opt, lr=5e-3, lr_net=5e-4, update_extra_interval=16, iters=200000, lambda_amb=0.1,
-                 prefer_rocblas=True, capturable=False, patch_criterion=None):
+                 prefer_rocblas=True, capturable=False, patch_criterion=None, ema_decay=None, ema_update_interval=1000, lr_gamma=None):
         # The weight gradients of the 64-wide MLPs are [64 x ~40 000] x [~40 000 x 96] products: all reduction, almost
         # no output.  On this stack hipBLASLt runs them without a K split (132 us each, measured), rocBLAS in 37 us;
         # eight of them per step make that the largest single item of the step.
         if prefer_rocblas and torch.cuda.is_available() and getattr(torch.version, "hip", None):
             torch.backends.cuda.preferred_blas_library("cublas")      # "cublas" selects rocBLAS on ROCm builds
         self.model, self.opt = model, opt
-        self.optimizer = make_optimizer(model, lr, lr_net, capturable=capturable)
+        # the reference's schedule around the step (main.py:204-224), both opt-in: ema_decay (0.95 there) keeps averaged weights,
+        # updated when the step count is a multiple of ema_update_interval; lr_gamma (0.1; 0.05 for --finetune_lips) decays every
+        # group's rate by lr_gamma ** (step / iters).  HipAdam carries both on the device; another optimizer gets them from the host
+        self.ema = self.lr_gamma = None
+        if ema_decay is not None:
+            from radnerf.ema import ParamEma
+            self.ema = ParamEma(model.parameters(), ema_decay, ema_update_interval)
+        if lr_gamma is not None:
+            self.lr_gamma = float(lr_gamma)
+            if not self.lr_gamma > 0 or iters <= 0:
+                raise ValueError("Trainer: lr_gamma needs lr_gamma > 0 and iters > 0")
+        schedule = None if self.lr_gamma is None else (self.lr_gamma, iters)
+        self.optimizer = make_optimizer(model, lr, lr_net, capturable=capturable, schedule=schedule, ema=self.ema)
+        if schedule is not None:
+            for g in self.optimizer.param_groups:
+                g.setdefault("initial_lr", g["lr"])      # the host route's base rate (HipAdam sets it itself)
+        self._device_schedule = isinstance(self.optimizer, HipAdam) and self.optimizer._sched
         self.update_extra_interval, self.iters, self.lambda_amb = update_extra_interval, iters, lambda_amb
         self.patch_criterion = patch_criterion
         self.global_step = 0
+
+    def _host_schedule(self):
+        """After a step of an optimizer that does not carry the schedule itself (the CPU route, RN_ADAM=torch): the rate of the
+        next step (LambdaLR.step()) and the EMA update on its cadence (nerf/utils.py:1018, 1030-1034)."""
+        if self._device_schedule:
+            return
+        if self.lr_gamma is not None:
+            for g in self.optimizer.param_groups:
+                g["lr"] = g["initial_lr"] * self.lr_gamma ** (self.global_step / self.iters)
+        if self.ema is not None and self.global_step % self.ema.update_interval == 0:
+            self.ema.update()
+
+    @contextlib.contextmanager
+    def ema_scope(self):
+        """The model under its averaged weights (ema.store(); ema.copy_to() ... ema.restore(), nerf/utils.py:1233-1235, 1297-1298);
+        the trained weights come back on exit, also on an exception.  On the GPU one launch exchanges weights and shadows
+        (rn_param_swap) -- no third copy of the model -- and the tensors' versions are bumped, so caches of packed weights
+        (FusedState) re-pack.  Without an EMA: nothing happens."""
+        ema = self.ema
+        if ema is None:
+            yield
+            return
+        pairs = ema.pairs()
+        if pairs and pairs[0][0].is_cuda:
+            import ctypes
+            import radnerf_hip as hip
+            n = len(pairs)
+            a = (ctypes.c_void_p * n)(*[p.data_ptr() for p, _ in pairs])
+            b = (ctypes.c_void_p * n)(*[s.data_ptr() for _, s in pairs])
+            numel = (ctypes.c_uint32 * n)(*[p.numel() for p, _ in pairs])
+            if any(not p.is_contiguous() or p.dtype != torch.float32 for p, _ in pairs):
+                raise RuntimeError("ema_scope: parameters must be contiguous fp32")
+
+            def swap():
+                hip.call("rn_param_swap", a, b, numel, n, hip.stream())
+                hip.mark_written([p for p, _ in pairs])
+            swap()
+            try:
+                yield
+            finally:
+                swap()
+        else:
+            ema.store()
+            ema.copy_to()
+            try:
+                yield
+            finally:
+                ema.restore()
+
+    def evaluate(self, train_set, indices, rect=None):
+        """Validation over the frames `indices` of a DeviceTrainSet, as Trainer.evaluate_one_epoch does it (nerf/utils.py:1220-1300):
+        eval mode, the averaged weights when there is an EMA, no_grad; per frame train_set.frame(i), model.render as eval_step
+        calls it (:810-838) and the frame's squared error summed on the device (rn_image_error) into row i of one array -- ONE
+        read-back after the last frame where the reference reads every frame back twice.
+        rect: None, "face" / "lips" (the set's rect of each frame), an [F,4] or [4] integer array (xmin, xmax, ymin, ymax; x along
+        the ROWS).  -> dict(loss = mean over frames of the MSE, psnr = mean over frames of -10 log10(mse_f) (PSNRMeter's averaging),
+        per_frame = [(mse, psnr)], rect_psnr = the same mean over the rect's pixels, None without a rect)."""
+        import numpy as np
+        m = self.model
+        indices = [int(i) for i in indices]
+        if not indices:
+            raise ValueError("evaluate: no frames")
+        dev = next(m.parameters()).device
+        on_gpu = dev.type == "cuda"
+        rects = _eval_rects(train_set, rect, dev)
+        H, W = train_set.H, train_set.W
+        sums = torch.zeros(len(indices), 4, dtype=torch.float64, device=dev)
+        if on_gpu:
+            import radnerf_hip as hip
+            ws = hip.persistent_buffer("image_error", int(hip._lib.rn_image_error_workspace(H, W)), dev)
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad(), self.ema_scope():
+                for k, i in enumerate(indices):
+                    f = train_set.frame(i)
+                    out = m.render(f["rays_o"], f["rays_d"], f["auds"], f["bg_coords"], f["poses"], eye=f["eye"], index=f["index"],
+                                   staged=True, bg_color=f["bg_color"], perturb=False, dt_gamma=self.opt.dt_gamma,
+                                   max_steps=self.opt.max_steps)
+                    pred = out["image"].reshape(H * W, 3)
+                    truth = f["images"].reshape(H * W, 3)
+                    r = None if rects is None else (rects if rects.dim() == 1 else rects[f["index"][0]])
+                    if on_gpu:
+                        pred = pred if pred.dtype == torch.float32 and pred.is_contiguous() else pred.float().contiguous()
+                        hip.call("rn_image_error", hip.ptr(pred), hip.ptr(truth), H, W, hip.ptr(r), hip.ptr(ws), hip.ptr(sums[k]), hip.stream())
+                    else:
+                        sums[k] = _image_error_host(pred, truth, H, W, r)
+        finally:
+            m.train(was_training)
+        s = sums.cpu().numpy()                                   # the one read-back
+        mse = s[:, 0] / s[:, 2]
+        psnr = -10.0 * np.log10(mse)
+        res = dict(loss=float(mse.mean()), psnr=float(psnr.mean()), per_frame=[(float(a), float(b)) for a, b in zip(mse, psnr)],
+                   rect_psnr=None)
+        if rects is not None:
+            with np.errstate(divide="ignore", invalid="ignore"):
+                res["rect_psnr"] = float((-10.0 * np.log10(s[:, 1] / s[:, 3])).mean())
+        return res
 
     def _begin_step(self):
         """What comes before every step: train mode, the occupancy refresh on its cadence, the step count."""
@@ -384,7 +581,9 @@ class Trainer:
 
     def step(self, data):
         m = self._begin_step()
-        return self._forward_backward_update(data, self._device_budget(m)).detach()
+        loss = self._forward_backward_update(data, self._device_budget(m)).detach()
+        self._host_schedule()
+        return loss
 
     def _device_budget(self, m):
         """(device int32 budget, row capacity) for the renderer's one-launch marcher, or None (first window, CPU).  The budget is
@@ -399,6 +598,39 @@ class Trainer:
             t.fill_(budget)
             self._budget_held = held = (budget, t)
         return held[1], budget
+
+
+def _eval_rects(train_set, rect, dev):
+    """evaluate()'s `rect` as an int32 tensor on `dev`: [F,4] (one row per frame), [4] (the same for every frame) or None."""
+    if rect is None:
+        return None
+    if isinstance(rect, str):
+        if rect == "face":
+            return train_set.face_rect.to(dev)
+        if rect == "lips":
+            if train_set.lips_rect is None:
+                raise ValueError("evaluate: the set has no lips rects")
+            held = getattr(train_set, "_lips_dev", None)
+            if held is None or held.device != dev:
+                held = train_set._lips_dev = torch.tensor(train_set.lips_rect, dtype=torch.int32, device=dev)
+            return held
+        raise ValueError(f"evaluate: rect={rect!r} (None, 'face', 'lips' or an integer array)")
+    r = torch.as_tensor(rect).to(dev, torch.int32).contiguous()
+    if r.shape != (4,) and (r.dim() != 2 or r.shape[1] != 4):
+        raise ValueError("evaluate: rect must be [4] or [F,4] = (xmin, xmax, ymin, ymax)")
+    return r
+
+
+def _image_error_host(pred, truth, H, W, rect):
+    """rn_image_error's four numbers with torch operators (the CPU route): the difference in fp32, squares and sums in double."""
+    sq = (pred.float() - truth.float()).double().square().reshape(H, W, 3)
+    out = torch.zeros(4, dtype=torch.float64, device=pred.device)
+    out[0], out[2] = sq.sum(), sq.numel()
+    if rect is not None:
+        xmin, xmax, ymin, ymax = (int(v) for v in rect.tolist())
+        inside = sq[max(xmin, 0):max(xmax, 0), max(ymin, 0):max(ymax, 0)]
+        out[1], out[3] = inside.sum(), inside.numel()
+    return out
 
 
 def _aligned_budget(mean_count):
@@ -430,6 +662,9 @@ class GraphedTrainer(Trainer):
 
     def __init__(self, model, opt, capacity_step=4096, max_graphs=8, **kw):
         super().__init__(model, opt, capturable=True, **kw)
+        if (self.ema is not None or self.lr_gamma is not None) and not self._device_schedule and next(model.parameters()).is_cuda:
+            raise ValueError("GraphedTrainer: ema_decay / lr_gamma ride inside HipAdam's launches; a captured step of another "
+                             "optimizer (RN_ADAM=torch) cannot carry them")
         self.capacity_step = int(capacity_step)
         self.max_graphs = int(max_graphs)
         self._capacity = 0
@@ -493,7 +728,9 @@ class GraphedTrainer(Trainer):
         if self._torso_route():
             route.kernels("train_torso").pin_mean(m)   # a mean set from the host since the last step goes into the scalar the graph reads
         if m.mean_count <= 0 or not next(m.parameters()).is_cuda:        # first window / CPU: the eager step
-            return self._forward_backward_update(data, None).detach()
+            loss = self._forward_backward_update(data, None).detach()
+            self._host_schedule()
+            return loss
         budget = _aligned_budget(m.mean_count)
         step = self.capacity_step
         if not (budget <= self._capacity <= budget + 2 * step):         # keep the capacity while the budget stays inside its window
@@ -534,6 +771,7 @@ class GraphedTrainer(Trainer):
         self._graph.replay()
         if isinstance(self.optimizer, HipAdam):     # the replayed update went through raw pointers (see HipAdam.step)
             self.optimizer._hip.mark_written(self.optimizer._written)
+            self.optimizer.note_replayed()
         m.step_counter[m.local_step % 16].copy_(self._counter)
         m.local_step += 1
         self.replays += 1

@@ -96,6 +96,12 @@ class TrainSetT(C.Structure):
                 ("Fa", _u32), ("C", _u32), ("att", _u32), ("torso_mode", _u32)]
 
 
+class SchedTensorT(C.Structure):
+    c_name = "rn_sched_tensor_t"
+    _fields_ = [("param", _ptr), ("grad", _ptr), ("exp_avg", _ptr), ("exp_avg_sq", _ptr), ("shadow", _ptr), ("numel", _u32),
+                ("lr0", _f32)]
+
+
 # name -> (restype, argtypes).  rn_stream_t and pointers to device or host buffers are void *; pointers to the structs above
 # are typed, as are the few host arrays the callers hand over as ctypes objects.
 FUNCTIONS = {
@@ -257,6 +263,10 @@ FUNCTIONS = {
                                        _ptr, _ptr, _ptr]),
     "rn_train_set_batch_patch": (_int, [_P(TrainSetT), _u32, _u32, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
                                         _ptr, _ptr]),
+    "rn_adam_step_sched": (_int, [_P(SchedTensorT), _u32, _f32, _f32, _f32, _f64, _u32, _f64, _u32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_param_swap": (_int, [_ptr, _ptr, _P(_u32), _u32, _ptr]),
+    "rn_image_error_workspace": (_sz, [_u32, _u32]),
+    "rn_image_error": (_int, [_ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr]),
 }
 
 
