@@ -418,6 +418,49 @@ size_t rn_image_error_workspace(uint32_t H, uint32_t W);
 int rn_image_error(const float *pred, const float *target, uint32_t H, uint32_t W, const int32_t *rect, void *workspace,
                    double *out, rn_stream_t stream);
 
+/*
+ * The perceptual term of lip fine-tuning: lpips.LPIPS(net='alex') in eval mode (nerf/utils.py:649-650, 766, 781; LPIPSMeter
+ * :438-466), forward and the gradient with respect to the prediction (csrc/rn_percep.hip).  The weights are frozen: there is no
+ * weight gradient, and none with respect to the target.
+ *   x' = (x - shift) / scale per channel (normalize != 0: x = 2 x - 1 first);
+ *   five convolutions with bias and ReLU -- 3 -> 64 k 11 s 4 p 2 | 64 -> 192 k 5 p 2 | 192 -> 384 k 3 p 1 | 384 -> 256 k 3 p 1 |
+ *   256 -> 256 k 3 p 1 -- conv2 and conv3 on the 3 x 3 / stride 2 max-pool (no padding, floor) of the tap before them;
+ *   per tap: n(x) = x / (sqrt(sum_c x^2) + 1e-10), d = sum_c lin[c] (n(x) - n(y))^2, mean over the positions; value = sum of the five.
+ * Decisions: at a position whose channels are all zero d|x| / dx is taken as 0 (torch's sqrt backward gives NaN there); the
+ * gradient of a pool window goes to its first maximum in row-major order (torch's choice).
+ * Every layer is an implicit GEMM on the fp32 matrix cores, pred and target as one batch of 2P images, K split over the
+ * workgroups and the partial tiles summed in slice order (the split depends on the shape alone).  No float atomics: two calls on
+ * the same inputs give the same bits.  pred, target and g_pred are read and written through element strides
+ * (image, pixel, channel; a row is `w` pixels), so [P,3,h,w] and the [n,3] rows of train_step both go in without a copy.
+ * Nothing is allocated, read back or synchronised inside a call (capturable).  h, w >= 31.
+ */
+/* Floats of the packed image: forward images of the five layers | data-gradient images of conv2..5 | biases | lin | shift, scale. */
+size_t rn_percep_image_floats(void);
+/* weights, biases, lins: HOST arrays of five device pointers -- conv weights [Cout,Cin,k,k], biases [Cout], lin [Cout]; shift_scale:
+ * device [6] = shift[3] | scale[3].  One launch. */
+int rn_percep_pack(const float *const *weights, const float *const *biases, const float *const *lins, const float *shift_scale,
+                   float *image, rn_stream_t stream);
+/* Bytes of the workspace for P image pairs of h x w (taps, gradient maps, split-K partials); 0 for a shape that is refused. */
+size_t rn_percep_workspace(uint32_t P, uint32_t h, uint32_t w);
+/* Where tap `layer` (0..4) of a forward lives: offset in floats into the workspace and its [channels][2P][oh][ow] dimensions
+ * (images 0..P-1 are pred, P..2P-1 target). */
+int rn_percep_tap(uint32_t P, uint32_t h, uint32_t w, uint32_t layer, size_t *offset_floats, uint32_t *channels, uint32_t *oh,
+                  uint32_t *ow);
+/* Where the five per-tap values of a forward live, [5][P] floats (value_out[p] is their sum over the taps, in tap order). */
+int rn_percep_tap_values(uint32_t P, uint32_t h, uint32_t w, size_t *offset_floats);
+/* value_out [P].  Leaves the taps and d value[p] / d tap (pred half) in the workspace for rn_percep_backward. */
+int rn_percep_forward(const float *image, void *workspace, size_t workspace_bytes, const float *pred, int64_t pred_image_stride,
+                      int64_t pred_pixel_stride, int64_t pred_channel_stride, const float *target, int64_t target_image_stride,
+                      int64_t target_pixel_stride, int64_t target_channel_stride, uint32_t P, uint32_t h, uint32_t w, int normalize,
+                      float *value_out, rn_stream_t stream);
+/* g_pred[p] = upstream[p * upstream_stride] * d value[p] / d pred[p] (upstream: device floats, stride 0 = one factor for all
+ * images; the factor is the last fp32 multiply), every element written -- a pixel no conv1 window covers gets 0.  Same P, h, w,
+ * normalize and workspace as the forward before it.  keep: NULL, or a HOST array of five device pointers (each nullable) that
+ * receive the gradient of `value` with respect to the pred half of each tap, [channels][P][oh][ow] (before the upstream factor). */
+int rn_percep_backward(const float *image, void *workspace, size_t workspace_bytes, const float *upstream, uint32_t upstream_stride,
+                       float *g_pred, int64_t g_image_stride, int64_t g_pixel_stride, int64_t g_channel_stride, uint32_t P,
+                       uint32_t h, uint32_t w, int normalize, float *const *keep, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,7 @@ TABLE = (
     ("RN_AUDIO_TRAIN", "hip", ("hip", "torch"), "`encode_audio` on the GPU: the audio kernels (`radnerf/audio.py`) or the `nn.Module` path"),
     ("RN_LIVE_LIST", "1", ("1", "0"), "fused inference engine: hand the loop the list of live sample slots (`0`: every launch scans all slots)"),
     ("RN_MLP_TRAIN", "hip", ("hip", "torch"), "the per-operator MLP stacks under autograd: `rn_mlp64_*` (`radnerf/mlp_train.py`) or `nn.Linear`"),
+    ("RN_PERCEP", "hip", ("hip", "torch"), "`PerceptualAlex` (`radnerf/percep.py`) on the GPU in fp32: the perceptual kernels (`rn_percep_*`), or the same arithmetic in plain torch (unfold + matmul)"),
     ("RN_SCATTER", "lbc", ("lbc", "binned"), "table-gradient scatter: the line merge for every level, or hashed levels of the first grid summed by table region"),
     ("RN_TORSO_STEP", "device", ("device", "host"), "with `RN_TORSO_TRAIN=fused`: the whole torso step on a device-side count, or the fused layer on the index list the host asks for"),
     ("RN_TORSO_TRAIN", "ops", ("ops", "fused"), "torso layer of a training call: the per-operator layers, or the fused kernels of `radnerf/train_torso.py` (opt-in)"),

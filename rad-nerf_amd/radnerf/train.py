@@ -503,14 +503,17 @@ class Trainer:
             finally:
                 ema.restore()
 
-    def evaluate(self, train_set, indices, rect=None):
+    def evaluate(self, train_set, indices, rect=None, perceptual=None):
         """Validation over the frames `indices` of a DeviceTrainSet, as Trainer.evaluate_one_epoch does it (nerf/utils.py:1220-1300):
         eval mode, the averaged weights when there is an EMA, no_grad; per frame train_set.frame(i), model.render as eval_step
         calls it (:810-838) and the frame's squared error summed on the device (rn_image_error) into row i of one array -- ONE
         read-back after the last frame where the reference reads every frame back twice.
         rect: None, "face" / "lips" (the set's rect of each frame), an [F,4] or [4] integer array (xmin, xmax, ymin, ymax; x along
         the ROWS).  -> dict(loss = mean over frames of the MSE, psnr = mean over frames of -10 log10(mse_f) (PSNRMeter's averaging),
-        per_frame = [(mse, psnr)], rect_psnr = the same mean over the rect's pixels, None without a rect)."""
+        per_frame = [(mse, psnr)], rect_psnr = the same mean over the rect's pixels, None without a rect).
+        perceptual: a criterion such as percep.PerceptualAlex; the dict then also has lpips = mean over frames of
+        perceptual(truth, pred, normalize=True) on [1,3,H,W] views (LPIPSMeter's argument order and averaging, nerf/utils.py:438-466)
+        and lpips_per_frame; the values stay on the device until the same single read-back."""
         import numpy as np
         m = self.model
         indices = [int(i) for i in indices]
@@ -520,7 +523,7 @@ class Trainer:
         on_gpu = dev.type == "cuda"
         rects = _eval_rects(train_set, rect, dev)
         H, W = train_set.H, train_set.W
-        sums = torch.zeros(len(indices), 4, dtype=torch.float64, device=dev)
+        sums = torch.zeros(len(indices), 5 if perceptual is not None else 4, dtype=torch.float64, device=dev)
         if on_gpu:
             import radnerf_hip as hip
             ws = hip.persistent_buffer("image_error", int(hip._lib.rn_image_error_workspace(H, W)), dev)
@@ -540,7 +543,10 @@ class Trainer:
                         pred = pred if pred.dtype == torch.float32 and pred.is_contiguous() else pred.float().contiguous()
                         hip.call("rn_image_error", hip.ptr(pred), hip.ptr(truth), H, W, hip.ptr(r), hip.ptr(ws), hip.ptr(sums[k]), hip.stream())
                     else:
-                        sums[k] = _image_error_host(pred, truth, H, W, r)
+                        sums[k, :4] = _image_error_host(pred, truth, H, W, r)
+                    if perceptual is not None:
+                        nchw = lambda t: t.reshape(1, H, W, 3).permute(0, 3, 1, 2)
+                        sums[k, 4] = perceptual(nchw(truth.float()), nchw(pred.float()), normalize=True).reshape(())
         finally:
             m.train(was_training)
         s = sums.cpu().numpy()                                   # the one read-back
@@ -551,6 +557,8 @@ class Trainer:
         if rects is not None:
             with np.errstate(divide="ignore", invalid="ignore"):
                 res["rect_psnr"] = float((-10.0 * np.log10(s[:, 1] / s[:, 3])).mean())
+        if perceptual is not None:
+            res["lpips"], res["lpips_per_frame"] = float(s[:, 4].mean()), [float(v) for v in s[:, 4]]
         return res
 
     def _begin_step(self):

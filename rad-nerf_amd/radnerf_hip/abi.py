@@ -12,6 +12,7 @@ does not read include/ at run time.
 import ctypes as C
 
 _int, _u32, _f32, _f64, _sz, _ptr, _P = C.c_int, C.c_uint32, C.c_float, C.c_double, C.c_size_t, C.c_void_p, C.POINTER
+_i64 = C.c_int64
 
 # ====================================================================================================== radnerf_hip.h
 RN_F32, RN_F16 = 0, 1
@@ -267,6 +268,13 @@ FUNCTIONS = {
     "rn_param_swap": (_int, [_ptr, _ptr, _P(_u32), _u32, _ptr]),
     "rn_image_error_workspace": (_sz, [_u32, _u32]),
     "rn_image_error": (_int, [_ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr, _ptr]),
+    "rn_percep_image_floats": (_sz, []),
+    "rn_percep_pack": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_percep_workspace": (_sz, [_u32, _u32, _u32]),
+    "rn_percep_tap": (_int, [_u32, _u32, _u32, _u32, _P(_sz), _P(_u32), _P(_u32), _P(_u32)]),
+    "rn_percep_tap_values": (_int, [_u32, _u32, _u32, _P(_sz)]),
+    "rn_percep_forward": (_int, [_ptr, _ptr, _sz, _ptr, _i64, _i64, _i64, _ptr, _i64, _i64, _i64, _u32, _u32, _u32, _int, _ptr, _ptr]),
+    "rn_percep_backward": (_int, [_ptr, _ptr, _sz, _ptr, _u32, _ptr, _i64, _i64, _i64, _u32, _u32, _u32, _int, _ptr, _ptr]),
 }
 
 
