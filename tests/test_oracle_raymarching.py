@@ -222,6 +222,16 @@ def test_composite_train_forward_against_cumprod_and_backward_against_autograd(p
         o, k = rays[i, 1], rays[i, 2]
         assert np.all(ga[o:o + k] == g_am[rays[i, 0]])
 
+    # T_thresh = 1e-4: the early-termination branch of both directions, which the cumprod above never takes, through the
+    # float64 restatement with its per-element bounds (tests/compref64.py; every case of it is in test_compref64.py)
+    import composite_cases as cc
+    import compref64
+    from test_compref64 import oracle_train_backward, oracle_train_forward
+    case = cc.train_case("N257-T0.0001")
+    assert compref64.train_reference(case)["truncated"] > 100
+    compref64.check_train_forward(case, oracle_train_forward(po, case))
+    compref64.check_train_backward(case, oracle_train_backward(po, case))
+
 
 def test_march_rays_train_backward_against_autograd(po, rng):
     N, S = 40, 6
