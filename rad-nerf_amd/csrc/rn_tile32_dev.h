@@ -1,6 +1,7 @@
 // rn_tile32_dev.h -- the fp32 matrix-core machine on 32-sample tiles, shared by the inference kernel (rn_fused.hip), the
-// fused training network (rn_train_head.hip; rn_train_head_f16.hip keeps the tiles and their VALU rows), the torso layer
-// (rn_torso.hip, rn_train_torso.hip) and the per-MLP training kernels (rn_mlp.hip).
+// fused training network (rn_train_head.hip; rn_train_head_f16.hip and the backward walk both arithmetics share,
+// rn_train_head_walk_dev.h, keep the tiles and their VALU rows), the torso layer (rn_torso.hip, rn_train_torso.hip) and
+// the per-MLP training kernels (rn_mlp.hip).
 //
 // One wavefront owns 32 samples.  v_mfma_f32_32x32x2_f32 puts the output row on the register index and the sample on the
 // lane, so the accumulators of a 64-row layer (two row tiles of 16 registers) ARE the B operand of the next layer; the k

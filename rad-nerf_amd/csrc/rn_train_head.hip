@@ -18,16 +18,16 @@
 //    with rn_mlp.hip); k_train_wreduce folds its per-workgroup partial sums into the nn.Linear layout.  The columns of the
 //    per-call constants (audio code, eye, individual code) ride along as one more feature that is 1 for every sample: its
 //    gradient column is the bias gradient, from which k_train_const derives the constants' and their columns' gradients.
-// The table gradient of the two grids is rn_grid_scatter.hip.
-#include "rn_train_head_dev.h"
+// The table gradient of the two grids is rn_grid_scatter.hip.  The text of the backward walk is rn_train_head_walk_dev.h, shared
+// with the 16-bit arithmetic (rn_train_head_f16.hip); here are the fp32 contractions it calls.
+#include "rn_train_head_walk_dev.h"
 #include "rn_wgrad_dev.h"
-
-#include <stdlib.h>
 
 namespace rn {
 namespace th {
 
-// The weight image, the workspace and the parameter blocks: rn_train_head_dev.h (shared with the 16-bit arithmetic).
+// The weight image, the workspace, the parameter blocks and the host side of pack / forward / backward: rn_train_head_dev.h
+// (shared with the 16-bit arithmetic).
 __global__ void __launch_bounds__(256) k_train_pack(RawW w, const float *__restrict__ enc_a, const float *__restrict__ eye,
                                                     const float *__restrict__ ind_code, const int64_t *__restrict__ ind_index,
                                                     float *__restrict__ image) {
@@ -37,8 +37,11 @@ __global__ void __launch_bounds__(256) k_train_pack(RawW w, const float *__restr
     image[e] = train_image_elem(w, enc_a, eye, ind_code, e);
 }
 
-template <int GX, int GA>   // gather rounds in flight per wave (xyz grid / ambient grid): independent load chains hide each other's latency
 __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
+    // gather rounds in flight per wave (xyz grid / ambient grid).  Measured at 62 k samples (tools/bench_train_head.py): <1,1>
+    // 82.5 us, <1,2> 82.4, <2,2> 84.5, <2,4> 85.9 -- with one tile per wave the two waves of a SIMD already hide each other's
+    // gathers; more rounds in flight only cost registers
+    constexpr int GX = 1, GA = 1;
     __shared__ __attribute__((aligned(16))) float lds[kPacked + kBias];
     __shared__ LevelPlan plan_x[16], plan_w[16];
     const uint32_t M = live_count(p.M, p.m_dev);
@@ -186,8 +189,7 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
             float *st = ws.sh + (size_t)tile * kTile8;
 #pragma unroll
             for (int s = 0; s < 8; s++) {
-                const uint32_t m = 0u - (uint32_t)h;   // lane half h supplies k = 2 s + h (bit-select: no dynamic indexing of sh[])
-                const float b = __uint_as_float((__float_as_uint(sh[2 * s]) & ~m) | (__float_as_uint(sh[2 * s + 1]) & m));
+                const float b = select_h(sh[2 * s], sh[2 * s + 1], h);   // lane half h supplies k = 2 s + h
                 step32(a1, lds + OFF_C0, s, lane_off, b);
                 st[s * 64 + lane] = b;
             }
@@ -207,121 +209,32 @@ __global__ void __launch_bounds__(kThreads) k_train_fwd(FwdParams p) {
     }
 }
 
-__global__ void __launch_bounds__(kThreads) k_train_bwd(BwdParams p) {
-    __shared__ __attribute__((aligned(16))) float lds[kBwd];
-    const uint32_t M = live_count(p.M, p.m_dev);
-    const uint32_t n_tiles = (M + 31u) >> 5;
-    if (blockIdx.x * kWaves >= n_tiles) return;
-    for (int i = threadIdx.x; i < kBwd / 4; i += kThreads)
-        reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image + kPacked)[i];
-    __syncthreads();
-    const Ws ws = make_ws(p.ws, p.M);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int lane_off = h * 64 + j * 2;
+// The fp32 arithmetic of the backward tile walk (rn_train_head_walk_dev.h): v_mfma_f32_32x32x2_f32, one float of B per lane and
+// step, k in kmap order.  LDS = transposed image | narrow rows.
+struct ArithF32 {
+    static constexpr int kLdsBwd = kBwd;
+    static constexpr int RT_C1 = N_C1, RT_S2R = N_S2R, RT_A2 = N_A2;
+    static constexpr int WT_C0 = T_C0, WT_S2 = T_S2, WT_S1 = T_S1, WT_S0 = T_S0, WT_A1 = T_A1;   // floats into the LDS
+    const float *lds;
+    int lane_off, j, h;
+    __device__ ArithF32(const float *l, int j_, int h_) : lds(l), lane_off(h_ * 64 + j_ * 2), j(j_), h(h_) {}
 
-    for (uint32_t tile = blockIdx.x * kWaves + wave; tile < n_tiles; tile += gridDim.x * kWaves) {
-        const uint32_t sample = tile * 32 + j;
-        const bool live = sample < M;
-        Acc32 g, w;
-        // ---- colour net: sigmoid', last layer transposed, ReLU mask
-        {
-            float d[3] = {0.0f, 0.0f, 0.0f};
-            if (live) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float y = p.rgbs[3 * (size_t)sample + c];
-                    d[c] = p.g_rgbs[3 * (size_t)sample + c] * ((1.0f - y) * y);
-                }
-            }
-            if (h == 0) {
-#pragma unroll
-                for (int c = 0; c < 3; c++) ws.dprec[3 * (size_t)sample + c] = d[c];
-            }
-            acc_zero(g);
-            valu_out_T<3>(g, lds + N_C1, h, d);
-        }
-        relu_mask(g, ws.hc0 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dzc0 + (size_t)tile * kTile32, g, lane);
-        acc_zero(w);
-        layer_from_acc(w, g, lds + T_C0, lane_off);       // d geo_feat
-        tile_store(ws.dgeo + (size_t)tile * kTile32, w, lane);
-        // ---- sigma net
-        {
-            float d[1] = {0.0f};
-            if (live) d[0] = p.g_sigmas[sample] * expf(fminf(fmaxf(ws.sraw[sample], -15.0f), 15.0f));   // activation.py:13-17
-            if (h == 0) ws.dsraw[sample] = d[0];
-            acc_zero(g);
-            layer_from_acc(g, w, lds + T_S2, lane_off);
-            valu_out_T<1>(g, lds + N_S2R, h, d);
-        }
-        relu_mask(g, ws.hs1 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dzs1 + (size_t)tile * kTile32, g, lane);
-        acc_zero(w);
-        layer_from_acc(w, g, lds + T_S1, lane_off);
-        relu_mask(w, ws.hs0 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dzs0 + (size_t)tile * kTile32, w, lane);
-        // d [enc_x | enc_w]: row tile 0 = enc_x, row tile 1 = enc_w, register 2 q + c of half h = (level 2 q + h, channel c)
-        f32x16 x0, x1;
-#pragma unroll
-        for (int r = 0; r < 16; r++) { x0[r] = 0.0f; x1[r] = 0.0f; }
-#pragma unroll
-        for (int s = 0; s < 32; s++) {
-            const float2 wv = *reinterpret_cast<const float2 *>(lds + T_S0 + s * kStep + lane_off);
-            const float b = w.v[s >> 4][s & 15];
-            x0 = mfma32(wv.x, b, x0);
-            x1 = mfma32(wv.y, b, x1);
-        }
-        // ---- ambient grid: feature gradients out (level-major), input gradient = sum_l g . dy_dx (gridencoder.cu:342-368);
-        // the encoder sees (ambient + 1) / 2 (gridencoder/grid.py:151, bound = 1): a factor 1/2 on the way back
-        float da[2] = {0.0f, 0.0f};
-        {
-            const float *dw = ws.dw + (size_t)tile * kTile32;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const float g0 = x1[2 * q], g1 = x1[2 * q + 1];
-                const float d00 = dw[(4 * q + 0) * 64 + lane], d01 = dw[(4 * q + 1) * 64 + lane];
-                const float d10 = dw[(4 * q + 2) * 64 + lane], d11 = dw[(4 * q + 3) * 64 + lane];
-                da[0] = __builtin_fmaf(g0, d00, da[0]); da[0] = __builtin_fmaf(g1, d01, da[0]);
-                da[1] = __builtin_fmaf(g0, d10, da[1]); da[1] = __builtin_fmaf(g1, d11, da[1]);
-                if (live) *reinterpret_cast<float2 *>(p.g_enc_w + ((size_t)(2 * q + h) * p.M + sample) * 2) = make_float2(g0, g1);
-            }
-            da[0] += __shfl_xor(da[0], 32, 64);
-            da[1] += __shfl_xor(da[1], 32, 64);
-        }
-        // ---- ambient net: + the direct gradients of the ambient output, tanh'
-        {
-            float d[2] = {0.0f, 0.0f};
-            if (live) {
-                const float a0v = p.ambient[2 * (size_t)sample], a1v = p.ambient[2 * (size_t)sample + 1];
-                float t0 = 0.5f * da[0], t1 = 0.5f * da[1];
-                if (p.g_ambient) { t0 += p.g_ambient[2 * (size_t)sample]; t1 += p.g_ambient[2 * (size_t)sample + 1]; }
-                if (p.g_ambient_abs) {   // d |a| = sign(a), 0 at 0
-                    const float ga = p.g_ambient_abs[sample];
-                    t0 += a0v > 0.0f ? ga : (a0v < 0.0f ? -ga : 0.0f);
-                    t1 += a1v > 0.0f ? ga : (a1v < 0.0f ? -ga : 0.0f);
-                }
-                d[0] = t0 * (1.0f - a0v * a0v);
-                d[1] = t1 * (1.0f - a1v * a1v);
-            }
-            if (h == 0) { ws.daraw[2 * (size_t)sample] = d[0]; ws.daraw[2 * (size_t)sample + 1] = d[1]; }
-            acc_zero(g);
-            valu_out_T<2>(g, lds + N_A2, h, d);
-        }
-        relu_mask(g, ws.ha1 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dza1 + (size_t)tile * kTile32, g, lane);
-        acc_zero(w);
-        layer_from_acc(w, g, lds + T_A1, lane_off);
-        relu_mask(w, ws.ha0 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dza0 + (size_t)tile * kTile32, w, lane);
-#pragma unroll
-        for (int s = 0; s < 32; s++) x0 = mfma32(lds[T_A0 + s * 64 + h * 32 + j], w.v[s >> 4][s & 15], x0);
-        if (live) {
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                *reinterpret_cast<float2 *>(p.g_enc_x + ((size_t)(2 * q + h) * p.M + sample) * 2) = make_float2(x0[2 * q], x0[2 * q + 1]);
-        }
+    static __device__ __forceinline__ void fill_bwd(float *lds, const float *image) {
+        for (int i = threadIdx.x; i < kBwd / 4; i += kThreads) reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(image + kPacked)[i];
     }
+    __device__ __forceinline__ void layer_T(Acc32 &out, const Acc32 &dy, int at) const {
+        acc_zero(out);
+        layer_from_acc(out, dy, lds + at, lane_off);
+    }
+    __device__ __forceinline__ void a0_T(f32x16 &x0, const Acc32 &dz) const {
+#pragma unroll
+        for (int s = 0; s < 32; s++) x0 = mfma32(lds[T_A0 + s * 64 + h * 32 + j], dz.v[s >> 4][s & 15], x0);
+    }
+};
+
+__global__ void __launch_bounds__(kThreads) k_train_bwd(BwdParams p) {
+    __shared__ __attribute__((aligned(16))) float lds[ArithF32::kLdsBwd];
+    train_bwd_tiles<ArithF32>(p, lds);
 }
 
 // ---- input gradients (--train_camera) -----------------------------------------------------------------------------------
@@ -645,53 +558,27 @@ size_t rn_train_head_wgrad_workspace(void) { return ((size_t)kJobs * kWPartsMax 
 
 int rn_train_head_pack(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_code, float *image,
                        rn_stream_t stream) {
-    if (int rc = check_w(w)) return rc;
-    RN_REQUIRE(image && ((uintptr_t)image & 15u) == 0, "train_head_pack: image must be 16-byte aligned");
-    RN_REQUIRE((enc_a || w->audio_dim == 0) && (eye || !w->has_eye) && (ind_code || w->ind_dim == 0), "train_head_pack: null constant");
-    hipLaunchKernelGGL(k_train_pack, dim3(div_up(kImage, 256)), dim3(256), 0, as_stream(stream), raw_w(w), enc_a, eye, ind_code,
-                       static_cast<const int64_t *>(nullptr), image);
-    return check_launch("train_head_pack");
+    return pack(k_train_pack, kImage, "train_head_pack", w, enc_a, eye, ind_code, nullptr, false, image, stream);
 }
 
 int rn_train_head_pack_row(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_table,
                            const int64_t *ind_index, float *image, rn_stream_t stream) {
-    if (int rc = check_w(w)) return rc;
-    RN_REQUIRE(image && ((uintptr_t)image & 15u) == 0, "train_head_pack_row: image must be 16-byte aligned");
-    RN_REQUIRE((enc_a || w->audio_dim == 0) && (eye || !w->has_eye) && ind_table && ind_index && w->ind_dim, "train_head_pack_row: null constant");
-    hipLaunchKernelGGL(k_train_pack, dim3(div_up(kImage, 256)), dim3(256), 0, as_stream(stream), raw_w(w), enc_a, eye, ind_table, ind_index,
-                       image);
-    return check_launch("train_head_pack_row");
+    return pack(k_train_pack, kImage, "train_head_pack_row", w, enc_a, eye, ind_table, ind_index, true, image, stream);
 }
 
 int rn_train_head_forward(const float *xyzs, const float *dirs, uint32_t M, const int32_t *m_dev, const rn_grid_t *grid_xyz,
                           const rn_grid_t *grid_amb, const float *image, float bound, float *sigmas, float *rgbs,
                           float *ambient, float *ambient_abs, float *xn, float *wn, float *workspace, rn_stream_t stream) {
-    if (M == 0) return RN_OK;
-    if (int rc = check_train_grid(grid_xyz, 3, "train_head: xyz")) return rc;
-    if (int rc = check_train_grid(grid_amb, 2, "train_head: ambient")) return rc;
-    RN_REQUIRE(xyzs && dirs && image && sigmas && rgbs && ambient && xn && wn && workspace, "train_head_forward: null pointer");
-    RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_head_forward: image / workspace must be 16-byte aligned");
-    FwdParams p{xyzs, dirs, M, m_dev, grid_args(grid_xyz), grid_args(grid_amb), image, bound, sigmas, rgbs, ambient, ambient_abs, xn, wn, workspace};
-    const uint32_t blocks = tile_blocks((M + 31u) >> 5, kWaves, 1);
-    static int groups = -1;
-    if (groups < 0) { const char *e = getenv("RN_TRAIN_FWD_GROUPS"); groups = e ? atoi(e) : 11; }
-    // measured at 62 k samples (tools/bench_train_head.py): <1,1> 82.5 us, <1,2> 82.4, <2,2> 84.5, <2,4> 85.9 -- with one tile per
-    // wave the two waves of a SIMD already hide each other's gathers; more rounds in flight only cost registers
-    if (groups == 12) hipLaunchKernelGGL((k_train_fwd<1, 2>), dim3(blocks), dim3(kThreads), 0, as_stream(stream), p);
-    else hipLaunchKernelGGL((k_train_fwd<1, 1>), dim3(blocks), dim3(kThreads), 0, as_stream(stream), p);
-    return check_launch("train_head_forward");
+    return forward(k_train_fwd, "train_head_forward", xyzs, dirs, M, m_dev, grid_xyz, grid_amb, image, bound, sigmas, rgbs, ambient,
+                   ambient_abs, xn, wn, workspace, stream);
 }
 
 int rn_train_head_backward(const float *grad_sigmas, const float *grad_rgbs, const float *grad_ambient,
                            const float *grad_ambient_abs, const float *rgbs, const float *ambient, uint32_t M,
                            const int32_t *m_dev, const float *image, float *workspace, float *grad_enc_x, float *grad_enc_w,
                            rn_stream_t stream) {
-    if (M == 0) return RN_OK;
-    RN_REQUIRE(grad_sigmas && grad_rgbs && rgbs && ambient && image && workspace && grad_enc_x && grad_enc_w, "train_head_backward: null pointer");
-    RN_REQUIRE(((uintptr_t)grad_enc_x & 7u) == 0 && ((uintptr_t)grad_enc_w & 7u) == 0, "train_head_backward: feature gradients must be 8-byte aligned");
-    BwdParams p{grad_sigmas, grad_rgbs, grad_ambient, grad_ambient_abs, rgbs, ambient, M, m_dev, image, workspace, grad_enc_x, grad_enc_w};
-    hipLaunchKernelGGL(k_train_bwd, dim3(tile_blocks((M + 31u) >> 5, kWaves, 1)), dim3(kThreads), 0, as_stream(stream), p);
-    return check_launch("train_head_backward");
+    return backward(k_train_bwd, false, "train_head_backward", grad_sigmas, grad_rgbs, grad_ambient, grad_ambient_abs, rgbs, ambient, M,
+                    m_dev, image, workspace, grad_enc_x, grad_enc_w, stream);
 }
 
 int rn_train_head_input_grads(const float *xn, const float *dirs, const float *grad_enc_x, uint32_t M, const int32_t *m_dev,

@@ -1,8 +1,9 @@
 // rn_train_head_dev.h -- what the two arithmetics of the fused training network share (rn_train_head.hip: fp32 matrix cores;
 // rn_train_head_f16.hip: 16-bit operands, fp32 sums): the layout of the fp32 weight image of a step and its elements, the
-// workspace of native tiles, and the parameter blocks of the forward and the backward kernel.  Both arithmetics write the same
-// fp32 image and the same fp32 workspace, so everything downstream of the two network kernels (weight gradients, input
-// gradients, table scatters) reads either one's results.
+// workspace of native tiles, the parameter blocks of the forward and the backward kernel, and the host side of the pack,
+// forward and backward entries.  Both arithmetics write the same fp32 image and the same fp32 workspace, so everything
+// downstream of the two network kernels (weight gradients, input gradients, table scatters) reads either one's results; the
+// tile walk that writes the workspace is rn_train_head_walk_dev.h.
 #pragma once
 
 #include "rn_nerf_image_dev.h"
@@ -131,6 +132,48 @@ static inline int check_w(const rn_nerf_weights_t *w) {
                "train_head: null weight pointer");
     RN_REQUIRE(w->has_eye <= 1, "train_head: has_eye must be 0 or 1");
     return RN_OK;
+}
+
+// ---- host side of the pack / forward / backward entries -------------------------------------------------------------------
+// Written once; an entry hands over its arithmetic's kernel (a kernel is launched from its own translation unit) and its
+// name `what` for the messages.
+typedef void (*PackKernel)(RawW, const float *, const float *, const float *, const int64_t *, float *);
+
+// elems: threads of the pack launch.  row: `ind` is the table individual_codes, ind_index picks its row on the device.
+static inline int pack(PackKernel kernel, int elems, const char *what, const rn_nerf_weights_t *w, const float *enc_a, const float *eye,
+                       const float *ind, const int64_t *ind_index, bool row, float *image, rn_stream_t stream) {
+    if (int rc = check_w(w)) return rc;
+    RN_REQUIRE(image && ((uintptr_t)image & 15u) == 0, "%s: image must be 16-byte aligned", what);
+    RN_REQUIRE((enc_a || w->audio_dim == 0) && (eye || !w->has_eye) && (ind || w->ind_dim == 0), "%s: null constant", what);
+    RN_REQUIRE(!row || (ind && ind_index && w->ind_dim), "%s: the code table and its row index are required", what);
+    hipLaunchKernelGGL(kernel, dim3(div_up(elems, 256)), dim3(256), 0, as_stream(stream), raw_w(w), enc_a, eye, ind, ind_index, image);
+    return check_launch(what);
+}
+
+static inline int forward(void (*kernel)(FwdParams), const char *what, const float *xyzs, const float *dirs, uint32_t M, const int32_t *m_dev,
+                          const rn_grid_t *grid_xyz, const rn_grid_t *grid_amb, const float *image, float bound, float *sigmas, float *rgbs,
+                          float *ambient, float *ambient_abs, float *xn, float *wn, float *workspace, rn_stream_t stream) {
+    if (M == 0) return RN_OK;
+    if (int rc = check_train_grid(grid_xyz, 3, "train_head: xyz")) return rc;
+    if (int rc = check_train_grid(grid_amb, 2, "train_head: ambient")) return rc;
+    RN_REQUIRE(xyzs && dirs && image && sigmas && rgbs && ambient && xn && wn && workspace, "%s: null pointer", what);
+    RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "%s: image / workspace must be 16-byte aligned", what);
+    FwdParams p{xyzs, dirs, M, m_dev, grid_args(grid_xyz), grid_args(grid_amb), image, bound, sigmas, rgbs, ambient, ambient_abs, xn, wn, workspace};
+    hipLaunchKernelGGL(kernel, dim3(tile_blocks((M + 31u) >> 5, kWaves, 1)), dim3(kThreads), 0, as_stream(stream), p);
+    return check_launch(what);
+}
+
+// image16: the backward kernel copies 16-bit images out of `image` 16 bytes at a time
+static inline int backward(void (*kernel)(BwdParams), bool image16, const char *what, const float *grad_sigmas, const float *grad_rgbs,
+                           const float *grad_ambient, const float *grad_ambient_abs, const float *rgbs, const float *ambient, uint32_t M,
+                           const int32_t *m_dev, const float *image, float *workspace, float *grad_enc_x, float *grad_enc_w, rn_stream_t stream) {
+    if (M == 0) return RN_OK;
+    RN_REQUIRE(grad_sigmas && grad_rgbs && rgbs && ambient && image && workspace && grad_enc_x && grad_enc_w, "%s: null pointer", what);
+    RN_REQUIRE(!image16 || ((uintptr_t)image & 15u) == 0, "%s: image must be 16-byte aligned", what);
+    RN_REQUIRE(((uintptr_t)grad_enc_x & 7u) == 0 && ((uintptr_t)grad_enc_w & 7u) == 0, "%s: feature gradients must be 8-byte aligned", what);
+    BwdParams p{grad_sigmas, grad_rgbs, grad_ambient, grad_ambient_abs, rgbs, ambient, M, m_dev, image, workspace, grad_enc_x, grad_enc_w};
+    hipLaunchKernelGGL(kernel, dim3(tile_blocks((M + 31u) >> 5, kWaves, 1)), dim3(kThreads), 0, as_stream(stream), p);
+    return check_launch(what);
 }
 
 }  // namespace th

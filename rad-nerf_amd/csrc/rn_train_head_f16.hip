@@ -1,9 +1,9 @@
 // rn_train_head_f16.hip -- the fused training network with 16-bit matrix products (opt-in: RN_TRAIN_MLP=f16).
 //
 // C ABI: include/radnerf_train.h (the *_h16 entries).  Same computation, same tile ownership and same saved state as
-// rn_train_head.hip -- one wavefront owns 32 samples, a layer's accumulators (sample on the lane, output row on the register
-// index) are the next layer's B operand, everything the backward pass and the weight gradients read is stored as fp32 native
-// tiles in the workspace of rn_train_head_dev.h -- but the contractions of the 64-row layers run on v_mfma_f32_32x32x8f16
+// rn_train_head.hip (the backward walk is the same text, rn_train_head_walk_dev.h) -- one wavefront owns 32 samples, a layer's
+// accumulators (sample on the lane, output row on the register index) are the next layer's B operand, everything the backward
+// pass and the weight gradients read is stored as fp32 native tiles in the workspace of rn_train_head_dev.h -- but the contractions of the 64-row layers run on v_mfma_f32_32x32x8f16
 // (K = 8 only: DESIGN.md section 3 on the K = 16 form) with fp32 accumulators.  This is the arithmetic of the reference's `-O`
 // runs for its eight nn.Linear layers (nerf/utils.py:1168-1172: fp16 operands, fp32 sums).
 //
@@ -20,7 +20,7 @@
 //  * fp32 as in rn_train_head.hip: gathers and interpolation, dy_dx of the ambient grid, SH, tanh / trunc_exp / sigmoid, the
 //    narrow layers (VALU rows), the first-layer biases of the per-call constants, every saved tile, the pre-activation
 //    gradients and the level-major feature gradients.  No float atomics: two runs give the same bits.
-#include "rn_train_head_dev.h"
+#include "rn_train_head_walk_dev.h"
 
 namespace rn {
 namespace th {
@@ -122,11 +122,6 @@ __device__ __forceinline__ f16x4 acc_frag4(const Acc32 &in, int rt, int g) {
 __device__ __forceinline__ void hlayer_from_acc(Acc32 &out, const Acc32 &in, const _Float16 *wl, int kb0, int lane_off4) {
 #pragma unroll
     for (int b = 0; b < 8; b++) hblock(out, wl, kb0 + b, lane_off4, acc_frag4(in, b >> 2, b & 3));
-}
-
-__device__ __forceinline__ float select_h(float lo, float hi, int h) {   // h ? hi : lo without a dynamic register index
-    const uint32_t m = 0u - (uint32_t)h;
-    return __uint_as_float((__float_as_uint(lo) & ~m) | (__float_as_uint(hi) & m));
 }
 
 // LDS of the forward kernel (floats): 16-bit forward image | narrow fp32 rows | first-layer biases
@@ -343,135 +338,41 @@ __device__ __forceinline__ void hlayer_T(Acc32 &out, const Acc32 &dy, const _Flo
     }
 }
 
-// LDS of the backward kernel (floats): transposed 16-bit image | narrow fp32 rows (N_C1 | N_S2R | N_A2 of the fp32 image)
-constexpr int LB_C1 = kHBwdFloats, LB_S2R = LB_C1 + 192, LB_A2 = LB_S2R + 64, kLdsBwd = LB_A2 + 128;
+// The 16-bit arithmetic of the backward tile walk (rn_train_head_walk_dev.h).
+// LDS (floats): transposed 16-bit image | narrow fp32 rows (N_C1 | N_S2R | N_A2 of the fp32 image, in that order).
+struct ArithF16 {
+    static constexpr int RT_C1 = kHBwdFloats, RT_S2R = RT_C1 + 192, RT_A2 = RT_S2R + 64, kLdsBwd = RT_A2 + 128;
+    static constexpr int WT_C0 = HT_C0, WT_S2 = HT_S2, WT_S1 = HT_S1, WT_S0 = HT_S0, WT_A1 = HT_A1;   // first k-block of the layer
+    const _Float16 *wl;
+    int lane_off4;
+    __device__ ArithF16(const float *lds, int j, int h) : wl(reinterpret_cast<const _Float16 *>(lds)), lane_off4((h * 32 + j) * 4) {}
 
-__global__ void __launch_bounds__(kThreads) k_train_bwd_h16(BwdParams p) {
-    __shared__ __attribute__((aligned(16))) float lds[kLdsBwd];
-    const uint32_t M = live_count(p.M, p.m_dev);
-    const uint32_t n_tiles = (M + 31u) >> 5;
-    if (blockIdx.x * kWaves >= n_tiles) return;
-    for (int i = threadIdx.x; i < kHBwdFloats / 4; i += kThreads)
-        reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(p.image + kHBwdOff)[i];
-    if (threadIdx.x < 384) lds[LB_C1 + threadIdx.x] = p.image[kPacked + N_C1 + threadIdx.x];
-    __syncthreads();
-    const Ws ws = make_ws(p.ws, p.M);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 31, h = lane >> 5;
-    const int lane_off4 = (h * 32 + j) * 4;
-    const _Float16 *wl = reinterpret_cast<const _Float16 *>(lds);
-
-    for (uint32_t tile = blockIdx.x * kWaves + wave; tile < n_tiles; tile += gridDim.x * kWaves) {
-        const uint32_t sample = tile * 32 + j;
-        const bool live = sample < M;
-        Acc32 g, w;
-        // ---- colour net: sigmoid', last layer transposed (fp32 rows), ReLU mask
-        {
-            float d[3] = {0.0f, 0.0f, 0.0f};
-            if (live) {
+    static __device__ __forceinline__ void fill_bwd(float *lds, const float *image) {
+        for (int i = threadIdx.x; i < kHBwdFloats / 4; i += kThreads)
+            reinterpret_cast<float4 *>(lds)[i] = reinterpret_cast<const float4 *>(image + kHBwdOff)[i];
+        if (threadIdx.x < 384) lds[RT_C1 + threadIdx.x] = image[kPacked + N_C1 + threadIdx.x];
+    }
+    __device__ __forceinline__ void layer_T(Acc32 &out, const Acc32 &dy, int kb0) const { hlayer_T(out, dy, wl, kb0, lane_off4); }
+    // a 32-row layer, scaled like the others, added after the unscaling
+    __device__ __forceinline__ void a0_T(f32x16 &x0, const Acc32 &dz) const {
+        float scale, inv;
+        if (tile_scale(dz, scale, inv)) {
+            f32x16 xa = zero16();
 #pragma unroll
-                for (int c = 0; c < 3; c++) {
-                    const float y = p.rgbs[3 * (size_t)sample + c];
-                    d[c] = p.g_rgbs[3 * (size_t)sample + c] * ((1.0f - y) * y);
-                }
-            }
-            if (h == 0) {
+            for (int b = 0; b < 8; b++)
+                xa = mfma8h(*reinterpret_cast<const f16x4 *>(wl + kHT_A0 + b * kHB32 + lane_off4), acc_frag4(dz, b >> 2, b & 3, scale), xa);
 #pragma unroll
-                for (int c = 0; c < 3; c++) ws.dprec[3 * (size_t)sample + c] = d[c];
-            }
-            acc_zero(g);
-            valu_out_T<3>(g, lds + LB_C1, h, d);
-        }
-        relu_mask(g, ws.hc0 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dzc0 + (size_t)tile * kTile32, g, lane);
-        hlayer_T(w, g, wl, HT_C0, lane_off4);             // d geo_feat
-        tile_store(ws.dgeo + (size_t)tile * kTile32, w, lane);
-        // ---- sigma net
-        {
-            float d[1] = {0.0f};
-            if (live) d[0] = p.g_sigmas[sample] * expf(fminf(fmaxf(ws.sraw[sample], -15.0f), 15.0f));   // activation.py:13-17
-            if (h == 0) ws.dsraw[sample] = d[0];
-            hlayer_T(g, w, wl, HT_S2, lane_off4);
-            valu_out_T<1>(g, lds + LB_S2R, h, d);
-        }
-        relu_mask(g, ws.hs1 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dzs1 + (size_t)tile * kTile32, g, lane);
-        hlayer_T(w, g, wl, HT_S1, lane_off4);
-        relu_mask(w, ws.hs0 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dzs0 + (size_t)tile * kTile32, w, lane);
-        // d [enc_x | enc_w]: row tile 0 = enc_x, row tile 1 = enc_w, register 2 q + c of half h = (level 2 q + h, channel c)
-        hlayer_T(g, w, wl, HT_S0, lane_off4);
-        f32x16 x0 = g.v[0];
-        const f32x16 x1 = g.v[1];
-        // ---- ambient grid: feature gradients out (level-major), input gradient = sum_l g . dy_dx (gridencoder.cu:342-368);
-        // the encoder sees (ambient + 1) / 2 (gridencoder/grid.py:151, bound = 1): a factor 1/2 on the way back
-        float da[2] = {0.0f, 0.0f};
-        {
-            const float *dw = ws.dw + (size_t)tile * kTile32;
-#pragma unroll
-            for (int q = 0; q < 8; q++) {
-                const float g0 = x1[2 * q], g1 = x1[2 * q + 1];
-                const float d00 = dw[(4 * q + 0) * 64 + lane], d01 = dw[(4 * q + 1) * 64 + lane];
-                const float d10 = dw[(4 * q + 2) * 64 + lane], d11 = dw[(4 * q + 3) * 64 + lane];
-                da[0] = __builtin_fmaf(g0, d00, da[0]); da[0] = __builtin_fmaf(g1, d01, da[0]);
-                da[1] = __builtin_fmaf(g0, d10, da[1]); da[1] = __builtin_fmaf(g1, d11, da[1]);
-                if (live) *reinterpret_cast<float2 *>(p.g_enc_w + ((size_t)(2 * q + h) * p.M + sample) * 2) = make_float2(g0, g1);
-            }
-            da[0] += __shfl_xor(da[0], 32, 64);
-            da[1] += __shfl_xor(da[1], 32, 64);
-        }
-        // ---- ambient net: + the direct gradients of the ambient output, tanh'
-        {
-            float d[2] = {0.0f, 0.0f};
-            if (live) {
-                const float a0v = p.ambient[2 * (size_t)sample], a1v = p.ambient[2 * (size_t)sample + 1];
-                float t0 = 0.5f * da[0], t1 = 0.5f * da[1];
-                if (p.g_ambient) { t0 += p.g_ambient[2 * (size_t)sample]; t1 += p.g_ambient[2 * (size_t)sample + 1]; }
-                if (p.g_ambient_abs) {   // d |a| = sign(a), 0 at 0
-                    const float ga = p.g_ambient_abs[sample];
-                    t0 += a0v > 0.0f ? ga : (a0v < 0.0f ? -ga : 0.0f);
-                    t1 += a1v > 0.0f ? ga : (a1v < 0.0f ? -ga : 0.0f);
-                }
-                d[0] = t0 * (1.0f - a0v * a0v);
-                d[1] = t1 * (1.0f - a1v * a1v);
-            }
-            if (h == 0) { ws.daraw[2 * (size_t)sample] = d[0]; ws.daraw[2 * (size_t)sample + 1] = d[1]; }
-            acc_zero(g);
-            valu_out_T<2>(g, lds + LB_A2, h, d);
-        }
-        relu_mask(g, ws.ha1 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dza1 + (size_t)tile * kTile32, g, lane);
-        hlayer_T(w, g, wl, HT_A1, lane_off4);
-        relu_mask(w, ws.ha0 + (size_t)tile * kTile32, lane);
-        tile_store(ws.dza0 + (size_t)tile * kTile32, w, lane);
-        {   // d enc_x += W_amb0[:, 0:32]^T dZ_a0: a 32-row layer, scaled like the others, added after the unscaling
-            float scale, inv;
-            if (tile_scale(w, scale, inv)) {
-                f32x16 xa = zero16();
-#pragma unroll
-                for (int b = 0; b < 8; b++)
-                    xa = mfma8h(*reinterpret_cast<const f16x4 *>(wl + kHT_A0 + b * kHB32 + lane_off4), acc_frag4(w, b >> 2, b & 3, scale), xa);
-#pragma unroll
-                for (int r = 0; r < 16; r++) x0[r] += xa[r] * inv;
-            }
-        }
-        if (live) {
-#pragma unroll
-            for (int q = 0; q < 8; q++)
-                *reinterpret_cast<float2 *>(p.g_enc_x + ((size_t)(2 * q + h) * p.M + sample) * 2) = make_float2(x0[2 * q], x0[2 * q + 1]);
+            for (int r = 0; r < 16; r++) x0[r] += xa[r] * inv;
         }
     }
+};
+
+__global__ void __launch_bounds__(kThreads) k_train_bwd_h16(BwdParams p) {
+    __shared__ __attribute__((aligned(16))) float lds[ArithF16::kLdsBwd];
+    train_bwd_tiles<ArithF16>(p, lds);
 }
 
-static int pack_h16(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind, const int64_t *ind_index,
-                    float *image, rn_stream_t stream, const char *what) {
-    if (int rc = check_w(w)) return rc;
-    RN_REQUIRE(image && ((uintptr_t)image & 15u) == 0, "%s: image must be 16-byte aligned", what);
-    RN_REQUIRE((enc_a || w->audio_dim == 0) && (eye || !w->has_eye) && (ind || w->ind_dim == 0), "%s: null constant", what);
-    constexpr int kElems = kImage + kHFwdHalves + kHBwdHalves;   // one thread per fp32 element, then one per half
-    hipLaunchKernelGGL(k_train_pack_h16, dim3(div_up(kElems, 256)), dim3(256), 0, as_stream(stream), raw_w(w), enc_a, eye, ind, ind_index, image);
-    return check_launch(what);
-}
+constexpr int kPackElems = kImage + kHFwdHalves + kHBwdHalves;   // one thread per fp32 element, then one per half
 
 }  // namespace th
 }  // namespace rn
@@ -485,39 +386,27 @@ size_t rn_train_head_image_floats_h16(void) { return (size_t)kImageH16; }
 
 int rn_train_head_pack_h16(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_code, float *image,
                            rn_stream_t stream) {
-    return pack_h16(w, enc_a, eye, ind_code, nullptr, image, stream, "train_head_pack_h16");
+    return pack(k_train_pack_h16, kPackElems, "train_head_pack_h16", w, enc_a, eye, ind_code, nullptr, false, image, stream);
 }
 
 int rn_train_head_pack_row_h16(const rn_nerf_weights_t *w, const float *enc_a, const float *eye, const float *ind_table,
                                const int64_t *ind_index, float *image, rn_stream_t stream) {
-    RN_REQUIRE(ind_table && ind_index && w && w->ind_dim, "train_head_pack_row_h16: the code table and its row index are required");
-    return pack_h16(w, enc_a, eye, ind_table, ind_index, image, stream, "train_head_pack_row_h16");
+    return pack(k_train_pack_h16, kPackElems, "train_head_pack_row_h16", w, enc_a, eye, ind_table, ind_index, true, image, stream);
 }
 
 int rn_train_head_forward_h16(const float *xyzs, const float *dirs, uint32_t M, const int32_t *m_dev, const rn_grid_t *grid_xyz,
                               const rn_grid_t *grid_amb, const float *image, float bound, float *sigmas, float *rgbs,
                               float *ambient, float *ambient_abs, float *xn, float *wn, float *workspace, rn_stream_t stream) {
-    if (M == 0) return RN_OK;
-    if (int rc = check_train_grid(grid_xyz, 3, "train_head: xyz")) return rc;
-    if (int rc = check_train_grid(grid_amb, 2, "train_head: ambient")) return rc;
-    RN_REQUIRE(xyzs && dirs && image && sigmas && rgbs && ambient && xn && wn && workspace, "train_head_forward_h16: null pointer");
-    RN_REQUIRE(((uintptr_t)image & 15u) == 0 && ((uintptr_t)workspace & 15u) == 0, "train_head_forward_h16: image / workspace must be 16-byte aligned");
-    FwdParams p{xyzs, dirs, M, m_dev, grid_args(grid_xyz), grid_args(grid_amb), image, bound, sigmas, rgbs, ambient, ambient_abs, xn, wn, workspace};
-    hipLaunchKernelGGL(k_train_fwd_h16, dim3(tile_blocks((M + 31u) >> 5, kWaves, 1)), dim3(kThreads), 0, as_stream(stream), p);
-    return check_launch("train_head_forward_h16");
+    return forward(k_train_fwd_h16, "train_head_forward_h16", xyzs, dirs, M, m_dev, grid_xyz, grid_amb, image, bound, sigmas, rgbs, ambient,
+                   ambient_abs, xn, wn, workspace, stream);
 }
 
 int rn_train_head_backward_h16(const float *grad_sigmas, const float *grad_rgbs, const float *grad_ambient,
                                const float *grad_ambient_abs, const float *rgbs, const float *ambient, uint32_t M,
                                const int32_t *m_dev, const float *image, float *workspace, float *grad_enc_x, float *grad_enc_w,
                                rn_stream_t stream) {
-    if (M == 0) return RN_OK;
-    RN_REQUIRE(grad_sigmas && grad_rgbs && rgbs && ambient && image && workspace && grad_enc_x && grad_enc_w, "train_head_backward_h16: null pointer");
-    RN_REQUIRE(((uintptr_t)image & 15u) == 0, "train_head_backward_h16: image must be 16-byte aligned");
-    RN_REQUIRE(((uintptr_t)grad_enc_x & 7u) == 0 && ((uintptr_t)grad_enc_w & 7u) == 0, "train_head_backward_h16: feature gradients must be 8-byte aligned");
-    BwdParams p{grad_sigmas, grad_rgbs, grad_ambient, grad_ambient_abs, rgbs, ambient, M, m_dev, image, workspace, grad_enc_x, grad_enc_w};
-    hipLaunchKernelGGL(k_train_bwd_h16, dim3(tile_blocks((M + 31u) >> 5, kWaves, 1)), dim3(kThreads), 0, as_stream(stream), p);
-    return check_launch("train_head_backward_h16");
+    return backward(k_train_bwd_h16, true, "train_head_backward_h16", grad_sigmas, grad_rgbs, grad_ambient, grad_ambient_abs, rgbs, ambient,
+                    M, m_dev, image, workspace, grad_enc_x, grad_enc_w, stream);
 }
 
 }  // extern "C"

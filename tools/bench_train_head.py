@@ -70,8 +70,7 @@ def main():
         if key.split("_h16")[0].endswith(("head_forward", "head_backward")):
             us = sorted(a.elapsed_time(b) * 1e3 for a, b in evs)
             out[key + "_median_min_max_us"] = [round(us[len(us) // 2], 1), round(us[0], 1), round(us[-1], 1)]
-    out.update(M=M, grid=args.grid, mlp=args.mlp, fwd_groups=os.environ.get("RN_TRAIN_FWD_GROUPS", "11"), wparts=os.environ.get("RN_TRAIN_WPARTS", "96"),
-               scatter=os.environ.get("RN_SCATTER", "lbc"))
+    out.update(M=M, grid=args.grid, mlp=args.mlp, wparts=os.environ.get("RN_TRAIN_WPARTS", "128"), scatter=os.environ.get("RN_SCATTER", "lbc"))
     print(json.dumps(out))
 
 
