@@ -216,6 +216,33 @@ int rn_torso_blend_frame(const float *bg_coords, uint32_t N, const float *densit
                          float *bg_out, float *torso_alpha, float *image, const float *weights_sum, float *depth,
                          const float *nears, const float *fars, uint8_t *image_u8, rn_stream_t stream);
 
+/* ---- torso plan: the frame-invariant half of rn_torso_blend_frame, built once per view ---------------------
+ * Of the torso pass, the occupancy test and enc_x = freq(x * shrink, 10) -- 40 sines and cosines per covered pixel, two
+ * thirds of the pass's vector instructions -- depend only on (bg_coords, density_grid_torso, thresh, torso_shrink): a
+ * renderer hands the same pixel grid to every frame, and only the pose and the individual code change.  A plan keeps the
+ * covered pixels (ascending), a per-pixel flag and enc_x of the covered pixels as matrix operands, 168 B per covered pixel;
+ * the planned frame call runs the covered pixels as dense 32-pixel tiles and blends the rest.  Its outputs equal
+ * rn_torso_blend_frame's bit for bit (the same products summed in the same order).  A plan is valid for exactly the inputs
+ * it was built from; the caller rebuilds it when one of them changes.
+ *
+ *   rn_torso_plan_bytes   bytes of a plan of N pixels of which n_on are covered (n_on = 0: the part every build needs).
+ *   rn_torso_plan_build   `plan` (device, 256-byte aligned, plan_bytes >= rn_torso_plan_bytes(N, 0)).  Finds the covered
+ *                         pixels, waits for the stream and stores their count in *n_on; writes enc_x when plan_bytes
+ *                         >= rn_torso_plan_bytes(N, *n_on) -- otherwise the caller allocates that much and calls again.
+ *                         An error while the stream is capturing.
+ *   rn_torso_blend_frame_planned   rn_torso_blend_frame over a complete plan (n_on as the build returned it); `deform`
+ *                         (nullable) [N,2] as rn_torso_fused writes it.  One launch. */
+/* 256 MiB: callers keep to rn_torso_blend_frame where a plan would be larger */
+#define RN_TORSO_PLAN_MAX_BYTES 268435456
+size_t rn_torso_plan_bytes(uint32_t N, uint32_t n_on);
+int rn_torso_plan_build(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,
+                        float torso_shrink, void *plan, size_t plan_bytes, uint32_t *n_on, rn_stream_t stream);
+int rn_torso_blend_frame_planned(const void *plan, size_t plan_bytes, uint32_t N, uint32_t n_on, const float *poses6,
+                                 const float *ind_code, float torso_shrink, const rn_torso_weights_t *w, const float *packed,
+                                 const rn_grid_t *grid_torso, const float *bg_in, float *bg_out, float *torso_alpha,
+                                 float *deform, float *image, const float *weights_sum, float *depth, const float *nears,
+                                 const float *fars, uint8_t *image_u8, rn_stream_t stream);
+
 /* mask[i] = 1 where the bilinear torso occupancy at bg_coords[i] exceeds `thresh` (F.grid_sample(bilinear, zeros,
  * align_corners=True) > thresh, nerf/renderer.py:281-283) -- the test rn_torso_fused applies per pixel, exposed for the
  * differentiable training formulation that gathers those pixels. */

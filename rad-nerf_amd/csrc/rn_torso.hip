@@ -4,6 +4,8 @@
 // nerf/network.py:188-219 per background pixel, and the blend of renderer.py:306-311.  k_torso_fused keeps the older
 // 64-sample form of the fused network kernel: two column tiles per wave on v_mfma_f32_32x32x2_f32, one v_permlane32_swap
 // per feature pair to build both B operands; the weights sit in LDS, the per-frame inputs enter as accumulator biases.
+// k_torso_planned is the same pass over a torso plan (rn_torso_plan_*): the covered pixels and their position encoding, built
+// once per view, so that a frame runs the covered pixels as dense 32-sample tiles (rn_tile32_dev.h) and computes no sine.
 #include "rn_torso_dev.h"
 
 #include "../../include/radnerf_train.h"   // rn_torso_select: the covered pixels of a training step
@@ -341,6 +343,239 @@ k_blend(float *__restrict__ image, const float *__restrict__ weights_sum, const 
     blend_pixel(BlendArgs{image, weights_sum, depth, nears, fars, u8}, n, b);
 }
 
+// ==========================================================================================================
+// The torso plan: what the pass computes from (bg_coords, occupancy grid, thresh, shrink) alone, built once for a view and
+// read by every frame after it: the covered pixels in ascending order (32 to a tile), a per-pixel flag, and enc_x =
+// freq(x * shrink, 10) of the covered pixels as the B operands of the 21 first-layer steps (native tiles: row s = the
+// operand of step s, one coalesced 256-B row).  That is the 40 sines and cosines per pixel with their large-argument
+// reduction, two thirds of k_torso_fused's VALU work.  The frame feeds them to the same MFMA chains in the same order
+// (bias first, then the steps), so a planned frame equals k_torso_fused's bit for bit on every pixel.
+//
+// Layout (bytes; every part 256-aligned): count int32 | on flag u8 [N] | on-list int32 [N] | their xy float2 [N] | enc_x.
+constexpr size_t kPlanAlign = 256;
+constexpr uint32_t kPlanTileFloats = 21 * 64;   // 21 operand rows of 64 lanes per 32-pixel tile
+__host__ __device__ constexpr size_t plan_up(size_t b) { return (b + kPlanAlign - 1) / kPlanAlign * kPlanAlign; }
+struct PlanView {
+    int32_t *count;
+    uint8_t *flags;
+    int32_t *on_list;
+    float *xy;
+    float *enc;
+};
+__host__ __device__ inline size_t plan_head_bytes(uint32_t N) {
+    return kPlanAlign + plan_up(N) + plan_up(4 * (size_t)N) + plan_up(8 * (size_t)N);
+}
+__host__ __device__ inline PlanView plan_view(void *plan, uint32_t N) {
+    unsigned char *b = static_cast<unsigned char *>(plan);
+    PlanView v;
+    v.count = reinterpret_cast<int32_t *>(b); b += kPlanAlign;
+    v.flags = b; b += plan_up(N);
+    v.on_list = reinterpret_cast<int32_t *>(b); b += plan_up(4 * (size_t)N);
+    v.xy = reinterpret_cast<float *>(b); b += plan_up(8 * (size_t)N);
+    v.enc = reinterpret_cast<float *>(b);
+    return v;
+}
+
+// the 21 features of coordinate xs = x[h] * shrink that lane half h feeds: feature 2 s + h of enc_x at MFMA step s
+__device__ __forceinline__ void enc_x_half(float xs, float (&fq)[21]) {
+    fq[0] = xs;
+#pragma unroll
+    for (int f = 0; f < 10; f++) {
+        const float a = freq_angle(xs, f);
+        fq[1 + 2 * f] = freq_sin(a);
+        fq[2 + 2 * f] = freq_cos(a);
+    }
+}
+
+// enc_x of every 32-pixel tile of the on-list: one wave per tile.  Lanes past the end of the list store zeros.
+constexpr int kPlanThreads = 256, kPlanWaves = kPlanThreads / kWave;
+__global__ void __launch_bounds__(kPlanThreads)
+k_torso_plan_enc(const float *__restrict__ xy, uint32_t n_on, float shrink, float *__restrict__ enc) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const uint32_t tile = blockIdx.x * kPlanWaves + wave;
+    if (tile >= (n_on + 31u) >> 5) return;
+    const uint32_t i = tile * 32 + j;
+    float fq[21];
+#pragma unroll
+    for (int s = 0; s < 21; s++) fq[s] = 0.0f;
+    if (i < n_on) enc_x_half(xy[2 * (size_t)i + h] * shrink, fq);
+    float *dst = enc + (size_t)tile * kPlanTileFloats;
+#pragma unroll
+    for (int s = 0; s < 21; s++) dst[s * 64 + lane] = fq[s];
+}
+
+struct PlannedParams {
+    const uint8_t *flags;
+    const int32_t *on_list;
+    const float *xy;
+    const float *enc;
+    uint32_t N, n_on, on_blocks;
+    const float *poses6, *ind_code;
+    float shrink;
+    RawT w;
+    const float *packed;
+    GridArgs gt;
+    const float *bg_in;
+    float *bg_out, *alpha_out, *deform_out;
+    BlendArgs blend;
+};
+
+#ifndef RN_PLAN_GATHER
+#define RN_PLAN_GATHER 4
+#endif
+// the launch bound's second argument.  Without one the compiler parks values in 64 AGPRs (119 + 64 registers, 2 waves per SIMD);
+// with 2 or 3 it keeps to 122 - 124 VGPRs and 3 waves fit.  2, 3 and gather depths 2 / 4 / 8 measure the same
+#ifndef RN_PLAN_WAVES_PER_SIMD
+#define RN_PLAN_WAVES_PER_SIMD 2
+#endif
+constexpr int kPlanGather = RN_PLAN_GATHER;   // gather rounds in flight (a round = two levels, one per lane half; divides 8)
+constexpr uint32_t kPlanOffPixels = 4;   // pixels per thread of a pixel-range workgroup
+
+__device__ __forceinline__ float load_nt(const float *p) { return __builtin_nontemporal_load(p); }
+
+// The frame's torso pass + blend over a plan, one launch, two kinds of workgroup and nothing shared between them:
+//  * workgroups [0, on_blocks): one 32-pixel tile of the on-list per wave on the 32-sample machine (rn_tile32_dev.h);
+//  * the rest: kPlanThreads * kPlanOffPixels consecutive pixels each; every pixel whose flag is off gets what k_torso_fused
+//    gives it (background passes through, blend), the on pixels are left to the tiles.
+template <typename TT, bool BLEND>
+__global__ void __launch_bounds__(kPlanThreads, RN_PLAN_WAVES_PER_SIMD) k_torso_planned(PlannedParams p) {
+    if (blockIdx.x >= p.on_blocks) {
+        const uint32_t base = (blockIdx.x - p.on_blocks) * (kPlanThreads * kPlanOffPixels) + threadIdx.x;
+#pragma unroll
+        for (uint32_t q = 0; q < kPlanOffPixels; q++) {
+            const uint32_t px = base + q * kPlanThreads;
+            if (px >= p.N || p.flags[px]) continue;
+            float bgc[3] = {1.0f, 1.0f, 1.0f};
+            if (p.bg_in) { bgc[0] = p.bg_in[3 * (size_t)px]; bgc[1] = p.bg_in[3 * (size_t)px + 1]; bgc[2] = p.bg_in[3 * (size_t)px + 2]; }
+            if (p.bg_out) { p.bg_out[3 * (size_t)px] = bgc[0]; p.bg_out[3 * (size_t)px + 1] = bgc[1]; p.bg_out[3 * (size_t)px + 2] = bgc[2]; }
+            if constexpr (BLEND) blend_pixel(p.blend, px, bgc);
+            if (p.alpha_out) p.alpha_out[px] = 0.0f;
+            if (p.deform_out) { p.deform_out[2 * (size_t)px] = 0.0f; p.deform_out[2 * (size_t)px + 1] = 0.0f; }
+        }
+        return;
+    }
+    __shared__ __attribute__((aligned(16))) float lds_[kTorsoPacked + kTorsoBias + 64];
+    __shared__ LevelPlan plan_t[16];
+    constexpr int D0 = TOFF_D0, D1 = TOFF_D1, D2 = TOFF_D2, T0 = TOFF_T0, T1 = TOFF_T1, T2 = TOFF_T2;
+    const float *lds = lds_;
+    float *bias_def = lds_ + kTorsoPacked, *bias_tor = bias_def + 64, *enc_pose = bias_tor + 32;
+    if (threadIdx.x >= 64 && threadIdx.x < 80) {
+        const int t = threadIdx.x - 64;
+        const uint32_t o = (uint32_t)p.gt.offsets[t];
+        plan_t[t] = plan_level<2>(p.gt.lc.scale[t], p.gt.lc.resolution[t], o, (uint32_t)p.gt.offsets[t + 1] - o, p.gt.gridtype,
+                                  (uint32_t)sizeof(TT) * 2u);
+    }
+    for (int i = threadIdx.x; i < kTorsoPacked / 4; i += kPlanThreads)
+        reinterpret_cast<float4 *>(lds_)[i] = reinterpret_cast<const float4 *>(p.packed)[i];
+    if (threadIdx.x < 54) enc_pose[threadIdx.x] = enc_pose_elem(p.poses6, threadIdx.x);
+    __syncthreads();
+    if (threadIdx.x < kTorsoBias) bias_def[threadIdx.x] = torso_const_bias(p.w, enc_pose, p.ind_code, threadIdx.x);
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j = lane & 31, h = lane >> 5;
+    const int lane_off = h * 64 + j * 2, lane_off32 = h * 32 + j;
+    const uint32_t tile = blockIdx.x * kPlanWaves + wave;
+    if (tile >= (p.n_on + 31u) >> 5) return;
+    const uint32_t i = tile * 32 + j;   // both lane halves work on the same 32 pixels
+    const bool live = i < p.n_on;
+    uint32_t px = 0;
+    float x0 = 0.0f, x1 = 0.0f;
+    if (live) {
+        px = (uint32_t)p.on_list[i];
+        const float2 c = *reinterpret_cast<const float2 *>(p.xy + 2 * (size_t)i);
+        x0 = c.x * p.shrink; x1 = c.y * p.shrink;
+    }
+    // enc_x of the tile as the plan holds it: fq[s] = this lane's B operand of first-layer step s (k = 2 s + h)
+    const float *et = p.enc + (size_t)tile * kPlanTileFloats;
+    float fq[21];
+#pragma unroll
+    for (int s = 0; s < 21; s++) fq[s] = load_nt(et + s * 64 + lane);
+    // deform net 104 -> 64 -> 64 -> 2
+    Acc32 a0, a1;
+    acc_bias(a0, bias_def, h);
+#pragma unroll
+    for (int s = 0; s < 21; s++) step32(a0, lds + D0, s, lane_off, fq[s]);
+    acc_relu(a0);
+    acc_zero(a1);
+    layer_from_acc(a1, a0, lds + D1, lane_off);
+    acc_relu(a1);
+    float dxy[2];
+    valu_out<2>(a1, lds + D2, h, dxy);
+    f32x16 t0;
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        const float4 b = *reinterpret_cast<const float4 *>(bias_tor + 8 * g + 4 * h);
+        t0[4 * g] = b.x; t0[4 * g + 1] = b.y; t0[4 * g + 2] = b.z; t0[4 * g + 3] = b.w;
+    }
+    // x = clamp(x + dx, -1, 1); torso grid (bound = 1): lane half h gathers level 2 r + h in round r, one lane swap per
+    // round turns its two channels into the level-ordered B operands of steps 2 r and 2 r + 1
+    {
+        float in[2] = {(fminf(fmaxf(x0 + dxy[0], -1.0f), 1.0f) + 1.0f) / 2.0f,
+                       (fminf(fmaxf(x1 + dxy[1], -1.0f), 1.0f) + 1.0f) / 2.0f};
+        const bool ok = live && !(in[0] < 0 || in[0] > 1 || in[1] < 0 || in[1] > 1);
+        LevelFetch<TT, 2, 2> f[kPlanGather];
+#pragma unroll
+        for (int g = 0; g < 8; g += kPlanGather) {
+            if (ok) {
+#pragma unroll
+                for (int q = 0; q < kPlanGather; q++)
+                    issue_planned<TT, 2, 2, false, false>(static_cast<const TT *>(p.gt.table), plan_t[2 * (g + q) + h], in, f[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < kPlanGather; q++) {
+                float f0 = 0.0f, f1 = 0.0f;
+                if (ok) {
+                    TT res[2];
+                    TT dummy[1];
+                    blend_level<TT, 2, 2, false>(f[q], 0.0f, res, dummy);
+                    f0 = to_f<TT>(res[0]);
+                    f1 = to_f<TT>(res[1]);
+                }
+                float b0, b1;
+                to_b_operands(f0, f1, b0, b1);
+                const int s = 2 * (g + q);
+                t0 = mfma32(lds[T0 + s * kS32 + lane_off32], b0, t0);
+                t0 = mfma32(lds[T0 + (s + 1) * kS32 + lane_off32], b1, t0);
+            }
+        }
+    }
+    // torso net 136 -> 32 -> 32 -> 4 on one row tile: the grid steps above, then enc_x, in k_torso_fused's order
+#pragma unroll
+    for (int s = 0; s < 21; s++) t0 = mfma32(lds[T0 + (16 + s) * kS32 + lane_off32], fq[s], t0);
+    f32x16 t1 = zero16();
+#pragma unroll
+    for (int r = 0; r < 16; r++) t0[r] = fmaxf(t0[r], 0.0f);
+#pragma unroll
+    for (int s = 0; s < 16; s++) t1 = mfma32(lds[T1 + s * kS32 + lane_off32], t0[s], t1);
+    float o4[4];
+#pragma unroll
+    for (int o = 0; o < 4; o++) {
+        float s = 0.0f;
+        const float *wo = lds + T2 + (o * 2 + h) * 16;
+#pragma unroll
+        for (int r = 0; r < 16; r++) s = __builtin_fmaf(fmaxf(t1[r], 0.0f), wo[r], s);
+        o4[o] = s + __shfl_xor(s, 32, 64);
+    }
+    if (live && h == 0) {
+        float bgc[3] = {1.0f, 1.0f, 1.0f};
+        if (p.bg_in) { bgc[0] = p.bg_in[3 * (size_t)px]; bgc[1] = p.bg_in[3 * (size_t)px + 1]; bgc[2] = p.bg_in[3 * (size_t)px + 2]; }
+        const float alpha = sigmoid_out(o4[0]);
+        // bg = torso_color * alpha + bg * (1 - alpha)  (renderer.py:299)
+        float bgf[3];
+#pragma unroll
+        for (int c = 0; c < 3; c++) bgf[c] = sigmoid_out(o4[1 + c]) * alpha + bgc[c] * (1 - alpha);
+        if (p.bg_out) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) p.bg_out[3 * (size_t)px + c] = bgf[c];
+        }
+        if constexpr (BLEND) blend_pixel(p.blend, px, bgf);
+        if (p.alpha_out) p.alpha_out[px] = alpha;
+        if (p.deform_out) { p.deform_out[2 * (size_t)px] = dxy[0]; p.deform_out[2 * (size_t)px + 1] = dxy[1]; }
+    }
+}
+
 // the launch behind rn_torso_fused and rn_torso_blend_frame: one 64-pixel tile per wave, at most two workgroups per CU
 template <bool BLEND>
 static int launch_torso(const TorsoParams &p, int table_dtype, rn_stream_t stream, const char *what) {
@@ -393,6 +628,63 @@ int rn_torso_blend_frame(const float *bg_coords, uint32_t N, const float *densit
     TorsoParams p{bg_coords, N, density_grid_torso, grid_size, thresh, poses6, ind_code, torso_shrink, raw_t(w), packed,
                   grid_args(grid_torso), bg_in, bg_out, torso_alpha, nullptr, BlendArgs{image, weights_sum, depth, nears, fars, image_u8}};
     return launch_torso<true>(p, grid_torso->dtype, stream, "torso_blend_frame");
+}
+
+size_t rn_torso_plan_bytes(uint32_t N, uint32_t n_on) {
+    return plan_head_bytes(N) + (size_t)((n_on + 31u) >> 5) * kPlanTileFloats * sizeof(float);
+}
+
+int rn_torso_plan_build(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,
+                        float torso_shrink, void *plan, size_t plan_bytes, uint32_t *n_on, rn_stream_t stream) {
+    RN_REQUIRE(bg_coords && density_grid_torso && plan && n_on, "torso_plan_build: null pointer");
+    RN_REQUIRE(N > 0 && N <= (1u << 30) && grid_size >= 2, "torso_plan_build: N = %u, grid_size = %u", N, grid_size);
+    RN_REQUIRE(((uintptr_t)plan & (kPlanAlign - 1)) == 0, "torso_plan_build: plan must be 256-byte aligned");
+    RN_REQUIRE(plan_bytes >= plan_head_bytes(N), "torso_plan_build: plan_bytes = %zu is less than rn_torso_plan_bytes(N, 0) = %zu", plan_bytes,
+               plan_head_bytes(N));
+    hipStream_t s = as_stream(stream);
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    RN_REQUIRE(hipStreamIsCapturing(s, &cap) == hipSuccess && cap == hipStreamCaptureStatusNone,
+               "torso_plan_build: the stream is capturing (the build reads the covered count back)");
+    const PlanView v = plan_view(plan, N);
+    hipLaunchKernelGGL(k_torso_mask, dim3(div_up(N, 256)), dim3(256), 0, s, bg_coords, N, density_grid_torso, grid_size, thresh, v.flags);
+    hipLaunchKernelGGL(k_torso_select, dim3(1), dim3(kSelectThreads), 0, s, bg_coords, N, density_grid_torso, grid_size, thresh,
+                       (const float *)nullptr, v.on_list, v.xy, v.count);
+    if (int rc = check_launch("torso_plan_build(select)")) return rc;
+    int32_t count = 0;
+    if (hipMemcpyAsync(&count, v.count, sizeof(count), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        set_error("torso_plan_build: reading the covered count failed");
+        return RN_ERR_LAUNCH;
+    }
+    RN_REQUIRE(count >= 0 && (uint32_t)count <= N, "torso_plan_build: covered count %d of %u pixels", count, N);
+    *n_on = (uint32_t)count;
+    if (count == 0 || plan_bytes < rn_torso_plan_bytes(N, (uint32_t)count)) return RN_OK;
+    const uint32_t n_tiles = ((uint32_t)count + 31u) >> 5;
+    hipLaunchKernelGGL(k_torso_plan_enc, dim3(div_up(n_tiles, kPlanWaves)), dim3(kPlanThreads), 0, s, v.xy, (uint32_t)count, torso_shrink,
+                       v.enc);
+    return check_launch("torso_plan_build");
+}
+
+int rn_torso_blend_frame_planned(const void *plan, size_t plan_bytes, uint32_t N, uint32_t n_on, const float *poses6, const float *ind_code,
+                                 float torso_shrink, const rn_torso_weights_t *w, const float *packed, const rn_grid_t *grid_torso,
+                                 const float *bg_in, float *bg_out, float *torso_alpha, float *deform, float *image,
+                                 const float *weights_sum, float *depth, const float *nears, const float *fars, uint8_t *image_u8,
+                                 rn_stream_t stream) {
+    if (N == 0) return RN_OK;
+    RN_REQUIRE(plan && poses6 && w && packed, "torso_blend_frame_planned: null pointer");
+    RN_REQUIRE(image && weights_sum && depth && nears && fars, "torso_blend_frame_planned: null frame buffers");
+    RN_REQUIRE(ind_code || w->ind_dim == 0, "torso_blend_frame_planned: ind_code required when ind_dim > 0");
+    RN_REQUIRE(((uintptr_t)packed & 15u) == 0 && ((uintptr_t)plan & (kPlanAlign - 1)) == 0, "torso_blend_frame_planned: packed must be 16-byte, plan 256-byte aligned");
+    RN_REQUIRE(n_on <= N && N <= (1u << 30) && plan_bytes >= rn_torso_plan_bytes(N, n_on),
+               "torso_blend_frame_planned: a plan of %zu bytes does not hold %u covered of %u pixels", plan_bytes, n_on, N);
+    if (int rc = check_fused_grid(grid_torso, 2, "torso_blend_frame_planned(torso grid)")) return rc;
+    const PlanView v = plan_view(const_cast<void *>(plan), N);
+    const uint32_t on_blocks = div_up((n_on + 31u) >> 5, kPlanWaves), off_blocks = div_up(N, kPlanThreads * kPlanOffPixels);
+    PlannedParams p{v.flags, v.on_list, v.xy, v.enc, N, n_on, on_blocks, poses6, ind_code, torso_shrink, raw_t(w), packed,
+                    grid_args(grid_torso), bg_in, bg_out, torso_alpha, deform, BlendArgs{image, weights_sum, depth, nears, fars, image_u8}};
+    const dim3 grid(on_blocks + off_blocks);
+    if (grid_torso->dtype == RN_F32) hipLaunchKernelGGL((k_torso_planned<float, true>), grid, dim3(kPlanThreads), 0, as_stream(stream), p);
+    else hipLaunchKernelGGL((k_torso_planned<__half, true>), grid, dim3(kPlanThreads), 0, as_stream(stream), p);
+    return check_launch("torso_blend_frame_planned");
 }
 
 int rn_torso_mask(const float *bg_coords, uint32_t N, const float *density_grid_torso, uint32_t grid_size, float thresh,

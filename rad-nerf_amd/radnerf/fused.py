@@ -10,6 +10,9 @@ Per frame the host enqueues, on torch's current stream and without reading anyth
     rn_torso_fused       torso occupancy test + deformation / torso MLPs + blend over the background
     rn_blend_frame       image + (1 - weights_sum) * bg, clamp, depth normalisation [, uint8]
 
+(a whole-frame render folds the last two into rn_torso_blend_frame, and from the second frame of a view on into
+rn_torso_blend_frame_planned over the view's torso plan, see FusedState.torso_plan).
+
 Results equal the per-operator engine's (same DDA samples, same grid features, fp32 MLPs; parity tests in
 tests/test_gpu_fused.py).
 """
@@ -21,7 +24,7 @@ import torch
 import radnerf_hip as hip
 from radnerf_hip.abi import (RN_F16, RN_F32, RN_F32_SPLIT, RN_HEAD_ST_HIST, RN_HEAD_ST_ITERS, RN_HEAD_ST_SLOTS, RN_HEAD_ST_STALLED,
                              RN_HEAD_ST_UNFINISHED, RN_HEAD_STATE_INTS, RN_LOOP_CLOSE_FRAME, RN_LOOP_COOP, RN_LOOP_FIRST_MARCHED,
-                             GridT, HeadT, NerfWeightsT, TorsoWeightsT)
+                             RN_TORSO_PLAN_MAX_BYTES, GridT, HeadT, NerfWeightsT, TorsoWeightsT)
 
 from . import switches
 
@@ -87,9 +90,22 @@ def supported(model):
         return False
 
 
+class TorsoPlan:
+    """One built torso plan (rn_torso_plan_build): `buf` holds it (None: the plan would be larger than
+    RN_TORSO_PLAN_MAX_BYTES, the frames of this key stay on rn_torso_blend_frame), `n_on` its covered pixels.  `refs` keeps
+    the tensors of the key alive, so none of their addresses can be handed to another tensor while the plan lives."""
+
+    def __init__(self, key, refs, buf, n_on, stream):
+        self.key, self.refs, self.buf, self.n_on, self.stream = key, refs, buf, n_on, stream
+        self.event = torch.cuda.Event()
+        self.event.record()
+        self.waited = {stream}
+
+
 class FusedState:
     """Device-side constants + scratch of one model: packed weights (re-packed when parameters change),
-    grid descriptors, per-frame bias block, loop scratch for N rays."""
+    grid descriptors, per-frame bias block, loop scratch for N rays, and the torso plan of the view being rendered
+    (`plan`; `plan_builds` counts the plans this state has built)."""
 
     def __init__(self, model):
         if not supported(model):
@@ -107,6 +123,8 @@ class FusedState:
         self._versions = None
         self._N = 0
         self._zero_eye = torch.zeros(1, dtype=torch.float32, device=self.dev)
+        self.plan = None
+        self.plan_builds = 0
 
     # -- weights --------------------------------------------------------------------------------------
     def _weights(self):
@@ -156,6 +174,62 @@ class FusedState:
         self.gw = _grid_desc(m.encoder_ambient, self.tables[1])
         self.gt = _grid_desc(m.torso_encoder, self.tables[2]) if m.torso else None
         self._versions = versions
+
+    # -- torso plan -----------------------------------------------------------------------------------
+    def torso_plan(self, bg_coords, coords, thresh):
+        """The plan for this frame's torso pass, or None (the frame then runs rn_torso_blend_frame).  `bg_coords` is the
+        caller's tensor, `coords` its contiguous fp32 form.  A plan is built when the same key -- (address, version, shape) of
+        the coordinates and of the occupancy grid, thresh, shrink -- was seen on the call before, by any of the model's
+        streams: a caller whose coordinates change with every call (patch batches, validation renders during training) never
+        pays for a build.  A changed key drops the plan.  Never builds under stream capture.  (The weights, the grid table and
+        the pose reach a planned frame as they reach any other: nothing of them is in the plan.)"""
+        if not switches.on("RN_TORSO_PLAN"):
+            return None
+        m = self.model
+        refs = [bg_coords, m.density_grid_torso]
+        key = (tuple((t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype) for t in refs),
+               float(thresh), float(m.opt.torso_shrink))
+        cur = torch.cuda.current_stream()
+        plan = self.plan
+        if plan is None or plan.key != key:
+            # another stream of the model may hold the plan of this view already
+            plan = next((st.plan for st in (getattr(m, "_fused_states", None) or {}).values()
+                         if st.plan is not None and st.plan.key == key), None)
+            self.plan = plan
+        if plan is None:
+            seen = getattr(m, "_fused_plan_seen", None)
+            if seen is None or seen[0] != key:
+                object.__setattr__(m, "_fused_plan_seen", (key, refs))
+                return None
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            plan = self.plan = self._build_plan(key, refs, coords, thresh, cur)
+        if plan.buf is None:
+            return None
+        if cur.cuda_stream not in plan.waited:     # built on another stream: order this one behind the build, once
+            cur.wait_event(plan.event)
+            plan.buf.record_stream(cur)
+            plan.waited.add(cur.cuda_stream)
+        return plan
+
+    def _build_plan(self, key, refs, coords, thresh, cur):
+        m = self.model
+        N = int(coords.shape[0])
+        n_on = C.c_uint32(0)
+        nbytes = int(_lib.rn_torso_plan_bytes(N, 0))
+        for _ in range(2):      # the first call finds the covered count, the second has room for its tiles
+            buf = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+            hip.call("rn_torso_plan_build", hip.ptr(coords), N, hip.ptr(m.density_grid_torso), int(m.grid_size), float(thresh),
+                     float(m.opt.torso_shrink), hip.ptr(buf), nbytes, C.byref(n_on), cur.cuda_stream)
+            need = int(_lib.rn_torso_plan_bytes(N, n_on.value))
+            if need <= nbytes:
+                break
+            if need > RN_TORSO_PLAN_MAX_BYTES:
+                buf = None
+                break
+            nbytes = need
+        self.plan_builds += 1
+        return TorsoPlan(key, refs, buf, int(n_on.value), cur.cuda_stream)
 
     # -- scratch --------------------------------------------------------------------------------------
     def scratch(self, N):
@@ -486,10 +560,17 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
         bg_final = torch.empty(N, 3, dtype=torch.float32, device=dev) if keep else None
         coords = bg_coords.contiguous().float()
         p6, ict = torso_constants(poses, ind_code_torso)
-        hip.call("rn_torso_blend_frame", hip.ptr(coords), N, hip.ptr(model.density_grid_torso), int(model.grid_size), float(thresh),
-                 hip.ptr(p6), hip.ptr(ict), float(model.opt.torso_shrink), C.byref(st.tw), hip.ptr(st.tpacked), C.byref(st.gt),
-                 hip.ptr(bg_in), hip.ptr(bg_final), hip.ptr(talpha), hip.ptr(image), hip.ptr(weights_sum), hip.ptr(depth),
-                 hip.ptr(st.nears), hip.ptr(st.fars), hip.ptr(u8), s)
+        plan = st.torso_plan(bg_coords, coords, thresh)
+        if plan is not None:
+            hip.call("rn_torso_blend_frame_planned", hip.ptr(plan.buf), plan.buf.numel(), N, plan.n_on, hip.ptr(p6), hip.ptr(ict),
+                     float(model.opt.torso_shrink), C.byref(st.tw), hip.ptr(st.tpacked), C.byref(st.gt), hip.ptr(bg_in),
+                     hip.ptr(bg_final), hip.ptr(talpha), None, hip.ptr(image), hip.ptr(weights_sum), hip.ptr(depth),
+                     hip.ptr(st.nears), hip.ptr(st.fars), hip.ptr(u8), s)
+        else:
+            hip.call("rn_torso_blend_frame", hip.ptr(coords), N, hip.ptr(model.density_grid_torso), int(model.grid_size), float(thresh),
+                     hip.ptr(p6), hip.ptr(ict), float(model.opt.torso_shrink), C.byref(st.tw), hip.ptr(st.tpacked), C.byref(st.gt),
+                     hip.ptr(bg_in), hip.ptr(bg_final), hip.ptr(talpha), hip.ptr(image), hip.ptr(weights_sum), hip.ptr(depth),
+                     hip.ptr(st.nears), hip.ptr(st.fars), hip.ptr(u8), s)
         if keep:
             results["torso_alpha"], results["torso_color"] = talpha, bg_final
     else:

@@ -104,6 +104,8 @@ def refresh_torso(model, enc_a, pose6, ind_code, decay=0.95, noise=None):
         sc.alphas.copy_(model.forward_torso(sc.xys, pose6, enc_a, ind_code)[0].float())
     hip.call("rn_torso_grid_update", hip.ptr(sc.alphas), hip.ptr(model.density_grid_torso), H, float(decay),
              hip.ptr(sc.stats_torso), s)
+    # written through its address: tell torch, so that whatever is keyed on the grid's version (the fused engine's torso plan) sees it
+    torch.autograd.graph.increment_version(model.density_grid_torso)
     return sc.stats_torso
 
 

@@ -13,6 +13,7 @@ TABLE = (
     ("RN_MLP_TRAIN", "hip", ("hip", "torch"), "the per-operator MLP stacks under autograd: `rn_mlp64_*` (`radnerf/mlp_train.py`) or `nn.Linear`"),
     ("RN_PERCEP", "hip", ("hip", "torch"), "`PerceptualAlex` (`radnerf/percep.py`) on the GPU in fp32: the perceptual kernels (`rn_percep_*`), or the same arithmetic in plain torch (unfold + matmul)"),
     ("RN_SCATTER", "lbc", ("lbc", "binned"), "table-gradient scatter: the line merge for every level, or hashed levels of the first grid summed by table region"),
+    ("RN_TORSO_PLAN", "1", ("1", "0"), "fused inference engine: a frame whose pixel grid and torso occupancy grid are those of the frame before runs its torso pass over a plan built once (`rn_torso_plan_build`: the covered pixels and their position encoding; same bits); `0`: every frame computes them (`rn_torso_blend_frame`)"),
     ("RN_TORSO_STEP", "device", ("device", "host"), "with `RN_TORSO_TRAIN=fused`: the whole torso step on a device-side count, or the fused layer on the index list the host asks for"),
     ("RN_TORSO_TRAIN", "ops", ("ops", "fused"), "torso layer of a training call: the per-operator layers, or the fused kernels of `radnerf/train_torso.py` (opt-in)"),
     ("RN_TRAIN_CAMERA", "torch", ("torch", "fused"), "pose code of `--train_camera`: torch's expressions, or `rn_camera_rays_*` (`radnerf/train_camera.py`, opt-in; lets a captured camera step keep the fused head)"),

@@ -21,6 +21,7 @@ RN_LAYOUT_LBC, RN_LAYOUT_BLC, RN_LAYOUT_BLC_LEVELMAJOR = 0, 1, 2
 # ==================================================================================================== radnerf_fused.h
 RN_F32_SPLIT = 2
 RN_HEAD_STATE_INTS = 64
+RN_TORSO_PLAN_MAX_BYTES = 256 << 20
 RN_LOOP_FIRST_MARCHED, RN_LOOP_CLOSE_FRAME, RN_LOOP_COOP = 1, 2, 4
 RN_HEAD_ST_ACTIVE, RN_HEAD_ST_ITERS, RN_HEAD_ST_LIVE, RN_HEAD_ST_SLOTS = 4, 16, 17, 18
 RN_HEAD_ST_UNFINISHED, RN_HEAD_ST_STALLED, RN_HEAD_ST_HIST = 19, 22, 32
@@ -175,6 +176,10 @@ FUNCTIONS = {
                               _ptr, _ptr, _ptr]),
     "rn_torso_blend_frame": (_int, [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr, _f32, _P(TorsoWeightsT), _ptr, _P(GridT), _ptr,
                                     _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_torso_plan_bytes": (_sz, [_u32, _u32]),
+    "rn_torso_plan_build": (_int, [_ptr, _u32, _ptr, _u32, _f32, _f32, _ptr, _sz, C.POINTER(_u32), _ptr]),
+    "rn_torso_blend_frame_planned": (_int, [_ptr, _sz, _u32, _u32, _ptr, _ptr, _f32, _P(TorsoWeightsT), _ptr, _P(GridT), _ptr, _ptr,
+                                            _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "rn_torso_mask": (_int, [_ptr, _u32, _ptr, _u32, _f32, _ptr, _ptr]),
     "rn_blend_frame": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr]),
     "rn_occupancy_workspace": (_sz, [_u32, _u32]),
