@@ -123,6 +123,11 @@ typedef struct {
                                              W % 8 == 0, N % W == 0, (N / W) % 8 == 0; otherwise treated as 0): the list
                                              starts in 8 x 8 pixel blocks, so neighbouring samples share more grid rows.
                                              Speed only -- rays are independent, every pixel is unchanged. */
+    const int32_t *occ_box;               /* [8] as rn_occ_box wrote it for THIS bitfield, or NULL.  With one cascade and a constant
+                                             step, a ray steps over the lattice points in front of the box around the set bits
+                                             without looking their cells up and ends its walk where it leaves that box, instead of
+                                             testing every cell up to `far`.  Speed only: no set bit lies outside the box, so the
+                                             samples are the same, bit for bit.  NULL (and every other configuration): the full walk. */
 } rn_head_t;
 
 /* near/far + loop initialisation (rays_alive = arange(N), rays_t = nears, accumulators = 0, step = 0). */
@@ -281,6 +286,10 @@ int rn_mark_untrained_grid(const float *poses, uint32_t n_poses, uint32_t pose_s
                            uint32_t C, uint32_t H, float bound, float *density_grid, rn_stream_t stream);
 int rn_torso_grid_points(uint32_t H, const float *noise, uint32_t seed, float *xys, rn_stream_t stream);
 int rn_torso_grid_update(const float *alphas, float *density_grid_torso, uint32_t H, float decay, float *stats, rn_stream_t stream);
+/* The box around the set bits of cascade 0 of a bitfield ([cascade * H^3 / 8] bytes, morton order), in cell coordinates:
+ * box[0..2] = the lowest x, y, z of a set cell, box[3..5] = the highest, box[6] = box[7] = 0; no bit set: box[0..2] = H,
+ * box[3..5] = -1 (lo > hi).  Stays on the device (rn_head_t.occ_box reads it); valid until the bitfield changes.  Two launches. */
+int rn_occ_box(const uint8_t *bitfield, uint32_t cascade, uint32_t grid_size, int32_t *box, rn_stream_t stream);
 uint32_t rn_hash_u01_bits(uint32_t seed, uint32_t idx);   /* the 24 random bits behind the built-in jitter (host-callable) */
 
 /* ---- audio code ------------------------------------------------------------------------------

@@ -5,6 +5,8 @@
 
 #include "rn_common.h"
 
+#include <float.h>
+
 namespace rn {
 
 constexpr float kSqrt3 = 1.7320508075688772f;
@@ -31,6 +33,8 @@ struct Dda {
     float mb1, rmb1;  // one cascade: mip_bound = min(2^0, bound) and its reciprocal are the same for every lattice point
     bool one_cascade;
     bool one_step_skips;  // see init()
+    bool span = false;    // walk<true>() tests lattice points in [t_lo, t_hi) only: set by set_span(), off for everyone else
+    float t_lo = 0.0f, t_hi = 0.0f;
     uint32_t H;
     const uint8_t *grid;
 
@@ -55,6 +59,49 @@ struct Dda {
         // (all rays but those within 0.3 deg of a space diagonal) that is < 0.9955 dt: the loop body runs exactly once whatever
         // tx, ty, tz round to, so the 30-odd operations that compute them are skipped.  Same t, same samples, bit for bit.
         one_step_skips = C == 1 && dt_min == dt_max && fmaxf(fabsf(dx), fmaxf(fabsf(dy), fabsf(dz))) > 0.58f;
+    }
+
+    // The occupied box's span (opt-in; the inference loop's marchers call it after init()).  box = {lo[3], hi[3]}: the cell
+    // coordinates between which every set bit of cascade 0 lies (rn_occ_box; lo > hi: no bit is set).
+    //
+    // t advances by t += clampf(t * dt_gamma, dt_min, dt_max) whatever the grid holds, and on a one_step_skips ray every lattice
+    // point is tested on its own: it is a sample iff its cell's bit is set.  A point whose cell lies outside the box has no bit
+    // set, so not testing it changes no sample, no count and no t.  [t_lo, t_hi] is the slab test of the ray against the box
+    // GROWN BY ONE WHOLE CELL on every side: at t < t_lo (t >= t_hi) the point has not entered (has left) the grown slab of some
+    // axis, i.e. it is a whole cell -- 2 mb1 / H -- away from the box on that axis, while everything that rounds between the
+    // slab's face and the point's cell (the face, face - o, 1 / d, the product, o + t * d, the cell coordinate) is off by less than
+    // 8 * 2^-24 (|o| + 2 mb1): under a tenth of a cell for H <= 256 (one_cascade) and |o_i| <= 4096 mb1, which set_span() requires.
+    // Every other ray keeps the full walk: more than one cascade, variable dt, max|d_i| <= 0.58, a far origin, a span that
+    // overflowed.  A NaN never narrows the span: fmaxf / fminf return their other operand.
+    //
+    // One axis: the slab of cells lo - 1 .. hi + 1 in world coordinates narrows [a, b].  A side on which the box reaches the
+    // grid's border has no face (cell_of() clamps every point beyond onto the border cells).  A ray that does not move on the
+    // axis (d == 0: o + t * d is o for every finite t) is inside or outside by its origin alone.
+    __device__ __forceinline__ void span_axis(float o, float d, float rd, int lo, int hi, float &a, float &b) const {
+        const bool open_lo = lo <= 0, open_hi = hi >= (int)H - 1;
+        const float f_lo = ((float)(lo - 1) * rH * 2 - 1) * mb1, f_hi = ((float)(hi + 2) * rH * 2 - 1) * mb1;
+        if (d == 0.0f) {
+            if ((!open_lo && o < f_lo) || (!open_hi && o > f_hi)) { a = FLT_MAX; b = -FLT_MAX; }
+            return;
+        }
+        const float t_f_lo = (f_lo - o) * rd, t_f_hi = (f_hi - o) * rd;
+        if (d > 0.0f) {
+            if (!open_lo) a = fmaxf(a, t_f_lo);
+            if (!open_hi) b = fminf(b, t_f_hi);
+        } else {
+            if (!open_hi) a = fmaxf(a, t_f_hi);
+            if (!open_lo) b = fminf(b, t_f_lo);
+        }
+    }
+    __device__ __forceinline__ void set_span(const int32_t *__restrict__ box) {
+        if (!(one_cascade && one_step_skips)) return;
+        if (!(fmaxf(fabsf(ox), fmaxf(fabsf(oy), fabsf(oz))) <= 4096.0f * mb1)) return;
+        float a = -FLT_MAX, b = FLT_MAX;
+        span_axis(ox, dx, rdx, box[0], box[3], a, b);
+        span_axis(oy, dy, rdy, box[1], box[4], a, b);
+        span_axis(oz, dz, rdz, box[2], box[5], a, b);
+        if (!(fabsf(a) <= FLT_MAX && fabsf(b) <= FLT_MAX)) return;   // overflowed: the full walk
+        t_lo = a; t_hi = b; span = true;
     }
 
     // occupancy-grid cell of the lattice point at parameter t (raymarching.cu:404-419); returns the bit index.
@@ -96,12 +143,25 @@ struct Dda {
     // (Measured on MI355X: the walk is bound by its own arithmetic, ~100 VALU ops per lattice point, not by the
     // dependent bitfield loads -- fetching the occupancy of the next 4 / 8 / 16 lattice points together and replaying the
     // decisions on a bit mask made k_head_march 10-17 % slower, so the loop keeps the reference's shape.)
-    template <class Sink>
+    // SPAN (opt-in, see set_span()): on lanes with `span` the lattice points before t_lo are stepped over by the loop's own
+    // t += dt without a cell or a load, and the walk ends at t_hi; the guard counts the stepped-over points too.
+    template <bool SPAN = false, class Sink>
     __device__ __forceinline__ uint32_t walk(float &t_io, uint32_t limit, Sink sink) const {
         float t = t_io;
         uint32_t step = 0;
         uint32_t guard = 0;  // not in the reference: bounds the walk on degenerate inputs (far = inf)
-        while (t < far && step < limit && guard < (1u << 20)) {
+        float end = far;
+        if constexpr (SPAN) {
+            if (span) {
+                end = t_hi < far ? t_hi : far;               // a NaN far stays: no t is below it, as in the full walk
+                const float first = t_lo < end ? t_lo : end;
+                while (t < first && guard < (1u << 20)) {
+                    t += clampf(t * dt_gamma, dt_min, dt_max);
+                    guard++;
+                }
+            }
+        }
+        while (t < (SPAN ? end : far) && step < limit && guard < (1u << 20)) {
             float x, y, z, dt, mip_bound;
             int nx, ny, nz;
             const uint32_t index = cell_of(t, x, y, z, dt, mip_bound, nx, ny, nz);
@@ -165,8 +225,11 @@ struct Dda {
 
     // One ray's share of a loop iteration: at most n_step samples from t into rows base .. base + n_step - 1; the rows the walk
     // did not reach get deltas = 0 (the network and the compositor skip them), so the sample buffers never need a memset.
+    // t is taken by value: where the walk stops is not visible to anyone (the compositor writes rays_t from deltas), which is
+    // what lets SPAN end a walk at t_hi instead of far.
+    template <bool SPAN = false>
     __device__ __forceinline__ uint32_t march_slot(float t, uint32_t n_step, uint32_t base, float *xyzs, float *dirs, float *deltas) const {
-        const uint32_t emitted = walk(t, n_step, EmitSamples{xyzs + (size_t)base * 3, dirs + (size_t)base * 3, deltas + (size_t)base * 2});
+        const uint32_t emitted = walk<SPAN>(t, n_step, EmitSamples{xyzs + (size_t)base * 3, dirs + (size_t)base * 3, deltas + (size_t)base * 2});
         for (uint32_t k = emitted; k < n_step; k++) { deltas[((size_t)base + k) * 2] = 0.0f; deltas[((size_t)base + k) * 2 + 1] = 0.0f; }
         return emitted;
     }

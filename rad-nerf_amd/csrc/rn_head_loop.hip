@@ -79,7 +79,8 @@ k_head_march(const int32_t *__restrict__ st, const int32_t *__restrict__ rays_al
              const float *__restrict__ rays_o, const float *__restrict__ rays_d, float bound, float dt_gamma,
              uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t *__restrict__ grid,
              const float *__restrict__ fars, float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas, int32_t *__restrict__ stats,
-             uint32_t *__restrict__ block_live, int32_t *__restrict__ live_count, int32_t *__restrict__ live_slots) {
+             uint32_t *__restrict__ block_live, int32_t *__restrict__ live_count, int32_t *__restrict__ live_slots,
+             const int32_t *__restrict__ occ_box) {
     if (!st[4]) return;
     const uint32_t n_alive = (uint32_t)st[0], n_step = (uint32_t)st[2];
     const uint32_t n = blockIdx.x * kLoopBlock + threadIdx.x;
@@ -89,7 +90,8 @@ k_head_march(const int32_t *__restrict__ st, const int32_t *__restrict__ rays_al
         const int index = rays_alive[n];
         Dda s;
         s.init(rays_o + (size_t)index * 3, rays_d + (size_t)index * 3, bound, dt_gamma, max_steps, C, H, grid, fars[index]);
-        emitted = s.march_slot(rays_t[index], n_step, base, xyzs, dirs, deltas);  // perturb is off at inference: no noise term (renderer.py:251)
+        if (occ_box) s.set_span(occ_box);
+        emitted = s.march_slot<true>(rays_t[index], n_step, base, xyzs, dirs, deltas);  // perturb is off at inference: no noise term (renderer.py:251)
     }
     // live samples of this iteration: listed for the network kernel, and counted -- one partial sum per workgroup, added up by
     // the compaction kernel (a same-address atomic per wavefront for the statistic cost 38 us per frame)
@@ -117,7 +119,8 @@ k_frame_begin(RaySource rs, float *__restrict__ rays_o, float *__restrict__ rays
               const uint8_t *__restrict__ grid, float *__restrict__ nears, float *__restrict__ fars, float *__restrict__ weights_sum,
               float *__restrict__ depth, float *__restrict__ image, int32_t *__restrict__ rays_alive, float *__restrict__ rays_t,
               int32_t *__restrict__ state, uint32_t order_w, float *__restrict__ xyzs, float *__restrict__ dirs,
-              float *__restrict__ deltas, uint32_t *__restrict__ block_live, int32_t *__restrict__ live_slots) {
+              float *__restrict__ deltas, uint32_t *__restrict__ block_live, int32_t *__restrict__ live_slots,
+              const int32_t *__restrict__ occ_box) {
     const uint32_t n = blockIdx.x * kLoopBlock + threadIdx.x;
     if (n == 0) {
         next_state(state, N, N, 0, max_steps);
@@ -144,7 +147,8 @@ k_frame_begin(RaySource rs, float *__restrict__ rays_o, float *__restrict__ rays
         // iteration 0 (k_head_march with n_alive = N, n_step = 1): slot n
         Dda s;
         s.init(o, d, bound, dt_gamma, max_steps, C, H, grid, far);
-        emitted = s.march_slot(near, 1u, n, xyzs, dirs, deltas);
+        if (occ_box) s.set_span(occ_box);
+        emitted = s.march_slot<true>(near, 1u, n, xyzs, dirs, deltas);
     }
     __shared__ uint32_t sh[kLoopBlock / kWave + 1];
     const uint32_t total = list_live_slots(emitted, n, state + 6, live_slots, sh);
@@ -214,6 +218,7 @@ struct MarchArgs {
     float *xyzs, *dirs, *deltas;
     uint32_t *block_live_next;
     int32_t *live_slots;
+    const int32_t *occ_box;   // the occupied box (rn_head_t.occ_box) or NULL
 };
 
 // What a launch does when the loop is already over (st[4] == 0): carry the state over, close the frame's counters.
@@ -312,7 +317,8 @@ __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, con
             Dda s;
             s.init(m.rays_o + (size_t)v * 3, m.rays_d + (size_t)v * 3, m.bound, m.dt_gamma, max_steps, m.cascade, m.grid_size, m.grid,
                    m.fars[v]);
-            emitted = s.march_slot(m.rays_t[v], n_step_next, base, m.xyzs, m.dirs, m.deltas);
+            if (m.occ_box) s.set_span(m.occ_box);
+            emitted = s.march_slot<true>(m.rays_t[v], n_step_next, base, m.xyzs, m.dirs, m.deltas);
         }
         __shared__ uint32_t sh[kLoopBlock / kWave + 1];
         const uint32_t total = list_live_slots(emitted, base, st_next + 6, m.live_slots, sh);
@@ -442,13 +448,13 @@ int rn_head_iterate_ex(const rn_head_t *h, const rn_grid_t *grid_xyz, const rn_g
         if (it == first_iter && !(flags & RN_LOOP_FIRST_MARCHED))
             hipLaunchKernelGGL(k_head_march, rgrid, rblock, 0, s, st, alive, h->rays_t, h->rays_o, h->rays_d, h->bound,
                                h->dt_gamma, h->max_steps, h->cascade, h->grid_size, h->bitfield, h->fars, h->xyzs, h->dirs,
-                               h->deltas, h->state, block_live[it & 1u], st + 6, h->live_slots);
+                               h->deltas, h->state, block_live[it & 1u], st + 6, h->live_slots, h->occ_box);
         // the network runs over the iteration's live list when the caller gave room for one (st[6] entries), else over all
         // st[3] slots, skipping the dead ones by their deltas
         run_fused(h->xyzs, h->dirs, h->deltas, h->N, h->live_slots ? st + 6 : st + 3, grid_xyz, grid_amb, packed, bias, h->bound,
                   h->sigmas, h->rgbs, nullptr, mlp_dtype, s, h->live_slots);
         const MarchArgs m{h->rays_t, h->rays_o, h->rays_d, h->fars, h->bound, h->dt_gamma, h->cascade, h->grid_size, h->bitfield,
-                          h->xyzs, h->dirs, h->deltas, block_live[(it + 1) & 1u], h->live_slots};
+                          h->xyzs, h->dirs, h->deltas, block_live[(it + 1) & 1u], h->live_slots, h->occ_box};
         const bool march_next = it + 1 < first_iter + n_iters;
         const uint32_t close = (!march_next && (flags & RN_LOOP_CLOSE_FRAME)) ? 1u : 0u;
         if (flags & RN_LOOP_COOP) {  // compositor + compaction (+ next march) behind one launch (k_head_step)
@@ -502,7 +508,8 @@ int rn_frame_begin(const rn_head_t *h, const float *pose, float fx, float fy, fl
     hipLaunchKernelGGL(k_frame_begin, dim3(div_up(h->N, kLoopBlock)), dim3(kLoopBlock), 0, as_stream(stream), rs,
                        const_cast<float *>(h->rays_o), const_cast<float *>(h->rays_d), h->aabb, h->N, h->min_near, h->max_steps, h->bound,
                        h->dt_gamma, h->cascade, h->grid_size, h->bitfield, h->nears, h->fars, h->weights_sum, h->depth, h->image,
-                       h->rays_alive_a, h->rays_t, h->state, order_w, h->xyzs, h->dirs, h->deltas, h->block_counts + nb, h->live_slots);
+                       h->rays_alive_a, h->rays_t, h->state, order_w, h->xyzs, h->dirs, h->deltas, h->block_counts + nb, h->live_slots,
+                       h->occ_box);
     return check_launch("frame_begin");
 }
 

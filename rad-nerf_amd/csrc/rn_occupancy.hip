@@ -121,6 +121,43 @@ k_occ_pack(const float *__restrict__ grid, uint32_t N, const float *__restrict__
     bitfield[n] = (uint8_t)bits;
 }
 
+// ---- the box around the set bits of cascade 0 (rn_head_t.occ_box) ------------------------------------------------
+// Byte n holds the cells with morton codes 8 n .. 8 n + 7: one 2 x 2 x 2 block, bit i at offset (i & 1, i >> 1 & 1, i >> 2) from
+// the cell of code 8 n.  A lane takes a byte, a wave folds its lanes' bounds, and the waves that saw a set bit fold theirs into
+// box[] with integer atomics (an ellipsoid in 128^3: a few hundred waves, once per grid).
+__global__ void k_occ_box_init(uint32_t H, int32_t *__restrict__ box) {
+    if (threadIdx.x < 8) box[threadIdx.x] = threadIdx.x < 3 ? (int32_t)H : (threadIdx.x < 6 ? -1 : 0);
+}
+
+__global__ void __launch_bounds__(kOccBlock)
+k_occ_box(const uint8_t *__restrict__ bitfield, uint32_t n_bytes, int32_t *__restrict__ box) {
+    const uint32_t n = blockIdx.x * kOccBlock + threadIdx.x;
+    const uint32_t bits = n < n_bytes ? bitfield[n] : 0u;
+    int32_t lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+    if (bits) {
+        const uint32_t mo = n * 8u;
+        const int32_t c[3] = {(int32_t)morton3D_invert(mo), (int32_t)morton3D_invert(mo >> 1), (int32_t)morton3D_invert(mo >> 2)};
+#pragma unroll
+        for (int d = 0; d < 3; d++) {
+            // bits whose offset on axis d is 0 / 1: d = 0: 0x55 / 0xAA, d = 1: 0x33 / 0xCC, d = 2: 0x0F / 0xF0
+            const uint32_t at0 = d == 0 ? 0x55u : (d == 1 ? 0x33u : 0x0Fu);
+            lo[d] = (bits & at0) ? c[d] : c[d] + 1;
+            hi[d] = (bits & ~at0 & 0xFFu) ? c[d] + 1 : c[d];
+        }
+    }
+#pragma unroll
+    for (int d = 0; d < 3; d++)
+        for (int off = 32; off > 0; off >>= 1) {
+            const int32_t l = __shfl_down(lo[d], off, 64), h = __shfl_down(hi[d], off, 64);
+            lo[d] = l < lo[d] ? l : lo[d];
+            hi[d] = h > hi[d] ? h : hi[d];
+        }
+    if ((threadIdx.x & 63) == 0 && hi[0] >= 0) {
+#pragma unroll
+        for (int d = 0; d < 3; d++) { atomicMin(&box[d], lo[d]); atomicMax(&box[3 + d], hi[d]); }
+    }
+}
+
 // ---- untrained cells (renderer.py:318-379) -----------------------------------------------------------------------
 // One lane per (cascade, cell), poses staged in LDS 64 at a time; a cell is "seen" when some camera has it in front
 // (cam_z > 0) and inside the frustum widened by one cell.  The reference counts the cameras and then tests count == 0;
@@ -253,6 +290,17 @@ int rn_occupancy_update(const float *sigmas, float density_scale, float *density
     hipLaunchKernelGGL(k_occ_mean, dim3(1), dim3(kOccBlock), 0, s, partial, blocks, total, density_thresh, stats);
     hipLaunchKernelGGL(k_occ_pack, dim3(div_up(total / 8, kOccBlock)), dim3(kOccBlock), 0, s, density_grid, total / 8, stats, bitfield);
     return check_launch("occupancy_update");
+}
+
+int rn_occ_box(const uint8_t *bitfield, uint32_t cascade, uint32_t grid_size, int32_t *box, rn_stream_t stream) {
+    RN_REQUIRE(bitfield && box, "occ_box: null pointer");
+    RN_REQUIRE(cascade >= 1 && cascade <= 16 && grid_size >= 2 && grid_size <= 1024 && (grid_size * grid_size * grid_size) % 8 == 0,
+               "occ_box: bad cascade / grid_size");
+    const uint32_t n_bytes = grid_size * grid_size * grid_size / 8;      // cascade 0 is the first H^3 bits
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(k_occ_box_init, dim3(1), dim3(kWave), 0, s, grid_size, box);
+    hipLaunchKernelGGL(k_occ_box, dim3(div_up(n_bytes, kOccBlock)), dim3(kOccBlock), 0, s, bitfield, n_bytes, box);
+    return check_launch("occ_box");
 }
 
 int rn_mark_untrained_grid(const float *poses, uint32_t n_poses, uint32_t pose_stride, double fx, double fy, double cx, double cy,

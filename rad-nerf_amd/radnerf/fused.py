@@ -125,6 +125,28 @@ class FusedState:
         self._zero_eye = torch.zeros(1, dtype=torch.float32, device=self.dev)
         self.plan = None
         self.plan_builds = 0
+        self.box = None
+        self._box_key = None
+        self.box_builds = 0
+
+    # -- occupied box ---------------------------------------------------------------------------------
+    def occ_box(self):
+        """The box around the set bits of the model's bitfield (rn_occ_box: 8 int32 on the device, never read back) for
+        rn_head_t.occ_box, or None with RN_OCC_BOX=0.  Built on the current stream when the bitfield's address or version, the
+        cascade count or the grid size differ from the last build's -- a grid refresh (update_extra_state) and an in-place edit
+        both move the version -- so a stream of frames over one grid builds it once."""
+        if not switches.on("RN_OCC_BOX"):
+            return None
+        m = self.model
+        bits = m.density_bitfield
+        key = (bits.data_ptr(), bits._version, int(m.cascade), int(m.grid_size))
+        if key != self._box_key:
+            if self.box is None:
+                self.box = torch.zeros(8, dtype=torch.int32, device=self.dev)
+            hip.call("rn_occ_box", hip.ptr(bits), int(m.cascade), int(m.grid_size), hip.ptr(self.box), hip.stream())
+            self._box_key = key
+            self.box_builds += 1
+        return self.box
 
     # -- weights --------------------------------------------------------------------------------------
     def _weights(self):
@@ -502,6 +524,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
     # image width, if the caller said the rays are the row-major pixels of an image (SyntheticScene does): the loop then
     # walks the rays in 8 x 8 pixel blocks (more shared grid rows per wave; no pixel changes)
     h.order_w = int(getattr(model, "ray_order_width", 0) or 0)
+    h.occ_box = hip.ptr(st.occ_box())
 
     # The whole <= max_steps loop is enqueued without reading anything back: iterations past the end of the loop
     # are no-ops decided on the device (a few microseconds each), so the host can run ahead of the GPU.

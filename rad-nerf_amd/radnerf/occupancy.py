@@ -85,6 +85,8 @@ def refresh_head(model, enc_a, eye, decay=0.95, noise=None):
         raise RuntimeError("density_grid must be contiguous")
     hip.call("rn_occupancy_update", hip.ptr(sc.sigmas), float(model.density_scale), hip.ptr(grid), Cc, H, float(decay),
              float(model.density_thresh), hip.ptr(model.density_bitfield), hip.ptr(sc.stats), hip.ptr(sc.ws), s)
+    # written through its address: tell torch, so that whatever is keyed on the bitfield's version (the fused engine's occupied box) sees it
+    torch.autograd.graph.increment_version(model.density_bitfield)
     return sc.stats
 
 

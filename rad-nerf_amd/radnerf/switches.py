@@ -11,6 +11,7 @@ TABLE = (
     ("RN_AUDIO_TRAIN", "hip", ("hip", "torch"), "`encode_audio` on the GPU: the audio kernels (`radnerf/audio.py`) or the `nn.Module` path"),
     ("RN_LIVE_LIST", "1", ("1", "0"), "fused inference engine: hand the loop the list of live sample slots (`0`: every launch scans all slots)"),
     ("RN_MLP_TRAIN", "hip", ("hip", "torch"), "the per-operator MLP stacks under autograd: `rn_mlp64_*` (`radnerf/mlp_train.py`) or `nn.Linear`"),
+    ("RN_OCC_BOX", "1", ("1", "0"), "fused inference engine: hand the loop the box around the occupancy grid's set bits (`rn_occ_box`, built once per grid): with one cascade and a constant step a ray tests only the cells between its entry into and its exit from that box (same bits); `0`: every ray tests every cell from `near` to `far`"),
     ("RN_PERCEP", "hip", ("hip", "torch"), "`PerceptualAlex` (`radnerf/percep.py`) on the GPU in fp32: the perceptual kernels (`rn_percep_*`), or the same arithmetic in plain torch (unfold + matmul)"),
     ("RN_SCATTER", "lbc", ("lbc", "binned"), "table-gradient scatter: the line merge for every level, or hashed levels of the first grid summed by table region"),
     ("RN_TORSO_PLAN", "1", ("1", "0"), "fused inference engine: a frame whose pixel grid and torso occupancy grid are those of the frame before runs its torso pass over a plan built once (`rn_torso_plan_build`: the covered pixels and their position encoding; same bits); `0`: every frame computes them (`rn_torso_blend_frame`)"),

@@ -47,7 +47,7 @@ class HeadT(C.Structure):
                 ("grid_size", _u32), ("T_thresh", _f32), ("nears", _ptr), ("fars", _ptr), ("weights_sum", _ptr),
                 ("depth", _ptr), ("image", _ptr), ("rays_alive_a", _ptr), ("rays_alive_b", _ptr), ("rays_t", _ptr),
                 ("xyzs", _ptr), ("dirs", _ptr), ("deltas", _ptr), ("sigmas", _ptr), ("rgbs", _ptr), ("state", _ptr),
-                ("block_counts", _ptr), ("live_slots", _ptr), ("order_w", _u32)]
+                ("block_counts", _ptr), ("live_slots", _ptr), ("order_w", _u32), ("occ_box", _ptr)]
 
 
 class TorsoWeightsT(C.Structure):
@@ -188,6 +188,7 @@ FUNCTIONS = {
     "rn_mark_untrained_grid": (_int, [_ptr, _u32, _u32, _f64, _f64, _f64, _f64, _u32, _u32, _f32, _ptr, _ptr]),
     "rn_torso_grid_points": (_int, [_u32, _ptr, _u32, _ptr, _ptr]),
     "rn_torso_grid_update": (_int, [_ptr, _ptr, _u32, _f32, _ptr, _ptr]),
+    "rn_occ_box": (_int, [_ptr, _u32, _u32, _ptr, _ptr]),
     "rn_hash_u01_bits": (_u32, [_u32, _u32]),
     "rn_audio_encode_windows": (_int, [_P(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _ptr]),
     "rn_audio_encode_windows_backward": (_int, [_P(AudioWeightsT), _ptr, _u32, _ptr, _ptr, _P(AudioGradsT), _ptr, _ptr]),
