@@ -11,7 +11,7 @@
 //     [L,B,C], only one level's table is live in an XCD's L2 at a time) and sample-major (one
 //     sample per lane walks all levels and stores its whole [L*C] row, layout [B, L*C], which
 //     removes the reference's permute copy).
-#include "rn_grid_dev.h"
+#include "rn_scatter_dev.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -21,24 +21,6 @@
 #endif
 
 namespace rn {
-
-// GridEncoder.forward's `inputs = (inputs + bound) / (2 * bound)` (gridencoder/grid.py:149) folded into the lookup's coordinate
-// load: x -> (x + add) * mul with mul = 1 / (2 * bound) in fp32 -- what the division by a host scalar computes on the device
-// in PyTorch -- so the module needs no pass of its own over the coordinates.  on = 0: coordinates are used as given.
-struct InXform { float add, mul; uint32_t on; };
-
-template <uint32_t D>
-__device__ __forceinline__ bool load_input(const float *__restrict__ inputs, uint32_t b, float (&in)[D], const InXform xf = InXform{0, 1, 0}) {
-    bool oob = false;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        float x = inputs[(size_t)b * D + d];
-        if (xf.on) x = (x + xf.add) * xf.mul;
-        in[d] = x;
-        oob |= (in[d] < 0 || in[d] > 1);  // gridencoder.cu:113-117
-    }
-    return oob;
-}
 
 // One level of one sample.  The common case (align_corners off, linear interpolation, D = 2 / 3) goes through the per-level
 // plan of rn_grid_dev.h -- the level's facts are wave-uniform here, so plan_level() runs on the scalar unit -- and costs
@@ -381,39 +363,7 @@ __device__ __forceinline__ void atomic_add_row(__half *p, const float (&v)[2]) {
     __builtin_amdgcn_global_atomic_fadd_v2f16((gptr_t)(p), x);
 }
 
-// Scatter-add with wave-level pre-reduction.  Samples arrive ray-ordered, so neighbouring lanes often hit the same
-// table row (always on the coarse levels; on every level of the ambient grid, whose coordinates cluster around 0) and
-// plain atomics then serialise on one address in L2.  Lanes with equal keys in consecutive lanes form a run; a
-// segmented inclusive scan (6 shuffle steps, the run heads taken from one ballot) sums each run and only its last lane
-// issues the atomic.  Waves with few repeats skip the scan.  `key` must be ~0u on lanes that contribute nothing.
-template <typename T, uint32_t N_C>
-__device__ __forceinline__ void scatter_add_runs(T *__restrict__ table, uint32_t key, float (&v)[N_C]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
-    const bool head = lane == 0 || key != prev;
-    const unsigned long long heads = __ballot(head);
-    const bool valid = key != ~0u;
-    if (__popcll(heads) > 40) {  // mostly distinct rows: the scan would not pay
-        if (valid) atomic_add_row(table + key, v);
-        return;
-    }
-    // first lane of my run: highest head bit at or below my lane
-    const unsigned long long below = heads & ((2ull << lane) - 1ull);
-    const uint32_t start = 63u - (uint32_t)__clzll(below);
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        float up[N_C];
-#pragma unroll
-        for (uint32_t c = 0; c < N_C; c++) up[c] = __shfl_up(v[c], off, 64);
-        if (lane >= start + off) {
-#pragma unroll
-            for (uint32_t c = 0; c < N_C; c++) v[c] += up[c];
-        }
-    }
-    const bool tail = lane == 63u || ((heads >> (lane + 1)) & 1ull);
-    if (tail && valid) atomic_add_row(table + key, v);
-}
-
+// Run sums first (sum_runs, rn_scatter_dev.h): only the last lane of a run of equal addresses issues the atomic.
 template <typename T, uint32_t D, uint32_t C, uint32_t N_C, int LAYOUT>
 __global__ void __launch_bounds__(256)
 k_grid_bwd_table(const T *__restrict__ grad, const float *__restrict__ inputs, const int32_t *__restrict__ offsets,
@@ -452,65 +402,32 @@ k_grid_bwd_table(const T *__restrict__ grad, const float *__restrict__ inputs, c
     T *gg = grad_grid + (size_t)off * C;
 #pragma unroll
     for (uint32_t idx = 0; idx < (1u << D); idx++) {
-        float w = 1;
         uint32_t pgl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            const bool hi = (idx >> d) & 1u;
-            w *= hi ? pos[d] : 1 - pos[d];
-            pgl[d] = pos_grid[d] + (hi ? 1u : 0u);
-        }
+        const float w = corner<D>(idx, pos, pos_grid, pgl);
         const uint32_t row = live ? grid_row<D>(gridtype, align_corners, hashmap_size, resolution, pgl) : 0u;
         float v[N_C];
 #pragma unroll
         for (uint32_t c = 0; c < N_C; c++) v[c] = w * grad_cur[c];
-        scatter_add_runs<T, N_C>(gg, live ? row * C + ch : ~0u, v);
+        const uint32_t key[1] = {live ? row * C + ch : kNoRow};
+        if (sum_runs(key, v)) atomic_add_row(gg + key[0], v);
     }
-}
-
-// Wave-level pre-reduction for the LDS merge below: lanes hold (key, v); consecutive lanes with equal keys form a run
-// (ray-ordered samples sit in the same coarse cell for many steps, so on the coarse levels a run is most of a ray).  A
-// segmented inclusive scan sums each run into its last lane, which alone goes on to the LDS table: without it the coarse
-// levels spend their time in same-address LDS atomics (thousands of inserts into a few dozen slots: 600 us per training
-// step on the xyz grid, measured).  Returns true on the lanes that must insert.  Waves with few repeats skip the scan.
-template <uint32_t N_C>
-__device__ __forceinline__ bool merge_runs(uint32_t key, float (&v)[N_C]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64);
-    const bool head = lane == 0 || key != prev;
-    const unsigned long long heads = __ballot(head);
-    if (__popcll(heads) > 40) return key != ~0u;
-    const unsigned long long below = heads & ((2ull << lane) - 1ull);
-    const uint32_t start = 63u - (uint32_t)__clzll(below);
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        float up[N_C];
-#pragma unroll
-        for (uint32_t c = 0; c < N_C; c++) up[c] = __shfl_up(v[c], off, 64);
-        if (lane >= start + off) {
-#pragma unroll
-            for (uint32_t c = 0; c < N_C; c++) v[c] += up[c];
-        }
-    }
-    const bool tail = lane == 63u || ((heads >> (lane + 1)) & 1ull);
-    return tail && key != ~0u;
 }
 
 // Scatter-add with block-level pre-reduction (C <= 2, D <= 3: one lane per sample and level).  The 256 samples of a
 // block touch 256 * 2^D rows of one level; ray-ordered samples share most of them on the coarse levels, and the
-// corners of neighbouring samples coincide, so the block first sums them in an LDS hash table (open addressing,
-// load factor <= 0.5, ds_cmpst + ds_add_f32) and then issues ONE global atomic per distinct row.  Device-scope
-// float atomics on this part resolve behind the per-XCD L2s, so their count -- not their bytes -- is the cost.
+// corners of neighbouring samples coincide, so the block first sums them -- runs of lanes in registers (sum_runs), then in
+// an LDS hash table (open addressing, load factor <= 0.5, ds_cmpst + ds_add_f32) -- and then issues ONE global atomic per
+// distinct row.  Device-scope float atomics on this part resolve behind the per-XCD L2s, so their count -- not their
+// bytes -- is the cost.
 template <typename T, uint32_t D, uint32_t C, int LAYOUT>
 __global__ void __launch_bounds__(256)
 k_grid_bwd_table_merge(const T *__restrict__ grad, const float *__restrict__ inputs, const int32_t *__restrict__ offsets,
                        T *__restrict__ grad_grid, uint32_t B, uint32_t L, LevelConsts lc, uint32_t gridtype,
                        bool align_corners, uint32_t interp) {
     constexpr uint32_t kSlots = 256u * (1u << D) * 2u;
-    constexpr uint32_t kEmpty = 0xffffffffu;
     __shared__ uint32_t keys[kSlots];
     __shared__ float vals[kSlots * C];
-    for (uint32_t i = threadIdx.x; i < kSlots; i += 256) keys[i] = kEmpty;
+    for (uint32_t i = threadIdx.x; i < kSlots; i += 256) keys[i] = kNoRow;
     for (uint32_t i = threadIdx.x; i < kSlots * C; i += 256) vals[i] = 0.0f;
     __syncthreads();
 
@@ -539,25 +456,21 @@ k_grid_bwd_table_merge(const T *__restrict__ grad, const float *__restrict__ inp
 #pragma unroll
         for (uint32_t idx = 0; idx < (1u << D); idx++) {
             float w = 1;
-            uint32_t pgl[D];
-            uint32_t row = ~0u;
+            uint32_t key[1] = {kNoRow};
             if (live) {
-#pragma unroll
-                for (uint32_t d = 0; d < D; d++) {
-                    const bool hi = (idx >> d) & 1u;
-                    w *= hi ? pos[d] : 1 - pos[d];
-                    pgl[d] = pos_grid[d] + (hi ? 1u : 0u);
-                }
-                row = grid_row<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
+                uint32_t pgl[D];
+                w = corner<D>(idx, pos, pos_grid, pgl);
+                key[0] = grid_row<D>(gridtype, align_corners, hashmap_size, resolution, pgl);
             }
             float v[C];
 #pragma unroll
             for (uint32_t c = 0; c < C; c++) v[c] = live ? w * g0[c] : 0.0f;
-            if (merge_runs<C>(row, v)) {
+            if (sum_runs(key, v)) {
+                const uint32_t row = key[0];
                 uint32_t slot = (row * 2654435761u) & (kSlots - 1u);
                 while (true) {
-                    const uint32_t prev = atomicCAS(&keys[slot], kEmpty, row);
-                    if (prev == kEmpty || prev == row) break;
+                    const uint32_t prev = atomicCAS(&keys[slot], kNoRow, row);
+                    if (prev == kNoRow || prev == row) break;
                     slot = (slot + 1u) & (kSlots - 1u);
                 }
 #pragma unroll
@@ -575,12 +488,12 @@ k_grid_bwd_table_merge(const T *__restrict__ grad, const float *__restrict__ inp
         for (uint32_t i = threadIdx.x; i < kSlots * 2u; i += 256) {
             const uint32_t slot = i >> 1, c = i & 1u;
             const uint32_t row = keys[slot];
-            if (row != kEmpty) atomicAdd(reinterpret_cast<float *>(gg) + (size_t)row * 2u + c, vals[slot * 2u + c]);
+            if (row != kNoRow) atomicAdd(reinterpret_cast<float *>(gg) + (size_t)row * 2u + c, vals[slot * 2u + c]);
         }
     } else {
         for (uint32_t i = threadIdx.x; i < kSlots; i += 256) {
             const uint32_t row = keys[i];
-            if (row != kEmpty) {
+            if (row != kNoRow) {
                 float v[C];
 #pragma unroll
                 for (uint32_t c = 0; c < C; c++) v[c] = vals[i * C + c];
@@ -722,16 +635,9 @@ static int dispatch_fwd_d(uint32_t D, uint32_t C, const FwdArgs &a) {
 // staged); D = 2 / 3, align_corners off, linear interpolation, no dy_dx -- everything else takes the per-level kernels.
 constexpr size_t kCoarseTableBytes = 3u << 20;   // coarse levels gathered together: their tables share an XCD's 4 MB L2
 
+// every dimension indexed densely: neither a dimension dropped (tiled) nor the level hashed, as plan_level() evaluates it
 template <uint32_t D>
-static bool host_level_is_dense(uint32_t resolution, uint32_t size, uint32_t gridtype) {
-    uint64_t stride = 1;                             // gridencoder.cu:66-84, as plan_level() evaluates it
-    for (uint32_t d = 0; d < D; d++) {
-        if (stride > size) return false;             // a dimension dropped (tiled) or the level hashed
-        stride *= (uint64_t)resolution + 1u;
-    }
-    (void)gridtype;
-    return stride <= size;
-}
+static bool host_level_is_dense(uint32_t resolution, uint32_t size) { return level_stride(D, resolution, size) <= size; }
 
 static int grid_cus() {
     static int cus = 0;
@@ -755,7 +661,7 @@ static CoarseSplit coarse_split(const int32_t *oh, uint32_t L, const LevelConsts
     while (!no_lds && cs.n_lds < L && cs.n_lds < kCoarseMaxLevels) {
         const uint32_t size = (uint32_t)(oh[cs.n_lds + 1] - oh[cs.n_lds]);
         const size_t bytes = (size_t)oh[cs.n_lds + 1] * C * sizeof(T);
-        if (oh[0] != 0 || !host_level_is_dense<D>(lc.resolution[cs.n_lds], size, gridtype) || bytes > kCoarseLdsBudget) break;
+        if (oh[0] != 0 || !host_level_is_dense<D>(lc.resolution[cs.n_lds], size) || bytes > kCoarseLdsBudget) break;
         cs.lds_bytes = (uint32_t)bytes;
         cs.n_lds++;
     }
@@ -929,34 +835,26 @@ struct BwdArgs {
     hipStream_t stream;
 };
 
-template <typename T, uint32_t D, uint32_t C>
-static void launch_bwd(const BwdArgs &a) {
+template <typename T, uint32_t D, uint32_t C, int LAYOUT>
+static void launch_bwd_layout(const BwdArgs &a) {
     constexpr uint32_t N_C = C < 2 ? C : 2;  // gridencoder.cu:404
     const T *grad = static_cast<const T *>(a.grad);
     T *gt = static_cast<T *>(a.grad_table);
     const dim3 block(256), grid(div_up(a.B * C / N_C, 256), a.L);
-    if constexpr (C <= 2 && D <= 3) {
-        if (a.layout == RN_LAYOUT_LBC)
-            hipLaunchKernelGGL((k_grid_bwd_table_merge<T, D, C, RN_LAYOUT_LBC>), grid, block, 0, a.stream, grad, a.inputs,
-                               a.offsets, gt, a.B, a.L, a.lc, a.gridtype, a.align_corners, a.interp);
-        else
-            hipLaunchKernelGGL((k_grid_bwd_table_merge<T, D, C, RN_LAYOUT_BLC>), grid, block, 0, a.stream, grad, a.inputs,
-                               a.offsets, gt, a.B, a.L, a.lc, a.gridtype, a.align_corners, a.interp);
-    } else if (a.layout == RN_LAYOUT_LBC)
-        hipLaunchKernelGGL((k_grid_bwd_table<T, D, C, N_C, RN_LAYOUT_LBC>), grid, block, 0, a.stream, grad, a.inputs,
-                           a.offsets, gt, a.B, a.L, a.lc, a.gridtype, a.align_corners, a.interp);
+    if constexpr (C <= 2 && D <= 3)
+        hipLaunchKernelGGL((k_grid_bwd_table_merge<T, D, C, LAYOUT>), grid, block, 0, a.stream, grad, a.inputs, a.offsets, gt, a.B, a.L,
+                           a.lc, a.gridtype, a.align_corners, a.interp);
     else
-        hipLaunchKernelGGL((k_grid_bwd_table<T, D, C, N_C, RN_LAYOUT_BLC>), grid, block, 0, a.stream, grad, a.inputs,
-                           a.offsets, gt, a.B, a.L, a.lc, a.gridtype, a.align_corners, a.interp);
-    if (a.dy_dx && a.grad_inputs) {
-        const T *dy = static_cast<const T *>(a.dy_dx);
-        T *gi = static_cast<T *>(a.grad_inputs);
-        const dim3 g2(div_up(a.B * D, 256));
-        if (a.layout == RN_LAYOUT_LBC)
-            hipLaunchKernelGGL((k_grid_bwd_input<T, D, C, RN_LAYOUT_LBC>), g2, block, 0, a.stream, grad, dy, gi, a.B, a.L);
-        else
-            hipLaunchKernelGGL((k_grid_bwd_input<T, D, C, RN_LAYOUT_BLC>), g2, block, 0, a.stream, grad, dy, gi, a.B, a.L);
-    }
+        hipLaunchKernelGGL((k_grid_bwd_table<T, D, C, N_C, LAYOUT>), grid, block, 0, a.stream, grad, a.inputs, a.offsets, gt, a.B, a.L,
+                           a.lc, a.gridtype, a.align_corners, a.interp);
+    if (a.dy_dx && a.grad_inputs)
+        hipLaunchKernelGGL((k_grid_bwd_input<T, D, C, LAYOUT>), dim3(div_up(a.B * D, 256)), block, 0, a.stream, grad,
+                           static_cast<const T *>(a.dy_dx), static_cast<T *>(a.grad_inputs), a.B, a.L);
+}
+template <typename T, uint32_t D, uint32_t C>
+static void launch_bwd(const BwdArgs &a) {
+    if (a.layout == RN_LAYOUT_LBC) launch_bwd_layout<T, D, C, RN_LAYOUT_LBC>(a);
+    else launch_bwd_layout<T, D, C, RN_LAYOUT_BLC>(a);
 }
 template <typename T, uint32_t D>
 static int dispatch_bwd_c(uint32_t C, const BwdArgs &a) {

@@ -25,6 +25,18 @@ static inline LevelConsts make_level_consts(uint32_t L, float S, uint32_t H) {
     return lc;
 }
 
+// The dense index stride after the last dimension that still fits a level of `rows` rows (gridencoder.cu:66-84, align_corners
+// off): <= rows when every dimension is indexed densely; past it, a hash grid hashes the level and a tiled grid drops the rest.
+static inline uint64_t level_stride(uint32_t D, uint32_t resolution, uint32_t rows) {
+    uint64_t stride = 1;
+    for (uint32_t d = 0; d < D; d++)
+        if (stride <= rows) stride *= (uint64_t)resolution + 1u;
+    return stride;
+}
+static inline bool level_is_hashed(uint32_t D, uint32_t resolution, uint32_t rows, uint32_t gridtype) {
+    return gridtype == 0 && level_stride(D, resolution, rows) > rows;
+}
+
 // ---- scalar helpers ---------------------------------------------------------------------------
 template <typename T> __device__ __forceinline__ float to_f(T v);
 template <> __device__ __forceinline__ float to_f<float>(float v) { return v; }

@@ -9,12 +9,13 @@
 //    x-neighbours of a corner pair share a line 7 times out of 8, on hashed levels too: the x prime is 1) and then issues the
 //    16 floats of a slot from 16 adjacent lanes -- one request per touched line instead of one per row.
 //  * k_grid_bin / k_grid_scatter_buckets: the opt-in binned form for large hashed levels (below).
+// What an addend is (sample load, corner weight and row), the wave-level run sum, the job description and its checks are shared
+// with the operator's and the ordered route: rn_scatter_dev.h.
 // The kernels keep namespace rn::th, the one they had inside rn_train_head.hip: profiles and tools match on their names.
 #include "rn_fused_dev.h"
+#include "rn_scatter_dev.h"
 
 #include <stdlib.h>
-
-#include "../../include/radnerf_train.h"
 
 namespace rn {
 namespace th {
@@ -28,44 +29,8 @@ namespace th {
 constexpr uint32_t kScThreads = 256, kScSlots = RN_SC_SLOTS, kScProbes = 24;
 constexpr uint32_t kScSlotBits = kScSlots == 1024 ? 10 : (kScSlots == 512 ? 9 : 8);
 static_assert((1u << kScSlotBits) == kScSlots, "slot count must be 256, 512 or 1024");
-constexpr uint32_t kScEmpty = 0xffffffffu;
-
-// Lanes hold (key, v[4]); consecutive lanes with equal keys form a run (ray-ordered samples stay in one coarse cell for many
-// steps).  A segmented inclusive scan sums each run into its last lane, which alone goes on to the LDS table.
-__device__ __forceinline__ bool merge_runs4(uint32_t key, uint32_t key2, float (&v)[4]) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t prev = (uint32_t)__shfl_up((int)key, 1, 64), prev2 = (uint32_t)__shfl_up((int)key2, 1, 64);
-    const bool head = lane == 0 || key != prev || key2 != prev2;   // a run = both destination rows equal
-    const unsigned long long heads = __ballot(head);
-    if (__popcll(heads) > 40) return key != kScEmpty;
-    const unsigned long long below = heads & ((2ull << lane) - 1ull);
-    const uint32_t start = 63u - (uint32_t)__clzll(below);
-#pragma unroll
-    for (uint32_t off = 1; off < 64; off <<= 1) {
-        float up[4];
-#pragma unroll
-        for (int c = 0; c < 4; c++) up[c] = __shfl_up(v[c], off, 64);
-        if (lane >= start + off) {
-#pragma unroll
-            for (int c = 0; c < 4; c++) v[c] += up[c];
-        }
-    }
-    const bool tail = lane == 63u || ((heads >> (lane + 1)) & 1ull);
-    return tail && key != kScEmpty;
-}
 
 // One level of one chunk of samples through the LDS line merge (the non-binned levels).
-struct ScatterJob {
-    const float *grad, *inputs;
-    const int32_t *offsets;
-    float *grad_grid;
-    LevelConsts lc;
-    uint32_t gridtype, n_levels;
-    uint32_t level_of[kMaxLevels];    // the levels this job covers (blockIdx.y indexes this list)
-    uint32_t direct_mask;             // bit i: entry i of level_of goes straight to memory (a hashed level: nothing to merge)
-    uint32_t chunks_of[kMaxLevels];   // line-merged levels: chunks of samples a workgroup sums in its LDS table before it flushes
-};
-
 template <uint32_t D>
 __device__ __forceinline__ void scatter_lines(const ScatterJob &j, uint32_t Mcap, uint32_t M, uint32_t *keys, float *vals, uint32_t *occupied,
                                               uint32_t block_x) {
@@ -79,7 +44,7 @@ __device__ __forceinline__ void scatter_lines(const ScatterJob &j, uint32_t Mcap
     const uint32_t chunks = direct ? 1u : j.chunks_of[blockIdx.y];
     if (block_x * chunks * kScSamples >= M) return;
     if (!direct) {
-        for (uint32_t i = threadIdx.x; i < kScSlots; i += kScThreads) keys[i] = kScEmpty;
+        for (uint32_t i = threadIdx.x; i < kScSlots; i += kScThreads) keys[i] = kNoRow;
         for (uint32_t i = threadIdx.x; i < kScSlots * 16; i += kScThreads) vals[i] = 0.0f;
         if (threadIdx.x == 0) *occupied = 0u;
         __syncthreads();
@@ -91,37 +56,22 @@ __device__ __forceinline__ void scatter_lines(const ScatterJob &j, uint32_t Mcap
     const uint32_t resolution = j.lc.resolution[level];
   for (uint32_t chunk = 0; chunk < chunks; chunk++) {
     const uint32_t b = (block_x * chunks + chunk) * kScSamples + (threadIdx.x & (kScSamples - 1u));
-    float in[D];
-    bool live = b < M;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        in[d] = live ? j.inputs[(size_t)b * D + d] : 0.0f;
-        live = live && !(in[d] < 0 || in[d] > 1);     // gridencoder.cu:275-280
-    }
+    float in[D] = {};
+    const bool live = b < M && !load_input<D>(j.inputs, b, in);     // rows at or past the live count are not read
     float pos[D], pos_deriv[D];
     uint32_t pos_grid[D];
     lattice_pos<D>(in, j.lc.scale[level], false, 0, pos, pos_deriv, pos_grid);
     float2 g = make_float2(0.0f, 0.0f);
     if (live) g = *reinterpret_cast<const float2 *>(j.grad + ((size_t)level * Mcap + b) * 2);
     {
-        uint32_t pgl[D];
-        pgl[0] = pos_grid[0];
-        float wyz[2] = {1.0f - pos[0], pos[0]};       // the reference multiplies the x term first (gridencoder.cu:298-308)
-#pragma unroll
-        for (uint32_t d = 1; d < D; d++) {
-            const bool hi = (q >> (d - 1)) & 1u;
-            const float wd = hi ? pos[d] : 1 - pos[d];
-            wyz[0] *= wd;
-            wyz[1] *= wd;
-            pgl[d] = pos_grid[d] + (hi ? 1u : 0u);
-        }
-        uint32_t row0 = kScEmpty, row1 = kScEmpty;
+        uint32_t pgl0[D], pgl1[D];                    // the x-pair: corners 2 q and 2 q + 1
+        const float w0 = corner<D>(2u * q, pos, pos_grid, pgl0), w1 = corner<D>(2u * q + 1u, pos, pos_grid, pgl1);
+        uint32_t row0 = kNoRow, row1 = kNoRow;
         if (live) {
-            row0 = grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl);
-            pgl[0] += 1u;
-            row1 = grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl);
+            row0 = grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl0);
+            row1 = grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl1);
         }
-        float v[4] = {wyz[0] * g.x, wyz[0] * g.y, wyz[1] * g.x, wyz[1] * g.y};
+        float v[4] = {w0 * g.x, w0 * g.y, w1 * g.x, w1 * g.y};
         if (direct) {
             // A hashed level: the workgroup's samples never touch a line twice, so an LDS merge would spend ~3.6 clocks per lane
             // and float on LDS atomics to remove nothing.  The four floats of an x-pair (two rows that share a 64-B line 7 times out
@@ -135,21 +85,21 @@ __device__ __forceinline__ void scatter_lines(const ScatterJob &j, uint32_t Mcap
                 const float a0 = __shfl(v[0], src, 64), a1 = __shfl(v[1], src, 64), a2 = __shfl(v[2], src, 64), a3 = __shfl(v[3], src, 64);
                 const uint32_t row = f < 2u ? r0 : r1;
                 const float val = f == 0u ? a0 : (f == 1u ? a1 : (f == 2u ? a2 : a3));
-                if (row != kScEmpty && val != 0.0f) atomicAdd(gg + (size_t)row * 2 + (f & 1u), val);
+                if (row != kNoRow && val != 0.0f) atomicAdd(gg + (size_t)row * 2 + (f & 1u), val);
             }
             return;
         }
-        if (merge_runs4(row0, row1, v)) {
-            const uint32_t rows[2] = {row0, row1};
+        const uint32_t rows[2] = {row0, row1};        // a run = both destination rows equal
+        if (sum_runs(rows, v)) {
 #pragma unroll
             for (int e = 0; e < 2; e++) {
                 const uint32_t line = rows[e] >> 3, sub = rows[e] & 7u;
                 uint32_t slot = (line * 2654435761u) >> (32u - kScSlotBits);
                 bool placed = false;
                 for (uint32_t probe = 0; probe < kScProbes; probe++) {
-                    const uint32_t prev = atomicCAS(&keys[slot], kScEmpty, line);
-                    if (prev == kScEmpty) atomicAdd(occupied, 1u);
-                    if (prev == kScEmpty || prev == line) { placed = true; break; }
+                    const uint32_t prev = atomicCAS(&keys[slot], kNoRow, line);
+                    if (prev == kNoRow) atomicAdd(occupied, 1u);
+                    if (prev == kNoRow || prev == line) { placed = true; break; }
                     slot = (slot + 1u) & (kScSlots - 1u);
                 }
                 if (placed) {
@@ -169,12 +119,12 @@ __device__ __forceinline__ void scatter_lines(const ScatterJob &j, uint32_t Mcap
     if (last || *occupied > kScSlots / 2 - kScSlots / 8) {
         for (uint32_t i = threadIdx.x; i < kScSlots * 16; i += kScThreads) {
             const uint32_t line = keys[i >> 4];
-            if (line != kScEmpty) {
+            if (line != kNoRow) {
                 const float v = vals[i];
                 if (v != 0.0f) atomicAdd(gg + (size_t)line * 16 + (i & 15u), v);
                 if (!last) {                                    // leave an empty table for the next chunk
                     vals[i] = 0.0f;
-                    if ((i & 15u) == 15u) keys[i >> 4] = kScEmpty;   // the 16 lanes of the slot have read the key above
+                    if ((i & 15u) == 15u) keys[i >> 4] = kNoRow;   // the 16 lanes of the slot have read the key above
                 }
             }
         }
@@ -239,13 +189,8 @@ __global__ void __launch_bounds__(kBinThreads) k_grid_bin(ScatterJob j, uint32_t
     const uint32_t off = (uint32_t)j.offsets[level];
     const uint32_t hashmap_size = (uint32_t)j.offsets[level + 1] - off;
     const uint32_t b = blockIdx.x * kBinThreads + threadIdx.x;      // one sample per thread, all 2^D corners
-    float in[D];
-    bool live = b < M;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        in[d] = live ? j.inputs[(size_t)b * D + d] : 0.0f;
-        live = live && !(in[d] < 0 || in[d] > 1);
-    }
+    float in[D] = {};
+    const bool live = b < M && !load_input<D>(j.inputs, b, in);
     float pos[D], pos_deriv[D];
     uint32_t pos_grid[D];
     lattice_pos<D>(in, j.lc.scale[level], false, 0, pos, pos_deriv, pos_grid);
@@ -256,15 +201,8 @@ __global__ void __launch_bounds__(kBinThreads) k_grid_bin(ScatterJob j, uint32_t
     float w[NC];
 #pragma unroll
     for (uint32_t idx = 0; idx < NC; idx++) {
-        float wt = 1;                                 // gridencoder.cu:298-308: x term first
         uint32_t pgl[D];
-#pragma unroll
-        for (uint32_t d = 0; d < D; d++) {
-            const bool hi = (idx >> d) & 1u;
-            wt *= hi ? pos[d] : 1 - pos[d];
-            pgl[d] = pos_grid[d] + (hi ? 1u : 0u);
-        }
-        w[idx] = wt;
+        w[idx] = corner<D>(idx, pos, pos_grid, pgl);
         rows[idx] = live ? grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl) : 0u;
         rank[idx] = live ? atomicAdd(&hist[rows[idx] >> bp.shift], 1u) : 0u;
     }
@@ -391,10 +329,7 @@ static uint32_t plan_bins(const rn_grid_t *grid, const int32_t *offsets_host, ui
     uint32_t total = 0, min_b = kMaxBucketsPerLevel;
     for (uint32_t l = 0; l < grid->L; l++) {
         const uint32_t rows = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
-        uint64_t stride = 1;                                      // gridencoder.cu:66-84: hashed when the dense index does not fit
-        for (uint32_t d = 0; d < grid->D; d++)
-            if (stride <= rows) stride *= (uint64_t)lc.resolution[l] + 1u;
-        const bool hashed = grid->gridtype == 0 && stride > rows;
+        const bool hashed = level_is_hashed(grid->D, lc.resolution[l], rows, grid->gridtype);
         const uint32_t nb = (rows + (1u << bp.shift) - 1u) >> bp.shift;
         const bool bin = hashed && nb >= kMinBuckets && nb <= kMaxBucketsPerLevel;
         if (binned) binned[l] = bin;
@@ -410,6 +345,20 @@ static uint32_t plan_bins(const rn_grid_t *grid, const int32_t *offsets_host, ui
     bp.cap = total ? (uint32_t)(2u * (((uint64_t)M << grid->D) / min_b) + 2048u) : 0u;   // 2 x the mean load of a bucket + slack
     return total;
 }
+// The bin workspace of a plan with `total` buckets at row capacity M, as byte offsets: cursors (zeroed once by the caller; pass B
+// leaves them zero) and the two spill counters at 0 | bucket values | spill values | bucket rows | spill keys.  The spill list has
+// room for every entry of a launch.
+struct BinLayout { size_t e_val, spill_val, e_row, spill_key, bytes; };
+static BinLayout bin_layout(uint32_t M, const rn_grid_t *grid, const BinPlan &bp, uint32_t total) {
+    const size_t entries = (size_t)total * bp.cap, spill = ((size_t)M << grid->D) * bp.n_levels;
+    BinLayout w;
+    w.e_val = ((size_t)(total + 2) * sizeof(uint32_t) + 255u) & ~(size_t)255u;
+    w.spill_val = w.e_val + entries * sizeof(float2);
+    w.e_row = w.spill_val + spill * sizeof(float2);
+    w.spill_key = w.e_row + entries * sizeof(uint32_t);
+    w.bytes = w.spill_key + spill * sizeof(uint32_t) + 256;
+    return w;
+}
 static bool scatter_direct_enabled() {
     static int on = -1;
     if (on < 0) { const char *e = getenv("RN_SCATTER_DIRECT"); on = e ? atoi(e) : 1; }
@@ -419,16 +368,6 @@ static uint32_t scatter_chunks() {
     static int n = 0;
     if (!n) { const char *e = getenv("RN_SCATTER_CHUNKS"); n = e ? atoi(e) : 8; if (n < 1) n = 1; if (n > 16) n = 16; }
     return (uint32_t)n;
-}
-static ScatterJob make_job(const rn_scatter_job_t &j) {
-    ScatterJob s{};
-    s.grad = j.grad;
-    s.inputs = j.inputs;
-    s.offsets = j.grid->offsets;
-    s.grad_grid = j.grad_table;
-    s.lc = make_level_consts(j.grid->L, j.grid->S, j.grid->H);
-    s.gridtype = j.grid->gridtype;
-    return s;
 }
 template <uint32_t D0>
 static void launch_lines(uint32_t D1, dim3 g, hipStream_t s, const ScatterJob &a, const ScatterJob &b, uint32_t n_jobs, uint32_t M,
@@ -449,9 +388,7 @@ size_t rn_grid_scatter_workspace(uint32_t M, const rn_grid_t *grid, const int32_
     if (!grid || !offsets_host || grid->L > kMaxLevels) return 0;
     BinPlan bp;
     const uint32_t total = plan_bins(grid, offsets_host, M, bp, nullptr);
-    if (!total) return 256;
-    const size_t spill = ((size_t)M << grid->D) * bp.n_levels;        // every entry of a launch fits the spill list
-    return (((size_t)(total + 2) * sizeof(uint32_t) + 255u) & ~(size_t)255u) + ((size_t)total * bp.cap + spill) * (sizeof(uint32_t) + sizeof(float2)) + 256;
+    return total ? bin_layout(M, grid, bp, total).bytes : 256;
 }
 
 uint32_t rn_grid_scatter_binned_levels(const rn_grid_t *grid, const int32_t *offsets_host) {
@@ -467,13 +404,7 @@ uint32_t rn_grid_scatter_binned_levels(const rn_grid_t *grid, const int32_t *off
 int rn_grid_scatter_jobs(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t M, const int32_t *m_dev, void *workspace,
                          size_t workspace_bytes, rn_stream_t stream) {
     if (M == 0) return RN_OK;
-    RN_REQUIRE(jobs && (n_jobs == 1 || n_jobs == 2), "grid_scatter_jobs: one or two jobs");
-    for (uint32_t i = 0; i < n_jobs; i++) {
-        const rn_scatter_job_t &j = jobs[i];
-        RN_REQUIRE(j.grad && j.inputs && j.grid && j.grid->offsets && j.grad_table, "grid_scatter_jobs: null pointer in job %u", i);
-        RN_REQUIRE((j.grid->D == 2 || j.grid->D == 3) && j.grid->L >= 1 && j.grid->L <= kMaxLevels, "grid_scatter_jobs: D must be 2 or 3, L <= 32");
-        RN_REQUIRE(((uintptr_t)j.grad_table & 63u) == 0 && ((uintptr_t)j.grad & 7u) == 0, "grid_scatter_jobs: grad_table must be 64-byte, grad 8-byte aligned");
-    }
+    if (int rc = check_jobs("grid_scatter_jobs", jobs, n_jobs, 64)) return rc;
     hipStream_t s = as_stream(stream);
     ScatterJob sj[2] = {make_job(jobs[0]), n_jobs == 2 ? make_job(jobs[1]) : ScatterJob{}};
     // job 0 may have binned levels (needs the host copy of its offsets and the workspace)
@@ -483,21 +414,16 @@ int rn_grid_scatter_jobs(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t
     if (jobs[0].offsets_host && workspace && workspace_bytes > 256) {
         total = plan_bins(jobs[0].grid, jobs[0].offsets_host, M, bp, binned);
         if (total) {
-            RN_REQUIRE(((uintptr_t)workspace & 255u) == 0 && workspace_bytes >= rn_grid_scatter_workspace(M, jobs[0].grid, jobs[0].offsets_host),
+            const BinLayout at = bin_layout(M, jobs[0].grid, bp, total);
+            RN_REQUIRE(((uintptr_t)workspace & 255u) == 0 && workspace_bytes >= at.bytes,
                        "grid_scatter_jobs: workspace too small / not 256-byte aligned");
-            // workspace = cursors (zeroed once by the caller; pass B leaves them zero) | values | rows
             char *w = static_cast<char *>(workspace);
-            const size_t spill = ((size_t)M << jobs[0].grid->D) * bp.n_levels;
             bp.cursor = reinterpret_cast<uint32_t *>(w);
             bp.spill_count = bp.cursor + total;
-            size_t at = ((size_t)(total + 2) * sizeof(uint32_t) + 255u) & ~(size_t)255u;
-            bp.e_val = reinterpret_cast<float2 *>(w + at);
-            at += (size_t)total * bp.cap * sizeof(float2);
-            bp.spill_val = reinterpret_cast<float2 *>(w + at);
-            at += spill * sizeof(float2);
-            bp.e_row = reinterpret_cast<uint32_t *>(w + at);
-            at += (size_t)total * bp.cap * sizeof(uint32_t);
-            bp.spill_key = reinterpret_cast<uint32_t *>(w + at);
+            bp.e_val = reinterpret_cast<float2 *>(w + at.e_val);
+            bp.spill_val = reinterpret_cast<float2 *>(w + at.spill_val);
+            bp.e_row = reinterpret_cast<uint32_t *>(w + at.e_row);
+            bp.spill_key = reinterpret_cast<uint32_t *>(w + at.spill_key);
         }
     }
     uint32_t max_levels = 0, max_blocks = 0;
@@ -511,10 +437,7 @@ int rn_grid_scatter_jobs(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t
             bool direct = false;
             if (jobs[i].offsets_host && scatter_direct_enabled()) {
                 const uint32_t rows = (uint32_t)(jobs[i].offsets_host[l + 1] - jobs[i].offsets_host[l]);
-                uint64_t stride = 1;
-                for (uint32_t d = 0; d < gr->D; d++)
-                    if (stride <= rows) stride *= (uint64_t)lc.resolution[l] + 1u;
-                direct = gr->gridtype == 0 && stride > rows && rows >= (1u << 17);
+                direct = level_is_hashed(gr->D, lc.resolution[l], rows, gr->gridtype) && rows >= (1u << 17);
             }
             if (direct) sj[i].direct_mask |= 1u << sj[i].n_levels;
             uint32_t chunks = 1;

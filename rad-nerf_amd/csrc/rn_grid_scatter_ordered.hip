@@ -16,46 +16,35 @@
 //                    whole wave: 64 lanes compute 64 contributions side by side, then every lane adds them in item order (the
 //                    adds stay one chain, only the loads and multiplies run in parallel) -- never split into partial sums, which
 //                    would change the bits.
-// Everything is sized on the host from the row capacity M; the device count only decides which items are live.
+// Everything is sized on the host from the row capacity M; the device count only decides which items are live.  The sample
+// load, the corner's weight and row, the job description and its checks are the atomic routes' (rn_scatter_dev.h).
 #include "rn_fused_dev.h"
+#include "rn_scatter_dev.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
 #include <rocprim/iterator/counting_iterator.hpp>
-
-#include "../../include/radnerf_train.h"
 
 namespace rn {
 namespace th {
 
 constexpr uint32_t kOrdThreads = 256;
 
-struct OrderedJob {
-    const float *grad, *inputs;
-    const int32_t *offsets;
-    float *grad_grid;
-    LevelConsts lc;
-    uint32_t gridtype, n_levels;
-    uint32_t sentinel;      // the key of an item that contributes nothing: sorts behind every row
-};
+// The kernels take the shared ScatterJob (n_levels = L; the level list is not used) and `sentinel`, the key of an item that
+// contributes nothing: it sorts behind every row.
 
-// Lattice position of sample b at `level`: false when a coordinate lies outside [0, 1] (gridencoder.cu:275-280)
+// Lattice position of sample b at `level`: false when a coordinate lies outside [0, 1]
 template <uint32_t D>
-__device__ __forceinline__ bool ordered_pos(const OrderedJob &j, uint32_t level, uint32_t b, float (&pos)[D], uint32_t (&pos_grid)[D]) {
+__device__ __forceinline__ bool ordered_pos(const ScatterJob &j, uint32_t level, uint32_t b, float (&pos)[D], uint32_t (&pos_grid)[D]) {
     float in[D], pos_deriv[D];
-    bool inside = true;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) {
-        in[d] = j.inputs[(size_t)b * D + d];
-        inside = inside && !(in[d] < 0 || in[d] > 1);
-    }
+    const bool inside = !load_input<D>(j.inputs, b, in);
     lattice_pos<D>(in, j.lc.scale[level], false, 0, pos, pos_deriv, pos_grid);
     return inside;
 }
 
 // Pass 1: one thread per (level, sample); its 2^D keys are adjacent items.
 template <uint32_t D>
-__global__ void __launch_bounds__(kOrdThreads) k_ordered_keys(OrderedJob j, uint32_t Mcap, const int32_t *__restrict__ m_dev,
-                                                             uint32_t *__restrict__ keys) {
+__global__ void __launch_bounds__(kOrdThreads) k_ordered_keys(ScatterJob j, uint32_t sentinel, uint32_t Mcap,
+                                                             const int32_t *__restrict__ m_dev, uint32_t *__restrict__ keys) {
     constexpr uint32_t NC = 1u << D;
     const uint32_t M = live_count(Mcap, m_dev);
     const uint32_t t = blockIdx.x * kOrdThreads + threadIdx.x;
@@ -63,7 +52,7 @@ __global__ void __launch_bounds__(kOrdThreads) k_ordered_keys(OrderedJob j, uint
     const uint32_t level = t / Mcap, b = t - level * Mcap;
     uint32_t rows[NC];
 #pragma unroll
-    for (uint32_t c = 0; c < NC; c++) rows[c] = j.sentinel;
+    for (uint32_t c = 0; c < NC; c++) rows[c] = sentinel;
     if (b < M) {
         float pos[D];
         uint32_t pos_grid[D];
@@ -74,8 +63,7 @@ __global__ void __launch_bounds__(kOrdThreads) k_ordered_keys(OrderedJob j, uint
 #pragma unroll
             for (uint32_t c = 0; c < NC; c++) {
                 uint32_t pgl[D];
-#pragma unroll
-                for (uint32_t d = 0; d < D; d++) pgl[d] = pos_grid[d] + ((c >> d) & 1u);
+                (void)corner<D>(c, pos, pos_grid, pgl);
                 rows[c] = off + grid_row<D>(j.gridtype, false, hashmap_size, resolution, pgl);
             }
         }
@@ -85,33 +73,31 @@ __global__ void __launch_bounds__(kOrdThreads) k_ordered_keys(OrderedJob j, uint
     for (uint32_t c = 0; c < NC; c += 4) *reinterpret_cast<uint4 *>(dst + c) = make_uint4(rows[c], rows[c + 1], rows[c + 2], rows[c + 3]);
 }
 
-// w * g of one item, every operation rounded on its own (orc_grid.c:241-251).  Only called for live items.
+// w * g of one item, every operation rounded on its own (corner(): orc_grid.c:241-251).  Only called for live items.
 template <uint32_t D>
-__device__ __forceinline__ float2 ordered_term(const OrderedJob &j, uint32_t Mcap, uint32_t item) {
+__device__ __forceinline__ float2 ordered_term(const ScatterJob &j, uint32_t Mcap, uint32_t item) {
     constexpr uint32_t NC = 1u << D;
     const uint32_t c = item & (NC - 1u), t = item >> D;
     const uint32_t level = t / Mcap, b = t - level * Mcap;
     float pos[D];
-    uint32_t pos_grid[D];
+    uint32_t pos_grid[D], pgl[D];
     (void)ordered_pos<D>(j, level, b, pos, pos_grid);
-    float w = 1;
-#pragma unroll
-    for (uint32_t d = 0; d < D; d++) w *= ((c >> d) & 1u) ? pos[d] : 1 - pos[d];
+    const float w = corner<D>(c, pos, pos_grid, pgl);
     const float2 g = *reinterpret_cast<const float2 *>(j.grad + ((size_t)level * Mcap + b) * 2);
     return make_float2(w * g.x, w * g.y);
 }
 
 // Pass 3: one thread per sorted position.
 template <uint32_t D>
-__global__ void __launch_bounds__(kOrdThreads) k_ordered_sum(OrderedJob j, uint32_t Mcap, uint32_t n_items, const uint32_t *__restrict__ keys,
-                                                            const uint32_t *__restrict__ items) {
+__global__ void __launch_bounds__(kOrdThreads) k_ordered_sum(ScatterJob j, uint32_t sentinel, uint32_t Mcap, uint32_t n_items,
+                                                            const uint32_t *__restrict__ keys, const uint32_t *__restrict__ items) {
     const uint32_t i = blockIdx.x * kOrdThreads + threadIdx.x;      // n_items < 2^31: no wrap
     const uint32_t lane = threadIdx.x & 63u;
-    uint32_t key = j.sentinel;
+    uint32_t key = sentinel;
     bool head = false;
     if (i < n_items) {
         key = keys[i];
-        head = key != j.sentinel && (i == 0 || keys[i - 1] != key);
+        head = key != sentinel && (i == 0 || keys[i - 1] != key);
     }
     const bool wide = head && i + 64u < n_items && keys[i + 64u] == key;     // a run of more than 64 items
     if (head && !wide) {
@@ -160,7 +146,7 @@ static bool ordered_plan(const rn_scatter_job_t &j, uint32_t M, OrderedPlan &p) 
     if (n >= (1ull << 31)) return false;
     p.n_items = (uint32_t)n;
     // with a host view of the level sizes the sentinel is the first row past the table and the sort stops at its top bit
-    p.sentinel = j.offsets_host ? (uint32_t)j.offsets_host[g->L] : 0xffffffffu;
+    p.sentinel = j.offsets_host ? (uint32_t)j.offsets_host[g->L] : kNoRow;
     p.key_bits = 32;
     if (j.offsets_host) {
         p.key_bits = 1;
@@ -177,18 +163,19 @@ static bool ordered_plan(const rn_scatter_job_t &j, uint32_t M, OrderedPlan &p) 
 }
 
 template <uint32_t D>
-static int ordered_run(const OrderedJob &oj, const OrderedPlan &p, uint32_t M, const int32_t *m_dev, char *w, hipStream_t s) {
+static int ordered_run(const ScatterJob &oj, const OrderedPlan &p, uint32_t M, const int32_t *m_dev, char *w, hipStream_t s) {
     const size_t arr = align256((size_t)p.n_items * sizeof(uint32_t));
     uint32_t *keys = reinterpret_cast<uint32_t *>(w), *keys_sorted = reinterpret_cast<uint32_t *>(w + arr);
     uint32_t *items_sorted = reinterpret_cast<uint32_t *>(w + 2 * arr);
     void *temp = w + 3 * arr;
     size_t temp_bytes = p.sort_temp;
-    hipLaunchKernelGGL(k_ordered_keys<D>, dim3(div_up(oj.n_levels * M, kOrdThreads)), dim3(kOrdThreads), 0, s, oj, M, m_dev, keys);
+    hipLaunchKernelGGL(k_ordered_keys<D>, dim3(div_up(oj.n_levels * M, kOrdThreads)), dim3(kOrdThreads), 0, s, oj, p.sentinel, M, m_dev,
+                       keys);
     const hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, keys, keys_sorted, rocprim::counting_iterator<uint32_t>(0), items_sorted,
                                                    (size_t)p.n_items, 0u, p.key_bits, s);
     RN_REQUIRE(e == hipSuccess, "grid_scatter_ordered: the sort could not be enqueued (%s)", hipGetErrorString(e));
-    hipLaunchKernelGGL(k_ordered_sum<D>, dim3(div_up(p.n_items, kOrdThreads)), dim3(kOrdThreads), 0, s, oj, M, p.n_items, keys_sorted,
-                       items_sorted);
+    hipLaunchKernelGGL(k_ordered_sum<D>, dim3(div_up(p.n_items, kOrdThreads)), dim3(kOrdThreads), 0, s, oj, p.sentinel, M, p.n_items,
+                       keys_sorted, items_sorted);
     return RN_OK;
 }
 
@@ -200,19 +187,8 @@ using namespace rn::th;
 
 extern "C" {
 
-static int ordered_check(const rn_scatter_job_t *jobs, uint32_t n_jobs) {
-    RN_REQUIRE(jobs && (n_jobs == 1 || n_jobs == 2), "grid_scatter_ordered: one or two jobs");
-    for (uint32_t i = 0; i < n_jobs; i++) {
-        const rn_scatter_job_t &j = jobs[i];
-        RN_REQUIRE(j.grad && j.inputs && j.grid && j.grid->offsets && j.grad_table, "grid_scatter_ordered: null pointer in job %u", i);
-        RN_REQUIRE((j.grid->D == 2 || j.grid->D == 3) && j.grid->L >= 1 && j.grid->L <= kMaxLevels, "grid_scatter_ordered: D must be 2 or 3, L <= 32");
-        RN_REQUIRE(((uintptr_t)j.grad_table & 7u) == 0 && ((uintptr_t)j.grad & 7u) == 0, "grid_scatter_ordered: grad_table and grad must be 8-byte aligned");
-    }
-    return RN_OK;
-}
-
 size_t rn_grid_scatter_ordered_workspace(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t M) {
-    if (ordered_check(jobs, n_jobs) != RN_OK) return 0;
+    if (check_jobs("grid_scatter_ordered", jobs, n_jobs, 8) != RN_OK) return 0;
     size_t need = 256;
     if (M == 0) return need;
     for (uint32_t i = 0; i < n_jobs; i++) {          // the jobs run one after the other on one stream and share the workspace
@@ -226,7 +202,7 @@ size_t rn_grid_scatter_ordered_workspace(const rn_scatter_job_t *jobs, uint32_t 
 int rn_grid_scatter_ordered(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint32_t M, const int32_t *m_dev, void *workspace,
                             size_t workspace_bytes, rn_stream_t stream) {
     if (M == 0) return RN_OK;
-    if (int rc = ordered_check(jobs, n_jobs)) return rc;
+    if (int rc = check_jobs("grid_scatter_ordered", jobs, n_jobs, 8)) return rc;
     OrderedPlan plan[2];
     for (uint32_t i = 0; i < n_jobs; i++) {
         RN_REQUIRE(ordered_plan(jobs[i], M, plan[i]), "grid_scatter_ordered: L * M * 2^D must stay below 2^31 (job %u, M = %u)", i, M);
@@ -237,15 +213,8 @@ int rn_grid_scatter_ordered(const rn_scatter_job_t *jobs, uint32_t n_jobs, uint3
     hipStream_t s = as_stream(stream);
     for (uint32_t i = 0; i < n_jobs; i++) {
         const rn_scatter_job_t &j = jobs[i];
-        OrderedJob oj{};
-        oj.grad = j.grad;
-        oj.inputs = j.inputs;
-        oj.offsets = j.grid->offsets;
-        oj.grad_grid = j.grad_table;
-        oj.lc = make_level_consts(j.grid->L, j.grid->S, j.grid->H);
-        oj.gridtype = j.grid->gridtype;
+        ScatterJob oj = make_job(j);
         oj.n_levels = j.grid->L;
-        oj.sentinel = plan[i].sentinel;
         const int rc = j.grid->D == 3 ? ordered_run<3>(oj, plan[i], M, m_dev, static_cast<char *>(workspace), s)
                                       : ordered_run<2>(oj, plan[i], M, m_dev, static_cast<char *>(workspace), s);
         if (rc) return rc;

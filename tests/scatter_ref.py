@@ -16,7 +16,7 @@ SC_THREADS, SC_SLOTS, SC_PROBES = 256, 512, 24
 FLUSH_ABOVE = SC_SLOTS // 2 - SC_SLOTS // 8          # a table with more occupied slots than this is flushed after the chunk
 DIRECT_ROWS, CHUNK_ROWS, CHUNKS = 1 << 17, 1 << 16, 8
 BUCKET_SHIFT, MIN_BUCKETS, MAX_BUCKETS, BIN_THREADS = 12, 16, 128, 256
-MERGE_HEADS = 40                                     # merge_runs4 scans a wave with at most this many run heads
+MERGE_HEADS = 40                                     # sum_runs scans a wave with at most this many run heads
 
 GRIDS = {
     "hash17": dict(input_dim=3, log2_hashmap_size=17, gridtype="hash"),

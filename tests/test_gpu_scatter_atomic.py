@@ -8,7 +8,10 @@ and summed in float64.  For every table element, with n addends of total magnitu
              which covers run merges, LDS atomics, memory-side atomics and bucket sums alike.
 No other tolerance appears below.  Routes: `lbc` (rn_grid_scatter_lbc: no host offsets, every level line-merged, one chunk), `jobs`
 (rn_grid_scatter_jobs with host offsets: direct levels, 8-chunk tables -- the default training route), `binned` (the same with a
-workspace: hashed levels through k_grid_bin / k_grid_scatter_buckets), `wrapper` (train_head.grid_scatter).  Grids: the smallest
+workspace: hashed levels through k_grid_bin / k_grid_scatter_buckets), `wrapper` (train_head.grid_scatter), `encode`
+(rn_grid_encode_backward, csrc/rn_grid.hip: k_grid_bwd_table_merge, fp32, C = 2, no dy_dx, in both layouts; it has no device count,
+so it gets the live rows alone; every addition on its way to memory is an fp32 add -- run sum, ds_add_f32, global atomic -- and a
+row with one addend is 0 + w g throughout, so the same three clauses hold).  Grids: the smallest
 at which every path exists (scatter_ref.plan).  What each input pattern is for, and that it gets there, is asserted on the CPU in
 tests/test_scatter_ref.py; rows past the live count are NaN in the inputs and the gradients, so reading one would show.
 """
@@ -86,6 +89,23 @@ def _scatter(route, entries, M, cnt, ws=None):
     torch.cuda.synchronize()
 
 
+def _encode(case, layout):
+    """The table gradient of the case's live rows through rn_grid_encode_backward into a zero table: `lbc` takes the gradient as
+    the case holds it, [L, B, 2]; `blc` takes its transpose [B, L * 2]."""
+    import radnerf_hip as hip
+    enc, live = case["enc"], case["live"]
+    L = case["g"].shape[0]
+    x, g = case["xd"][:live].contiguous(), case["gd"][:, :live].contiguous()
+    if layout == "blc":
+        g = g.permute(1, 0, 2).contiguous()
+    table = torch.zeros_like(enc.embeddings)
+    hip.call("rn_grid_encode_backward", hip.ptr(g), hip.ptr(x), hip.ptr(enc.embeddings.detach()), hip.ptr(enc.offsets, torch.int32), hip.ptr(table),
+             live, enc.input_dim, 2, L, float(np.log2(enc.per_level_scale)), ref.BASE, None, None, enc.gridtype_id, 0, 0, hip.RN_F32,
+             {"lbc": hip.RN_LAYOUT_LBC, "blc": hip.RN_LAYOUT_BLC}[layout], hip.stream())
+    torch.cuda.synchronize()
+    return table.cpu().numpy()
+
+
 def _cursors(ws, enc):
     """The bucket cursors and both spill counters at the start of the workspace."""
     p = ref.plan(enc)
@@ -133,19 +153,25 @@ def test_the_library_plans_the_levels_as_restated(hiplib):
 
 
 PATTERN_CASES = ([(route, grid, pattern) for route in ("lbc", "jobs") for grid in ref.GRIDS for pattern in ("uniform", "ray_runs", "coincident")]
-                 + [("jobs", grid, "mixed") for grid in ref.GRIDS] + [("binned", "hash17", pattern) for pattern in ("uniform", "ray_runs", "mixed", "coincident")])
+                 + [("jobs", grid, "mixed") for grid in ref.GRIDS] + [("binned", "hash17", pattern) for pattern in ("uniform", "ray_runs", "mixed", "coincident")]
+                 + [("encode", grid, pattern) for grid in ref.GRIDS for pattern in ("uniform", "ray_runs", "coincident")])
 
 
 @pytest.mark.parametrize("route,grid,pattern", PATTERN_CASES)
 def test_every_element_within_the_bound_of_its_exact_sum(po, hiplib, route, grid, pattern):
     """uniform: the table is emptied in the middle of the chunk loop (a contribution dropped or added twice there breaks a row with
     one addend); most touched rows of the fine levels have one addend, so equality carries most of the test; the direct path's
-    lane-to-float mapping is held the same way.  ray_runs: the segmented scan of merge_runs4.  mixed: a chunk is inserted into a
+    lane-to-float mapping is held the same way.  ray_runs: the segmented scan of sum_runs.  mixed: a chunk is inserted into a
     table that holds close to its slot count, which makes the probe-limit fallback LIKELY; the test cannot see which path a line
     took and does not claim the fallback ran.  coincident: runs of 4 608 (and, binned, ~256 spilled entries per bucket); the derived
     bound is wide there (gamma(4607) ~ 2.7e-4 of the magnitude), so ONE dropped addend can hide inside it -- this case checks the
-    long-run machinery to that bound only; the patterns with short runs are the sharp ones."""
+    long-run machinery to that bound only; the patterns with short runs are the sharp ones.  encode: both layouts of the operator's
+    own table gradient, whose workgroups (256 samples of one level) each flush on their own."""
     case = _case(po, grid, pattern)
+    if route == "encode":
+        for layout in ("lbc", "blc"):
+            _check(f"encode {layout} {grid} {pattern}", _encode(case, layout), case)
+        return
     _check(f"{route} {grid} {pattern}", _run(case, route), case)
 
 
@@ -187,17 +213,22 @@ def test_an_overfull_bucket_spills_and_the_cursors_return_to_zero(po, hiplib):
 
 
 EDGES = [1, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1025]
+ENCODE_EDGES = [1, 63, 64, 65, 255, 256, 257, 513]        # rn_grid_encode_backward: a wave is 64 samples, a workgroup 256
 
 
 @pytest.mark.parametrize("M", EDGES)
 @pytest.mark.parametrize("grid", ["hash17", "tiled2"])
 def test_live_counts_around_the_chunk_the_bin_block_and_eight_chunks(po, hiplib, grid, M):
     """Every row live, no device count: M around the samples of a workgroup (64 for D = 3, 128 for D = 2), k_grid_bin's 256, and
-    eight chunks (512 / 1 024) -- the last partial chunk of a table that has summed others before it."""
+    eight chunks (512 / 1 024) -- the last partial chunk of a table that has summed others before it.  The operator's own table
+    gradient (route `encode`, both layouts) at the counts around its wave and its workgroup."""
     enc = _encoder(grid)
     case = _device(enc, *ref.uniform(enc, seed=100 + M, live=M, cap=M), po)
     for route in ("jobs", "binned") if grid == "hash17" else ("jobs",):
         _check(f"{route} {grid} M={M}", _run(case, route, cnt=None), case)
+    if M in ENCODE_EDGES:
+        for layout in ("lbc", "blc"):
+            _check(f"encode {layout} {grid} M={M}", _encode(case, layout), case)
 
 
 ROUTES = [("lbc", "hash17"), ("lbc", "tiled2"), ("lbc", "tiled3"), ("jobs", "hash17"), ("jobs", "tiled2"), ("jobs", "tiled3"), ("binned", "hash17")]

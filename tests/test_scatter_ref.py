@@ -84,7 +84,7 @@ def test_uniform_flushes_mid_loop_and_most_fine_rows_have_one_addend(grid):
     for level in range(16):
         flushes, peaks, per_chunk = ref.simulate_tables(enc, x, live, level, int(p["chunks"][level]))
         heads = ref.wave_heads(enc, x, live, level)
-        assert heads.min() > ref.MERGE_HEADS                               # merge_runs4's early return: nothing to merge
+        assert heads.min() > ref.MERGE_HEADS                               # sum_runs's early return: nothing to merge
         if p["chunks"][level] == 8 and not (grid == "tiled2" and level < 4):
             # every workgroup empties its table for the next chunk at least once (tiled2's levels 0-2 have fewer lines in all
             # than the threshold, level 3 flushes in some workgroups only)
