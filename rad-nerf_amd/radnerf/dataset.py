@@ -14,7 +14,8 @@ features' .npy) is not part of this module: a loader hands over arrays.
 The two samplings of lip fine-tuning (nerf/utils.py:277-303) are further instantiations of the same kernel: batch_rect() takes
 every pixel of a rect -- by default the frame's lips rect (provider.py:488-502, lips_rect_from_landmarks) -- and batch_patch()
 `num_rays // patch_size^2` square patches whose corners the kernel draws.  Their ray count follows the rect, so such a batch
-feeds the eager trainer only (radnerf/train.py: train_step's patch_criterion, lips_schedule).
+feeds the eager trainer (radnerf/train.py: train_step's patch_criterion, lips_schedule) or, opt-in, a GraphedTrainer that keeps
+one captured graph per rect shape (lips_graphs; lips_shapes() counts the shapes).
 
 On CPU tensors, or with RN_TRAIN_SET=torch (or kernel="torch"), the same class runs a plain-torch path that restates collate on
 the N picked pixels: the oracle of the kernel's tests, itself pinned to the reference by tests/golden/reference_batch.npz.
@@ -197,6 +198,17 @@ class DeviceTrainSet:
     def lips_rect(self):
         """[F][4] host integers (xmin, xmax, ymin, ymax), or None."""
         return self._lips_host
+
+    def lips_shapes(self):
+        """{(h, w): number of frames} of the set's lips rects, h along the rows -- what batch_rect() will hand out.  A captured
+        lips step needs one graph per shape and row capacity (radnerf/train.py: GraphedTrainer's lips_graphs is sized from this).
+        Host only."""
+        if self._lips_host is None:
+            raise ValueError("DeviceTrainSet.batch_rect: the set has no lips_rect; pass rect=(xmin, xmax, ymin, ymax)")
+        shapes = {}
+        for xmin, xmax, ymin, ymax in self._lips_host:
+            shapes[(xmax - xmin, ymax - ymin)] = shapes.get((xmax - xmin, ymax - ymin), 0) + 1
+        return shapes
 
     def check(self):
         """Raises when an explicit `inds` held pixels outside the image -- or explicit patch corners start positions outside

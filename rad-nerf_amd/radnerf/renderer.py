@@ -194,7 +194,11 @@ class NeRFRenderer(nn.Module):
         from .network import _train_head
         th = _train_head()
         marcher = "reference"
-        if getattr(self, "_sample_budget", None) is not None and not force_all_rays and self.mean_count > 0:
+        budget = getattr(self, "_sample_budget", None)
+        # a forced call (a patch batch marches every ray) can take the budgeted marcher only under a budget whose third field says
+        # that it covers every row of every ray (GraphedTrainer's patch graphs: n * max_steps rows); any other one reads back
+        covers_all = budget is not None and len(budget) > 2 and bool(budget[2])
+        if budget is not None and (not force_all_rays or covers_all) and self.mean_count > 0:
             # a device-side budget is set (radnerf/train.py); in one launch when the rays fit one workgroup per CU
             from raymarching.ops import step_marcher_supported
             one = (switches.get("RN_TRAIN_MARCH") == "step" and training_call(rays_o)
@@ -215,7 +219,7 @@ class NeRFRenderer(nn.Module):
         counter = getattr(self, "_static_counter", None)           # a captured training step counts into a fixed pair
         if counter is None:
             counter = self.step_counter[self.local_step % 16]
-        budget = getattr(self, "_sample_budget", None)             # (device int32 budget, row capacity): see radnerf/train.py
+        budget = getattr(self, "_sample_budget", None)             # (device int32 budget, row capacity[, covers all]): see radnerf/train.py
         self.local_step += 1
         if route.marcher == "step":
             # one launch: near / far, count, slices, samples, counters (set, not added to).  The fused network pass stops at the

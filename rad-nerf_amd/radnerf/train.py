@@ -666,56 +666,94 @@ class GraphedTrainer(Trainer):
     within it) and the budget itself is a device scalar the marcher reads (rn_march_rays_train_budget), so a refresh changes a
     number, not the graph; rows between budget and capacity stay zero and belong to no ray.  A new graph is captured only
     when the budget leaves the capacity window for a capacity not seen before (the last `max_graphs` graphs are kept: the
-    budget of a model whose density depends on the audio swings by +-20 % between refreshes).  Same arithmetic as Trainer.step."""
+    budget of a model whose density depends on the audio swings by +-20 % between refreshes).  Same arithmetic as Trainer.step.
 
-    def __init__(self, model, opt, capacity_step=4096, max_graphs=8, **kw):
-        super().__init__(model, opt, capturable=True, **kw)
+    Lip fine-tuning batches (`rect` / `patch_size`, DeviceTrainSet.batch_rect / batch_patch) are refused by default: their ray
+    count follows the frame.  lips_graphs = G > 0 opts in: such a batch is captured at its first occurrence after the first window
+    and replayed like a plain one, ONE GRAPH PER SHAPE.  A rect batch is keyed by the row capacity, the rays' shape and the rect's
+    (h, w) -- not by its position or frame, so another frame's rect of the same shape replays the same graph, while 32 x 40 and
+    40 x 32 (the same rays, other perceptual views) do not share one.  A patch batch has one key, ("patch", n, patch_size),
+    whatever the running budget: it marches every ray, which the one-launch marcher does under a device budget of n * max_steps
+    rows (aligned as the running budget is) at a capacity of the same size -- no ray can need more, and nothing is read back.
+    Every ray layout has static inputs of its own; the lips graphs live in a least-recently-used cache of G entries beside the
+    plain graphs' `max_graphs` (size it from DeviceTrainSet.lips_shapes(): the shapes times the two or three capacities a run
+    visits), each graph with its private memory pool, and an evicted graph takes its static inputs with it when no other graph
+    uses them.  The patch_criterion runs inside the capture: PerceptualAlex's weight image is packed before it begins, and a
+    criterion that cannot be captured (one that asks the host for a value, say) fails with torch's own capture error.  The first
+    window and a CPU model take the eager step for these batches too; without a patch_criterion such a batch trains as a plain
+    one (train_step's rule), under its own key."""
+
+    # no lips graphs: a trainer assembled without __init__ (bench.py's) refuses lip fine-tuning batches as it always did
+    lips_graphs = 0
+
+    def __init__(self, model, opt, capacity_step=4096, max_graphs=8, lips_graphs=0, **kw):
+        if int(lips_graphs) < 0:
+            raise ValueError(f"GraphedTrainer: lips_graphs = {lips_graphs} (0: lip fine-tuning batches are refused; G > 0: up to G "
+                             "captured lips graphs are kept)")
+        # a CPU model only ever takes the eager step, and torch's Adam refuses capturable=True for parameters off the device
+        super().__init__(model, opt, capturable=next(model.parameters()).is_cuda, **kw)
         if (self.ema is not None or self.lr_gamma is not None) and not self._device_schedule and next(model.parameters()).is_cuda:
             raise ValueError("GraphedTrainer: ema_decay / lr_gamma ride inside HipAdam's launches; a captured step of another "
                              "optimizer (RN_ADAM=torch) cannot carry them")
         self.capacity_step = int(capacity_step)
         self.max_graphs = int(max_graphs)
+        self.lips_graphs = int(lips_graphs)
         self._capacity = 0
         self._graphs = {}              # key -> (graph, loss): a budget that comes back to an earlier capacity replays that graph
         self._graph = self._static = self._loss = self._key = None
         self._static_index = None
+        self._lips = {}                # key -> (graph, loss, layout): the lips graphs, least recently used first
+        self._lips_static = {}         # layout -> _LipsInputs: the static inputs of one ray layout, shared by its graphs
         dev = next(model.parameters()).device
         self._amb_weight = torch.zeros((), dtype=torch.float32, device=dev)
         self._counter = torch.zeros(2, dtype=torch.int32, device=dev)
         self._budget = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.captures = self.replays = 0
-        self.capture_log = []          # (step, budget, capacity) of every capture
+        self.captures = self.replays = self.lips_captures = 0
+        self.capture_log = []          # (step, budget, capacity) of every capture of a plain batch
+        self.lips_capture_log = []     # (step, budget, capacity, "rect" | "patch", (h, w) | (P, ps, ps)) of every lips capture
 
-    def _capture(self, data, key):
+    def _static_inputs(self, data):
+        """-> (static, index list): clones of a batch's tensors for a graph to read, the frame index as a device tensor."""
+        if "_packed" in data:        # a batch that is one table of rows: one static tensor, the step's inputs are its views
+            static = dict(data["_unpack"](data["_packed"].clone()))
+        else:
+            static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()}
+        held = None
+        if isinstance(static.get("index"), (list, tuple)):     # a Python list would be uploaded inside the capture
+            held = list(static["index"])
+            static["index"] = torch.tensor(static["index"], dtype=torch.long, device=self._counter.device)
+        return static, held
+
+    def _record(self, static, budget, capacity):
+        """Capture one step over `static` with `budget` as the renderer's sample budget; what the step would create lazily is
+        created first.  -> (graph, loss)."""
         m = self.model
-        self._loss = None
-        if self._static is None:
-            if "_packed" in data:        # a batch that is one table of rows: one static tensor, the step's inputs are its views
-                self._static = dict(data["_unpack"](data["_packed"].clone()))
-            else:
-                self._static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()}
-            if isinstance(self._static.get("index"), (list, tuple)):     # a Python list would be uploaded inside the capture
-                self._static_index = list(self._static["index"])
-                self._static["index"] = torch.tensor(self._static["index"], dtype=torch.long, device=self._counter.device)
         from raymarching.ops import step_marcher_prepare, step_marcher_supported
-        n_rays = int(self._static["rays_o"].reshape(-1, 3).shape[0])
+        n_rays = int(static["rays_o"].reshape(-1, 3).shape[0])
         if step_marcher_supported(n_rays, self._counter.device):
             step_marcher_prepare(n_rays, self._counter.device)       # persistent state: must not be born inside the capture
         if self._torso_route():
             route.kernels("train_torso").prepare(m, n_rays)          # the same for the torso route: pinned mean density, workspaces
         elif not self.opt.torso and route.kernels("train_head").supported(m):
             # RN_TRAIN_DETERMINISTIC=1: the ordered table scatter's workspace at this graph's row capacity
-            route.kernels("train_head").prepare_scatter((m.encoder, m.encoder_ambient), self._capacity, self._counter.device)
+            route.kernels("train_head").prepare_scatter((m.encoder, m.encoder_ambient), capacity, self._counter.device)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)            # gradients of earlier steps go before the capture begins
         m._static_counter = self._counter                     # renderer._head_training counts into this pair while captured
         try:
             with torch.cuda.graph(g):                         # a private memory pool per graph: cached graphs never alias each other
-                loss = self._forward_backward_update(self._static, (self._budget, self._capacity), self._amb_weight)
+                loss = self._forward_backward_update(static, budget, self._amb_weight)
         finally:
             m._static_counter = None
         m.local_step -= 1                                     # the capture pass went through the Python bookkeeping once
+        return g, loss
+
+    def _capture(self, data, key):
+        self._loss = None
+        if self._static is None:
+            self._static, self._static_index = self._static_inputs(data)
+        g, loss = self._record(self._static, (self._budget, self._capacity), self._capacity)
         self._graph, self._loss, self._key = g, loss, key
         self._graphs[key] = (g, loss)
         while len(self._graphs) > self.max_graphs:           # drop the oldest (dicts keep insertion order); never the newest
@@ -723,13 +761,60 @@ class GraphedTrainer(Trainer):
         self.captures += 1
         self.capture_log.append((self.global_step, int(self._budget.item()), self._capacity))
 
+    def _capture_lips(self, data, key, kind, shape):
+        """The graph of a lips key seen for the first time (or evicted since): static inputs of its ray layout unless another
+        graph of that layout made them, the capture, and the least-recently-used bound.  -> the cache entry."""
+        layout = key[-3:]                                      # the key without the capacity
+        inputs = self._lips_static.get(layout)
+        if inputs is None:
+            static, held = self._static_inputs(data)
+            if kind == "rect":
+                static["rect"], budget = tuple(int(v) for v in data["rect"]), None      # train_step reads (h, w) off it, nothing else
+            else:
+                static["patch_size"] = int(data["patch_size"])
+                # every sample of every ray: none takes more than max_steps, so this budget drops no ray (force_all_rays)
+                rows = _aligned_budget(shape[0] * shape[1] * shape[2] * int(self.opt.max_steps))
+                budget = (torch.full((1,), rows, dtype=torch.int32, device=self._counter.device), rows, True)
+            inputs = self._lips_static[layout] = _LipsInputs(static, held, budget)
+        if hasattr(self.patch_criterion, "packed_image"):
+            self.patch_criterion.packed_image()                # PerceptualAlex's weight image: packed before the capture begins
+        budget = inputs.budget if inputs.budget is not None else (self._budget, self._capacity)
+        g, loss = self._record(inputs.static, budget, budget[1])
+        entry = self._lips[key] = (g, loss, layout)
+        while len(self._lips) > self.lips_graphs:             # drop the least recently used; never the newest
+            gone = self._lips.pop(next(iter(self._lips)))[2]
+            if not any(e[2] == gone for e in self._lips.values()):
+                del self._lips_static[gone]                    # no other graph reads that layout's static inputs
+        self.captures += 1
+        self.lips_captures += 1
+        self.lips_capture_log.append((self.global_step, int(budget[0].item()), budget[1], kind, shape[1:] if kind == "rect" else shape))
+        return entry
+
+    def _lips_graph(self, data):
+        """(graph, loss, static inputs) of a lip fine-tuning batch under lips_graphs > 0: the cached graph of its key, most
+        recently used from now on, or a new capture."""
+        rgb = data["bg_torso_color"] if self.opt.torso else data["images"]
+        n = int(rgb.reshape(-1, 3).shape[0])
+        shape = _patch_views(data, n)[1]                       # (P, h, w); also refuses views that do not hold the batch's rays
+        if data.get("rect") is not None:
+            kind, key = "rect", (self._capacity, tuple(data["rays_o"].shape), "rect", shape[1:])
+        else:
+            kind, key = "patch", ("patch", n, int(data["patch_size"]))
+        entry = self._lips.pop(key, None)
+        if entry is not None:
+            self._lips[key] = entry
+        else:
+            entry = self._capture_lips(data, key, kind, shape)
+        return entry[0], entry[1], self._lips_static[entry[2]]
+
     def _torso_route(self):
         """A torso step can be captured only on the device-resident route (opt-in RN_TORSO_TRAIN=fused, radnerf/train_torso.py):
         the default one asks the host for the covered pixels."""
         return bool(self.opt.torso) and next(self.model.parameters()).is_cuda and route.kernels("train_torso").step_enabled()
 
     def step(self, data):
-        if data.get("rect") is not None or int(data.get("patch_size") or 1) > 1:
+        lips = data.get("rect") is not None or int(data.get("patch_size") or 1) > 1
+        if lips and self.lips_graphs <= 0:
             raise ValueError("GraphedTrainer: a lip fine-tuning batch (`rect` / `patch_size`) cannot be replayed from a captured "
                              "step -- its ray count follows the frame's rect; take such steps with Trainer")
         m = self._begin_step()
@@ -746,41 +831,60 @@ class GraphedTrainer(Trainer):
         if budget != getattr(self, "_budget_value", None):               # the running average moves every 16 steps, not every step
             self._budget.fill_(budget)
             self._budget_value = budget
-        key = (self._capacity, tuple(data["rays_o"].shape))
-        if key != self._key:
-            hit = self._graphs.pop(key, None)
-            if hit is not None:                                  # seen before: replay that graph (and mark it most recent)
-                self._graphs[key] = hit
-                self._graph, self._loss, self._key = hit[0], hit[1], key
-            else:
-                self._capture(data, key)
-        if "_packed" in data and "_packed" in self._static:
-            self._static["_packed"].copy_(data["_packed"])
-            for k in ("poses", "eye", "auds"):
-                if data[k] is not self._static[k]:
-                    self._static[k].copy_(data[k])
+        if lips:
+            graph, loss, inputs = self._lips_graph(data)
+            inputs.index = self._feed(data, inputs.static, inputs.index)
         else:
-            for k, v in data.items():
-                if torch.is_tensor(v) and k != "_packed":
-                    self._static[k].copy_(v)
-        v = data.get("index")
-        if isinstance(v, (list, tuple)) and list(v) != self._static_index:
-            # a feed whose frame changes every step brings the index as a device tensor too (DeviceTrainSet): a copy on the
-            # stream instead of an upload from pageable memory, which the host waits for
-            src = data.get("_index_dev")
-            self._static["index"].copy_(src if src is not None else torch.tensor(v, dtype=torch.long))
-            self._static_index = list(v)
+            key = (self._capacity, tuple(data["rays_o"].shape))
+            if key != self._key:
+                hit = self._graphs.pop(key, None)
+                if hit is not None:                                  # seen before: replay that graph (and mark it most recent)
+                    self._graphs[key] = hit
+                    self._graph, self._loss, self._key = hit[0], hit[1], key
+                else:
+                    self._capture(data, key)
+            graph, loss = self._graph, self._loss
+            self._static_index = self._feed(data, self._static, self._static_index)
         w_amb = min(self.global_step / self.iters, 1.0) * self.lambda_amb
         if w_amb != getattr(self, "_amb_value", None):                   # constant once the ramp is over
             self._amb_weight.fill_(w_amb)
             self._amb_value = w_amb
         if isinstance(self.optimizer, HipAdam):
             self.optimizer.refresh_lr()             # a schedule may have rewritten param_groups[i]["lr"] since the last step
-        self._graph.replay()
+        graph.replay()
         if isinstance(self.optimizer, HipAdam):     # the replayed update went through raw pointers (see HipAdam.step)
             self.optimizer._hip.mark_written(self.optimizer._written)
             self.optimizer.note_replayed()
         m.step_counter[m.local_step % 16].copy_(self._counter)
         m.local_step += 1
         self.replays += 1
-        return self._loss.detach()
+        return loss.detach()
+
+    @staticmethod
+    def _feed(data, static, held):
+        """Copy a batch into a graph's static inputs; -> the frame index list they now hold."""
+        if "_packed" in data and "_packed" in static:
+            static["_packed"].copy_(data["_packed"])
+            for k in ("poses", "eye", "auds"):
+                if data[k] is not static[k]:
+                    static[k].copy_(data[k])
+        else:
+            for k, v in data.items():
+                if torch.is_tensor(v) and k != "_packed":
+                    static[k].copy_(v)
+        v = data.get("index")
+        if isinstance(v, (list, tuple)) and list(v) != held:
+            # a feed whose frame changes every step brings the index as a device tensor too (DeviceTrainSet): a copy on the
+            # stream instead of an upload from pageable memory, which the host waits for
+            src = data.get("_index_dev")
+            static["index"].copy_(src if src is not None else torch.tensor(v, dtype=torch.long))
+            held = list(v)
+        return held
+
+
+class _LipsInputs:
+    """The static inputs of one ray layout of lip fine-tuning: the batch dict a graph reads, the frame index list it holds, and
+    for a patch layout the sample budget of its own, (device int32, rows, True) -- True: it covers every row of every ray."""
+
+    def __init__(self, static, index, budget):
+        self.static, self.index, self.budget = static, index, budget
