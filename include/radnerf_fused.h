@@ -436,6 +436,40 @@ int rn_adam_step(const rn_adam_tensor_t *tensors, uint32_t count, float beta1, f
 int rn_adam_step_lr(const rn_adam_tensor_t *tensors, uint32_t count, float beta1, float beta2, float eps, int32_t *step, float *corr,
                     const float *lr_dev, rn_stream_t stream);
 
+/* ---- mesh export (nerf/utils.py:369-399, 871-891) ------------------------------------------------------------------
+ * The density lattice of Trainer.save_mesh and its isosurface, on the device.  The reference queries 256^3 points in 128^3
+ * blocks, reads each back and runs mcubes on the CPU; here the lattice points are generated by range, the density query is
+ * rn_nerf_fused_forward's sigma branch, and the surface is marching tetrahedra on the Kuhn subdivision (six tetrahedra per
+ * cell, one per permutation of the axes; csrc/rn_mesh_dev.h states every convention) with a specified, reproducible order.
+ * A lattice is [X, Y, Z] fp32 in C order, every axis >= 2 and 12 (X-1)(Y-1)(Z-1) < 2^31, 7 X Y Z < 2^31 (so that every count and
+ * index fits an int32); anything else is RN_ERR_INVALID_ARG (rn_mesh_workspace: 0).  `box`: DEVICE pointer to
+ * {min x, y, z, max x, y, z}.
+ *
+ *   rn_mesh_lattice_points   points[n, 3] = lattice points first .. first + n - 1 (C order) of torch.linspace(min, max, R) per
+ *                            axis through meshgrid(indexing = 'ij'): step = (max - min) / (R - 1) in fp32, the lower half
+ *                            min + i * step, the upper half max - (R - 1 - i) * step, each as ONE fused multiply-add -- what
+ *                            torch's own kernels compute, bit for bit.
+ *   rn_mesh_count            pass 1 .. 3: a code byte per point (which of its seven owned edges cross the surface, and whether it is
+ *                            inside: u > threshold), per-chunk sums of vertices and triangles, their exclusive scan;
+ *                            totals[0] = V, totals[1] = T (device int32).  workspace: rn_mesh_workspace(X, Y, Z) bytes, 16-byte
+ *                            aligned; about 5 bytes per point (code | int32 base index).
+ *   rn_mesh_emit             after the host has read the totals and allocated vertices [V, 3] fp32 and triangles [T, 3] int32:
+ *                            vertices ordered by owning point (C order), then edge kind; triangles by cell (C order), then
+ *                            tetrahedron, then position in the split; winding: (v1 - v0) x (v2 - v0) points from inside to
+ *                            outside.  box = NULL: lattice units, else v / (R - 1) * (max - min) + min per axis.  The same
+ *                            field, threshold and workspace as rn_mesh_count.  No atomic decides an index: two runs, same bytes.
+ *   rn_mesh_tet_case         host-callable: the triangles of a tetrahedron (not a mirror image) whose corner l is inside iff bit l
+ *                            of mask, as local edge numbers 0 .. 5 = (c0,c1) (c0,c2) (c0,c3) (c1,c2) (c1,c3) (c2,c3):
+ *                            *n_triangles = 0, 1 or 2, edges[3 * t + c]. */
+size_t rn_mesh_workspace(uint32_t X, uint32_t Y, uint32_t Z);
+int rn_mesh_lattice_points(uint32_t X, uint32_t Y, uint32_t Z, const float *box, uint32_t first, uint32_t n, float *points,
+                           rn_stream_t stream);
+int rn_mesh_count(const float *field, uint32_t X, uint32_t Y, uint32_t Z, float threshold, void *workspace, int32_t *totals,
+                  rn_stream_t stream);
+int rn_mesh_emit(const float *field, uint32_t X, uint32_t Y, uint32_t Z, float threshold, const float *box, void *workspace,
+                 uint32_t n_vertices, uint32_t n_triangles, float *vertices, int32_t *triangles, rn_stream_t stream);
+int rn_mesh_tet_case(uint32_t mask, int32_t *n_triangles, int32_t *edges);
+
 #ifdef __cplusplus
 }
 #endif

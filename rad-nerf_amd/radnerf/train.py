@@ -561,6 +561,33 @@ class Trainer:
             res["lpips"], res["lpips_per_frame"] = float(s[:, 4].mean()), [float(v) for v in s[:, 4]]
         return res
 
+    def save_mesh(self, path, resolution=256, threshold=10, auds=None, enc_a=None, eye=None):
+        """The head's surface sigma = threshold inside aabb_infer as a binary PLY (Trainer.save_mesh, nerf/utils.py:871-891), on
+        the device (radnerf/mesh.py): eval mode, no_grad, the averaged weights when there is an EMA, as evaluate().  The geometry
+        depends on the audio and the eye, so exactly one of auds (a window [8, audio_in_dim, 16], encoded with
+        model.encode_audio) and enc_a (an audio code) is given, and eye ([1,1]) on a model with exp_eye.
+        -> (vertices, triangles), the device tensors that were written."""
+        import os
+        from radnerf import mesh
+        m = self.model
+        if (auds is None) == (enc_a is None):
+            raise ValueError("save_mesh: give exactly one of auds (an audio window) and enc_a (an audio code)")
+        if eye is None and getattr(m, "exp_eye", False):
+            raise ValueError("save_mesh: the model has exp_eye, so the export needs an eye value")
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad(), self.ema_scope():
+                if enc_a is None:
+                    enc_a = m.encode_audio(auds)
+                vertices, triangles = mesh.extract_geometry(m, resolution, threshold, enc_a, eye)
+        finally:
+            m.train(was_training)
+        if os.path.dirname(path):
+            os.makedirs(os.path.dirname(path), exist_ok=True)
+        mesh.write_ply(path, vertices, triangles)
+        return vertices, triangles
+
     def _begin_step(self):
         """What comes before every step: train mode, the occupancy refresh on its cadence, the step count."""
         m = self.model

@@ -220,6 +220,11 @@ FUNCTIONS = {
     "rn_train_loss": (_int, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _u32, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "rn_adam_step": (_int, [_P(AdamTensorT), _u32, _f32, _f32, _f32, _ptr, _ptr, _ptr]),
     "rn_adam_step_lr": (_int, [_P(AdamTensorT), _u32, _f32, _f32, _f32, _ptr, _ptr, _ptr, _ptr]),
+    "rn_mesh_workspace": (_sz, [_u32, _u32, _u32]),
+    "rn_mesh_lattice_points": (_int, [_u32, _u32, _u32, _ptr, _u32, _u32, _ptr, _ptr]),
+    "rn_mesh_count": (_int, [_ptr, _u32, _u32, _u32, _f32, _ptr, _ptr, _ptr]),
+    "rn_mesh_emit": (_int, [_ptr, _u32, _u32, _u32, _f32, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr]),
+    "rn_mesh_tet_case": (_int, [_u32, _P(C.c_int32), _P(C.c_int32)]),
     # ---- include/radnerf_train.h
     "rn_train_head_image_floats": (_sz, []),
     "rn_train_head_workspace_floats": (_sz, [_u32]),
