@@ -15,224 +15,10 @@ import contextlib
 
 import torch
 
-from radnerf import route, switches      # by the package's name: this file is also loaded on its own (tests/test_train_host.py)
-
-
-def make_optimizer(model, lr=5e-3, lr_net=5e-4, fused=None, capturable=False, kernel=None, schedule=None, ema=None):
-    """main.py:204; lr for the grid tables, lr_net for the MLPs / audio nets / individual codes.  On the GPU the update runs
-    as ONE kernel over all tensors (HipAdam; `kernel="torch"` or RN_ADAM=torch: torch's fused Adam, one launch per parameter
-    group) -- the 49 MB table is read and written once per step either way; same arithmetic as the default implementation.
-    schedule = (gamma, iters) / ema = ParamEma: HipAdam carries them inside its launches; any other optimizer ignores them here
-    (Trainer then applies both from the host after each step)."""
-    on_gpu = next(model.parameters()).is_cuda
-    if kernel is None:
-        kernel = switches.get("RN_ADAM") if on_gpu else "torch"
-    if kernel == "hip" and on_gpu:
-        return HipAdam(model.get_params(lr, lr_net), schedule=schedule, ema=ema)
-    if fused is None:
-        fused = on_gpu
-    return torch.optim.Adam(model.get_params(lr, lr_net), betas=(0.9, 0.99), eps=1e-15, fused=bool(fused),
-                            capturable=bool(capturable))
-
-
-class HipAdam:
-    """torch.optim.Adam(betas, eps, weight_decay=0) over the model's parameter groups with ONE update kernel for all
-    tensors (C ABI rn_adam_step, csrc/rn_train.hip) -- the table, its moments and its gradient stream through HBM once.
-    Same interface as far as Trainer needs it (param_groups, zero_grad, step, state_dict / load_state_dict in
-    torch.optim.Adam's format, so reference checkpoints carry over); the step counter lives on the device, so a step is
-    capturable in a hipGraph.
-
-    schedule = (gamma, iters) and / or ema = ParamEma select rn_adam_step_sched: every tensor's rate is lr0 * gamma ** ((s - 1) / iters)
-    at step s (LambdaLR as the reference drives it, main.py:219), computed by the begin kernel from the device-side step counter,
-    and on steps with s % ema.update_interval == 0 the same launches fold the new weights into the shadows (which stay in the
-    ParamEma; its update counter moves to the device).  Nothing is uploaded per step on that route: refresh_lr() is a no-op,
-    current_lr() is a host mirror for logging, and param_groups[i]["lr"] is only rewritten by state_dict()."""
-
-    # what torch.optim.Adam keeps in every param_group (torch/optim/adam.py): a state dict written here loads into the
-    # reference's torch.optim.Adam (nerf/utils.py:1302-1426 saves / restores optimizer.state_dict())
-    _TORCH_ADAM_DEFAULTS = dict(weight_decay=0, amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False,
-                                fused=None, decoupled_weight_decay=False)
-
-    def __init__(self, params, betas=(0.9, 0.99), eps=1e-15, schedule=None, ema=None):
-        import radnerf_hip as hip
-        self._hip = hip
-        self.param_groups = []
-        for g in params:
-            g = dict(g)
-            g["params"] = [g["params"]] if torch.is_tensor(g["params"]) else list(g["params"])    # a bare tensor is one parameter
-            if g.get("weight_decay", 0):
-                raise ValueError("HipAdam: weight decay is not part of the reference's configuration (main.py:204) and not implemented")
-            g.setdefault("betas", betas)
-            g.setdefault("eps", eps)
-            for k, v in self._TORCH_ADAM_DEFAULTS.items():
-                g.setdefault(k, v)
-            g.setdefault("initial_lr", g["lr"])      # what torch's LR schedulers look for (LambdaLR, main.py:219)
-            self.param_groups.append(g)
-        self.betas, self.eps = betas, eps
-        self.defaults = dict(lr=self.param_groups[0]["lr"], betas=betas, eps=eps, **self._TORCH_ADAM_DEFAULTS)
-        dev = self.param_groups[0]["params"][0].device
-        self.state = {p: {"exp_avg": torch.zeros_like(p, memory_format=torch.contiguous_format),
-                          "exp_avg_sq": torch.zeros_like(p, memory_format=torch.contiguous_format)}
-                      for g in self.param_groups for p in g["params"]}
-        self._step = torch.zeros(1, dtype=torch.int32, device=dev)
-        self._corr = torch.zeros(2, dtype=torch.float32, device=dev)
-        n = sum(len(g["params"]) for g in self.param_groups)
-        # learning rates live on the device, one per updated tensor in the order of the last step(): a captured step reads
-        # them at run time, so a schedule that rewrites param_groups[i]["lr"] is followed by every replay (refresh_lr())
-        self._lr_dev = torch.zeros(max(n, 1), dtype=torch.float32, device=dev)
-        self._lr_groups, self._lr_sent, self._written = [], None, []
-        self._sched = schedule is not None or ema is not None
-        self.ema, self._host_step, self.uploads = ema, 0, 0       # uploads: host -> device copies refresh_lr() made
-        self.gamma, self.sched_iters = (float(schedule[0]), int(schedule[1])) if schedule is not None else (1.0, 0)
-        if self._sched:
-            if not self.gamma > 0 or (self.gamma != 1.0 and self.sched_iters <= 0):
-                raise ValueError("HipAdam: schedule=(gamma, iters) needs gamma > 0, and iters > 0 unless gamma == 1")
-            self._corr = torch.zeros(4, dtype=torch.float32, device=dev)
-            if ema is not None:
-                ema.restrict([p for g in self.param_groups for p in g["params"]])
-                if ema.device_num_updates is None:
-                    ema.device_num_updates = torch.full((1,), ema._num_updates, dtype=torch.int32, device=dev)
-
-    def current_lr(self):
-        """Per group, the rate the NEXT step uses -- what param_groups[i]["lr"] shows in the reference once its scheduler has
-        stepped.  A host mirror (initial_lr, gamma and the number of steps taken); nothing is read from the device."""
-        if not self._sched:
-            return [float(g["lr"]) for g in self.param_groups]
-        f = 1.0 if self.gamma == 1.0 else self.gamma ** (self._host_step / self.sched_iters)
-        return [float(g["initial_lr"]) * f for g in self.param_groups]
-
-    def note_replayed(self, n=1):
-        """A captured step was replayed n times: the device-side counter advanced, the host mirror follows."""
-        self._host_step += int(n)
-
-    def zero_grad(self, set_to_none=True):
-        for g in self.param_groups:
-            for p in g["params"]:
-                if set_to_none:
-                    p.grad = None
-                elif p.grad is not None:
-                    p.grad.zero_()
-
-    def refresh_lr(self):
-        """Upload the groups' current learning rates when they changed since the last upload (call outside a capture; a
-        GraphedTrainer does so before every replay).  With a device-side schedule there is nothing to upload."""
-        if self._sched:
-            return
-        lrs = [float(self.param_groups[gi]["lr"]) for gi in self._lr_groups]
-        if lrs and lrs != self._lr_sent:
-            self._lr_dev[:len(lrs)].copy_(torch.tensor(lrs, dtype=torch.float32))
-            self._lr_sent = lrs
-            self.uploads += 1
-
-    @torch.no_grad()
-    def step(self):
-        pending = route.take_pending_events()    # table-gradient scatters still running on the side stream (route.deferred_join)
-        if pending:
-            held = {p.grad.data_ptr() for g in self.param_groups for p in g["params"] if p.grad is not None}
-            for ev, *ptrs in pending:
-                torch.cuda.current_stream().wait_event(ev)
-                if not all(q in held for q in ptrs):
-                    # autograd copied a table gradient instead of keeping the buffer the scatter writes (a parameter that
-                    # already had a .grad): that copy raced with the side stream
-                    raise RuntimeError("HipAdam: a table gradient was copied before its scatter had finished; use "
-                                       "zero_grad(set_to_none=True) or RN_TRAIN_OVERLAP=0")
-        if self._sched:
-            return self._step_sched()
-        entries, keep, written, groups = [], [], [], []
-        for gi, g in enumerate(self.param_groups):
-            for p in g["params"]:
-                if p.grad is None:
-                    continue
-                written.append(p)
-                groups.append(gi)
-                grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                if not p.is_contiguous() or p.dtype != torch.float32 or grad.dtype != torch.float32:
-                    raise RuntimeError("HipAdam: parameters and gradients must be contiguous fp32")
-                st = self.state[p]
-                keep.append(grad)
-                entries.append((p.data_ptr(), grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), p.numel(), float(g["lr"])))
-        arr = (self._hip.abi.AdamTensorT * max(len(entries), 1))()
-        for i, e in enumerate(entries):
-            arr[i].param, arr[i].grad, arr[i].exp_avg, arr[i].exp_avg_sq, arr[i].numel, arr[i].lr = e
-        if groups != self._lr_groups:
-            self._lr_groups, self._lr_sent = groups, None
-        if not torch.cuda.is_current_stream_capturing():
-            self.refresh_lr()
-        elif self._lr_sent is None:
-            raise RuntimeError("HipAdam: take one eager step (or call refresh_lr()) before capturing a step in a graph")
-        self._hip.call("rn_adam_step_lr", arr, len(entries), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                       self._hip.ptr(self._step), self._hip.ptr(self._corr), self._hip.ptr(self._lr_dev), self._hip.stream())
-        self._written = written
-        self._hip.mark_written(written)      # the kernel wrote through raw pointers: caches keyed on tensor versions must see it
-
-    def _step_sched(self):
-        """The same update through rn_adam_step_sched: rates and the EMA decision come from the device-side step counter.  A
-        parameter without a gradient this step still rides along when it has a shadow (torch_ema averages every parameter)."""
-        hip, ema = self._hip, self.ema
-        entries, keep, written = [], [], []
-        for g in self.param_groups:
-            for p in g["params"]:
-                shadow = ema.shadow_of(p) if ema is not None else None
-                if p.grad is None and shadow is None:
-                    continue
-                if not p.is_contiguous() or p.dtype != torch.float32:
-                    raise RuntimeError("HipAdam: parameters and gradients must be contiguous fp32")
-                grad = None
-                if p.grad is not None:
-                    grad = p.grad if p.grad.is_contiguous() else p.grad.contiguous()
-                    if grad.dtype != torch.float32:
-                        raise RuntimeError("HipAdam: parameters and gradients must be contiguous fp32")
-                    keep.append(grad)
-                    written.append(p)
-                st = self.state[p]
-                entries.append((p.data_ptr(), hip.ptr(grad), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), hip.ptr(shadow),
-                                p.numel(), float(g["initial_lr"])))
-        arr = (hip.abi.SchedTensorT * max(len(entries), 1))()
-        for i, e in enumerate(entries):
-            arr[i].param, arr[i].grad, arr[i].exp_avg, arr[i].exp_avg_sq, arr[i].shadow, arr[i].numel, arr[i].lr0 = e
-        if len(entries) > self._lr_dev.numel():
-            raise RuntimeError("HipAdam: more tensors than learning-rate slots")
-        decay, interval = (ema.decay, ema.update_interval) if ema is not None else (0.0, 0)
-        hip.call("rn_adam_step_sched", arr, len(entries), float(self.betas[0]), float(self.betas[1]), float(self.eps), self.gamma,
-                 self.sched_iters, float(decay), int(interval), hip.ptr(self._step), hip.ptr(self._corr), hip.ptr(self._lr_dev),
-                 hip.ptr(ema.device_num_updates) if ema is not None else None, hip.stream())
-        if not torch.cuda.is_current_stream_capturing():
-            self._host_step += 1
-        self._written = written
-        hip.mark_written(written)
-
-    def state_dict(self):
-        """torch.optim.Adam's layout: state by running parameter index, one `step` per tensor.  With a device-side schedule the
-        groups' `lr` is the rate the next step uses, as the reference's scheduler leaves it."""
-        if self._sched:
-            for g, lr in zip(self.param_groups, self.current_lr()):
-                g["lr"] = lr
-        step = self._step.to(torch.float32).reshape(()).clone()
-        state, groups, at = {}, [], 0
-        for g in self.param_groups:
-            ids = []
-            for p in g["params"]:
-                state[at] = {"step": step.clone(), "exp_avg": self.state[p]["exp_avg"], "exp_avg_sq": self.state[p]["exp_avg_sq"]}
-                ids.append(at)
-                at += 1
-            groups.append({**{k: v for k, v in g.items() if k != "params"}, "params": ids})
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd):
-        params = [p for g in self.param_groups for p in g["params"]]
-        steps = []
-        for i, p in enumerate(params):
-            st = sd["state"].get(i)
-            if st is None:
-                continue
-            self.state[p]["exp_avg"].copy_(st["exp_avg"])
-            self.state[p]["exp_avg_sq"].copy_(st["exp_avg_sq"])
-            steps.append(int(st["step"]))
-        if steps:
-            self._step.fill_(max(steps))
-            self._host_step = max(steps)
-        for g, sg in zip(self.param_groups, sd["param_groups"]):
-            g["lr"] = sg.get("lr", g["lr"])
+# by the package's name: this file is also loaded on its own (tests/test_train_host.py)
+from radnerf import route, switches
+from radnerf.optim import HipAdam, make_optimizer      # both stay part of this module's surface
+from radnerf.step_graphs import GraphCache, HeldScalar, StaticInputs
 
 
 def entropy_of(alphas):
@@ -425,6 +211,8 @@ class Trainer:
     # the same for the schedule around the step: such a trainer has no EMA and a constant rate
     ema = lr_gamma = None
     _device_schedule = False
+    # and for the device copy of the sample budget, made at the first step that has one
+    _budget = None
 
     def __init__(self, model, opt, lr=5e-3, lr_net=5e-4, update_extra_interval=16, iters=200000, lambda_amb=0.1,
                  prefer_rocblas=True, capturable=False, patch_criterion=None, ema_decay=None, ema_update_interval=1000, lr_gamma=None):
@@ -503,6 +291,19 @@ class Trainer:
             finally:
                 ema.restore()
 
+    @contextlib.contextmanager
+    def eval_scope(self):
+        """What evaluate() and save_mesh() run under: eval mode, no_grad, the averaged weights when there is an EMA; the mode the
+        model was in comes back on exit, also on an exception."""
+        m = self.model
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad(), self.ema_scope():
+                yield
+        finally:
+            m.train(was_training)
+
     def evaluate(self, train_set, indices, rect=None, perceptual=None):
         """Validation over the frames `indices` of a DeviceTrainSet, as Trainer.evaluate_one_epoch does it (nerf/utils.py:1220-1300):
         eval mode, the averaged weights when there is an EMA, no_grad; per frame train_set.frame(i), model.render as eval_step
@@ -527,28 +328,23 @@ class Trainer:
         if on_gpu:
             import radnerf_hip as hip
             ws = hip.persistent_buffer("image_error", int(hip._lib.rn_image_error_workspace(H, W)), dev)
-        was_training = m.training
-        m.eval()
-        try:
-            with torch.no_grad(), self.ema_scope():
-                for k, i in enumerate(indices):
-                    f = train_set.frame(i)
-                    out = m.render(f["rays_o"], f["rays_d"], f["auds"], f["bg_coords"], f["poses"], eye=f["eye"], index=f["index"],
-                                   staged=True, bg_color=f["bg_color"], perturb=False, dt_gamma=self.opt.dt_gamma,
-                                   max_steps=self.opt.max_steps)
-                    pred = out["image"].reshape(H * W, 3)
-                    truth = f["images"].reshape(H * W, 3)
-                    r = None if rects is None else (rects if rects.dim() == 1 else rects[f["index"][0]])
-                    if on_gpu:
-                        pred = pred if pred.dtype == torch.float32 and pred.is_contiguous() else pred.float().contiguous()
-                        hip.call("rn_image_error", hip.ptr(pred), hip.ptr(truth), H, W, hip.ptr(r), hip.ptr(ws), hip.ptr(sums[k]), hip.stream())
-                    else:
-                        sums[k, :4] = _image_error_host(pred, truth, H, W, r)
-                    if perceptual is not None:
-                        nchw = lambda t: t.reshape(1, H, W, 3).permute(0, 3, 1, 2)
-                        sums[k, 4] = perceptual(nchw(truth.float()), nchw(pred.float()), normalize=True).reshape(())
-        finally:
-            m.train(was_training)
+        with self.eval_scope():
+            for k, i in enumerate(indices):
+                f = train_set.frame(i)
+                out = m.render(f["rays_o"], f["rays_d"], f["auds"], f["bg_coords"], f["poses"], eye=f["eye"], index=f["index"],
+                               staged=True, bg_color=f["bg_color"], perturb=False, dt_gamma=self.opt.dt_gamma,
+                               max_steps=self.opt.max_steps)
+                pred = out["image"].reshape(H * W, 3)
+                truth = f["images"].reshape(H * W, 3)
+                r = None if rects is None else (rects if rects.dim() == 1 else rects[f["index"][0]])
+                if on_gpu:
+                    pred = pred if pred.dtype == torch.float32 and pred.is_contiguous() else pred.float().contiguous()
+                    hip.call("rn_image_error", hip.ptr(pred), hip.ptr(truth), H, W, hip.ptr(r), hip.ptr(ws), hip.ptr(sums[k]), hip.stream())
+                else:
+                    sums[k, :4] = _image_error_host(pred, truth, H, W, r)
+                if perceptual is not None:
+                    nchw = lambda t: t.reshape(1, H, W, 3).permute(0, 3, 1, 2)
+                    sums[k, 4] = perceptual(nchw(truth.float()), nchw(pred.float()), normalize=True).reshape(())
         s = sums.cpu().numpy()                                   # the one read-back
         mse = s[:, 0] / s[:, 2]
         psnr = -10.0 * np.log10(mse)
@@ -574,15 +370,10 @@ class Trainer:
             raise ValueError("save_mesh: give exactly one of auds (an audio window) and enc_a (an audio code)")
         if eye is None and getattr(m, "exp_eye", False):
             raise ValueError("save_mesh: the model has exp_eye, so the export needs an eye value")
-        was_training = m.training
-        m.eval()
-        try:
-            with torch.no_grad(), self.ema_scope():
-                if enc_a is None:
-                    enc_a = m.encode_audio(auds)
-                vertices, triangles = mesh.extract_geometry(m, resolution, threshold, enc_a, eye)
-        finally:
-            m.train(was_training)
+        with self.eval_scope():
+            if enc_a is None:
+                enc_a = m.encode_audio(auds)
+            vertices, triangles = mesh.extract_geometry(m, resolution, threshold, enc_a, eye)
         if os.path.dirname(path):
             os.makedirs(os.path.dirname(path), exist_ok=True)
         mesh.write_ply(path, vertices, triangles)
@@ -627,12 +418,9 @@ class Trainer:
         if m.mean_count <= 0 or dev.type != "cuda":
             return None
         budget = _aligned_budget(m.mean_count)
-        held = getattr(self, "_budget_held", None)
-        if held is None or held[0] != budget or held[1].device != dev:
-            t = held[1] if held is not None and held[1].device == dev else torch.zeros(1, dtype=torch.int32, device=dev)
-            t.fill_(budget)
-            self._budget_held = held = (budget, t)
-        return held[1], budget
+        if self._budget is None or self._budget.tensor.device != dev:
+            self._budget = HeldScalar(1, torch.int32, dev)
+        return self._budget.set(budget), budget
 
 
 def _eval_rects(train_set, rect, dev):
@@ -702,8 +490,9 @@ class GraphedTrainer(Trainer):
     40 x 32 (the same rays, other perceptual views) do not share one.  A patch batch has one key, ("patch", n, patch_size),
     whatever the running budget: it marches every ray, which the one-launch marcher does under a device budget of n * max_steps
     rows (aligned as the running budget is) at a capacity of the same size -- no ray can need more, and nothing is read back.
-    Every ray layout has static inputs of its own; the lips graphs live in a least-recently-used cache of G entries beside the
-    plain graphs' `max_graphs` (size it from DeviceTrainSet.lips_shapes(): the shapes times the two or three capacities a run
+    Every ray layout, a plain one too, has static inputs of its own; the lips graphs live in a least-recently-used cache of G
+    entries, the plain graphs in another of `max_graphs` (step_graphs.GraphCache; size G from DeviceTrainSet.lips_shapes(): the
+    shapes times the two or three capacities a run
     visits), each graph with its private memory pool, and an evicted graph takes its static inputs with it when no other graph
     uses them.  The patch_criterion runs inside the capture: PerceptualAlex's weight image is packed before it begins, and a
     criterion that cannot be captured (one that asks the host for a value, say) fails with torch's own capture error.  The first
@@ -726,34 +515,19 @@ class GraphedTrainer(Trainer):
         self.max_graphs = int(max_graphs)
         self.lips_graphs = int(lips_graphs)
         self._capacity = 0
-        self._graphs = {}              # key -> (graph, loss): a budget that comes back to an earlier capacity replays that graph
-        self._graph = self._static = self._loss = self._key = None
-        self._static_index = None
-        self._lips = {}                # key -> (graph, loss, layout): the lips graphs, least recently used first
-        self._lips_static = {}         # layout -> _LipsInputs: the static inputs of one ray layout, shared by its graphs
+        # the captured steps of plain and of lips batches, least recently used first over static inputs per ray layout (keys:
+        # _step_key): a budget that comes back to an earlier capacity replays that graph
+        self._plain, self._lips = GraphCache(max_graphs), GraphCache(lips_graphs)
         dev = next(model.parameters()).device
-        self._amb_weight = torch.zeros((), dtype=torch.float32, device=dev)
+        self._amb_weight = HeldScalar((), torch.float32, dev)
         self._counter = torch.zeros(2, dtype=torch.int32, device=dev)
-        self._budget = torch.zeros(1, dtype=torch.int32, device=dev)
         self.captures = self.replays = self.lips_captures = 0
         self.capture_log = []          # (step, budget, capacity) of every capture of a plain batch
         self.lips_capture_log = []     # (step, budget, capacity, "rect" | "patch", (h, w) | (P, ps, ps)) of every lips capture
 
-    def _static_inputs(self, data):
-        """-> (static, index list): clones of a batch's tensors for a graph to read, the frame index as a device tensor."""
-        if "_packed" in data:        # a batch that is one table of rows: one static tensor, the step's inputs are its views
-            static = dict(data["_unpack"](data["_packed"].clone()))
-        else:
-            static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()}
-        held = None
-        if isinstance(static.get("index"), (list, tuple)):     # a Python list would be uploaded inside the capture
-            held = list(static["index"])
-            static["index"] = torch.tensor(static["index"], dtype=torch.long, device=self._counter.device)
-        return static, held
-
-    def _record(self, static, budget, capacity):
-        """Capture one step over `static` with `budget` as the renderer's sample budget; what the step would create lazily is
-        created first.  -> (graph, loss)."""
+    def _record(self, static, budget):
+        """Capture one step over `static` with `budget` = (device int32 budget, row capacity[, True]) as the renderer's sample
+        budget; what the step would create lazily is created first.  -> (graph, loss)."""
         m = self.model
         from raymarching.ops import step_marcher_prepare, step_marcher_supported
         n_rays = int(static["rays_o"].reshape(-1, 3).shape[0])
@@ -763,76 +537,61 @@ class GraphedTrainer(Trainer):
             route.kernels("train_torso").prepare(m, n_rays)          # the same for the torso route: pinned mean density, workspaces
         elif not self.opt.torso and route.kernels("train_head").supported(m):
             # RN_TRAIN_DETERMINISTIC=1: the ordered table scatter's workspace at this graph's row capacity
-            route.kernels("train_head").prepare_scatter((m.encoder, m.encoder_ambient), capacity, self._counter.device)
+            route.kernels("train_head").prepare_scatter((m.encoder, m.encoder_ambient), budget[1], self._counter.device)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         self.optimizer.zero_grad(set_to_none=True)            # gradients of earlier steps go before the capture begins
         m._static_counter = self._counter                     # renderer._head_training counts into this pair while captured
         try:
             with torch.cuda.graph(g):                         # a private memory pool per graph: cached graphs never alias each other
-                loss = self._forward_backward_update(static, budget, self._amb_weight)
+                loss = self._forward_backward_update(static, budget, self._amb_weight.tensor)
         finally:
             m._static_counter = None
         m.local_step -= 1                                     # the capture pass went through the Python bookkeeping once
         return g, loss
 
-    def _capture(self, data, key):
-        self._loss = None
-        if self._static is None:
-            self._static, self._static_index = self._static_inputs(data)
-        g, loss = self._record(self._static, (self._budget, self._capacity), self._capacity)
-        self._graph, self._loss, self._key = g, loss, key
-        self._graphs[key] = (g, loss)
-        while len(self._graphs) > self.max_graphs:           # drop the oldest (dicts keep insertion order); never the newest
-            del self._graphs[next(iter(self._graphs))]
-        self.captures += 1
-        self.capture_log.append((self.global_step, int(self._budget.item()), self._capacity))
-
-    def _capture_lips(self, data, key, kind, shape):
-        """The graph of a lips key seen for the first time (or evicted since): static inputs of its ray layout unless another
-        graph of that layout made them, the capture, and the least-recently-used bound.  -> the cache entry."""
-        layout = key[-3:]                                      # the key without the capacity
-        inputs = self._lips_static.get(layout)
-        if inputs is None:
-            static, held = self._static_inputs(data)
-            if kind == "rect":
-                static["rect"], budget = tuple(int(v) for v in data["rect"]), None      # train_step reads (h, w) off it, nothing else
-            else:
-                static["patch_size"] = int(data["patch_size"])
-                # every sample of every ray: none takes more than max_steps, so this budget drops no ray (force_all_rays)
-                rows = _aligned_budget(shape[0] * shape[1] * shape[2] * int(self.opt.max_steps))
-                budget = (torch.full((1,), rows, dtype=torch.int32, device=self._counter.device), rows, True)
-            inputs = self._lips_static[layout] = _LipsInputs(static, held, budget)
-        if hasattr(self.patch_criterion, "packed_image"):
-            self.patch_criterion.packed_image()                # PerceptualAlex's weight image: packed before the capture begins
-        budget = inputs.budget if inputs.budget is not None else (self._budget, self._capacity)
-        g, loss = self._record(inputs.static, budget, budget[1])
-        entry = self._lips[key] = (g, loss, layout)
-        while len(self._lips) > self.lips_graphs:             # drop the least recently used; never the newest
-            gone = self._lips.pop(next(iter(self._lips)))[2]
-            if not any(e[2] == gone for e in self._lips.values()):
-                del self._lips_static[gone]                    # no other graph reads that layout's static inputs
-        self.captures += 1
-        self.lips_captures += 1
-        self.lips_capture_log.append((self.global_step, int(budget[0].item()), budget[1], kind, shape[1:] if kind == "rect" else shape))
-        return entry
-
-    def _lips_graph(self, data):
-        """(graph, loss, static inputs) of a lip fine-tuning batch under lips_graphs > 0: the cached graph of its key, most
-        recently used from now on, or a new capture."""
+    def _step_key(self, data):
+        """-> (cache, key, layout, kind, shape) of a batch after the first window.  A plain batch (kind None) is keyed by the row
+        capacity and the rays' shape.  A rect batch by those, "rect" and the rect's (h, w); a patch batch by ("patch", n,
+        patch_size) whatever the capacity: it marches under a budget of its own.  The layout is the key without the capacity."""
+        rays = tuple(data["rays_o"].shape)
+        if data.get("rect") is None and int(data.get("patch_size") or 1) <= 1:
+            return self._plain, (self._capacity, rays), ("plain", rays), None, None
         rgb = data["bg_torso_color"] if self.opt.torso else data["images"]
         n = int(rgb.reshape(-1, 3).shape[0])
         shape = _patch_views(data, n)[1]                       # (P, h, w); also refuses views that do not hold the batch's rays
         if data.get("rect") is not None:
-            kind, key = "rect", (self._capacity, tuple(data["rays_o"].shape), "rect", shape[1:])
+            layout = (rays, "rect", shape[1:])
+            return self._lips, (self._capacity,) + layout, layout, "rect", shape[1:]
+        key = ("patch", n, int(data["patch_size"]))
+        return self._lips, key, key, "patch", shape
+
+    def _capture(self, data, kind, shape, inputs):
+        """The graph of a key seen for the first time (or evicted since), over `inputs` -- or, where that is None, over new static
+        inputs of the batch's ray layout.  -> (graph, loss, inputs), GraphCache.get's capture."""
+        if inputs is None:
+            budget = None
+            if kind == "patch":
+                # every sample of every ray: none takes more than max_steps, so this budget drops no ray (force_all_rays)
+                rows = _aligned_budget(shape[0] * shape[1] * shape[2] * int(self.opt.max_steps))
+                budget = (torch.full((1,), rows, dtype=torch.int32, device=self._counter.device), rows, True)
+            inputs = StaticInputs(data, self._counter.device, budget)
+            if kind == "rect":
+                inputs.static["rect"] = tuple(int(v) for v in data["rect"])      # train_step reads (h, w) off it, nothing else
+            elif kind == "patch":
+                inputs.static["patch_size"] = int(data["patch_size"])
+        if kind is not None and hasattr(self.patch_criterion, "packed_image"):
+            self.patch_criterion.packed_image()                # PerceptualAlex's weight image: packed before the capture begins
+        budget = inputs.budget if inputs.budget is not None else (self._budget.tensor, self._capacity)
+        g, loss = self._record(inputs.static, budget)
+        self.captures += 1
+        row = (self.global_step, int(budget[0].item()), budget[1])
+        if kind is None:
+            self.capture_log.append(row)
         else:
-            kind, key = "patch", ("patch", n, int(data["patch_size"]))
-        entry = self._lips.pop(key, None)
-        if entry is not None:
-            self._lips[key] = entry
-        else:
-            entry = self._capture_lips(data, key, kind, shape)
-        return entry[0], entry[1], self._lips_static[entry[2]]
+            self.lips_captures += 1
+            self.lips_capture_log.append(row + (kind, shape))
+        return g, loss, inputs
 
     def _torso_route(self):
         """A torso step can be captured only on the device-resident route (opt-in RN_TORSO_TRAIN=fused, radnerf/train_torso.py):
@@ -847,71 +606,24 @@ class GraphedTrainer(Trainer):
         m = self._begin_step()
         if self._torso_route():
             route.kernels("train_torso").pin_mean(m)   # a mean set from the host since the last step goes into the scalar the graph reads
-        if m.mean_count <= 0 or not next(m.parameters()).is_cuda:        # first window / CPU: the eager step
+        running = self._device_budget(m)               # the device scalar every graph of a running budget reads
+        if running is None:                            # first window / CPU: the eager step
             loss = self._forward_backward_update(data, None).detach()
             self._host_schedule()
             return loss
-        budget = _aligned_budget(m.mean_count)
-        step = self.capacity_step
+        budget, step = running[1], self.capacity_step
         if not (budget <= self._capacity <= budget + 2 * step):         # keep the capacity while the budget stays inside its window
             self._capacity = -(-(budget + step // 4) // step) * step
-        if budget != getattr(self, "_budget_value", None):               # the running average moves every 16 steps, not every step
-            self._budget.fill_(budget)
-            self._budget_value = budget
-        if lips:
-            graph, loss, inputs = self._lips_graph(data)
-            inputs.index = self._feed(data, inputs.static, inputs.index)
-        else:
-            key = (self._capacity, tuple(data["rays_o"].shape))
-            if key != self._key:
-                hit = self._graphs.pop(key, None)
-                if hit is not None:                                  # seen before: replay that graph (and mark it most recent)
-                    self._graphs[key] = hit
-                    self._graph, self._loss, self._key = hit[0], hit[1], key
-                else:
-                    self._capture(data, key)
-            graph, loss = self._graph, self._loss
-            self._static_index = self._feed(data, self._static, self._static_index)
-        w_amb = min(self.global_step / self.iters, 1.0) * self.lambda_amb
-        if w_amb != getattr(self, "_amb_value", None):                   # constant once the ramp is over
-            self._amb_weight.fill_(w_amb)
-            self._amb_value = w_amb
+        cache, key, layout, kind, shape = self._step_key(data)
+        graph, loss, inputs = cache.get(key, layout, lambda held: self._capture(data, kind, shape, held))
+        inputs.feed(data)
+        self._amb_weight.set(min(self.global_step / self.iters, 1.0) * self.lambda_amb)
         if isinstance(self.optimizer, HipAdam):
             self.optimizer.refresh_lr()             # a schedule may have rewritten param_groups[i]["lr"] since the last step
         graph.replay()
-        if isinstance(self.optimizer, HipAdam):     # the replayed update went through raw pointers (see HipAdam.step)
-            self.optimizer._hip.mark_written(self.optimizer._written)
-            self.optimizer.note_replayed()
+        if isinstance(self.optimizer, HipAdam):
+            self.optimizer.replayed()
         m.step_counter[m.local_step % 16].copy_(self._counter)
         m.local_step += 1
         self.replays += 1
         return loss.detach()
-
-    @staticmethod
-    def _feed(data, static, held):
-        """Copy a batch into a graph's static inputs; -> the frame index list they now hold."""
-        if "_packed" in data and "_packed" in static:
-            static["_packed"].copy_(data["_packed"])
-            for k in ("poses", "eye", "auds"):
-                if data[k] is not static[k]:
-                    static[k].copy_(data[k])
-        else:
-            for k, v in data.items():
-                if torch.is_tensor(v) and k != "_packed":
-                    static[k].copy_(v)
-        v = data.get("index")
-        if isinstance(v, (list, tuple)) and list(v) != held:
-            # a feed whose frame changes every step brings the index as a device tensor too (DeviceTrainSet): a copy on the
-            # stream instead of an upload from pageable memory, which the host waits for
-            src = data.get("_index_dev")
-            static["index"].copy_(src if src is not None else torch.tensor(v, dtype=torch.long))
-            held = list(v)
-        return held
-
-
-class _LipsInputs:
-    """The static inputs of one ray layout of lip fine-tuning: the batch dict a graph reads, the frame index list it holds, and
-    for a patch layout the sample budget of its own, (device int32, rows, True) -- True: it covers every row of every ray."""
-
-    def __init__(self, static, index, budget):
-        self.static, self.index, self.budget = static, index, budget

@@ -50,7 +50,8 @@ def _alternation(rects):
 
 
 def _run(graphed, phases, criterion="alex", num_rays=1024, perturb_color=False, probe=False, **trainer_kw):
-    """phases: [(mean_count, [(kind, frame, rect | patch_size | None), ...]), ...] after three first-window steps on plain batches.
+    """phases: [(mean_count, [(kind, frame, rect | patch_size | pixel indices of a plain batch | None), ...]), ...] after three
+    first-window steps on plain batches.
     -> (bits: {name: uint32 array} of the per-step losses, the parameters and the Adam moments; losses; trainer; probe MSEs)."""
     from radnerf.dataset import DeviceTrainSet
     from radnerf.percep import PerceptualAlex
@@ -86,7 +87,7 @@ def _run(graphed, phases, criterion="alex", num_rays=1024, perturb_color=False, 
             return ds.batch_rect([frame], rect=arg)
         if kind == "patch":
             return ds.batch_patch([frame], arg)
-        return ds.batch([frame])
+        return ds.batch([frame]) if arg is None else ds.batch([frame], inds=arg)       # a plain batch: its own draw, or the pixels `arg`
 
     probes = [mse()] if probe else []
     losses = [trainer.step(ds.batch([i])).clone() for i in range(3)]
@@ -139,7 +140,7 @@ def test_rect_schedule_equals_the_eager_trainer_bit_for_bit(hiplib, monkeypatch)
         assert [(e[3], e[4]) for e in tr.lips_capture_log] == [("rect", (32, 40)), ("rect", (40, 32)), ("rect", (31, 31))] + (
             [("rect", (40, 32))] if slots == 2 else [])
         assert all(e[1:3] == (12032, 16384) for e in tr.lips_capture_log)
-        assert len(tr._lips) == min(slots, 3) and len(tr._lips_static) == len(tr._lips)
+        assert len(tr._lips.graphs) == min(slots, 3) and len(tr._lips.inputs) == len(tr._lips.graphs)
 
 
 def test_a_budget_that_leaves_and_comes_back(hiplib, monkeypatch):
@@ -155,7 +156,24 @@ def test_a_budget_that_leaves_and_comes_back(hiplib, monkeypatch):
     assert [c for _, _, c in tr.capture_log] == [16384, 20480] and [e[2] for e in tr.lips_capture_log] == [16384, 20480]
     assert tr.captures == 4 and tr.lips_captures == 2 and tr.replays == 12
     assert max(e[0] for e in tr.capture_log + tr.lips_capture_log) <= 3 + 8          # the third phase (steps 12 ...) captured nothing
-    assert len(tr._lips) == 2 and len(tr._lips_static) == 1
+    assert len(tr._lips.graphs) == 2 and len(tr._lips.inputs) == 1
+
+
+def test_plain_batches_of_two_ray_counts_equal_the_eager_trainer_bit_for_bit(hiplib, monkeypatch):
+    """Plain batches of 1 024 rays (the set's own draw) and of 512 rays (every 8th pixel) alternate for eight steps: two keys and
+    two ray layouts, each with static inputs of its own -- one capture each, then replays.  Before the plain graphs kept their
+    static inputs per layout, the second ray count was captured over the first one's and its feed raised."""
+    _set_environment(monkeypatch)
+    every_8th = torch.arange(0, 4096, 8)
+    phases = [(12000, [("plain", s, None if s % 2 == 0 else every_8th) for s in range(8)])]
+    eager, eager_losses, _, _ = _run(False, phases)
+    assert np.isfinite(eager_losses).all()
+    bits, _, tr, _ = _run(True, phases)
+    print(f"capture_log {tr.capture_log}")
+    _same_bits("two ray counts", eager, bits)
+    assert tr.captures == 2 and tr.replays == 8
+    assert [e[1:] for e in tr.capture_log] == [(12032, 16384)] * 2 and tr.lips_captures == 0
+    assert list(tr._plain.inputs) == [("plain", (1, 1024, 3)), ("plain", (1, 512, 3))]
 
 
 def test_patch_steps_equal_the_eager_trainer_bit_for_bit(hiplib, monkeypatch):

@@ -379,7 +379,7 @@ def test_captured_step(hiplib, monkeypatch):
     half = occupancy.torso_pixels(m, b["bg_coords"].reshape(-1, 2), m.density_thresh_torso).numel()
     assert 0 < half < n
     trainer.step(b)
-    alpha = trainer._loss._rn_torso_alpha
+    alpha = trainer._plain.newest()[1]._rn_torso_alpha
     assert int((alpha > 0).sum()) == half
     assert m._mean_density_torso_dev is not None
     m._mean_density_torso_dev.fill_(0.001)                   # under every cell of the grid

@@ -404,7 +404,7 @@ def test_graphed_trainer_keeps_its_graph_when_the_budget_moves(hiplib):
     for mc in (base + 200, base - 300, base + 100):
         m.mean_count = mc
         loss = trainer.step(stream.batch())
-        assert int(trainer._budget.item()) == mc + 128 - mc % 128 and int(m.step_counter[(m.local_step - 1) % 16, 0]) > 0
+        assert int(trainer._budget.tensor.item()) == mc + 128 - mc % 128 and int(m.step_counter[(m.local_step - 1) % 16, 0]) > 0
     assert trainer.captures == 1 and trainer._capacity == cap and np.isfinite(float(loss))
     m.mean_count = cap + 500                    # leaves the window
     trainer.step(stream.batch())

@@ -199,7 +199,7 @@ def test_graphed_trainer_follows_the_data(hiplib, torso):
         losses.append(float(trainer.step(data)))
         if trainer.replays:
             want = oracle.batch([i], inds=ds.inds)
-            st = trainer._static
+            st = trainer._plain.newest()[2].static
             tc.compare_batches(st, want, f"static inputs after step {step} (frame {i})", index=False)
             assert st["index"].tolist() == [i] and st["_packed"] is not data["_packed"]
             assert torch.equal(st["_packed"], data["_packed"])

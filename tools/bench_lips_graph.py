@@ -127,7 +127,7 @@ def bench_schedule(args, forms, lips_batch):
     rec["captures_after_warmup"] = captures[0]
     rec["captures_per_window"] = [b - a for a, b in zip(captures, captures[1:])]
     rec["graphs"] = dict(plain=len(graphed.capture_log), lips=graphed.lips_captures, lips_slots=graphed.lips_graphs,
-                         lips_held=len(graphed._lips), plain_held=len(graphed._graphs),
+                         lips_held=len(graphed._lips.graphs), plain_held=len(graphed._plain.graphs),
                          capacities=sorted({c for _, _, c in graphed.capture_log} | {e[2] for e in graphed.lips_capture_log}))
     rec["memory_reserved_growth_mib"] = grown / 2 ** 20
     rec["memory_reserved_growth_mib_per_graph"] = grown / 2 ** 20 / max(graphed.captures, 1)

@@ -42,9 +42,10 @@ def main():
     # GPU time of one replay alone (events around graph.replay())
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ts = []
+    graph, _, inputs = tr._plain.newest()
     for _ in range(20):
         a.record()
-        tr._graph.replay()
+        graph.replay()
         b.record()
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b))
@@ -60,7 +61,7 @@ def main():
     for _ in range(3):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        tr._capture(stream.batch(), tr._key)
+        tr._capture(stream.batch(), None, None, inputs)
         torch.cuda.synchronize()
         caps.append((time.perf_counter() - t0) * 1e3)
     out["capture_ms"] = caps
