@@ -9,7 +9,8 @@ step; here the decoded arrays stay uint8 (7 bytes per pixel and frame) and only 
 
 Values are the reference's float32 loader arithmetic (`--preload 0` / `1`: `astype(np.float32) / 255`, float32 blend).  Its
 `--preload 2` keeps fp16 copies of the images; that rounding is NOT reproduced.  Decoding files (cv2, json, the audio
-features' .npy) is not part of this module: a loader hands over arrays.
+features' .npy) is not part of this module: a loader hands over arrays -- radnerf/datafiles.py is that loader, and
+DeviceTrainSet.from_directory() builds the set from a dataset directory through it.
 
 The two samplings of lip fine-tuning (nerf/utils.py:277-303) are further instantiations of the same kernel: batch_rect() takes
 every pixel of a rect -- by default the frame's lips rect (provider.py:488-502, lips_rect_from_landmarks) -- and batch_patch()
@@ -433,6 +434,21 @@ class DeviceTrainSet:
         if self._eye is not None:
             self._eye.copy_(self.eye_area[frame:frame + 1])
         self._auds.copy_(get_audio_features(self.auds, self.att, aud_frame))
+
+    # ------------------------------------------------------------------------------------------------------ from files
+    @classmethod
+    def from_directory(cls, root, opt, split="train", num_rays=4096, seed=0, device="cuda", downscale=1, decode=None, kernel=None):
+        """The set of one split of a dataset directory (radnerf/datafiles.py load_split: decoded once, on the host, uploaded as
+        uint8).  The lips rects go in with opt.finetune_lips, the eye areas with opt.exp_eye, as the reference's loader keeps them
+        (provider.py:475, 487).  `loaded` on the result is the LoadedSplit without its images (radius, frame ids, landmarks, has_gt)."""
+        from .datafiles import load_split
+        d = load_split(root, opt, split, downscale=downscale, decode=decode)
+        ds = cls(d.images, d.torso, d.bg, d.poses, d.intrinsics, d.auds, d.face_rect,
+                 eye_area=d.eye_area if getattr(opt, "exp_eye", False) else None, opt=opt, num_rays=num_rays, seed=seed, device=device,
+                 kernel=kernel, lips_rect=d.lips_rect if getattr(opt, "finetune_lips", False) else None)
+        d.images = d.torso = None          # the set holds them on the device; no second copy stays on the host
+        ds.loaded = d
+        return ds
 
     # --------------------------------------------------------------------------------------------------------- stand-in
     @classmethod

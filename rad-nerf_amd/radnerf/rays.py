@@ -152,8 +152,17 @@ def nerf_matrix_to_ngp(pose, scale=0.33, offset=(0.0, 0.0, 0.0)):
 
 def _rotation_mean(rots):
     """Chordal L2 mean of rotation matrices [..., n, 3, 3] -> [..., 3, 3]: the unit quaternion that is the dominant
-    eigenvector of sum_j q_j q_j^T (what scipy's Rotation.mean() computes)."""
-    m = rots
+    eigenvector of sum_j q_j q_j^T (what scipy's Rotation.mean() computes).  In float64 from end to end, as scipy works: the result
+    is rounded to the input's type once, which is what makes a smoothed float32 path equal the reference's to the bit."""
+    dtype, m = rots.dtype, rots.double()
+    # scipy's from_matrix first replaces a matrix that is not orthogonal by its nearest orthogonal one (the polar factor U V^T of
+    # its SVD); "orthogonal" means |M M^T - I| <= 1e-12 + 1e-5 |I| entry by entry (found by trial against scipy 1.15: a float32 pose
+    # passes only when the off-diagonal products cancel exactly, e.g. a rotation about one axis).
+    eye = torch.eye(3, dtype=m.dtype, device=m.device)
+    ok = ((m @ m.transpose(-1, -2) - eye).abs() <= 1e-12 + 1e-5 * eye).all(-1).all(-1)
+    if not bool(ok.all()):
+        U, _, Vh = torch.linalg.svd(m)
+        m = torch.where(ok[..., None, None], m, U @ Vh)
     # quaternion (x, y, z, w) of each matrix, numerically safe branch per element
     t = m[..., 0, 0] + m[..., 1, 1] + m[..., 2, 2]
     q = torch.stack([m[..., 2, 1] - m[..., 1, 2], m[..., 0, 2] - m[..., 2, 0], m[..., 1, 0] - m[..., 0, 1], 1.0 + t], -1)
@@ -166,15 +175,18 @@ def _rotation_mean(rots):
         v[3] = m[..., k, j] - m[..., j, k]
         alt.append(torch.stack(v, -1))
     cand = torch.stack([q] + alt, -2)                                      # [..., n, 4 candidates, 4]
-    best = cand.norm(dim=-1).argmax(-1)                                    # the best conditioned candidate
+    # the candidate scipy's from_matrix takes: the largest of (m00, m11, m22, trace) -- on matrices that are orthogonal only to
+    # float32 the four differ at 1e-8, so the choice is part of the result
+    pick = torch.stack([m[..., 0, 0], m[..., 1, 1], m[..., 2, 2], t], -1).argmax(-1)
+    best = (pick + 1) % 4
     q = torch.gather(cand, -2, best[..., None, None].expand(best.shape + (1, 4))).squeeze(-2)
     q = q / q.norm(dim=-1, keepdim=True)
     K = torch.einsum("...ni,...nj->...ij", q, q)
-    _, vec = torch.linalg.eigh(K.double())
-    x, y, z, w = vec[..., :, -1].float().unbind(-1)
+    _, vec = torch.linalg.eigh(K)
+    x, y, z, w = vec[..., :, -1].unbind(-1)
     return torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w),
                         2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w),
-                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).reshape(x.shape + (3, 3))
+                        2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)], -1).reshape(x.shape + (3, 3)).to(dtype)
 
 
 def smooth_camera_path(poses, kernel_size=5):
@@ -187,6 +199,9 @@ def smooth_camera_path(poses, kernel_size=5):
     trans, rots = p[:, :3, 3].clone(), p[:, :3, :3].clone()
     for i in range(N):                     # windows differ in length only at the two ends; N is the clip length (host-side, once)
         lo, hi = max(0, i - K), min(N, i + K + 1)
-        p[i, :3, 3] = trans[lo:hi].mean(0)
+        acc = trans[lo]
+        for j in range(lo + 1, hi):        # the rows added one by one and one division, as numpy's mean(0) does it (torch's mean differs by an ulp)
+            acc = acc + trans[j]
+        p[i, :3, 3] = acc / (hi - lo)
         p[i, :3, :3] = _rotation_mean(rots[lo:hi])
     return p.numpy() if is_np else p
