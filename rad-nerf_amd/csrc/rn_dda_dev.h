@@ -145,7 +145,11 @@ struct Dda {
     // decisions on a bit mask made k_head_march 10-17 % slower, so the loop keeps the reference's shape.)
     // SPAN (opt-in, see set_span()): on lanes with `span` the lattice points before t_lo are stepped over by the loop's own
     // t += dt without a cell or a load, and the walk ends at t_hi; the guard counts the stepped-over points too.
-    template <bool SPAN = false, class Sink>
+    // AHEAD (opt-in, with SPAN): on lanes with `span` -- one cascade, one_step_skips, so the lattice point after t is t + dt whatever
+    // the grid holds -- the occupancy byte of the NEXT point is asked for before the current point's is looked at: its round trip
+    // passes under the current point's decision and the next point's arithmetic.  Same points, same tests, same order; the one
+    // byte read past the walk's last point lies in the grid like every other (cell_of() clamps the cell).
+    template <bool SPAN = false, bool AHEAD = false, class Sink>
     __device__ __forceinline__ uint32_t walk(float &t_io, uint32_t limit, Sink sink) const {
         float t = t_io;
         uint32_t step = 0;
@@ -158,6 +162,33 @@ struct Dda {
                 while (t < first && guard < (1u << 20)) {
                     t += clampf(t * dt_gamma, dt_min, dt_max);
                     guard++;
+                }
+                if constexpr (AHEAD) {
+                    // two points in flight, A and B by turns (no register is copied, so no copy waits for a byte on its way);
+                    // inside the loop the next point is fetched whether or not the walk will get to it
+                    if (!(t < end && limit > 0u)) { t_io = t; return 0u; }   // an empty span: nothing is fetched
+                    float xa, ya, za, dta, xb, yb, zb, dtb, mip_bound;
+                    int nx, ny, nz;
+                    uint32_t ia = cell_of(t, xa, ya, za, dta, mip_bound, nx, ny, nz), ib;
+                    uint32_t ba = grid[ia >> 3], bb;
+                    for (;;) {
+                        if (!(t < end && step < limit && guard < (1u << 20))) break;
+                        const float tb = t + dta;
+                        ib = cell_of(tb, xb, yb, zb, dtb, mip_bound, nx, ny, nz);
+                        bb = grid[ib >> 3];
+                        if (ba & (1u << (ia & 7u))) { sink(*this, step, t, xa, ya, za, dta); step++; } else { guard++; }
+                        guard++;
+                        t = tb;
+                        if (!(t < end && step < limit && guard < (1u << 20))) break;
+                        const float ta = t + dtb;
+                        ia = cell_of(ta, xa, ya, za, dta, mip_bound, nx, ny, nz);
+                        ba = grid[ia >> 3];
+                        if (bb & (1u << (ib & 7u))) { sink(*this, step, t, xb, yb, zb, dtb); step++; } else { guard++; }
+                        guard++;
+                        t = ta;
+                    }
+                    t_io = t;
+                    return step;
                 }
             }
         }
@@ -227,10 +258,17 @@ struct Dda {
     // did not reach get deltas = 0 (the network and the compositor skip them), so the sample buffers never need a memset.
     // t is taken by value: where the walk stops is not visible to anyone (the compositor writes rays_t from deltas), which is
     // what lets SPAN end a walk at t_hi instead of far.
-    template <bool SPAN = false>
+    // EXP: experiment only (the RN_EXP_LOOP_* switches of rn_head_loop.hip, 0 in every build that renders): kExpNoStores -- the
+    // walk without its sample stores; kExpNoFill -- without the zero fill; kExpNoWalk -- no lattice point is tested.
+    static constexpr int kExpNoStores = 1, kExpNoFill = 2, kExpNoWalk = 4;
+    template <bool SPAN = false, int EXP = 0, bool AHEAD = false>
     __device__ __forceinline__ uint32_t march_slot(float t, uint32_t n_step, uint32_t base, float *xyzs, float *dirs, float *deltas) const {
-        const uint32_t emitted = walk<SPAN>(t, n_step, EmitSamples{xyzs + (size_t)base * 3, dirs + (size_t)base * 3, deltas + (size_t)base * 2});
-        for (uint32_t k = emitted; k < n_step; k++) { deltas[((size_t)base + k) * 2] = 0.0f; deltas[((size_t)base + k) * 2 + 1] = 0.0f; }
+        const uint32_t limit = (EXP & kExpNoWalk) ? 0u : n_step;
+        uint32_t emitted;
+        if constexpr ((EXP & kExpNoStores) != 0) emitted = walk<SPAN, AHEAD>(t, limit, CountSamples{});
+        else emitted = walk<SPAN, AHEAD>(t, limit, EmitSamples{xyzs + (size_t)base * 3, dirs + (size_t)base * 3, deltas + (size_t)base * 2});
+        if constexpr ((EXP & kExpNoFill) == 0)
+            for (uint32_t k = emitted; k < n_step; k++) { deltas[((size_t)base + k) * 2] = 0.0f; deltas[((size_t)base + k) * 2 + 1] = 0.0f; }
         return emitted;
     }
 };

@@ -35,9 +35,31 @@ __device__ __forceinline__ void next_state(int32_t *st, uint32_t N, uint32_t n_a
     st[5] = 0;  // workgroups that hold live-sample partial sums of the coming iteration; 0 = ceil(n_alive / 256)
 }
 
+// Experiment switches (compile-time, off by default) that attribute a marcher's time, in the style of RN_EXP_NO_LOADS: each is a
+// mask of marchers -- 1 = k_frame_begin, 2 = the compaction's march (k_head_compact<true>, k_head_step<true>), 4 = k_head_march --
+// built without one term.  A build with any of them set renders nothing usable; it is for a profiler run only.
+//   -DRN_EXP_LOOP_NO_STORES=mask   the walk without the three stores of a sample
+//   -DRN_EXP_LOOP_NO_LIST=mask     without the zero fill of unused deltas rows and the live-list entry loop
+//   -DRN_EXP_LOOP_NO_WALK=mask     without the walk: no lattice point is tested, every ray emits nothing
+#ifndef RN_EXP_LOOP_NO_STORES
+#define RN_EXP_LOOP_NO_STORES 0
+#endif
+#ifndef RN_EXP_LOOP_NO_LIST
+#define RN_EXP_LOOP_NO_LIST 0
+#endif
+#ifndef RN_EXP_LOOP_NO_WALK
+#define RN_EXP_LOOP_NO_WALK 0
+#endif
+constexpr int kMarcherFrameBegin = 1, kMarcherCompact = 2, kMarcherMarch = 4;
+constexpr int exp_of(int marcher) {
+    return ((RN_EXP_LOOP_NO_STORES & marcher) ? Dda::kExpNoStores : 0) | ((RN_EXP_LOOP_NO_LIST & marcher) ? Dda::kExpNoFill : 0) |
+           ((RN_EXP_LOOP_NO_WALK & marcher) ? Dda::kExpNoWalk : 0);
+}
+
 // The marchers' epilogue: every lane holds `emitted` live samples in slots base .. base + emitted - 1.  One atomicAdd per
 // workgroup reserves a run of the iteration's live list (its order is arrival order -- irrelevant, every sample is
 // independent), a block-wide scan places each lane's entries.  Returns the workgroup's live-sample count.
+template <int EXP = 0>
 __device__ __forceinline__ uint32_t list_live_slots(uint32_t emitted, uint32_t base, int32_t *live_count,
                                                     int32_t *__restrict__ live_slots, uint32_t *sh /* [kLoopBlock / kWave + 1] */) {
     __syncthreads();  // sh may still be read by the caller's previous phase
@@ -47,7 +69,8 @@ __device__ __forceinline__ uint32_t list_live_slots(uint32_t emitted, uint32_t b
         if (threadIdx.x == 0) sh[kLoopBlock / kWave] = total ? (uint32_t)atomicAdd(live_count, (int32_t)total) : 0u;
         __syncthreads();
         const uint32_t at = sh[kLoopBlock / kWave] + before;
-        for (uint32_t k = 0; k < emitted; k++) live_slots[at + k] = (int32_t)(base + k);
+        if constexpr ((EXP & Dda::kExpNoFill) == 0)
+            for (uint32_t k = 0; k < emitted; k++) live_slots[at + k] = (int32_t)(base + k);
     }
     return total;
 }
@@ -80,23 +103,23 @@ k_head_march(const int32_t *__restrict__ st, const int32_t *__restrict__ rays_al
              uint32_t max_steps, uint32_t C, uint32_t H, const uint8_t *__restrict__ grid,
              const float *__restrict__ fars, float *__restrict__ xyzs, float *__restrict__ dirs, float *__restrict__ deltas, int32_t *__restrict__ stats,
              uint32_t *__restrict__ block_live, int32_t *__restrict__ live_count, int32_t *__restrict__ live_slots,
-             const int32_t *__restrict__ occ_box) {
+             const int32_t *__restrict__ occ_box, uint32_t N) {
+    const uint32_t n = blockIdx.x * kLoopBlock + threadIdx.x;
+    const int index = n < N ? rays_alive[n] : 0;   // the list holds N entries: asked for before the state words are in
     if (!st[4]) return;
     const uint32_t n_alive = (uint32_t)st[0], n_step = (uint32_t)st[2];
-    const uint32_t n = blockIdx.x * kLoopBlock + threadIdx.x;
     uint32_t emitted = 0;
     const uint32_t base = n * n_step;
     if (n < n_alive) {
-        const int index = rays_alive[n];
         Dda s;
         s.init(rays_o + (size_t)index * 3, rays_d + (size_t)index * 3, bound, dt_gamma, max_steps, C, H, grid, fars[index]);
         if (occ_box) s.set_span(occ_box);
-        emitted = s.march_slot<true>(rays_t[index], n_step, base, xyzs, dirs, deltas);  // perturb is off at inference: no noise term (renderer.py:251)
+        emitted = s.march_slot<true, exp_of(kMarcherMarch), true>(rays_t[index], n_step, base, xyzs, dirs, deltas);  // perturb is off at inference: no noise term (renderer.py:251)
     }
     // live samples of this iteration: listed for the network kernel, and counted -- one partial sum per workgroup, added up by
     // the compaction kernel (a same-address atomic per wavefront for the statistic cost 38 us per frame)
     __shared__ uint32_t sh[kLoopBlock / kWave + 1];
-    const uint32_t total = list_live_slots(emitted, base, live_count, live_slots, sh);
+    const uint32_t total = list_live_slots<exp_of(kMarcherMarch)>(emitted, base, live_count, live_slots, sh);
     if (threadIdx.x == 0) block_live[blockIdx.x] = total;
     if (n == 0) { atomicAdd(&stats[RN_HEAD_ST_ITERS], 1); atomicAdd(&stats[RN_HEAD_ST_SLOTS], (int32_t)(n_alive * n_step)); }
 }
@@ -148,10 +171,10 @@ k_frame_begin(RaySource rs, float *__restrict__ rays_o, float *__restrict__ rays
         Dda s;
         s.init(o, d, bound, dt_gamma, max_steps, C, H, grid, far);
         if (occ_box) s.set_span(occ_box);
-        emitted = s.march_slot<true>(near, 1u, n, xyzs, dirs, deltas);
+        emitted = s.march_slot<true, exp_of(kMarcherFrameBegin), true>(near, 1u, n, xyzs, dirs, deltas);
     }
     __shared__ uint32_t sh[kLoopBlock / kWave + 1];
-    const uint32_t total = list_live_slots(emitted, n, state + 6, live_slots, sh);
+    const uint32_t total = list_live_slots<exp_of(kMarcherFrameBegin)>(emitted, n, state + 6, live_slots, sh);
     if (threadIdx.x == 0) block_live[blockIdx.x] = total;
 }
 
@@ -235,7 +258,7 @@ __device__ __forceinline__ void loop_idle(const int32_t *__restrict__ st, int32_
 // workgroups of THIS launch -> agent-scope atomic loads.
 template <bool MARCH, bool COOP>
 __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, const int32_t *__restrict__ st, int32_t *__restrict__ st_next,
-                                              uint32_t N, uint32_t max_steps, const int32_t *__restrict__ rays_in,
+                                              uint32_t N, uint32_t max_steps, int32_t v_in,
                                               int32_t *__restrict__ rays_out, const uint32_t *__restrict__ block_counts,
                                               const uint32_t *__restrict__ block_live, int32_t *__restrict__ stats, const MarchArgs &m,
                                               uint32_t close_frame, uint32_t iter, uint32_t tag = 0) {
@@ -243,6 +266,19 @@ __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, con
     __shared__ uint32_t red_live[kLoopBlock / kWave];
     __shared__ uint32_t red_all[kLoopBlock / kWave];
     __shared__ uint32_t wave_off[kLoopBlock / kWave];
+    // Loads that depend on nothing computed here go first: v_in = rays_in[c * kLoopBlock + threadIdx.x], asked for by the caller
+    // (the list holds N entries, so it needs no state word; -1 beyond N), and, with MARCH, the ray of a survivor -- their round
+    // trips pass under the count summation and its barriers instead of following them.
+    float ray_o[3] = {0.0f, 0.0f, 0.0f}, ray_d[3] = {0.0f, 0.0f, 0.0f}, ray_far = 0.0f, ray_t = 0.0f;
+    auto load_ray = [&](int32_t v) {
+#pragma unroll
+        for (int k = 0; k < 3; k++) { ray_o[k] = m.rays_o[(size_t)v * 3 + k]; ray_d[k] = m.rays_d[(size_t)v * 3 + k]; }
+        ray_far = m.fars[v];
+        ray_t = m.rays_t[v];
+    };
+    if constexpr (MARCH && !COOP) {   // (k_head_step has no registers to hold a ray across its barrier: it loads where it marches)
+        if ((uint32_t)v_in < N) load_ray(v_in);   // an entry past n_alive is a leftover (not even written on a first frame): never an address
+    }
     const uint32_t n_alive = (uint32_t)st[0];
     const bool last = c == n_blocks - 1;
 
@@ -279,7 +315,7 @@ __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, con
     for (int w = 0; w < kLoopBlock / kWave; w++) { offset += red[w]; n_next += red_all[w]; }
 
     const uint32_t n = c * kLoopBlock + threadIdx.x;
-    const int32_t v = (n < n_alive) ? rays_in[n] : -1;
+    const int32_t v = (n < n_alive) ? v_in : -1;
     const bool keep = v >= 0;
     const unsigned long long mask = __ballot(keep);
     const uint32_t within = ballot_prefix(mask);
@@ -314,14 +350,14 @@ __device__ __forceinline__ void compact_chunk(uint32_t c, uint32_t n_blocks, con
         uint32_t emitted = 0;
         const uint32_t base = slot * n_step_next;
         if (keep) {
+            if constexpr (COOP) load_ray(v);
             Dda s;
-            s.init(m.rays_o + (size_t)v * 3, m.rays_d + (size_t)v * 3, m.bound, m.dt_gamma, max_steps, m.cascade, m.grid_size, m.grid,
-                   m.fars[v]);
+            s.init(ray_o, ray_d, m.bound, m.dt_gamma, max_steps, m.cascade, m.grid_size, m.grid, ray_far);
             if (m.occ_box) s.set_span(m.occ_box);
-            emitted = s.march_slot<true>(m.rays_t[v], n_step_next, base, m.xyzs, m.dirs, m.deltas);
+            emitted = s.march_slot<true, exp_of(kMarcherCompact), true>(ray_t, n_step_next, base, m.xyzs, m.dirs, m.deltas);
         }
         __shared__ uint32_t sh[kLoopBlock / kWave + 1];
-        const uint32_t total = list_live_slots(emitted, base, st_next + 6, m.live_slots, sh);
+        const uint32_t total = list_live_slots<exp_of(kMarcherCompact)>(emitted, base, st_next + 6, m.live_slots, sh);
         if (threadIdx.x == 0) m.block_live_next[c] = total;
     }
 }
@@ -332,10 +368,12 @@ k_head_compact(const int32_t *__restrict__ st, int32_t *__restrict__ st_next, ui
                const int32_t *__restrict__ rays_in, int32_t *__restrict__ rays_out,
                const uint32_t *__restrict__ block_counts, const uint32_t *__restrict__ block_live, int32_t *__restrict__ stats,
                MarchArgs m, uint32_t close_frame, uint32_t iter) {
+    const uint32_t n = blockIdx.x * kLoopBlock + threadIdx.x;
+    const int32_t v_in = n < N ? rays_in[n] : -1;   // asked for before the state words are in (see compact_chunk)
     if (!st[4]) { loop_idle(st, st_next, stats, close_frame, iter); return; }
     const uint32_t n_blocks = ((uint32_t)st[0] + kLoopBlock - 1) / kLoopBlock;
     if (blockIdx.x >= n_blocks) return;
-    compact_chunk<MARCH, false>(blockIdx.x, n_blocks, st, st_next, N, max_steps, rays_in, rays_out, block_counts, block_live, stats, m,
+    compact_chunk<MARCH, false>(blockIdx.x, n_blocks, st, st_next, N, max_steps, v_in, rays_out, block_counts, block_live, stats, m,
                                 close_frame, iter);
 }
 
@@ -376,7 +414,8 @@ k_head_step(const int32_t *__restrict__ st, int32_t *__restrict__ st_next, uint3
     }
     for (uint32_t c = blockIdx.x; c < n_chunks; c += G) {
         __syncthreads();  // the reduction arrays of compact_chunk are reused; all of this workgroup's counts are on their way
-        compact_chunk<MARCH, true>(c, n_chunks, st, st_next, N, max_steps, rays_in, rays_out, block_counts, block_live, stats, m,
+        const uint32_t n = c * kLoopBlock + threadIdx.x;
+        compact_chunk<MARCH, true>(c, n_chunks, st, st_next, N, max_steps, n < N ? rays_in[n] : -1, rays_out, block_counts, block_live, stats, m,
                                    close_frame, iter, tag);
     }
     // every workgroup has read the epoch before it stored its first count, and nobody gets here before all counts are in
@@ -448,7 +487,7 @@ int rn_head_iterate_ex(const rn_head_t *h, const rn_grid_t *grid_xyz, const rn_g
         if (it == first_iter && !(flags & RN_LOOP_FIRST_MARCHED))
             hipLaunchKernelGGL(k_head_march, rgrid, rblock, 0, s, st, alive, h->rays_t, h->rays_o, h->rays_d, h->bound,
                                h->dt_gamma, h->max_steps, h->cascade, h->grid_size, h->bitfield, h->fars, h->xyzs, h->dirs,
-                               h->deltas, h->state, block_live[it & 1u], st + 6, h->live_slots, h->occ_box);
+                               h->deltas, h->state, block_live[it & 1u], st + 6, h->live_slots, h->occ_box, h->N);
         // the network runs over the iteration's live list when the caller gave room for one (st[6] entries), else over all
         // st[3] slots, skipping the dead ones by their deltas
         run_fused(h->xyzs, h->dirs, h->deltas, h->N, h->live_slots ? st + 6 : st + 3, grid_xyz, grid_amb, packed, bias, h->bound,
