@@ -470,6 +470,31 @@ int rn_mesh_emit(const float *field, uint32_t X, uint32_t Y, uint32_t Z, float t
                  uint32_t n_vertices, uint32_t n_triangles, float *vertices, int32_t *triangles, rn_stream_t stream);
 int rn_mesh_tet_case(uint32_t mask, int32_t *n_triangles, int32_t *edges);
 
+/* ---- video write-out: Motion-JPEG on the device (nerf/utils.py:971 hands the frames to an encoder on the host) -------
+ * A batch of finished frames [F, H, W, 3] uint8 (device) becomes one baseline JPEG scan per frame: JFIF YCbCr, subsampling 420
+ * (MCU 16 x 16) or 444 (MCU 8 x 8), the Annex K quantisation tables under the IJG quality rule and the four Annex K Huffman tables;
+ * csrc/rn_jpeg_dev.h states every convention.  The host writes SOI .. SOS before a scan and EOI after it (radnerf/video.py).
+ * F, H, W >= 1, sides <= 65535, subsampling 420 or 444, quality 1 .. 100, a frame's worst-case stream below 2^31 bits; anything
+ * else is RN_ERR_INVALID_ARG before a launch (the three size functions: 0).
+ *
+ *   rn_jpeg_blocks           8 x 8 blocks of one frame, in MCU-interleaved scan order (420: Y Y Y Y Cb Cr per MCU; 444: Y Cb Cr).
+ *   rn_jpeg_stream_capacity  bytes no frame's scan can exceed: 416 per block = twice the 208 that hold the longest coded block
+ *                            (22 bits of DC, 63 x 26 of AC), byte stuffing at most doubling it.
+ *   rn_jpeg_workspace        bytes of scratch rn_jpeg_entropy needs for F frames (16-byte aligned).
+ *   rn_jpeg_coefficients     coefficients[F, blocks, 64] int16: quantised, zigzag order.
+ *   rn_jpeg_entropy          streams = the scans of frames 0 .. F - 1 one behind the other (0xFF stuffed with 0x00, the last byte of
+ *                            each padded with 1-bits), sizes[f] (device uint32) the byte count of frame f; capacity: bytes of
+ *                            `streams`, >= F * rn_jpeg_stream_capacity and that product < 2^31.  The bytes are a function
+ *                            of the coefficients alone: two runs, the same bytes.  A coefficient beyond the invariants of the
+ *                            coefficient pass (|DC difference| <= 2047, |AC| <= 1023) is coded as the nearest value within them. */
+size_t rn_jpeg_blocks(uint32_t H, uint32_t W, uint32_t subsampling);
+size_t rn_jpeg_stream_capacity(uint32_t H, uint32_t W, uint32_t subsampling);
+size_t rn_jpeg_workspace(uint32_t F, uint32_t H, uint32_t W, uint32_t subsampling);
+int rn_jpeg_coefficients(const uint8_t *frames, uint32_t F, uint32_t H, uint32_t W, uint32_t subsampling, uint32_t quality,
+                         int16_t *coefficients, rn_stream_t stream);
+int rn_jpeg_entropy(const int16_t *coefficients, uint32_t F, uint32_t H, uint32_t W, uint32_t subsampling, void *workspace,
+                    uint8_t *streams, size_t capacity, uint32_t *sizes, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

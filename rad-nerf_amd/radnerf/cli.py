@@ -3,7 +3,8 @@ checkpoint plus a pose file and an audio-feature file -- the wiring of the refer
 
     train     DeviceTrainSet.from_directory -> Trainer / GraphedTrainer (LR decay and EMA inside the Adam launches) ->
               workspace/checkpoints/ngp_ep%04d.pth every epoch, Trainer.evaluate on the val split every eval_interval epochs
-    render    ClipScene + FrameParallelRenderer -> workspace/results/<name>.npy (uint8 [F,H,W,3]) and <name>_depth.npy
+    render    ClipScene + FrameParallelRenderer -> workspace/results/<name>.npy (uint8 [F,H,W,3]) and <name>_depth.npy;
+              --video: <name>.avi beside it, Motion-JPEG encoded on the device, --audio_wav laid under it (radnerf/video.py)
 
 parse(argv) -> opt, plan(opt, n_frames) -> the schedule, main(argv) -> a dict of what was done.  parse and plan touch no GPU.
 
@@ -11,7 +12,8 @@ Everything this module adds runs once per run, epoch or frame on the host; per t
 launch and Trainer.step, per frame ClipScene.render.  Flags keep the reference's names and defaults.  `-O` records fp16 and
 exp_eye; fp16 only records: the arithmetic follows the RN_* switches (radnerf/switches.py is their only reader, nothing is set
 here).  `--preload` is accepted and ignored (the set is always device-resident uint8).  Not built here, and refused: --gui, --asr*
-(live audio), --emb, --train_camera from this entry point.  Video encoding stays out: the uint8 array is what an encoder reads.
+(live audio), --emb, --train_camera from this entry point.  --video writes Motion-JPEG in AVI with PCM audio and nothing else:
+no MP4 / H.264, no compressed audio; the .npy stays what any other encoder reads.
 Continuing from a checkpoint restores model, optimizer, EMA, epoch and step count; it is NOT bit-identical to an uninterrupted
 run, because the occupancy refresh draws from Python's `random`.
 """
@@ -88,6 +90,11 @@ def _parser():
     p.add_argument("--lpips_weights", type=str, default="", help="state dict of lpips.LPIPS(net='alex'); nothing is fetched")
     p.add_argument("--captured", action="store_true", help="replay the training step from captured graphs (GraphedTrainer)")
     p.add_argument("--png", action="store_true", help="also write the frames as PNG files (needs PIL)")
+    p.add_argument("--video", action="store_true", help="also write results/<name>.avi: Motion-JPEG encoded on the device")
+    p.add_argument("--video_quality", type=int, default=90, help="JPEG quality of --video, 1 .. 100")
+    p.add_argument("--video_subsampling", type=str, default="420", choices=("420", "444"))
+    p.add_argument("--video_fps", type=float, default=25, help="frame rate of --video (not --fps, the reference's ASR rate)")
+    p.add_argument("--audio_wav", type=str, default="", help="PCM .wav to lay under --video")
     p.add_argument("--name", type=str, default="ngp")
     p.add_argument("--engine", type=str, default="fused", choices=("ops", "fused"))
     return p
@@ -120,6 +127,16 @@ def parse(argv=None):
         p.error(f"--lpips_weights: {opt.lpips_weights} is not a file")
     if opt.iters <= 0:
         p.error("--iters must be positive")
+    if not 1 <= opt.video_quality <= 100:
+        p.error("--video_quality is 1 .. 100")
+    if not opt.video_fps > 0:
+        p.error("--video_fps must be positive")
+    if opt.audio_wav:
+        from radnerf.video import check_wav
+        try:
+            check_wav(opt.audio_wav)
+        except ValueError as e:
+            p.error(f"--audio_wav: {e}")
     opt.test_train = bool(opt.test_train)
     return opt
 
@@ -196,7 +213,8 @@ def clip_of_split(d):
 
 def render_clip(opt, model, device, out_dir, name, log=print, decode=None):
     """The clip through ClipScene + FrameParallelRenderer (one rank, or the ranks of torch.distributed.run) ->
-    <out_dir>/<name>.npy uint8 [F,H,W,3] and, on one rank, <name>_depth.npy float32 [F,H,W]; --png: the frames as PNG files.
+    <out_dir>/<name>.npy uint8 [F,H,W,3] and, on one rank, <name>_depth.npy float32 [F,H,W]; --png: the frames as PNG files;
+    --video: <name>.avi (one rank: every frame goes to the VideoSink as it is rendered; several: rank 0 encodes the gathered stack).
     The lip-smoothing state starts fresh.  -> (path of the frames, n_frames); the path is None off rank 0."""
     import torch
     from radnerf.clip import ClipScene
@@ -213,19 +231,28 @@ def render_clip(opt, model, device, out_dir, name, log=print, decode=None):
     steps = -(-n // world)
     model.enc_a = None
     frames, depths = [], []
+    sink = _video_sink(opt, scene.H, scene.W, device, out_dir, name) if opt.video and rank == 0 else None
     with torch.no_grad():
         for s in range(steps):
             u8 = renderer.step(s)
             if world == 1:
                 frames.append(u8.clone())
+                if sink is not None:
+                    sink.push(frames[-1])
                 depths.append(scene.last_out["depth"].reshape(scene.H, scene.W).float().clone())
         done = renderer.finish()
     if world > 1:
         if rank != 0:
             return None, n
-        video = torch.stack([f for stack in done for f in stack.unbind(0)])[:n].cpu().numpy()
+        video = torch.stack([f for stack in done for f in stack.unbind(0)])[:n]
+        if sink is not None:
+            for f in video.to(device).unbind(0):
+                sink.push(f)
+        video = video.cpu().numpy()
     else:
         video = torch.stack(frames).cpu().numpy()
+    if sink is not None:
+        log(f"[INFO] wrote {sink.finish()}: {sink.files} frames at {opt.video_fps:g} per second")
     os.makedirs(out_dir, exist_ok=True)
     path = os.path.join(out_dir, name + ".npy")
     np.save(path, video)
@@ -237,6 +264,17 @@ def render_clip(opt, model, device, out_dir, name, log=print, decode=None):
             Image.fromarray(frame).save(os.path.join(out_dir, f"{name}_{i:04d}.png"))
     log(f"[INFO] wrote {path}: {video.shape[0]} frames of {video.shape[1]} x {video.shape[2]}")
     return path, n
+
+
+def avi_path(out_dir, name):
+    return os.path.join(out_dir, name + ".avi")
+
+
+def _video_sink(opt, H, W, device, out_dir, name):
+    from radnerf.video import AviWriter, JpegEncoder, VideoSink
+    os.makedirs(out_dir, exist_ok=True)
+    writer = AviWriter(avi_path(out_dir, name), H, W, opt.video_fps, audio=opt.audio_wav or None)
+    return VideoSink(writer, JpegEncoder(H, W, opt.video_quality, opt.video_subsampling), batch=8, device=device)
 
 
 def _perceptual(opt, device):
@@ -279,7 +317,7 @@ def main(argv=None, log=print, decode=None):
     device = torch.device("cuda", torch.cuda.current_device())
     model = _model(opt, device, log)
     results_dir = os.path.join(opt.workspace, "results")
-    done = dict(opt=opt, losses=[], evals=[], checkpoints=[], video=None)
+    done = dict(opt=opt, losses=[], evals=[], checkpoints=[], video=None, avi=None)
 
     if opt.test or opt.test_train:
         path = _which_checkpoint(opt, log)
@@ -295,6 +333,7 @@ def main(argv=None, log=print, decode=None):
             done["evals"].append((epoch, _evaluate(Trainer(model, opt, iters=opt.iters), split, log, "test")))
             del split
         done["video"], done["n_frames"] = render_clip(opt, model, device, results_dir, f"{opt.name}_ep{epoch:04d}", log, decode)
+        done["avi"] = avi_path(results_dir, f"{opt.name}_ep{epoch:04d}") if opt.video and done["video"] else None
         return done
 
     if world > 1:
@@ -358,6 +397,7 @@ def main(argv=None, log=print, decode=None):
         done["evals"].append((epoch, _evaluate(trainer, val, log, "test")))
     with trainer.eval_scope():
         done["video"], done["n_frames"] = render_clip(opt, model, device, results_dir, f"{opt.name}_ep{epoch:04d}", log, decode)
+    done["avi"] = avi_path(results_dir, f"{opt.name}_ep{epoch:04d}") if opt.video and done["video"] else None
     return done
 
 

@@ -225,6 +225,11 @@ FUNCTIONS = {
     "rn_mesh_count": (_int, [_ptr, _u32, _u32, _u32, _f32, _ptr, _ptr, _ptr]),
     "rn_mesh_emit": (_int, [_ptr, _u32, _u32, _u32, _f32, _ptr, _ptr, _u32, _u32, _ptr, _ptr, _ptr]),
     "rn_mesh_tet_case": (_int, [_u32, _P(C.c_int32), _P(C.c_int32)]),
+    "rn_jpeg_blocks": (_sz, [_u32, _u32, _u32]),
+    "rn_jpeg_stream_capacity": (_sz, [_u32, _u32, _u32]),
+    "rn_jpeg_workspace": (_sz, [_u32, _u32, _u32, _u32]),
+    "rn_jpeg_coefficients": (_int, [_ptr, _u32, _u32, _u32, _u32, _u32, _ptr, _ptr]),
+    "rn_jpeg_entropy": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _sz, _ptr, _ptr]),
     # ---- include/radnerf_train.h
     "rn_train_head_image_floats": (_sz, []),
     "rn_train_head_workspace_floats": (_sz, [_u32]),

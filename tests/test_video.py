@@ -1,0 +1,362 @@
+"""Video write-out without a GPU (rad-nerf_amd/radnerf/video.py, csrc/rn_jpeg.hip, csrc/rn_jpeg_dev.h):
+  * the float64 restatement of tests/jpegref64.py against libjpeg (PIL): its files decode, its quality is PIL's own, its decoder
+    agrees with PIL's, and the test frames reach every branch of the coder;
+  * csrc/rn_jpeg_dev.h built into a stand-alone host program against that restatement: coefficients under the tie rule, scan bytes
+    byte for byte;
+  * the headers video.py writes, AviWriter through the RIFF reader, the argument checks of the entry points and of the command line."""
+import ctypes as C
+import io
+import os
+import shutil
+import struct
+import subprocess
+import wave
+
+import numpy as np
+import pytest
+
+import jpegref64 as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "rad-nerf_amd", "csrc")
+RN_ERR_INVALID_ARG = -1
+
+SIZES = [(48, 64), (17, 19), (90, 90), (40, 24)]
+SUBS = ["420", "444"]
+QUALITIES = [50, 75, 90, 100]
+CASES = [(hw, sub, q) for hw in SIZES for sub in SUBS for q in QUALITIES]
+
+
+@pytest.fixture(scope="module")
+def frames():
+    return {hw: R.scene(*hw, 1) for hw in SIZES}
+
+
+@pytest.fixture(scope="module")
+def encoded(frames):
+    """Every case through the float64 encoder, once: {case: file bytes} and the symbol counts over all of them."""
+    stats = dict(zrl=0, eob=0, c63=0, dc11=0, ac10=0, stuffed=0, blocks=0)
+    files = {(hw, sub, q): R.encode(frames[hw], q, sub, stats) for hw, sub, q in CASES}
+    return files, stats
+
+
+def _pil_open(data, mode=None):
+    from PIL import Image
+    im = Image.open(io.BytesIO(data))
+    if mode:
+        im.draft(mode, im.size)
+    im.load()
+    return im
+
+
+def _pil_encode(frame, quality, sub):
+    from PIL import Image
+    buf = io.BytesIO()
+    Image.fromarray(frame).save(buf, "JPEG", quality=quality, subsampling={"420": 2, "444": 0}[sub], optimize=False)
+    return buf.getvalue()
+
+
+# ------------------------------------------------------------------------------------------- what pins the reference
+@pytest.mark.parametrize("hw,sub,q", CASES)
+def test_reference_files_decode_with_libjpeg_at_its_own_quality(frames, encoded, hw, sub, q):
+    """PIL decodes the restatement's file; its PSNR against the source is at least that of PIL's own encoder (same quality,
+    subsampling, optimize=False: the same tables) minus 0.2 dB."""
+    frame, data = frames[hw], encoded[0][(hw, sub, q)]
+    im = _pil_open(data)
+    assert im.size == (hw[1], hw[0]) and im.mode == "RGB"
+    ours = R.psnr(np.asarray(im), frame)
+    pils = R.psnr(np.asarray(_pil_open(_pil_encode(frame, q, sub))), frame)
+    print(f"{hw} {sub} q{q}: {len(data)} bytes, PSNR {ours:.3f} dB, PIL's encoder {pils:.3f} dB")
+    assert ours >= pils - 0.2
+
+
+@pytest.mark.parametrize("hw,sub,q", CASES)
+def test_reference_decoder_agrees_with_libjpeg(encoded, hw, sub, q):
+    """+-2 levels per channel at 4:4:4, luma alone at 4:2:0 (the upsampling differs).  The channels are the ones the scan carries --
+    Y, Cb, Cr as libjpeg hands them over before its colour matrix: that matrix multiplies a difference of one level in Cr by 1.402
+    and adds luma's, so that two decoders one level apart per plane are up to three apart in R (printed; not asserted)."""
+    data = encoded[0][(hw, sub, q)]
+    im = _pil_open(data, "YCbCr")
+    assert im.mode == "YCbCr"
+    pil = np.asarray(im).astype(np.int64)
+    (yy, cb, cr), (H, W) = R.decode_planes(data)
+    own = np.stack([np.clip(np.rint(p), 0, 255)[:H, :W] for p in (yy, cb, cr)], -1).astype(np.int64)
+    diff = np.abs(own - pil).reshape(-1, 3).max(0)
+    rgb = np.abs(R.decode(data).astype(np.int64) - np.asarray(_pil_open(data)).astype(np.int64)).max()
+    print(f"{hw} {sub} q{q}: max |dY| {diff[0]} |dCb| {diff[1]} |dCr| {diff[2]}; after both colour matrices |dRGB| {rgb}")
+    assert diff[0] <= 2
+    if sub == "444":
+        assert diff.max() <= 2
+
+
+def test_the_cases_reach_every_branch_of_the_coder(encoded):
+    _, st = encoded
+    print(st)
+    for what in ("zrl", "eob", "c63", "dc11", "ac10", "stuffed"):
+        assert st[what] > 0, what
+
+
+def test_reference_round_trips_its_own_coefficients(frames):
+    for hw, sub, q in [((17, 19), "420", 100), ((40, 24), "444", 50)]:
+        want = R.coefficients(frames[hw], q, sub)
+        _, got, _, _ = R.decode_coefficients(R.encode(frames[hw], q, sub))
+        assert np.array_equal(got, want)
+
+
+def test_reference_flags_few_coefficients(frames):
+    """The tie rule's cap is a condition on the inputs: the reference alone flags at most 0.72 % at the 4e-3 margin (seeds 1-3), so
+    half of the 2 % cap is still a signal that the inputs changed."""
+    worst = max(R.flagged(R.quotients(R.scene(*hw, seed), q, sub)[0]).mean() for hw in SIZES for sub in SUBS for q in QUALITIES
+                for seed in (1, 2, 3))
+    print(f"largest flagged share {worst:.4f}")
+    assert worst <= 0.01
+
+
+# --------------------------------------------------------------------------------------- the dev header on the host
+# argv: H W subsampling quality frame.bin coefficients.bin scan.bin
+PROGRAM = r"""
+#include <stdio.h>
+#include <stdlib.h>
+#include <vector>
+#include "rn_jpeg_dev.h"
+using namespace rn::jpeg;
+int main(int argc, char **argv) {
+    if (argc != 8) return 2;
+    const uint32_t H = atoi(argv[1]), W = atoi(argv[2]), sub = atoi(argv[3]), quality = atoi(argv[4]);
+    if (!subsampling_ok(sub)) return 2;
+    std::vector<uint8_t> frame((size_t)H * W * 3);
+    FILE *f = fopen(argv[5], "rb");
+    if (!f || fread(frame.data(), 1, frame.size(), f) != frame.size()) return 3;
+    fclose(f);
+    const uint32_t mw = mcus_across(W, sub), mh = mcus_across(H, sub), per = blocks_per_mcu(sub), blocks = mw * mh * per;
+    std::vector<int16_t> coef((size_t)blocks * 64);
+    for (uint32_t b = 0; b < blocks; b++) {
+        const uint32_t mcu = b / per, k = b % per, table = block_component(k, sub) ? 1u : 0u;
+        float tile[64], rows[64];
+        for (uint32_t i = 0; i < 64; i++) tile[i] = block_sample(frame.data(), H, W, sub, mcu % mw, mcu / mw, k, i & 7u, i >> 3);
+        for (uint32_t i = 0; i < 64; i++) rows[i] = dct8(&tile[(i >> 3) * 8u], 1u, i & 7u);
+        for (uint32_t i = 0; i < 64; i++) {
+            if (zigzag_natural(zigzag_position(i)) != i) return 4;
+            coef[(size_t)b * 64 + zigzag_position(i)] = quantise(dct8(&rows[i & 7u], 8u, i >> 3), quant_step(table, i, quality));
+        }
+    }
+    f = fopen(argv[6], "wb");
+    fwrite(coef.data(), 2, coef.size(), f);
+    fclose(f);
+    // the scan: every position's bits as the kernels take them (position_bits over the non-zero mask), packed serially
+    const HuffCodes h = make_huff_codes();
+    std::vector<uint8_t> out;
+    uint64_t acc = 0;
+    uint32_t n = 0;
+    auto put = [&](uint64_t bits, uint32_t len) {
+        for (uint32_t i = len; i > 0; i--) {
+            acc = (acc << 1) | ((bits >> (i - 1)) & 1u);
+            if (++n == 8) {
+                out.push_back((uint8_t)acc);
+                if ((uint8_t)acc == 0xff) out.push_back(0);
+                acc = 0;
+                n = 0;
+            }
+        }
+    };
+    for (uint32_t b = 0; b < blocks; b++) {
+        const int16_t *c = &coef[(size_t)b * 64];
+        uint64_t nonzero = 0;
+        uint32_t total = 0;
+        for (uint32_t z = 0; z < 64; z++) nonzero |= (uint64_t)(c[z] != 0) << z;
+        const int32_t prev = previous_block(b, sub);
+        const int32_t pred = prev >= 0 ? coef[(size_t)prev * 64] : 0;
+        for (uint32_t z = 0; z < 64; z++) {
+            const Bits s = position_bits(h, block_component(b % per, sub) ? 1u : 0u, z, c[z], z == 0 ? pred : 0, nonzero);
+            if (s.len > 59) return 5;
+            put(s.bits, s.len);
+            total += s.len;
+        }
+        if (total > kMaxBlockBits) return 6;
+    }
+    if (n) put((1u << (8 - n)) - 1u, 8 - n);
+    f = fopen(argv[7], "wb");
+    fwrite(out.data(), 1, out.size(), f);
+    fclose(f);
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def host_program(tmp_path_factory):
+    """csrc/rn_jpeg_dev.h compiled for the host (RN_JPEG_CXXFLAGS adds flags, e.g. a sanitizer's) around the serial loops above."""
+    d = tmp_path_factory.mktemp("jpeg_host")
+    cxx = shutil.which("g++") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    src, exe = d / "jpeg.cpp", d / "jpeg"
+    src.write_text(PROGRAM)
+    flags = os.environ.get("RN_JPEG_CXXFLAGS", "").split()
+    subprocess.run([cxx, "-O1", "-std=c++17", "-ffp-contract=off", "-Wall", "-I", CSRC] + flags + ["-o", str(exe), str(src)], check=True)
+
+    def run(frame, quality, sub):
+        frame.tofile(d / "frame.bin")
+        r = subprocess.run([str(exe), str(frame.shape[0]), str(frame.shape[1]), sub, str(quality), str(d / "frame.bin"), str(d / "c.bin"),
+                            str(d / "s.bin")], capture_output=True, text=True)
+        assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
+        return np.fromfile(d / "c.bin", np.int16).reshape(-1, 64), (d / "s.bin").read_bytes()
+    return run
+
+
+@pytest.mark.parametrize("hw,sub,q", CASES)
+def test_dev_header_against_the_reference(host_program, frames, hw, sub, q):
+    """Coefficients: equal to the float64 reference's except where its quotient lies within 4e-3 of a half-integer (fp32 carries about
+    1e-4 absolute on a DC term of 1024 through colour, 64 DCT terms and the division at quality 100; 4e-3 leaves an order of
+    magnitude); flagged ones within 1 and at most 2 % of the case.  Scan: the reference's entropy coder on the program's OWN
+    coefficients gives the same bytes."""
+    coefs, scan = host_program(frames[hw], q, sub)
+    flags = R.compare_coefficients(coefs, frames[hw], q, sub)
+    print(f"{hw} {sub} q{q}: {int(flags.sum())} of {flags.size} flagged, {int((coefs != R.coefficients(frames[hw], q, sub)).sum())} differ")
+    assert scan == R.entropy(coefs, sub)
+
+
+# ------------------------------------------------------------------------------------------------------ video.py, host side
+def test_headers_and_tables_are_the_references(hiplib):
+    from radnerf import video
+    for q in (1, 37, 50, 90, 100):
+        for a, b in zip(video.quant_tables(q), R.quant_tables(q)):
+            assert np.array_equal(a, b)
+    for sub in SUBS:
+        assert video.jfif_header(17, 19, 75, sub) == R.headers(17, 19, 75, sub)
+    with pytest.raises(ValueError):
+        video.quant_tables(0)
+    with pytest.raises(ValueError):
+        video.jfif_header(8, 8, 50, "422")
+
+
+def _wav(path, rate, samples, channels=1):
+    pcm = (np.arange(samples * channels) * 37 % 65536 - 32768).astype("<i2").tobytes()
+    with wave.open(str(path), "wb") as w:
+        w.setnchannels(channels)
+        w.setsampwidth(2)
+        w.setframerate(rate)
+        w.writeframes(pcm)
+    return pcm
+
+
+@pytest.mark.parametrize("fps,audio", [(25, False), (25, True), (30, True)])
+def test_avi_writer_through_the_riff_reader(hiplib, tmp_path, frames, fps, audio):
+    """F = 3 frames, without and with a 16 kHz mono s16 track (16000 / 30 is not whole): every size, the index, the counts, the
+    padding, the frames and the samples come back."""
+    from radnerf import video
+    H, W = 17, 19
+    jpegs = [R.encode(R.scene(H, W, s), 75, "444") for s in (1, 2, 3)]
+    pcm = _wav(tmp_path / "a.wav", 16000, 16000 * 3 // fps + 7) if audio else None
+    path = tmp_path / "clip.avi"
+    with video.AviWriter(path, H, W, fps, audio=str(tmp_path / "a.wav") if audio else None) as avi:
+        for j in jpegs:
+            avi.add_frame(j)
+    data = path.read_bytes()
+    avi = R.read_avi(data)                                        # asserts the nesting, every chunk size and the even alignment
+    assert struct.unpack("<I", data[4:8])[0] == len(data) - 8 and len(data) % 2 == 0
+    h = avi["avih"]
+    assert (h["total_frames"], h["width"], h["height"], h["streams"]) == (3, W, H, 2 if audio else 1)
+    assert h["us_per_frame"] == round(1e6 / fps) and h["flags"] & 0x10
+    (vh, vf) = avi["streams"][0]
+    assert vh["type"] == b"vids" and vh["handler"] == b"MJPG" and vh["rate"] / vh["scale"] == fps and vh["length"] == 3
+    size, w, hgt, planes, bits, comp = struct.unpack("<IiiHH4s", vf[:20])
+    assert (size, w, hgt, planes, bits, comp) == (40, W, H, 1, 24, b"MJPG") and len(vf) == 40
+    video_chunks = [c for c in avi["movi"] if c[0] == b"00dc"]
+    audio_chunks = [c for c in avi["movi"] if c[0] == b"01wb"]
+    assert [c[2] for c in video_chunks] == jpegs
+    assert vh["suggested_buffer"] == max(len(j) for j in jpegs)
+    from PIL import Image
+    for (_, _, payload), seed in zip(video_chunks, (1, 2, 3)):
+        got = np.asarray(Image.open(io.BytesIO(payload)).convert("RGB"))
+        assert R.psnr(got, R.scene(H, W, seed)) > 25
+    # the index: one entry per chunk in file order, offsets from the 'movi' fourcc to the chunk header, key frames flagged
+    assert len(avi["idx1"]) == len(avi["movi"])
+    for (cc, flags, off, size), (cc2, off2, payload) in zip(avi["idx1"], avi["movi"]):
+        assert (cc, off, size) == (cc2, off2, len(payload)) and (flags == 0x10) == (cc == b"00dc")
+        assert data[avi["movi_at"] + off:avi["movi_at"] + off + 4] == cc
+    if audio:
+        (ah, af) = avi["streams"][1]
+        tag, ch, rate, bps, align, width = struct.unpack("<HHIIHH", af[:16])
+        assert (tag, ch, rate, bps, align, width) == (1, 1, 16000, 32000, 2, 16)
+        assert ah["type"] == b"auds" and ah["rate"] / ah["scale"] == 16000 and ah["sample_size"] == 2
+        assert b"".join(c[2] for c in audio_chunks) == pcm and ah["length"] == len(pcm) // 2
+        # interleaved one per frame, the running total rounded: frame i is followed by samples up to round((i + 1) rate / fps)
+        order = [c[0] for c in avi["movi"]]
+        assert order[:6] == [b"00dc", b"01wb"] * 3
+        ends = np.cumsum([len(c[2]) // 2 for c in audio_chunks])[:3]
+        assert list(ends) == [int(np.floor((i + 1) * 16000 / fps + 0.5)) for i in range(3)]
+    else:
+        assert not audio_chunks and len(avi["streams"]) == 1
+
+
+def test_avi_writer_pads_odd_chunks(hiplib, tmp_path):
+    from radnerf import video
+    with video.AviWriter(tmp_path / "odd.avi", 8, 8, 25) as avi:
+        avi.add_frame(b"\xff\xd8" + b"x" * 5 + b"\xff\xd9")        # 9 bytes
+        avi.add_frame(b"\xff\xd8" + b"y" * 6 + b"\xff\xd9")        # 10 bytes
+    got = R.read_avi((tmp_path / "odd.avi").read_bytes())
+    assert [len(c[2]) for c in got["movi"]] == [9, 10] and [e[2] for e in got["idx1"]] == [4, 4 + 8 + 10]
+
+
+def test_avi_writer_refuses_two_gib(hiplib, tmp_path, monkeypatch):
+    from radnerf import video
+    avi = video.AviWriter(tmp_path / "big.avi", 8, 8, 25)
+    avi.add_frame(b"\xff\xd8\xff\xd9")
+    monkeypatch.setattr(avi, "_position", lambda: (1 << 31) - 40)
+    with pytest.raises(ValueError, match="2 GiB"):
+        avi.add_frame(b"\xff\xd8\xff\xd9")
+    monkeypatch.undo()
+    avi.close()
+    assert R.read_avi((tmp_path / "big.avi").read_bytes())["avih"]["total_frames"] == 1      # what was written is a valid file
+
+
+# ---------------------------------------------------------------------------------------------------- argument checks
+def test_entry_points_refuse_bad_arguments(hiplib):
+    lib, err = hiplib._lib, hiplib.last_error
+    assert lib.rn_jpeg_blocks(17, 19, 420) == 2 * 2 * 6 and lib.rn_jpeg_blocks(17, 19, 444) == 3 * 3 * 3
+    assert lib.rn_jpeg_blocks(450, 450, 420) == 29 * 29 * 6
+    assert lib.rn_jpeg_stream_capacity(17, 19, 420) == 24 * 416            # 208 bytes hold the longest block, stuffing doubles it
+    assert lib.rn_jpeg_blocks(0, 8, 420) == 0 and lib.rn_jpeg_blocks(8, 8, 422) == 0 and lib.rn_jpeg_stream_capacity(8, 70000, 444) == 0
+    assert lib.rn_jpeg_workspace(0, 8, 8, 420) == 0 and lib.rn_jpeg_workspace(1, 8, 8, 411) == 0
+    # block offsets, the frame's bit count, one chunk's 0xFF count and total, 52 words per block
+    assert lib.rn_jpeg_workspace(2, 16, 16, 420) >= 2 * (6 * 4 + 4 + 4 + 4 + 6 * 208)
+    assert lib.rn_jpeg_workspace(1, 4096, 4096, 420) > 0 and lib.rn_jpeg_workspace(1, 8192, 8192, 420) == 0      # 2^31 bits
+    buf = (C.c_uint8 * 65536)()
+    p = C.cast(buf, C.c_void_p)
+    coef = lib.rn_jpeg_coefficients
+    assert coef(p, 0, 8, 8, 420, 90, p, None) == RN_ERR_INVALID_ARG and "subsampling" in err()
+    assert coef(p, 1, 8, 8, 422, 90, p, None) == RN_ERR_INVALID_ARG and "subsampling" in err()
+    assert coef(p, 1, 8, 8, 420, 0, p, None) == RN_ERR_INVALID_ARG and "quality" in err()
+    assert coef(p, 1, 8, 8, 420, 101, p, None) == RN_ERR_INVALID_ARG and "quality" in err()
+    assert coef(None, 1, 8, 8, 420, 90, p, None) == RN_ERR_INVALID_ARG and "null pointer" in err()
+    assert coef(p, 1, 8, 8, 420, 90, None, None) == RN_ERR_INVALID_ARG and "null pointer" in err()
+    ent = lib.rn_jpeg_entropy
+    assert ent(p, 1, 8, 0, 444, p, p, 1 << 20, p, None) == RN_ERR_INVALID_ARG and "subsampling" in err()
+    assert ent(p, 1, 8, 8, 1, p, p, 1 << 20, p, None) == RN_ERR_INVALID_ARG and "subsampling" in err()
+    assert ent(None, 1, 8, 8, 444, p, p, 1 << 20, p, None) == RN_ERR_INVALID_ARG and "null pointer" in err()
+    assert ent(p, 1, 8, 8, 444, None, p, 1 << 20, p, None) == RN_ERR_INVALID_ARG and "null pointer" in err()
+    assert ent(p, 1, 8, 8, 444, p, p, 1 << 20, None, None) == RN_ERR_INVALID_ARG and "null pointer" in err()
+    assert ent(p, 2, 8, 8, 444, p, p, 2 * 3 * 416 - 1, p, None) == RN_ERR_INVALID_ARG and "worst case" in err()
+    assert ent(p, 6000, 512, 512, 420, p, p, 1 << 40, p, None) == RN_ERR_INVALID_ARG and "2^31" in err()
+
+
+def test_command_line_video_flags(hiplib, tmp_path, capsys):
+    from radnerf import cli
+    opt = cli.parse(["data"])
+    assert opt.video is False and opt.audio_wav == "" and opt.video_quality == 90 and opt.video_subsampling == "420" and opt.video_fps == 25
+    _wav(tmp_path / "ok.wav", 16000, 100)
+    opt = cli.parse(["data", "--test", "--video", "--video_quality", "75", "--video_subsampling", "444", "--video_fps", "30",
+                     "--audio_wav", str(tmp_path / "ok.wav")])
+    assert opt.video and (opt.video_quality, opt.video_subsampling, opt.video_fps) == (75, "444", 30)
+    # IEEE-float samples (format tag 3) are a .wav that is not PCM; a missing file; a file that is no RIFF at all
+    fmt = struct.pack("<HHIIHH", 3, 1, 16000, 64000, 4, 32)
+    body = b"WAVE" + b"fmt " + struct.pack("<I", len(fmt)) + fmt + b"data" + struct.pack("<I", 16) + b"\0" * 16
+    (tmp_path / "float.wav").write_bytes(b"RIFF" + struct.pack("<I", len(body)) + body)
+    (tmp_path / "text.wav").write_text("not audio")
+    for bad in ("float.wav", "missing.wav", "text.wav"):
+        with pytest.raises(SystemExit) as e:
+            cli.parse(["data", "--video", "--audio_wav", str(tmp_path / bad)])
+        assert e.value.code == 2 and "--audio_wav" in capsys.readouterr().err
+    for bad in (["--video_quality", "0"], ["--video_subsampling", "422"], ["--video_fps", "0"]):
+        with pytest.raises(SystemExit) as e:
+            cli.parse(["data"] + bad)
+        assert e.value.code == 2
