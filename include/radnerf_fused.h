@@ -495,6 +495,51 @@ int rn_jpeg_coefficients(const uint8_t *frames, uint32_t F, uint32_t H, uint32_t
 int rn_jpeg_entropy(const int16_t *coefficients, uint32_t F, uint32_t H, uint32_t W, uint32_t subsampling, void *workspace,
                     uint8_t *streams, size_t capacity, uint32_t *sizes, rn_stream_t stream);
 
+/* ---- audio features from samples: the wav2vec2 CTC model of nerf/asr.py, file mode -------------------------------------
+ * The `Wav2Vec2ForCTC` variant with feat_extract_norm = "layer", conv_bias, do_stable_layer_norm, in eval mode without an
+ * attention mask, fp32 throughout, no float atomics and no split of K chosen from the batch: a window's logits do not depend on
+ * which other windows share the call, and two calls give the same bits.
+ *
+ *   input       per window of `samples` floats: (x - mean) / sqrt(var + 1e-7), population variance
+ *   encoder     n_conv layers: Conv1d(conv_dim[i-1] -> conv_dim[i], conv_kernel[i], conv_stride[i], no padding) + bias,
+ *               LayerNorm over the channels, exact (erf) GELU; layer 0 has one input channel
+ *   projection  LayerNorm over conv_dim[n_conv-1], Linear -> hidden
+ *   position    h += GELU(conv(h)): pos_taps taps (even), pos_groups groups, padding pos_taps / 2, last output step dropped;
+ *               the weight norm (over dims 0, 1 for each tap) is folded into the image by the pack
+ *   layers      h += out_proj(attention(LN(h))), queries scaled by 64^-1/2, softmax(Q K^T) V per head of 64 features;
+ *               h += W2 GELU(W1 LN(h))
+ *   output      LayerNorm, lm_head -> logits [B, T, vocab], T = steps after the last conv layer (at most 96)
+ *
+ * rn_asr_config_t: hidden = 64 * heads; conv_dim, intermediate and hidden / pos_groups multiples of 4.  Anything else is
+ * RN_ERR_INVALID_ARG naming the field, before any launch (the size functions: 0).
+ *
+ *   rn_asr_image_floats  floats of the packed weight image.
+ *   rn_asr_pack          tensors: host array of n_tensors DEVICE pointers, fp32, contiguous, in the layout of the model's state
+ *                        dict: per conv layer {conv.weight [Cout,Cin,k], conv.bias, layer_norm.weight, .bias}; projection
+ *                        {layer_norm.weight, .bias, projection.weight [H,C], .bias}; position {g [taps], v [H, H/groups, taps],
+ *                        bias}; encoder layer_norm {weight, bias}; per layer {layer_norm, q_proj, k_proj, v_proj, out_proj,
+ *                        final_layer_norm, intermediate_dense, output_dense} x {weight, bias}; lm_head {weight, bias}:
+ *                        4 n_conv + 11 + 16 layers pointers.
+ *   rn_asr_workspace     bytes of scratch for B windows of `samples` samples (16-byte aligned); 0: unsupported.
+ *   rn_asr_forward       windows [B, samples] -> logits [B, T, vocab].
+ *   rn_asr_features      the cut and the unfold of asr.py:331-338, 238-243 in one launch.  `logits`: logits_rows rows of C
+ *                        floats; segments: HOST array [n_segments <= 4][5] = {first row, windows, T, left, right}: `windows`
+ *                        windows of T rows one behind the other from `first row`, rows left .. right - 1 of each kept.  The M
+ *                        kept rows, in order, are unfolded (window 16, padding 8, stride 2) into features [F, C, 16],
+ *                        F = M / 2 + 1: features[f][c][j] = kept[2 f - 8 + j][c], 0 outside. */
+typedef struct {
+    uint32_t n_conv, conv_dim[8], conv_kernel[8], conv_stride[8];
+    uint32_t hidden, heads, intermediate, layers, pos_taps, pos_groups, vocab;
+    float layer_norm_eps;
+} rn_asr_config_t;
+size_t rn_asr_image_floats(const rn_asr_config_t *config);
+int rn_asr_pack(const rn_asr_config_t *config, const float *const *tensors, uint32_t n_tensors, float *image, rn_stream_t stream);
+size_t rn_asr_workspace(const rn_asr_config_t *config, uint32_t B, uint32_t samples);
+int rn_asr_forward(const rn_asr_config_t *config, const float *image, void *workspace, size_t workspace_bytes, const float *windows,
+                   uint32_t B, uint32_t samples, float *logits, rn_stream_t stream);
+int rn_asr_features(const float *logits, size_t logits_rows, uint32_t C, const uint32_t *segments, uint32_t n_segments,
+                    float *features, uint32_t F, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

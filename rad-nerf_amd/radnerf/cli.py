@@ -13,7 +13,9 @@ launch and Trainer.step, per frame ClipScene.render.  Flags keep the reference's
 exp_eye; fp16 only records: the arithmetic follows the RN_* switches (radnerf/switches.py is their only reader, nothing is set
 here).  `--preload` is accepted and ignored (the set is always device-resident uint8).  Not built here, and refused: --gui, --asr*
 (live audio), --emb, --train_camera from this entry point.  --video writes Motion-JPEG in AVI with PCM audio and nothing else:
-no MP4 / H.264, no compressed audio; the .npy stays what any other encoder reads.
+no MP4 / H.264, no compressed audio; the .npy stays what any other encoder reads.  --aud_wav FILE --asr_weights FILE drive the
+clip from a 16 kHz .wav: its wav2vec2 logits (radnerf/asr.py) go where --aud's would, and with --video the same file is laid
+under the frames unless --audio_wav names another.
 Continuing from a checkpoint restores model, optimizer, EMA, epoch and step count; it is NOT bit-identical to an uninterrupted
 run, because the occupancy refresh draws from Python's `random`.
 """
@@ -95,6 +97,12 @@ def _parser():
     p.add_argument("--video_subsampling", type=str, default="420", choices=("420", "444"))
     p.add_argument("--video_fps", type=float, default=25, help="frame rate of --video (not --fps, the reference's ASR rate)")
     p.add_argument("--audio_wav", type=str, default="", help="PCM .wav to lay under --video")
+    p.add_argument("--aud_wav", type=str, default="", help="16 kHz PCM .wav that drives the clip: its wav2vec2 logits replace --aud (radnerf/asr.py)")
+    p.add_argument("--asr_weights", type=str, default="", help="state dict of Wav2Vec2ForCTC for --aud_wav; nothing is fetched")
+    p.add_argument("--asr_config", type=str, default="", help="the model's config.json (default: the large shape)")
+    p.add_argument("-l", type=int, default=10, help="--aud_wav: chunks of left context per window")
+    p.add_argument("-m", type=int, default=50, help="--aud_wav: chunks a window contributes")
+    p.add_argument("-r", type=int, default=10, help="--aud_wav: chunks of right context per window")
     p.add_argument("--name", type=str, default="ngp")
     p.add_argument("--engine", type=str, default="fused", choices=("ops", "fused"))
     return p
@@ -137,6 +145,23 @@ def parse(argv=None):
             check_wav(opt.audio_wav)
         except ValueError as e:
             p.error(f"--audio_wav: {e}")
+    if opt.aud_wav:
+        if opt.aud:
+            p.error("--aud_wav and --aud both name the clip's audio features; give one")
+        if not opt.asr_weights:
+            p.error("--aud_wav needs --asr_weights FILE (the state dict of Wav2Vec2ForCTC): the model's weights are not fetched from anywhere")
+        for flag in ("aud_wav", "asr_weights", "asr_config"):
+            if getattr(opt, flag) and not os.path.isfile(getattr(opt, flag)):
+                p.error(f"--{flag}: {getattr(opt, flag)} is not a file")
+        if opt.l < 0 or opt.r < 0 or opt.m < 1:
+            p.error("-l and -r must not be negative, -m must be positive")
+        from radnerf.asr import check_wav as check_wav16k
+        try:
+            check_wav16k(opt.aud_wav)
+        except ValueError as e:
+            p.error(f"--aud_wav: {e}")
+    elif opt.asr_weights or opt.asr_config:
+        p.error("--asr_weights / --asr_config go with --aud_wav FILE")
     opt.test_train = bool(opt.test_train)
     return opt
 
@@ -273,8 +298,23 @@ def avi_path(out_dir, name):
 def _video_sink(opt, H, W, device, out_dir, name):
     from radnerf.video import AviWriter, JpegEncoder, VideoSink
     os.makedirs(out_dir, exist_ok=True)
-    writer = AviWriter(avi_path(out_dir, name), H, W, opt.video_fps, audio=opt.audio_wav or None)
+    writer = AviWriter(avi_path(out_dir, name), H, W, opt.video_fps, audio=opt.audio_wav or opt.aud_wav or None)
     return VideoSink(writer, JpegEncoder(H, W, opt.video_quality, opt.video_subsampling), batch=8, device=device)
+
+
+def wav_features(opt, model, device, log=print):
+    """--aud_wav: the wav2vec2 logits of the file as [F,C,16] on the device, left at opt.aud_features where datafiles' loaders take
+    the clip's audio from (in opt.aud's place).  The logit width must be the audio net's input width."""
+    from radnerf.asr import Wav2Vec2CTC, read_wav
+    asr = Wav2Vec2CTC.from_files(opt.asr_weights, opt.asr_config or None)
+    want = int(model.audio_in_dim)
+    if asr.vocab_size != want:
+        raise ValueError(f"--aud_wav: the model of --asr_weights gives logits of width {asr.vocab_size}, the audio net of this checkpoint "
+                         f"takes {want} (--asr_model picks it)")
+    feats = asr.to(device).features_from_samples(read_wav(opt.aud_wav), opt.l, opt.m, opt.r, layout="FC16")
+    log(f"[INFO] {opt.aud_wav}: {feats.shape[0]} audio frames of width {feats.shape[1]}")
+    opt.aud_features = feats
+    return feats
 
 
 def _perceptual(opt, device):
@@ -327,7 +367,9 @@ def main(argv=None, log=print, decode=None):
         log(f"[INFO] loaded {path}" + (f", missing {missing}" if missing else "") + (f", unexpected {unexpected}" if unexpected else ""))
         epoch = int(getattr(model, "checkpoint_meta", {}).get("epoch", 0))
         done.update(epoch=epoch, global_step=int(getattr(model, "checkpoint_meta", {}).get("global_step", 0)))
-        if not opt.pose and opt.aud == "" and rank == 0:           # has_gt: the set's own frames and audio
+        if opt.aud_wav:
+            wav_features(opt, model, device, log)
+        if not opt.pose and opt.aud == "" and not opt.aud_wav and rank == 0:           # has_gt: the set's own frames and audio
             split = _val_set(opt, device, "train" if opt.test_train else "test", decode)
             split.install(model)
             done["evals"].append((epoch, _evaluate(Trainer(model, opt, iters=opt.iters), split, log, "test")))
@@ -392,9 +434,11 @@ def main(argv=None, log=print, decode=None):
     # main.py:237-247: the test split with the averaged weights -- metrics when it carries its own frames, then the clip
     del ds
     torch.cuda.empty_cache()
-    if opt.aud == "":
+    if opt.aud == "" and not opt.aud_wav:
         val.install(model)
         done["evals"].append((epoch, _evaluate(trainer, val, log, "test")))
+    if opt.aud_wav:
+        wav_features(opt, model, device, log)
     with trainer.eval_scope():
         done["video"], done["n_frames"] = render_clip(opt, model, device, results_dir, f"{opt.name}_ep{epoch:04d}", log, decode)
     done["avi"] = avi_path(results_dir, f"{opt.name}_ep{epoch:04d}") if opt.video and done["video"] else None

@@ -5,7 +5,8 @@ Reference: NeRFDataset.__init__ (nerf/provider.py:311-612) -> load_split, NeRFDa
 
     <root>/transforms_train.json  transforms_val.json      focal_len | fl_x, fl_y | camera_angle_x, _y; cx, cy; h, w (optional);
                                                            frames: [{img_id, aud_id, transform_matrix [4][4]}, ...]
-    <root>/aud_eo.npy | aud_ds.npy | aud.npy                [N,16,K] logits (chosen by opt.asr_model; opt.aud overrides)
+    <root>/aud_eo.npy | aud_ds.npy | aud.npy                [N,16,K] logits (chosen by opt.asr_model; opt.aud overrides, and so
+                                                           does opt.aud_features: [N,K,16] values already in memory, --aud_wav)
     <root>/bc.jpg                                           the background (opt.bg_img = '')
     <root>/gt_imgs/<img_id>.jpg                             the frame, RGB
     <root>/torso_imgs/<img_id>.png                          the torso layer, RGBA
@@ -126,6 +127,17 @@ def _audio_features(path, opt):
                                   f"{'is' if _o(opt, 'emb', False) else 'would be'} needed: the --emb route (audio class + embedding) is "
                                   "not built here, the device routes take [N,16,K] logits only")
     return np.ascontiguousarray(aud.astype(np.float32).transpose(0, 2, 1))
+
+
+def _given_features(opt):
+    """opt.aud_features: the clip's audio as [N,K,16] float32 values already in memory (an array, or a tensor on any device) --
+    what radnerf.cli leaves there for --aud_wav; None without one.  It stands where opt.aud's file would."""
+    feats = _o(opt, "aud_features", None)
+    if feats is None:
+        return None
+    if feats.ndim != 3 or feats.shape[2] != 16:
+        raise ValueError(f"datafiles: opt.aud_features must be [N,K,16], got {tuple(feats.shape)}")
+    return feats
 
 
 def _default_audio_file(root, opt):
@@ -268,8 +280,9 @@ def load_split(root, opt, split="train", downscale=1, decode=None):
     elif split == "val":
         frames = frames[:100]
 
-    own_audio = _o(opt, "aud", "") == ""
-    aud_features = _audio_features(_default_audio_file(root, opt) if own_audio else opt.aud, opt)
+    given = _given_features(opt)
+    own_audio = _o(opt, "aud", "") == "" and given is None
+    aud_features = given if given is not None else _audio_features(_default_audio_file(root, opt) if own_audio else opt.aud, opt)
 
     kept = []
     for f in frames:
@@ -325,7 +338,9 @@ def load_clip(opt, decode=None, downscale=1):
     H, W = int(transform["cy"]) * 2 // downscale, int(transform["cx"]) * 2 // downscale
     frames = _sliced(transform["frames"], opt)
     root = _o(opt, "path", "") or None
-    if _o(opt, "aud", "") != "":
+    if _given_features(opt) is not None:
+        auds = _given_features(opt)
+    elif _o(opt, "aud", "") != "":
         auds = _audio_features(opt.aud, opt)
     else:
         if any("aud_id" not in f for f in frames):

@@ -8,6 +8,7 @@ import os
 # (name, default, accepted values, what the switch selects)
 TABLE = (
     ("RN_ADAM", "hip", ("hip", "torch"), "optimizer of `make_optimizer` on the GPU: `HipAdam` (one update kernel for all tensors) or torch's fused Adam"),
+    ("RN_ASR", "torch", ("torch", "hip"), "`Wav2Vec2CTC` (`radnerf/asr.py`) on the GPU in fp32: the same arithmetic in plain torch, or the wav2vec2 kernels (`rn_asr_*`, opt-in: bit-reproducible and independent of the batching, but 56 ms against 44 ms for a minute of audio at the real size, DESIGN.md §3)"),
     ("RN_AUDIO_TRAIN", "hip", ("hip", "torch"), "`encode_audio` on the GPU: the audio kernels (`radnerf/audio.py`) or the `nn.Module` path"),
     ("RN_LIVE_LIST", "1", ("1", "0"), "fused inference engine: hand the loop the list of live sample slots (`0`: every launch scans all slots)"),
     ("RN_MLP_TRAIN", "hip", ("hip", "torch"), "the per-operator MLP stacks under autograd: `rn_mlp64_*` (`radnerf/mlp_train.py`) or `nn.Linear`"),

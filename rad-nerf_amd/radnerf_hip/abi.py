@@ -74,6 +74,13 @@ class AdamTensorT(C.Structure):
     _fields_ = [("param", _ptr), ("grad", _ptr), ("exp_avg", _ptr), ("exp_avg_sq", _ptr), ("numel", _u32), ("lr", _f32)]
 
 
+class AsrConfigT(C.Structure):
+    c_name = "rn_asr_config_t"
+    _fields_ = [("n_conv", _u32), ("conv_dim", _u32 * 8), ("conv_kernel", _u32 * 8), ("conv_stride", _u32 * 8), ("hidden", _u32),
+                ("heads", _u32), ("intermediate", _u32), ("layers", _u32), ("pos_taps", _u32), ("pos_groups", _u32), ("vocab", _u32),
+                ("layer_norm_eps", _f32)]
+
+
 # ==================================================================================================== radnerf_train.h
 class HeadGradsT(C.Structure):
     c_name = "rn_train_head_grads_t"
@@ -230,6 +237,11 @@ FUNCTIONS = {
     "rn_jpeg_workspace": (_sz, [_u32, _u32, _u32, _u32]),
     "rn_jpeg_coefficients": (_int, [_ptr, _u32, _u32, _u32, _u32, _u32, _ptr, _ptr]),
     "rn_jpeg_entropy": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _sz, _ptr, _ptr]),
+    "rn_asr_image_floats": (_sz, [_P(AsrConfigT)]),
+    "rn_asr_pack": (_int, [_P(AsrConfigT), _ptr, _u32, _ptr, _ptr]),
+    "rn_asr_workspace": (_sz, [_P(AsrConfigT), _u32, _u32]),
+    "rn_asr_forward": (_int, [_P(AsrConfigT), _ptr, _ptr, _sz, _ptr, _u32, _u32, _ptr, _ptr]),
+    "rn_asr_features": (_int, [_ptr, _sz, _u32, _P(_u32), _u32, _ptr, _u32, _ptr]),
     # ---- include/radnerf_train.h
     "rn_train_head_image_floats": (_sz, []),
     "rn_train_head_workspace_floats": (_sz, [_u32]),
