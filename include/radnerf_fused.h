@@ -90,6 +90,26 @@ int rn_nerf_fused_forward(const float *xyzs, const float *dirs, const float *del
                           const float *packed, const float *bias, float bound, float *sigmas, float *rgbs,
                           float *ambient, int mlp_dtype, rn_stream_t stream);
 
+/* ---- dense image of a hash grid's coarser levels (inference) ------------------------------------------------------
+ * A hashed level spreads the corners of neighbouring cells over its whole slice of the table.  While the table does not change
+ * the level can be stored once as its whole lattice instead,
+ *     image[image_offsets[l] + x + y (R+1) + z (R+1)^2] = table[offsets[l] + hash(x, y, z) % size_l],      x, y, z in 0..R,
+ * and a descriptor {embeddings = image, offsets = image_offsets, everything else as in `grid`} then takes every kernel that
+ * reads an rn_grid_t down the dense path it has for the coarse levels: a level is dense when its slice holds (R+1)^3 rows,
+ * which is decided from the offsets alone.  Same rows, blended in the same order: the features are bit-identical.
+ *
+ * rn_grid_dense_plan (host only, launches nothing): which levels to store that way.  Hashed levels are taken in ascending
+ * order while the whole image stays within budget_bytes, below 4 GiB (the kernels form 32-bit byte offsets) and below 2^31
+ * rows; a taken level gets (R+1)^3 rows rounded up to a multiple of 8, every other level keeps its size and its rows.
+ * Writes image_offsets [L+1] (host, in rows), *levels (bit l: level l is taken) and *image_bytes.  Returns 1, or 0 = "no
+ * image" (tiled grid, D != 3, or no hashed level fits: keep the table; nothing is written), or a negative error.
+ * rn_grid_dense_build: fills `image` (image_bytes from the plan, 16-byte aligned) from the table, one launch per level;
+ * the rows of a taken level past (R+1)^3 are zero.  offsets_host / image_offsets are host arrays. */
+int rn_grid_dense_plan(const rn_grid_t *grid, const int32_t *offsets_host, size_t budget_bytes, int32_t *image_offsets,
+                       uint32_t *levels, size_t *image_bytes);
+int rn_grid_dense_build(const rn_grid_t *grid, const int32_t *offsets_host, const int32_t *image_offsets, uint32_t levels,
+                        void *image, size_t image_bytes, rn_stream_t stream);
+
 /* ---- device-side inference loop ------------------------------------------------------------------ */
 #define RN_HEAD_STATE_INTS 64 /* int32 words of loop state the caller provides (zeroed once before first use) */
 

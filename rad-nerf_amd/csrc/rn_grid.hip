@@ -894,11 +894,128 @@ static int dispatch_tv_c(uint32_t C, const float *inputs, const float *table, fl
     return RN_ERR_INVALID_ARG;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Dense image of a hash grid's coarser levels (radnerf_fused.h): one launch per level, one image row per lane, coalesced
+// writes; the level's slice of the table (4 MB at T = 2^19) stays in L2 for the length of its launch.
+// A taken level's image rows are its whole lattice: row i is the point (x, y, z) = (i % (R+1), i / (R+1) % (R+1), i / (R+1)^2)
+// and holds the table row grid_row() names for that point on the hashed level -- the row every encoder reads for that corner,
+// by the same integer arithmetic for power-of-two and generic level sizes.  Rows past (R+1)^3 (the rounding to 8) are zero.
+// Coordinates 0..R are all a lookup can ask for: lattice_pos() gives pg = floor(x * scale + 0.5) <= floor(scale + 0.5) <=
+// ceil(scale) = R - 1 for x in [0, 1], so the far corner is pg + 1 <= R -- the bound the dense coarse levels of every table
+// rely on already (the kernels skip samples outside [0, 1]).  Any other level: its rows, copied as they are.
+template <typename ROW>
+__global__ void __launch_bounds__(256) k_grid_dense_level(const ROW *__restrict__ src, ROW *__restrict__ dst, uint32_t n_rows,
+                                                          uint32_t src_size, uint32_t resolution, uint32_t taken) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_rows) return;
+    ROW v{};
+    if (!taken) {
+        v = src[i];
+    } else {
+        const uint32_t r1 = resolution + 1, plane = r1 * r1;
+        const uint32_t z = i / plane, rem = i - z * plane, y = rem / r1;
+        if (z < r1) {
+            const uint32_t pg[3] = {rem - y * r1, y, z};
+            v = src[grid_row<3>(0u, false, src_size, resolution, pg)];
+        }
+    }
+    dst[i] = v;
+}
+
+struct DensePlan {
+    uint32_t rows[kMaxLevels];   // image rows per level
+    uint32_t levels;             // bit l: level l is stored as its lattice
+    uint64_t total_rows;
+};
+
+static uint64_t dense_level_rows(uint32_t resolution) {
+    const uint64_t r1 = (uint64_t)resolution + 1u;
+    return (r1 * r1 * r1 + 7u) & ~(uint64_t)7u;
+}
+
+// false: no image (the caller keeps the table)
+static bool dense_plan(const rn_grid_t *g, const int32_t *oh, size_t budget_bytes, DensePlan &dp) {
+    if (g->gridtype != 0 || g->D != 3) return false;
+    const LevelConsts lc = make_level_consts(g->L, g->S, g->H);
+    const uint64_t row_bytes = g->dtype == RN_F16 ? 4u : 8u;
+    dp.levels = 0;
+    dp.total_rows = 0;
+    for (uint32_t l = 0; l < g->L; l++) dp.total_rows += (dp.rows[l] = (uint32_t)(oh[l + 1] - oh[l]));
+    for (uint32_t l = 0; l < g->L; l++) {
+        if (!level_is_hashed(3, lc.resolution[l], dp.rows[l], 0u)) continue;
+        const uint64_t full = dense_level_rows(lc.resolution[l]), rows = dp.total_rows - dp.rows[l] + full;
+        if (rows * row_bytes > budget_bytes || rows * row_bytes >= (1ull << 32) || rows >= (1ull << 31)) break;   // levels only grow
+        dp.total_rows = rows;
+        dp.rows[l] = (uint32_t)full;
+        dp.levels |= 1u << l;
+    }
+    return dp.levels != 0;
+}
+
+static int check_dense_grid(const rn_grid_t *g, const int32_t *oh, const char *who) {
+    RN_REQUIRE(g && oh, "%s: null pointer", who);
+    RN_REQUIRE(g->L >= 1 && g->L <= kMaxLevels, "%s: L=%u out of range (1..%u)", who, g->L, kMaxLevels);
+    RN_REQUIRE(g->dtype == RN_F32 || g->dtype == RN_F16, "%s: dtype must be RN_F32 or RN_F16", who);
+    for (uint32_t l = 0; l < g->L; l++) RN_REQUIRE(oh[l + 1] > oh[l] && oh[l] >= 0, "%s: offsets must ascend from >= 0", who);
+    return RN_OK;
+}
+
 }  // namespace rn
 
 using namespace rn;
 
 extern "C" {
+
+int rn_grid_dense_plan(const rn_grid_t *grid, const int32_t *offsets_host, size_t budget_bytes, int32_t *image_offsets,
+                       uint32_t *levels, size_t *image_bytes) {
+    const int rc = check_dense_grid(grid, offsets_host, "grid_dense_plan");
+    if (rc != RN_OK) return rc;
+    RN_REQUIRE(image_offsets && levels && image_bytes, "grid_dense_plan: null pointer");
+    DensePlan dp;
+    if (!dense_plan(grid, offsets_host, budget_bytes, dp)) return 0;
+    image_offsets[0] = 0;
+    for (uint32_t l = 0; l < grid->L; l++) image_offsets[l + 1] = image_offsets[l] + (int32_t)dp.rows[l];
+    *levels = dp.levels;
+    *image_bytes = (size_t)dp.total_rows * (grid->dtype == RN_F16 ? 4u : 8u);
+    return 1;
+}
+
+int rn_grid_dense_build(const rn_grid_t *grid, const int32_t *offsets_host, const int32_t *image_offsets, uint32_t levels,
+                        void *image, size_t image_bytes, rn_stream_t stream) {
+    const int rc = check_dense_grid(grid, offsets_host, "grid_dense_build");
+    if (rc != RN_OK) return rc;
+    RN_REQUIRE(grid->embeddings && image_offsets && image, "grid_dense_build: null pointer");
+    RN_REQUIRE(grid->gridtype == 0 && grid->D == 3, "grid_dense_build: a hash grid with D = 3");
+    RN_REQUIRE(((uintptr_t)grid->embeddings & 7u) == 0 && ((uintptr_t)image & 15u) == 0, "grid_dense_build: unaligned table or image");
+    const LevelConsts lc = make_level_consts(grid->L, grid->S, grid->H);
+    const size_t row_bytes = grid->dtype == RN_F16 ? 4u : 8u;
+    // every level's image slice is what the plan gives it: nothing is written past a slice, nothing of the image is left out
+    uint64_t at = 0;
+    for (uint32_t l = 0; l < grid->L; l++) {
+        const uint32_t size = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
+        const bool taken = (levels >> l) & 1u;
+        RN_REQUIRE(!taken || level_is_hashed(3, lc.resolution[l], size, 0u), "grid_dense_build: level %u is not hashed", l);
+        RN_REQUIRE((uint64_t)image_offsets[l] == at, "grid_dense_build: image_offsets[%u] does not follow from the levels", l);
+        at += taken ? dense_level_rows(lc.resolution[l]) : size;
+        RN_REQUIRE(at < (1ull << 31) && at * row_bytes < (1ull << 32), "grid_dense_build: image of 4 GiB or 2^31 rows and more");
+    }
+    RN_REQUIRE((uint64_t)image_offsets[grid->L] == at && at * row_bytes == image_bytes,
+               "grid_dense_build: image_bytes does not follow from the levels");
+    for (uint32_t l = 0; l < grid->L; l++) {
+        const uint32_t size = (uint32_t)(offsets_host[l + 1] - offsets_host[l]);
+        const uint32_t n_rows = (uint32_t)(image_offsets[l + 1] - image_offsets[l]), taken = (levels >> l) & 1u;
+        const char *src = static_cast<const char *>(grid->embeddings) + (size_t)offsets_host[l] * row_bytes;
+        char *dst = static_cast<char *>(image) + (size_t)image_offsets[l] * row_bytes;
+        const dim3 blocks(div_up(n_rows, 256));
+        if (grid->dtype == RN_F16)
+            hipLaunchKernelGGL((k_grid_dense_level<uint32_t>), blocks, dim3(256), 0, as_stream(stream), reinterpret_cast<const uint32_t *>(src),
+                               reinterpret_cast<uint32_t *>(dst), n_rows, size, lc.resolution[l], taken);
+        else
+            hipLaunchKernelGGL((k_grid_dense_level<uint2>), blocks, dim3(256), 0, as_stream(stream), reinterpret_cast<const uint2 *>(src),
+                               reinterpret_cast<uint2 *>(dst), n_rows, size, lc.resolution[l], taken);
+    }
+    return check_launch("grid_dense_build");
+}
 
 int rn_grid_encode_forward(const float *inputs, const void *embeddings, const int32_t *offsets, void *outputs,
                            uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, void *dy_dx,

@@ -41,6 +41,14 @@ def _grid_desc(enc, table):
     return g
 
 
+def _image_desc(g, image, offsets):
+    """The descriptor `g` over a dense image of its table (rn_grid_dense_build): same lattice, the image's rows and offsets."""
+    d = GridT()
+    C.pointer(d)[0] = g
+    d.embeddings, d.offsets = image.data_ptr(), offsets.data_ptr()
+    return d
+
+
 def head_weights(model):
     """The eight nn.Linear weights of the per-sample MLPs, in the order of rn_nerf_weights_t."""
     return [l.weight for l in model.ambient_net.net] + [l.weight for l in model.sigma_net.net] + [l.weight for l in model.color_net.net]
@@ -102,10 +110,23 @@ class TorsoPlan:
         self.waited = {stream}
 
 
+class DenseImage:
+    """One dense image of the xyz table (rn_grid_dense_build), shared by the model's streams: `buf` holds it (None: the planner
+    found no level within the budget, or the allocation failed -- the frames of this key stay on the table), `offsets` its
+    level offsets on the device, `gx` the descriptor the frame loop gets, `levels` the mask of the de-hashed levels.  `table`
+    keeps the tensor of the key alive, so its address cannot be handed to another tensor while the image lives."""
+
+    def __init__(self, key, table, buf, offsets, gx, levels, stream):
+        self.key, self.table, self.buf, self.offsets, self.gx, self.levels, self.stream = key, table, buf, offsets, gx, levels, stream
+        self.event = torch.cuda.Event()
+        self.event.record()
+        self.waited = {stream}
+
+
 class FusedState:
     """Device-side constants + scratch of one model: packed weights (re-packed when parameters change),
     grid descriptors, per-frame bias block, loop scratch for N rays, and the torso plan of the view being rendered
-    (`plan`; `plan_builds` counts the plans this state has built)."""
+    (`plan`; `plan_builds` counts the plans this state has built, `dense_builds` the dense images of the xyz table)."""
 
     def __init__(self, model):
         if not supported(model):
@@ -128,6 +149,66 @@ class FusedState:
         self.box = None
         self._box_key = None
         self.box_builds = 0
+        self.dense_builds = 0
+
+    # -- dense image of the xyz table -----------------------------------------------------------------
+    def frame_grid(self):
+        """grid_xyz of this frame's loop: the descriptor of the table (`gx`), or of its dense image -- the coarser hashed
+        levels stored once as whole lattices (rn_grid_dense_plan / rn_grid_dense_build; same rows, same features), which the
+        network kernels then walk as dense levels.  The image is built when the table's (address, version, dtype) and the
+        budget are those of the frame call before -- training moves the version with every step, so validation renders
+        between steps never pay for a build -- and dropped when they move (that frame reads the table).  Only the frame
+        loop asks: density() and network_forward() keep the table.  Never built and never used under stream capture (a
+        replayed graph would go on reading an image the table has moved away from).  RN_DENSE_LEVELS=0: always the table;
+        the budget is `opt.dense_budget_mb` or RN_DENSE_BUDGET_MB, in MiB."""
+        if not switches.on("RN_DENSE_LEVELS") or torch.cuda.is_current_stream_capturing():
+            return self.gx
+        m = self.model
+        table = self.tables[0]
+        mb = getattr(getattr(m, "opt", None), "dense_budget_mb", None)
+        budget = int(switches.get("RN_DENSE_BUDGET_MB") if mb is None else mb) << 20
+        key = (table.data_ptr(), m.encoder.embeddings._version, table.dtype, budget)
+        img = getattr(m, "_fused_dense", None)
+        if img is not None and img.key != key:
+            img = None
+            object.__setattr__(m, "_fused_dense", None)
+        if img is None:
+            seen = getattr(m, "_fused_dense_seen", None)
+            object.__setattr__(m, "_fused_dense_seen", key)
+            if seen != key:
+                return self.gx
+            img = self._build_dense(key, table, budget)
+            object.__setattr__(m, "_fused_dense", img)
+        if img.buf is None:
+            return self.gx
+        cur = torch.cuda.current_stream()
+        if cur.cuda_stream not in img.waited:      # built on another stream: order this one behind the build, once
+            cur.wait_event(img.event)
+            img.buf.record_stream(cur)
+            img.offsets.record_stream(cur)
+            img.waited.add(cur.cuda_stream)
+        return img.gx
+
+    def _build_dense(self, key, table, budget):
+        enc = self.model.encoder
+        oh = hip.host_offsets(enc.offsets)
+        new_off = (C.c_int32 * (enc.num_levels + 1))()
+        levels, nbytes = C.c_uint32(0), C.c_size_t(0)
+        rc = _lib.rn_grid_dense_plan(C.byref(self.gx), oh, budget, new_off, C.byref(levels), C.byref(nbytes))
+        if rc < 0:
+            raise RuntimeError(f"rn_grid_dense_plan failed ({rc}): {hip.last_error()}")
+        buf = offsets = gx = None
+        if rc == 1:
+            try:
+                buf = torch.empty(nbytes.value, dtype=torch.uint8, device=self.dev)
+                offsets = torch.tensor(list(new_off), dtype=torch.int32, device=self.dev)
+            except torch.cuda.OutOfMemoryError:       # no room for the image: the frames stay on the table
+                buf = None
+        if buf is not None:
+            hip.call("rn_grid_dense_build", C.byref(self.gx), oh, new_off, levels.value, hip.ptr(buf), nbytes.value, hip.stream())
+            gx = _image_desc(self.gx, buf, offsets)
+            self.dense_builds += 1
+        return DenseImage(key, table, buf, offsets, gx, levels.value, torch.cuda.current_stream().cuda_stream)
 
     # -- occupied box ---------------------------------------------------------------------------------
     def occ_box(self):
@@ -531,6 +612,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
     shard = getattr(model, "shard_schedule", None)
     merged = shard is None and getattr(model.opt, "frame_kernels", "merged") == "merged"
     n_iters = int(max_steps) if st.loop_hint is None else min(int(max_steps), st.loop_hint)
+    gx = st.frame_grid()      # the xyz table, or its dense image (same features)
     if merged:
         if ray_source is not None:
             pose, (fx, fy, cx, cy), W = ray_source
@@ -538,7 +620,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
             hip.call("rn_frame_begin", C.byref(h), hip.ptr(pose), float(fx), float(fy), float(cx), float(cy), int(W), s)
         else:
             hip.call("rn_frame_begin", C.byref(h), None, 0.0, 0.0, 0.0, 0.0, 0, s)
-        hip.call("rn_head_iterate_ex", C.byref(h), C.byref(st.gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias), 0, n_iters,
+        hip.call("rn_head_iterate_ex", C.byref(h), C.byref(gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias), 0, n_iters,
                  st.mlp_dtype, RN_LOOP_FIRST_MARCHED | RN_LOOP_CLOSE_FRAME | loop_flags(model), s)
     else:
         if ray_source is not None:
@@ -548,7 +630,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
                      hip.ptr(rays_d), s)
         hip.call("rn_head_begin", C.byref(h), s)
         if shard is None:
-            hip.call("rn_head_iterate_ex", C.byref(h), C.byref(st.gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias), 0,
+            hip.call("rn_head_iterate_ex", C.byref(h), C.byref(gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias), 0,
                      n_iters, st.mlp_dtype, loop_flags(model), s)
         else:
             # This call renders a shard of a frame (tile-parallel): the step schedule must be the whole frame's, so the
@@ -556,7 +638,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
             group, n_total = shard
             total = torch.empty(1, dtype=torch.int32, device=dev)
             for it in range(n_iters):
-                hip.call("rn_head_iterate_ex", C.byref(h), C.byref(st.gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias),
+                hip.call("rn_head_iterate_ex", C.byref(h), C.byref(gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias),
                          it, 1, st.mlp_dtype, loop_flags(model), s)
                 bank = ((it + 1) & 1) * 8
                 total.copy_(st.state[bank:bank + 1])

@@ -171,6 +171,8 @@ FUNCTIONS = {
     "rn_nerf_frame_bias_batch": (_int, [_P(NerfWeightsT), _ptr, _u32, _ptr, _ptr, _ptr, _ptr]),
     "rn_nerf_fused_forward": (_int, [_ptr, _ptr, _ptr, _u32, _ptr, _P(GridT), _P(GridT), _ptr, _ptr, _f32, _ptr, _ptr, _ptr,
                                      _int, _ptr]),
+    "rn_grid_dense_plan": (_int, [_P(GridT), _ptr, _sz, _ptr, _P(_u32), _P(_sz)]),
+    "rn_grid_dense_build": (_int, [_P(GridT), _ptr, _ptr, _u32, _ptr, _sz, _ptr]),
     "rn_head_begin": (_int, [_P(HeadT), _ptr]),
     "rn_head_iterate": (_int, [_P(HeadT), _P(GridT), _P(GridT), _ptr, _ptr, _u32, _u32, _int, _ptr]),
     "rn_head_iterate_ex": (_int, [_P(HeadT), _P(GridT), _P(GridT), _ptr, _ptr, _u32, _u32, _int, _u32, _ptr]),
