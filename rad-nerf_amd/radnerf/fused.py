@@ -27,6 +27,7 @@ from radnerf_hip.abi import (RN_F16, RN_F32, RN_F32_SPLIT, RN_HEAD_ST_HIST, RN_H
                              RN_TORSO_PLAN_MAX_BYTES, GridT, HeadT, NerfWeightsT, TorsoWeightsT)
 
 from . import switches
+from .frame_cache import FrameCaches, LoopStats
 
 _lib = hip._lib
 
@@ -98,98 +99,77 @@ def supported(model):
         return False
 
 
-class TorsoPlan:
-    """One built torso plan (rn_torso_plan_build): `buf` holds it (None: the plan would be larger than
-    RN_TORSO_PLAN_MAX_BYTES, the frames of this key stay on rn_torso_blend_frame), `n_on` its covered pixels.  `refs` keeps
-    the tensors of the key alive, so none of their addresses can be handed to another tensor while the plan lives."""
-
-    def __init__(self, key, refs, buf, n_on, stream):
-        self.key, self.refs, self.buf, self.n_on, self.stream = key, refs, buf, n_on, stream
-        self.event = torch.cuda.Event()
-        self.event.record()
-        self.waited = {stream}
-
-
-class DenseImage:
-    """One dense image of the xyz table (rn_grid_dense_build), shared by the model's streams: `buf` holds it (None: the planner
-    found no level within the budget, or the allocation failed -- the frames of this key stay on the table), `offsets` its
-    level offsets on the device, `gx` the descriptor the frame loop gets, `levels` the mask of the de-hashed levels.  `table`
-    keeps the tensor of the key alive, so its address cannot be handed to another tensor while the image lives."""
-
-    def __init__(self, key, table, buf, offsets, gx, levels, stream):
-        self.key, self.table, self.buf, self.offsets, self.gx, self.levels, self.stream = key, table, buf, offsets, gx, levels, stream
-        self.event = torch.cuda.Event()
-        self.event.record()
-        self.waited = {stream}
+def _caches(model):
+    """The model's FrameCaches, made on first use.  The one engine attribute on the module, besides _fused_loop_hint."""
+    if getattr(model, "_fused_cache", None) is None:
+        object.__setattr__(model, "_fused_cache", FrameCaches())
+    return model._fused_cache
 
 
 class FusedState:
-    """Device-side constants + scratch of one model: packed weights (re-packed when parameters change),
-    grid descriptors, per-frame bias block, loop scratch for N rays, and the torso plan of the view being rendered
-    (`plan`; `plan_builds` counts the plans this state has built, `dense_builds` the dense images of the xyz table)."""
+    """Device-side constants + scratch of one model on one stream: packed weights (re-packed when parameters change), grid
+    descriptors, per-frame bias block, loop scratch for N rays, the occupied box.  `cache` is the model's FrameCaches: the torso
+    plan and the dense image of the xyz table live in its slots, shared with the model's other streams (`plan_builds`,
+    `dense_builds`: the records those slots have made)."""
 
     def __init__(self, model):
         if not supported(model):
             raise RuntimeError("fused engine: unsupported network shape; use engine='ops'")
-        self.model = model
+        self.model, self.cache = model, _caches(model)
         self.dev = model.density_bitfield.device
         n_packed = max(int(_lib.rn_nerf_packed_floats()), int(_lib.rn_nerf_packed_floats_h16()),
                        int(_lib.rn_nerf_packed_floats_split()))
         self.packed = torch.empty(n_packed, dtype=torch.float32, device=self.dev)
         self.mlp_dtype = RN_F32
-        self.loop_hint = None
         self.bias = torch.empty(int(_lib.rn_nerf_bias_floats()), dtype=torch.float32, device=self.dev)
         self.tpacked = (torch.empty(int(_lib.rn_torso_packed_floats()), dtype=torch.float32, device=self.dev)
                         if model.torso else None)
         self._versions = None
         self._N = 0
         self._zero_eye = torch.zeros(1, dtype=torch.float32, device=self.dev)
-        self.plan = None
-        self.plan_builds = 0
         self.box = None
         self._box_key = None
         self.box_builds = 0
-        self.dense_builds = 0
+
+    loop_hint = property(lambda self: self.cache.loop_hint)
+    plan_builds = property(lambda self: self.cache.plan.builds)
+    dense_builds = property(lambda self: self.cache.image.builds)
+
+    # -- what is built once and reused across frames --------------------------------------------------
+    def _cached(self, slot, key, refs, build):
+        """The slot's record for `key` with the current stream ordered behind its build, or None (frame_cache.Slot.get)."""
+        rec = slot.get(key, refs, build, torch.cuda.is_current_stream_capturing())
+        if rec is not None:
+            rec.order(torch.cuda.current_stream())
+        return rec
+
+    def _built(self, slot, key, refs, tensors, **payload):
+        """A record of what was just enqueued on the current stream."""
+        event = torch.cuda.Event()
+        event.record()
+        return slot.record(key, refs, tensors, event, torch.cuda.current_stream().cuda_stream, **payload)
 
     # -- dense image of the xyz table -----------------------------------------------------------------
     def frame_grid(self):
         """grid_xyz of this frame's loop: the descriptor of the table (`gx`), or of its dense image -- the coarser hashed
         levels stored once as whole lattices (rn_grid_dense_plan / rn_grid_dense_build; same rows, same features), which the
-        network kernels then walk as dense levels.  The image is built when the table's (address, version, dtype) and the
-        budget are those of the frame call before -- training moves the version with every step, so validation renders
-        between steps never pay for a build -- and dropped when they move (that frame reads the table).  Only the frame
-        loop asks: density() and network_forward() keep the table.  Never built and never used under stream capture (a
-        replayed graph would go on reading an image the table has moved away from).  RN_DENSE_LEVELS=0: always the table;
-        the budget is `opt.dense_budget_mb` or RN_DENSE_BUDGET_MB, in MiB."""
-        if not switches.on("RN_DENSE_LEVELS") or torch.cuda.is_current_stream_capturing():
+        network kernels then walk as dense levels.  The key is the table's (address, version, dtype) and the budget, the
+        lifetime frame_cache's rule: training moves the version with every step, so validation renders between steps never
+        pay for a build.  Only the frame loop asks: density() and network_forward() keep the table.  RN_DENSE_LEVELS=0:
+        always the table; the budget is `opt.dense_budget_mb` or RN_DENSE_BUDGET_MB, in MiB."""
+        if not switches.on("RN_DENSE_LEVELS"):
             return self.gx
         m = self.model
         table = self.tables[0]
         mb = getattr(getattr(m, "opt", None), "dense_budget_mb", None)
         budget = int(switches.get("RN_DENSE_BUDGET_MB") if mb is None else mb) << 20
         key = (table.data_ptr(), m.encoder.embeddings._version, table.dtype, budget)
-        img = getattr(m, "_fused_dense", None)
-        if img is not None and img.key != key:
-            img = None
-            object.__setattr__(m, "_fused_dense", None)
-        if img is None:
-            seen = getattr(m, "_fused_dense_seen", None)
-            object.__setattr__(m, "_fused_dense_seen", key)
-            if seen != key:
-                return self.gx
-            img = self._build_dense(key, table, budget)
-            object.__setattr__(m, "_fused_dense", img)
-        if img.buf is None:
-            return self.gx
-        cur = torch.cuda.current_stream()
-        if cur.cuda_stream not in img.waited:      # built on another stream: order this one behind the build, once
-            cur.wait_event(img.event)
-            img.buf.record_stream(cur)
-            img.offsets.record_stream(cur)
-            img.waited.add(cur.cuda_stream)
-        return img.gx
+        img = self._cached(self.cache.image, key, [table], lambda: self._build_dense(key, table, budget))
+        return self.gx if img is None else img.gx
 
     def _build_dense(self, key, table, budget):
+        """-> the record of one dense image: `buf` holds it (None: the planner found no level within the budget, or the
+        allocation failed), `offsets` its level offsets on the device, `gx` its descriptor, `levels` the de-hashed levels' mask."""
         enc = self.model.encoder
         oh = hip.host_offsets(enc.offsets)
         new_off = (C.c_int32 * (enc.num_levels + 1))()
@@ -207,8 +187,8 @@ class FusedState:
         if buf is not None:
             hip.call("rn_grid_dense_build", C.byref(self.gx), oh, new_off, levels.value, hip.ptr(buf), nbytes.value, hip.stream())
             gx = _image_desc(self.gx, buf, offsets)
-            self.dense_builds += 1
-        return DenseImage(key, table, buf, offsets, gx, levels.value, torch.cuda.current_stream().cuda_stream)
+        return self._built(self.cache.image, key, [table], [] if buf is None else [buf, offsets], buf=buf, offsets=offsets, gx=gx,
+                           levels=levels.value)
 
     # -- occupied box ---------------------------------------------------------------------------------
     def occ_box(self):
@@ -281,41 +261,20 @@ class FusedState:
     # -- torso plan -----------------------------------------------------------------------------------
     def torso_plan(self, bg_coords, coords, thresh):
         """The plan for this frame's torso pass, or None (the frame then runs rn_torso_blend_frame).  `bg_coords` is the
-        caller's tensor, `coords` its contiguous fp32 form.  A plan is built when the same key -- (address, version, shape) of
-        the coordinates and of the occupancy grid, thresh, shrink -- was seen on the call before, by any of the model's
-        streams: a caller whose coordinates change with every call (patch batches, validation renders during training) never
-        pays for a build.  A changed key drops the plan.  Never builds under stream capture.  (The weights, the grid table and
-        the pose reach a planned frame as they reach any other: nothing of them is in the plan.)"""
+        caller's tensor, `coords` its contiguous fp32 form.  The key is (address, version, shape) of the coordinates and of the
+        occupancy grid, thresh and shrink, the lifetime frame_cache's rule: a caller whose coordinates change with every call
+        (patch batches, validation renders during training) never pays for a build.  (The weights, the grid table and the
+        pose reach a planned frame as they reach any other: nothing of them is in the plan.)"""
         if not switches.on("RN_TORSO_PLAN"):
             return None
         m = self.model
         refs = [bg_coords, m.density_grid_torso]
         key = (tuple((t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype) for t in refs),
                float(thresh), float(m.opt.torso_shrink))
-        cur = torch.cuda.current_stream()
-        plan = self.plan
-        if plan is None or plan.key != key:
-            # another stream of the model may hold the plan of this view already
-            plan = next((st.plan for st in (getattr(m, "_fused_states", None) or {}).values()
-                         if st.plan is not None and st.plan.key == key), None)
-            self.plan = plan
-        if plan is None:
-            seen = getattr(m, "_fused_plan_seen", None)
-            if seen is None or seen[0] != key:
-                object.__setattr__(m, "_fused_plan_seen", (key, refs))
-                return None
-            if torch.cuda.is_current_stream_capturing():
-                return None
-            plan = self.plan = self._build_plan(key, refs, coords, thresh, cur)
-        if plan.buf is None:
-            return None
-        if cur.cuda_stream not in plan.waited:     # built on another stream: order this one behind the build, once
-            cur.wait_event(plan.event)
-            plan.buf.record_stream(cur)
-            plan.waited.add(cur.cuda_stream)
-        return plan
+        return self._cached(self.cache.plan, key, refs, lambda: self._build_plan(key, refs, coords, thresh))
 
-    def _build_plan(self, key, refs, coords, thresh, cur):
+    def _build_plan(self, key, refs, coords, thresh):
+        """-> the record of one torso plan: `buf` (None: larger than RN_TORSO_PLAN_MAX_BYTES) and `n_on`, its covered pixels."""
         m = self.model
         N = int(coords.shape[0])
         n_on = C.c_uint32(0)
@@ -323,7 +282,7 @@ class FusedState:
         for _ in range(2):      # the first call finds the covered count, the second has room for its tiles
             buf = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
             hip.call("rn_torso_plan_build", hip.ptr(coords), N, hip.ptr(m.density_grid_torso), int(m.grid_size), float(thresh),
-                     float(m.opt.torso_shrink), hip.ptr(buf), nbytes, C.byref(n_on), cur.cuda_stream)
+                     float(m.opt.torso_shrink), hip.ptr(buf), nbytes, C.byref(n_on), hip.stream())
             need = int(_lib.rn_torso_plan_bytes(N, n_on.value))
             if need <= nbytes:
                 break
@@ -331,8 +290,7 @@ class FusedState:
                 buf = None
                 break
             nbytes = need
-        self.plan_builds += 1
-        return TorsoPlan(key, refs, buf, int(n_on.value), cur.cuda_stream)
+        return self._built(self.cache.plan, key, refs, [] if buf is None else [buf], buf=buf, n_on=int(n_on.value))
 
     # -- scratch --------------------------------------------------------------------------------------
     def scratch(self, N):
@@ -352,74 +310,39 @@ class FusedState:
         self.live_slots = torch.empty(N, dtype=i32, device=d)   # live-sample list of the iteration in flight
         self._N = N
 
+    def read_loop_stats(self):
+        """The frame just enqueued, for LoopStats: the device counters accumulate across frames, a frame's numbers are the
+        difference to the previous read.  Synchronises."""
+        cur = self.state[RN_HEAD_ST_ITERS:RN_HEAD_ST_SLOTS + 1].cpu().tolist()
+        prev, self.stats_prev = self.stats_prev, cur
+        return dict(zip(("iterations", "live_samples", "sample_slots"), ((c - p) & 0xFFFFFFFF for c, p in zip(cur, prev))))
 
-class LoopStats(dict):
-    """Loop statistics of the frame just enqueued, read back lazily (first access synchronises the stream).
-    The device counters accumulate across frames; a frame's numbers are the difference to the previous read."""
-
-    def __init__(self, st):
-        super().__init__()
-        self._st, self._loaded = st, False
-
-    def _load(self):
-        if not self._loaded:
-            st = self._st
-            cur = st.state[RN_HEAD_ST_ITERS:RN_HEAD_ST_SLOTS + 1].cpu().tolist()
-            prev = st.stats_prev
-            st.stats_prev = cur
-            super().update(iterations=(cur[0] - prev[0]) & 0xFFFFFFFF, live_samples=(cur[1] - prev[1]) & 0xFFFFFFFF,
-                           sample_slots=(cur[2] - prev[2]) & 0xFFFFFFFF)
-            self._loaded = True
-
-    def __getitem__(self, k):
-        self._load()
-        return super().__getitem__(k)
-
-    def get(self, k, default=None):
-        self._load()
-        return super().get(k, default)
-
-    def __contains__(self, k):
-        self._load()
-        return super().__contains__(k)
-
-    # iteration / copying / comparison / printing also see the loaded numbers (dict(stats) would otherwise copy nothing)
-    def __iter__(self):
-        self._load()
-        return super().__iter__()
-
-    def keys(self):
-        self._load()
-        return super().keys()
-
-    def items(self):
-        self._load()
-        return super().items()
-
-    def values(self):
-        self._load()
-        return super().values()
-
-    def __len__(self):
-        self._load()
-        return super().__len__()
-
-    def __eq__(self, other):
-        self._load()
-        return dict.__eq__(self, other)
-
-    __hash__ = None
-
-    def __repr__(self):
-        self._load()
-        return super().__repr__()
+    def head(self, rays_o, rays_d, dt_gamma, max_steps, T_thresh, weights_sum, depth, image):
+        """rn_head_t of one frame over this state's scratch (scratch(N) has been called) and the caller's rays and outputs."""
+        model, N = self.model, rays_o.shape[0]
+        h = HeadT()
+        h.rays_o, h.rays_d, h.N = rays_o.data_ptr(), rays_d.data_ptr(), N
+        h.aabb, h.min_near = model.aabb_infer.data_ptr(), float(model.min_near)
+        h.bitfield, h.bound, h.dt_gamma = model.density_bitfield.data_ptr(), float(model.bound), float(dt_gamma)
+        h.max_steps, h.cascade, h.grid_size, h.T_thresh = int(max_steps), int(model.cascade), int(model.grid_size), float(T_thresh)
+        h.nears, h.fars = self.nears.data_ptr(), self.fars.data_ptr()
+        h.weights_sum, h.depth, h.image = weights_sum.data_ptr(), depth.data_ptr(), image.data_ptr()
+        h.rays_alive_a, h.rays_alive_b = self.rays_alive[0].data_ptr(), self.rays_alive[1].data_ptr()
+        h.rays_t, h.xyzs = self.rays_t.data_ptr(), self.samples.data_ptr()
+        h.dirs, h.deltas = self.samples.data_ptr() + N * 3 * 4, self.samples.data_ptr() + N * 6 * 4
+        h.sigmas, h.rgbs = self.sigmas.data_ptr(), self.rgbs.data_ptr()
+        h.state, h.block_counts = self.state.data_ptr(), self.block_counts.data_ptr()
+        h.live_slots = self.live_slots.data_ptr() if (getattr(model.opt, "live_list", True) and switches.on("RN_LIVE_LIST")) else None
+        # image width, if the caller said the rays are the row-major pixels of an image (SyntheticScene does): the loop then
+        # walks the rays in 8 x 8 pixel blocks (more shared grid rows per wave; no pixel changes)
+        h.order_w = int(getattr(model, "ray_order_width", 0) or 0)
+        h.occ_box = hip.ptr(self.occ_box())
+        return h
 
 
 def _all_states(model):
-    """Every FusedState of the model: one per HIP stream frames are enqueued on (a renderer that keeps two frames in flight
-    uses two streams, and each needs its own loop state and scratch)."""
-    states = getattr(model, "_fused_states", None)
-    return [st for st in states.values() if st.model is model and st._N] if states else []
+    """Every FusedState of the model that has rendered a frame: one per HIP stream frames are enqueued on."""
+    return [st for st in _caches(model).states.values() if st._N]
 
 
 def loop_counters(model):
@@ -467,24 +390,17 @@ def set_loop_hint(model, iterations):
     records frames for which that was not enough (unfinished_frames); the caller checks it where it synchronises and
     renders those frames again.  Meant for streams whose iteration count is known from earlier frames."""
     hint = None if iterations is None else max(1, int(iterations))
-    object.__setattr__(model, "_fused_loop_hint", hint)
-    for st in (getattr(model, "_fused_states", None) or {}).values():
-        st.loop_hint = hint
+    _caches(model).loop_hint = hint
+    object.__setattr__(model, "_fused_loop_hint", hint)      # bench.py reads the hint by this name
 
 
 def _state(model):
     """The model's state for the CURRENT stream (created on first use)."""
-    states = getattr(model, "_fused_states", None)
-    if states is None:
-        states = {}
-        object.__setattr__(model, "_fused_states", states)
+    states = _caches(model).states
     key = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else 0
-    st = states.get(key)
-    if st is None or st.model is not model:
-        st = FusedState(model)
-        st.loop_hint = getattr(model, "_fused_loop_hint", None)
-        states[key] = st
-    return st
+    if key not in states:
+        states[key] = FusedState(model)
+    return states[key]
 
 
 def _frame_bias(st, enc_a, eye, ind_code, batch=False):
@@ -587,25 +503,7 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
     depth = torch.empty(N, dtype=torch.float32, device=dev)
     image = torch.empty(N, 3, dtype=torch.float32, device=dev)
 
-    h = HeadT()
-    h.rays_o, h.rays_d, h.N = rays_o.data_ptr(), rays_d.data_ptr(), N
-    h.aabb, h.min_near = model.aabb_infer.data_ptr(), float(model.min_near)
-    h.bitfield, h.bound, h.dt_gamma = model.density_bitfield.data_ptr(), float(model.bound), float(dt_gamma)
-    h.max_steps, h.cascade, h.grid_size, h.T_thresh = int(max_steps), int(model.cascade), int(model.grid_size), float(T_thresh)
-    h.nears, h.fars = st.nears.data_ptr(), st.fars.data_ptr()
-    h.weights_sum, h.depth, h.image = weights_sum.data_ptr(), depth.data_ptr(), image.data_ptr()
-    h.rays_alive_a, h.rays_alive_b = st.rays_alive[0].data_ptr(), st.rays_alive[1].data_ptr()
-    h.rays_t = st.rays_t.data_ptr()
-    h.xyzs = st.samples.data_ptr()
-    h.dirs = st.samples.data_ptr() + N * 3 * 4
-    h.deltas = st.samples.data_ptr() + N * 6 * 4
-    h.sigmas, h.rgbs = st.sigmas.data_ptr(), st.rgbs.data_ptr()
-    h.state, h.block_counts = st.state.data_ptr(), st.block_counts.data_ptr()
-    h.live_slots = st.live_slots.data_ptr() if (getattr(model.opt, "live_list", True) and switches.on("RN_LIVE_LIST")) else None
-    # image width, if the caller said the rays are the row-major pixels of an image (SyntheticScene does): the loop then
-    # walks the rays in 8 x 8 pixel blocks (more shared grid rows per wave; no pixel changes)
-    h.order_w = int(getattr(model, "ray_order_width", 0) or 0)
-    h.occ_box = hip.ptr(st.occ_box())
+    h = st.head(rays_o, rays_d, dt_gamma, max_steps, T_thresh, weights_sum, depth, image)
 
     # The whole <= max_steps loop is enqueued without reading anything back: iterations past the end of the loop
     # are no-ops decided on the device (a few microseconds each), so the host can run ahead of the GPU.
@@ -613,21 +511,17 @@ def render_frame(model, rays_o, rays_d, enc_a, ind_code, eye, bg_coords, poses, 
     merged = shard is None and getattr(model.opt, "frame_kernels", "merged") == "merged"
     n_iters = int(max_steps) if st.loop_hint is None else min(int(max_steps), st.loop_hint)
     gx = st.frame_grid()      # the xyz table, or its dense image (same features)
+    pose, cam, W = None, (0.0, 0.0, 0.0, 0.0), 0
+    if ray_source is not None:
+        pose, cam, W = ray_source
+        pose, cam, W = pose.reshape(-1, 4)[:4].contiguous().float(), tuple(float(v) for v in cam), int(W)
     if merged:
-        if ray_source is not None:
-            pose, (fx, fy, cx, cy), W = ray_source
-            pose = pose.reshape(-1, 4)[:4].contiguous().float()
-            hip.call("rn_frame_begin", C.byref(h), hip.ptr(pose), float(fx), float(fy), float(cx), float(cy), int(W), s)
-        else:
-            hip.call("rn_frame_begin", C.byref(h), None, 0.0, 0.0, 0.0, 0.0, 0, s)
+        hip.call("rn_frame_begin", C.byref(h), hip.ptr(pose), *cam, W, s)
         hip.call("rn_head_iterate_ex", C.byref(h), C.byref(gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias), 0, n_iters,
                  st.mlp_dtype, RN_LOOP_FIRST_MARCHED | RN_LOOP_CLOSE_FRAME | loop_flags(model), s)
     else:
         if ray_source is not None:
-            pose, (fx, fy, cx, cy), W = ray_source
-            pose = pose.reshape(-1, 4)[:4].contiguous().float()
-            hip.call("rn_get_rays", hip.ptr(pose), float(fx), float(fy), float(cx), float(cy), N // int(W), int(W), hip.ptr(rays_o),
-                     hip.ptr(rays_d), s)
+            hip.call("rn_get_rays", hip.ptr(pose), *cam, N // W, W, hip.ptr(rays_o), hip.ptr(rays_d), s)
         hip.call("rn_head_begin", C.byref(h), s)
         if shard is None:
             hip.call("rn_head_iterate_ex", C.byref(h), C.byref(gx), C.byref(st.gw), hip.ptr(st.packed), hip.ptr(bias), 0,

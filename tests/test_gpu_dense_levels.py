@@ -178,8 +178,8 @@ def _same(got, ref):
 
 
 def _forget(m):
-    object.__setattr__(m, "_fused_dense", None)
-    object.__setattr__(m, "_fused_dense_seen", None)
+    from radnerf import fused
+    fused._caches(m).image.forget()
 
 
 def test_frames_are_the_same_and_the_image_follows_the_table(hiplib, monkeypatch):
@@ -188,15 +188,16 @@ def test_frames_are_the_same_and_the_image_follows_the_table(hiplib, monkeypatch
     scene = _scene()
     m = scene.model
     st = fused._state(m)
+    slot = st.cache.image
     _forget(m)
     b0 = st.dense_builds
     on = [_render(scene, 0)]                                     # first sight of the table: no build
-    assert m._fused_dense is None and st.dense_builds == b0
+    assert slot.held is None and st.dense_builds == b0
     on.append(_render(scene, 1))                                 # seen on the call before: built and used
-    img = m._fused_dense
+    img = slot.held
     assert img is not None and img.buf is not None and st.dense_builds == b0 + 1 and img.levels != 0
     on += [_render(scene, 2), _render(scene, 3)]
-    assert m._fused_dense is img and st.dense_builds == b0 + 1
+    assert slot.held is img and st.dense_builds == b0 + 1
     off = [_off(scene, monkeypatch, i) for i in range(4)]
     assert st.dense_builds == b0 + 1
     for a, b in zip(on, off):
@@ -210,18 +211,18 @@ def test_frames_are_the_same_and_the_image_follows_the_table(hiplib, monkeypatch
         with torch.no_grad():
             emb.mul_(1.5)
         got = _render(scene, 1)
-        assert m._fused_dense is None and st.dense_builds == b0 + 1
+        assert slot.held is None and st.dense_builds == b0 + 1
         ref = _off(scene, monkeypatch, 1)
         _same(got, ref)
         assert not torch.equal(ref["image_u8"], off[1]["image_u8"])
         got = _render(scene, 1)
-        assert st.dense_builds == b0 + 2 and m._fused_dense is not None and m._fused_dense is not img
+        assert st.dense_builds == b0 + 2 and slot.held is not None and slot.held is not img
         _same(got, ref)
         # the switch: no image is looked at, none is built
         monkeypatch.setenv("RN_DENSE_LEVELS", "0")
         _forget(m)
         _render(scene, 0), _render(scene, 0), _render(scene, 0)
-        assert st.dense_builds == b0 + 2 and m._fused_dense is None
+        assert st.dense_builds == b0 + 2 and slot.held is None
         monkeypatch.delenv("RN_DENSE_LEVELS")
     finally:
         with torch.no_grad():
@@ -235,6 +236,7 @@ def test_a_table_that_changes_between_calls_builds_nothing(hiplib, monkeypatch):
     scene = _scene()
     m = scene.model
     st = fused._state(m)
+    slot = st.cache.image
     _forget(m)
     builds = st.dense_builds
     emb = m.encoder.embeddings
@@ -246,16 +248,53 @@ def test_a_table_that_changes_between_calls_builds_nothing(hiplib, monkeypatch):
             with torch.no_grad():
                 emb.add_(1e-3)
             fused.density_forward(m, x, enc_a, scene.eye if m.exp_eye else None)
-            assert m._fused_dense is None and st.dense_builds == builds
+            assert slot.held is None and st.dense_builds == builds
         for i in range(4):                                       # density queries over one table build nothing either
             fused.density_forward(m, x, enc_a, scene.eye if m.exp_eye else None)
-        assert m._fused_dense is None and st.dense_builds == builds
+        assert slot.held is None and st.dense_builds == builds
         for i in range(4):                                       # a validation frame after every step
             with torch.no_grad():
                 emb.add_(1e-3)
             _render(scene, i)
-            assert m._fused_dense is None and st.dense_builds == builds
+            assert slot.held is None and st.dense_builds == builds
     finally:
         with torch.no_grad():
             emb.copy_(keep)
         _forget(m)
+
+
+def test_a_second_stream_uses_what_the_first_built(hiplib, monkeypatch):
+    """The plan and the image are the model's, not a stream's: a frame on a side stream builds neither, is ordered behind both
+    builds once, and is the frame of a build without them."""
+    from radnerf import fused
+    monkeypatch.delenv("RN_DENSE_LEVELS", raising=False)
+    monkeypatch.delenv("RN_TORSO_PLAN", raising=False)
+    scene = _scene()
+    m = scene.model
+    assert m.torso
+    st = fused._state(m)
+    plan, image = st.cache.plan, st.cache.image
+    plan.forget(), image.forget()
+    try:
+        _render(scene, 0), _render(scene, 1)                     # second sight: both are built, on the current stream
+        assert plan.held is not None and plan.held.buf is not None and image.held is not None and image.held.buf is not None
+        builds = (st.plan_builds, st.dense_builds)
+        waited = (set(plan.held.waited), set(image.held.waited))
+        assert waited == ({torch.cuda.current_stream().cuda_stream},) * 2
+        torch.cuda.synchronize()
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            got = _render(scene, 2)
+        assert (st.plan_builds, st.dense_builds) == builds
+        assert side.cuda_stream in plan.held.waited and side.cuda_stream in image.held.waited
+        grown = (set(plan.held.waited), set(image.held.waited))
+        assert grown == tuple(w | {side.cuda_stream} for w in waited)
+        monkeypatch.setenv("RN_TORSO_PLAN", "0")
+        ref = _off(scene, monkeypatch, 2)
+        monkeypatch.delenv("RN_TORSO_PLAN")
+        _same(got, ref)
+        with torch.cuda.stream(side):
+            _render(scene, 3)
+        assert (set(plan.held.waited), set(image.held.waited)) == grown and (st.plan_builds, st.dense_builds) == builds
+    finally:
+        plan.forget(), image.forget()

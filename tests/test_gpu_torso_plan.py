@@ -284,13 +284,13 @@ def test_state_builds_once_per_view_and_follows_weights_and_grid(hiplib, monkeyp
     scene = _scene()
     m = scene.model
     st = fused._state(m)
-    st.plan = None
-    object.__setattr__(m, "_fused_plan_seen", None)
+    slot = st.cache.plan
+    slot.forget()
     b0 = st.plan_builds
     _render(scene)                                   # first sight of the key: no build
-    assert st.plan is None and st.plan_builds == b0
+    assert slot.held is None and st.plan_builds == b0
     got = _render(scene)                             # seen on the call before: built and used
-    assert st.plan is not None and st.plan.buf is not None and st.plan_builds == b0 + 1 and st.plan.n_on > 0
+    assert slot.held is not None and slot.held.buf is not None and st.plan_builds == b0 + 1 and slot.held.n_on > 0
     before = _fresh(scene, monkeypatch)
     _same_frame(got, before)
     _same_frame(_render(scene, 3), _fresh(scene, monkeypatch, 3))     # another pose, the same plan
@@ -314,7 +314,7 @@ def test_state_builds_once_per_view_and_follows_weights_and_grid(hiplib, monkeyp
     try:
         builds = st.plan_builds
         got = _render(scene)
-        assert st.plan is None and st.plan_builds == builds
+        assert slot.held is None and st.plan_builds == builds
         ref = _fresh(scene, monkeypatch)
         _same_frame(got, ref)
         assert int((ref["torso_alpha"] > 0).sum()) > int((before["torso_alpha"] > 0).sum())
@@ -336,20 +336,20 @@ def test_a_key_that_changes_every_call_builds_nothing(hiplib, monkeypatch):
     scene = _scene()
     m = scene.model
     st = fused._state(m)
-    st.plan = None
-    object.__setattr__(m, "_fused_plan_seen", None)
+    slot = st.cache.plan
+    slot.forget()
     builds = st.plan_builds
     keep = scene.bg_coords
     try:
         for i in range(4):                           # new coordinates every call, as a patch batch hands them over
             scene.bg_coords = keep + 1e-3 * (i + 1)
             _render(scene)
-            assert st.plan is None
+            assert slot.held is None
         scene.bg_coords = keep.clone()
         for i in range(4):                           # one buffer written in place between calls
             scene.bg_coords.add_(1e-4)
             _render(scene)
-            assert st.plan is None
+            assert slot.held is None
     finally:
         scene.bg_coords = keep
     assert st.plan_builds == builds
