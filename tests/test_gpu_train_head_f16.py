@@ -1,9 +1,9 @@
 """RN_TRAIN_MLP=f16: the fused training head with 16-bit matrix products (csrc/rn_train_head_f16.hip, the *_h16 entries of
 include/radnerf_train.h) -- the entry points and what the switch changes, every output and gradient against float64 with the
 bound err_gpu <= 2 E_model + bar_f32 (E_model: the distance of the arithmetic model tests/netref16.py from float64; bar_f32: the
-bar tests/test_gpu_train_head.py applies to the fp32 route), the per-tile gradient scaling, reproducibility, the live count, and
+bar tests/test_gpu_train_head.py applies to the fp32 route, which tests/test_gpu_train_head_ref.py now backs with measurements: the fp32
+route stands at most 1.2e-4 from float64 on a gradient and 6e-6 on an output), the per-tile gradient scaling, reproducibility, the live count, and
 16 training steps eager and captured."""
-import ctypes as C
 import os
 import random
 
@@ -12,107 +12,15 @@ import pytest
 import torch
 
 import netref16
+from head_cases import batch as _batch, direct as _direct, environment as _environment, head as _head, model as _model
 from netref64 import Net64
 
 pytestmark = pytest.mark.gpu
 
 # the bars of tests/test_gpu_train_head.py::test_fused_head_matches_the_operator_path, as max-normalised errors
 SIGMA_RTOL, SIGMA_ATOL, RGB_ATOL, AMBIENT_ATOL, GRAD_BAR = 2e-4, 1e-6, 2e-5, 2e-5, 2e-3
-_SCENES, _BATCHES = {}, {}
 ENTRIES = ["rn_train_head_image_floats_h16", "rn_train_head_pack_h16", "rn_train_head_pack_row_h16", "rn_train_head_forward_h16",
            "rn_train_head_backward_h16"]
-
-
-def _model(tag):
-    if tag not in _SCENES:
-        _SCENES[tag] = netref16.head_scene(tag, "cuda")
-    m = _SCENES[tag].model
-    m.train()
-    return m
-
-
-def _batch(tag, M, seed):
-    """netref16.stable_batch, once per (model, size, seed): the tests share it and leave it unchanged."""
-    key = (tag, M, seed)
-    if key not in _BATCHES:
-        _BATCHES[key] = netref16.stable_batch(netref16.Net16(_model(tag)), M, seed)
-    return _BATCHES[key]
-
-
-def _environment(monkeypatch, mlp, deterministic=False):
-    monkeypatch.setenv("RN_TRAIN_HEAD", "fused")
-    monkeypatch.setenv("RN_TRAIN_MLP", mlp)
-    monkeypatch.setenv("RN_TRAIN_DETERMINISTIC", "1" if deterministic else "0")
-
-
-def _direct(m, b, sfx, M=None, m_dev=None, up=None, sentinel=0.0):
-    """pack + forward (+ backward under `up`) through the C ABI on buffers of this function, every one pre-filled with `sentinel`
-    (the workspace with zeros) -> dict of the buffers."""
-    import radnerf_hip as hip
-    from radnerf.fused import _grid_desc, head_weights, weights_desc
-    lib = hip._lib
-    M = b["xyzs"].shape[0] if M is None else M
-    xyzs, dirs = b["xyzs"][:M].contiguous(), b["dirs"][:M].contiguous()
-    ws = [w.detach().contiguous() for w in head_weights(m)]
-    audio_dim, has_eye, ind_dim = ws[0].shape[1] - 32, ws[3].shape[1] - 64, ws[6].shape[1] - 80
-    enc_a = b["enc_a"].reshape(-1).contiguous()
-    eye = b["eye"].reshape(-1).contiguous() if has_eye else None
-    ind = m.individual_codes[0].detach().contiguous() if ind_dim else None
-    tx, tw = hip.aligned(m.encoder.embeddings.detach(), 64), hip.aligned(m.encoder_ambient.embeddings.detach(), 64)
-    nw = weights_desc(ws, audio_dim, has_eye, ind_dim)
-    gx, gw = _grid_desc(m.encoder, tx), _grid_desc(m.encoder_ambient, tw)
-    s = hip.stream()
-
-    def buf(*shape):
-        return torch.full(shape, sentinel, dtype=torch.float32, device="cuda")
-    image = torch.zeros(int(getattr(lib, "rn_train_head_image_floats" + sfx)()), dtype=torch.float32, device="cuda")
-    hip.call("rn_train_head_pack" + sfx, C.byref(nw), hip.ptr(enc_a), hip.ptr(eye), hip.ptr(ind), hip.ptr(image), s)
-    out = dict(image=image, work=torch.zeros(int(lib.rn_train_head_workspace_floats(M)), dtype=torch.float32, device="cuda"),
-               sigmas=buf(M), rgbs=buf(M, 3), ambient=buf(M, 2), amb_abs=buf(M), xn=buf(M, 3), wn=buf(M, 2))
-    hip.call("rn_train_head_forward" + sfx, hip.ptr(xyzs), hip.ptr(dirs), M, hip.ptr(m_dev), C.byref(gx), C.byref(gw), hip.ptr(image),
-             float(m.bound), *(out[k].data_ptr() for k in ("sigmas", "rgbs", "ambient", "amb_abs", "xn", "wn")), hip.ptr(out["work"]), s)
-    if up is not None:
-        up = [u[:M].contiguous() for u in up]
-        out["g_enc_x"], out["g_enc_w"] = buf(16, M, 2), buf(16, M, 2)
-        hip.call("rn_train_head_backward" + sfx, hip.ptr(up[0]), hip.ptr(up[1]), hip.ptr(up[3]), hip.ptr(up[2]), out["rgbs"].data_ptr(),
-                 out["ambient"].data_ptr(), M, hip.ptr(m_dev), hip.ptr(image), hip.ptr(out["work"]), out["g_enc_x"].data_ptr(),
-                 out["g_enc_w"].data_ptr(), s)
-    torch.cuda.synchronize()
-    return out
-
-
-def _head(m, b, up, live=None, row=False, input_grads=False, backwards=1):
-    """head_forward + backward under head_loss (rows below `live` only, the count handed over on the device) through autograd;
-    -> (outputs, [gradients of backward pass i under up * 2^(-20 i)]).  The environment selects the route."""
-    from radnerf import train_head
-    M = b["xyzs"].shape[0]
-    n = M if live is None else live
-    enc_a = b["enc_a"].clone().requires_grad_(True)
-    eye = b["eye"].clone().requires_grad_(True) if m.exp_eye else None
-    xyzs, dirs = b["xyzs"].clone().requires_grad_(input_grads), b["dirs"].clone().requires_grad_(input_grads)
-    m_dev = None if live is None else torch.tensor([live, 0], dtype=torch.int32, device="cuda")
-    kw = {}
-    if m.individual_dim:
-        kw = dict(ind_index=torch.tensor([0], dtype=torch.int64, device="cuda")) if row else dict(ind_code=m.individual_codes[0])
-    sigma, rgb, amb, amb_abs = train_head.head_forward(m, xyzs, dirs, enc_a, kw.get("ind_code"), eye, m_dev=m_dev, ind_index=kw.get("ind_index"))
-    out = {"sigma": sigma.detach()[:n].clone(), "rgb": rgb.detach()[:n].clone(), "ambient": amb.detach()[:n].clone()}
-    passes = []
-    for i in range(backwards):
-        for p in list(m.parameters()) + [enc_a, eye, xyzs, dirs]:
-            if p is not None:
-                p.grad = None
-        u = [t[:n] * 2.0 ** (-20 * i) for t in up]
-        loss = (sigma[:n] * u[0]).sum() + (rgb[:n] * u[1]).sum() + (amb_abs[:n] * u[2]).sum() + (amb[:n] * u[3]).sum()
-        loss.backward(retain_graph=i + 1 < backwards)
-        g = {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None}
-        g["enc_a"] = enc_a.grad.clone()
-        if eye is not None:
-            g["eye"] = eye.grad.clone()
-        if input_grads:
-            g["xyzs"], g["dirs"] = xyzs.grad[:n].clone(), dirs.grad[:n].clone()
-        passes.append(g)
-    torch.cuda.synchronize()
-    return out, passes
 
 
 # --------------------------------------------------------------------------------------------------------- 1: the entry points
