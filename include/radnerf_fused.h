@@ -546,7 +546,19 @@ int rn_jpeg_entropy(const int16_t *coefficients, uint32_t F, uint32_t H, uint32_
  *                        floats; segments: HOST array [n_segments <= 4][5] = {first row, windows, T, left, right}: `windows`
  *                        windows of T rows one behind the other from `first row`, rows left .. right - 1 of each kept.  The M
  *                        kept rows, in order, are unfolded (window 16, padding 8, stride 2) into features [F, C, 16],
- *                        F = M / 2 + 1: features[f][c][j] = kept[2 f - 8 + j][c], 0 outside. */
+ *                        F = M / 2 + 1: features[f][c][j] = kept[2 f - 8 + j][c], 0 outside.
+ *   rn_asr_forward_tile  rn_asr_forward with the tiling of its matrix products named: tile = 0 (per product, a function of the
+ *                        product's shape and the device's compute-unit count alone), 32 (one wave per 32 x 32 tile, for the few
+ *                        rows of one window) or 128 (128 x 128 tiles through LDS).  Both tilings run the same chain over k for
+ *                        every output: the logits have the same bits under every value, only the time differs.
+ *
+ * Live mode (nerf/asr.py:160-224): the logits of one window at a time go into a ring of ring_rows rows of C floats, and every
+ * video frame reads its attention window out of it.  Pure copies; the host passes every scalar, nothing is read back.
+ *   rn_asr_ring_push     rows left .. right - 1 of logits [T, C] -> ring rows (first_row + i) % ring_rows, then zero_rows rows of
+ *                        zeros behind them (0 while streaming; 16 behind the terminal window).  right - left + zero_rows <=
+ *                        ring_rows, ring_rows >= 16.
+ *   rn_asr_ring_window   frame k's window out [8, C, 16]: entry e is slice s = k - 4 + e, all zeros when s < 0 or s >= n_slices
+ *                        (UINT32_MAX while the stream is open), else out[e][c][t] = ring[(ring_rows - 8 + 2 s + t) % ring_rows][c]. */
 typedef struct {
     uint32_t n_conv, conv_dim[8], conv_kernel[8], conv_stride[8];
     uint32_t hidden, heads, intermediate, layers, pos_taps, pos_groups, vocab;
@@ -557,8 +569,13 @@ int rn_asr_pack(const rn_asr_config_t *config, const float *const *tensors, uint
 size_t rn_asr_workspace(const rn_asr_config_t *config, uint32_t B, uint32_t samples);
 int rn_asr_forward(const rn_asr_config_t *config, const float *image, void *workspace, size_t workspace_bytes, const float *windows,
                    uint32_t B, uint32_t samples, float *logits, rn_stream_t stream);
+int rn_asr_forward_tile(const rn_asr_config_t *config, const float *image, void *workspace, size_t workspace_bytes, const float *windows,
+                        uint32_t B, uint32_t samples, float *logits, uint32_t tile, rn_stream_t stream);
 int rn_asr_features(const float *logits, size_t logits_rows, uint32_t C, const uint32_t *segments, uint32_t n_segments,
                     float *features, uint32_t F, rn_stream_t stream);
+int rn_asr_ring_push(const float *logits, uint32_t T, uint32_t C, uint32_t left, uint32_t right, float *ring, uint32_t ring_rows,
+                     uint32_t first_row, uint32_t zero_rows, rn_stream_t stream);
+int rn_asr_ring_window(const float *ring, uint32_t ring_rows, uint32_t C, uint32_t k, uint32_t n_slices, float *out, rn_stream_t stream);
 
 #ifdef __cplusplus
 }

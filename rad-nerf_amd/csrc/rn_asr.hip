@@ -9,10 +9,14 @@
 //                   through (batch stride, row stride) and a (segment length, segment stride) walk of K, so the strided
 //                   convolutions and the grouped positional convolution need no im2col pass; blockIdx.z walks groups.
 //                   Epilogue: + bias, GELU, + residual.  K is never split: a row's sum order does not depend on M.
+//   k_gemm32        the same product on 32 x 32 tiles, one wave per tile straight from L2 (no LDS, no barrier), for a small M:
+//                   the same chain over k per output, so the same bits; pick_tile chooses between the two per product
 //   k_layer_norm    one row per wave, two-pass, optional GELU
 //   k_pad           h [B][T][H] -> [B][T + taps][H] with taps / 2 zero rows in front
 //   k_attention     one workgroup per (window, head): keys and values in LDS, a wave per query row, softmax in registers
 //   k_features      the cut and the unfold -> [F][C][16]
+//   k_ring_push     live mode: the kept rows of one window's logits into the feature ring, zero rows behind them
+//   k_ring_window   live mode: one frame's attention window [8][C][16] out of the ring
 //
 // No float atomics; every sum in one fixed order.
 #include "rn_asr_dev.h"
@@ -214,6 +218,70 @@ __global__ void __launch_bounds__(256) k_gemm(GemmArgs a) {
     epilogue(a, acc11, m0 + 32u, n0 + 32u, hh, col0);
 }
 
+// The 32-row tiling: a workgroup is four waves on four row tiles of one 32-column strip, a wave owns one 32 x 32 tile and walks all
+// of K alone.  Lane (j, hh) holds row m0 + j of A as whole float4 along k (both lane halves load the same 16 bytes and pick the
+// k's of their half) and column n0 + j of W for k = 2 s + hh.  Stages of kSK k's are fetched one stage ahead into registers.
+// Every output runs the MFMA chain of k_gemm: steps s = 0 .. up16(K) / 2 - 1 from a zero accumulator, zeros past K.
+constexpr uint32_t kSK = 64;
+
+__global__ void __launch_bounds__(256) k_gemm32(GemmArgs a) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, j = lane & 31u, hh = lane >> 5;
+    const uint32_t m0 = (blockIdx.y * 4u + wave) * 32u, n0 = blockIdx.x * 32u, z = blockIdx.z;
+    if (m0 >= a.M) return;
+    // a lane past M or past ldw, and a k past K, loads from a clamped address and drops the value: no branch sits between the loads
+    const bool alive = m0 + j < a.M, wlive = n0 + j < a.ldw;
+    const uint32_t m = alive ? m0 + j : a.M - 1u, b = m / a.rows_per_batch, t = m - b * a.rows_per_batch;
+    const float *arow = a.A + z * a.a_group + b * a.a_batch + t * a.a_row;
+    const float *wcol = a.W + z * a.w_group + (wlive ? n0 + j : 0u);
+    const uint32_t Kpad = (a.K + kBK - 1u) / kBK * kBK;
+
+    // the fetches come in order: the next k, its place in its segment and the segment's start in the row (the same in every lane)
+    uint32_t fk = 0, foff = 0;
+    size_t fbase = 0;
+    auto fetch = [&](float4 (&ra)[kSK / 4u], float (&rw)[kSK / 2u]) {
+#pragma unroll
+        for (uint32_t s = 0; s < kSK / 2u; s++) {
+            const uint32_t kw = fk + 2u * s + hh;
+            const bool ok = kw < a.K;
+            rw[s] = wcol[(size_t)(ok ? kw : 0u) * a.ldw];
+        }
+#pragma unroll
+        for (uint32_t q = 0; q < kSK / 4u; q++) {
+            const bool ok = fk < a.K;
+            ra[q] = *reinterpret_cast<const float4 *>(arow + (ok ? fbase + foff : (size_t)0));
+            fk += 4u; foff += 4u;
+            if (foff >= a.seg_len) { foff = 0u; fbase += a.seg_stride; }
+        }
+    };
+    f32x16 acc = zero16();
+    auto compute = [&](const float4 (&ra)[kSK / 4u], const float (&rw)[kSK / 2u], uint32_t k0) {
+#pragma unroll
+        for (uint32_t g = 0; g < kSK / kBK; g++) {
+            if (k0 + g * kBK < Kpad) {
+#pragma unroll
+                for (uint32_t s = g * (kBK / 2u); s < (g + 1u) * (kBK / 2u); s++) {
+                    const float4 v = ra[s >> 1];
+                    const uint32_t k = k0 + 2u * s + hh;        // dropped here, not at the load: the load stays in flight
+                    const float av = (s & 1u) ? (hh ? v.w : v.z) : (hh ? v.y : v.x);
+                    acc = mfma32((alive && k < a.K) ? av : 0.0f, (wlive && k < a.K) ? rw[s] : 0.0f, acc);
+                }
+            }
+        }
+    };
+    // two register stages in turn, each fetched while the other is multiplied (a fetch past K reads the clamped address again)
+    float4 ra0[kSK / 4u], ra1[kSK / 4u];
+    float rw0[kSK / 2u], rw1[kSK / 2u];
+    fetch(ra0, rw0);
+    for (uint32_t k0 = 0; k0 < Kpad; k0 += 2u * kSK) {
+        fetch(ra1, rw1);
+        compute(ra0, rw0, k0);
+        if (k0 + kSK >= Kpad) break;
+        fetch(ra0, rw0);
+        compute(ra1, rw1, k0 + kSK);
+    }
+    epilogue(a, acc, m0, n0 + j, hh, z * a.c_group);
+}
+
 // ------------------------------------------------------------------------------------------------------------------ rows
 __global__ void __launch_bounds__(256) k_layer_norm(const float *__restrict__ in, float *__restrict__ out, const float *__restrict__ gamma,
                                                     const float *__restrict__ beta, uint32_t rows, uint32_t C, float eps, int gelu) {
@@ -312,6 +380,29 @@ __global__ void __launch_bounds__(256) k_features(const float *__restrict__ logi
     out[idx] = v;
 }
 
+// ------------------------------------------------------------------------------------------------------------------ live ring
+// ring row (first_row + i) % ring_rows = logits row left + i for i < rows, zeros for rows <= i < rows + zero_rows
+__global__ void __launch_bounds__(256) k_ring_push(const float *__restrict__ logits, uint32_t C, uint32_t left, uint32_t rows,
+                                                   float *__restrict__ ring, uint32_t ring_rows, uint32_t first_row, uint32_t zero_rows) {
+    const size_t idx = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (idx >= (size_t)(rows + zero_rows) * C) return;
+    const uint32_t i = (uint32_t)(idx / C), c = (uint32_t)(idx - (size_t)i * C);
+    const uint32_t dst = (uint32_t)(((uint64_t)first_row + i) % ring_rows);
+    ring[(size_t)dst * C + c] = i < rows ? logits[(size_t)(left + i) * C + c] : 0.0f;
+}
+
+// out[e][c][t] = ring[(ring_rows - 8 + 2 s + t) % ring_rows][c] for slice s = k - 4 + e in 0 .. n_slices - 1, else 0
+__global__ void __launch_bounds__(256) k_ring_window(const float *__restrict__ ring, uint32_t ring_rows, uint32_t C, uint32_t k,
+                                                     uint32_t n_slices, float *__restrict__ out) {
+    const uint32_t idx = blockIdx.x * 256u + threadIdx.x;
+    if (idx >= 8u * C * 16u) return;
+    const uint32_t t = idx & 15u, c = (idx >> 4) % C, e = (idx >> 4) / C;
+    const int64_t s = (int64_t)k - 4 + e;
+    float v = 0.0f;
+    if (s >= 0 && s < (int64_t)n_slices) v = ring[(size_t)(((uint64_t)ring_rows - 8u + 2u * (uint64_t)s + t) % ring_rows) * C + c];
+    out[idx] = v;
+}
+
 // ------------------------------------------------------------------------------------------------------------------ host
 // one tensor [Cout][Cin][k] into columns col0 .. col0 + width - 1 of a [k * Cin][ld] matrix
 static void pack_one(const float *src, float *dst, uint32_t Cout, uint32_t Cin, uint32_t k, uint32_t width, uint32_t ld, uint32_t col0,
@@ -325,8 +416,13 @@ static void pack_mat(const float *src, float *dst, uint32_t Cout, uint32_t Cin, 
 }
 static void pack_vec(const float *src, float *dst, uint32_t n, hipStream_t st) { pack_mat(src, dst, n, 1u, 1u, st); }
 
-static void gemm(const GemmArgs &a, uint32_t groups, hipStream_t st) {
-    hipLaunchKernelGGL(k_gemm, dim3(div_up(a.N, kBN), div_up(a.M, kBM), groups), dim3(256), 0, st, a);
+// tile: 0 = pick_tile's choice, 32 or 128
+static void gemm(const GemmArgs &a, uint32_t groups, uint32_t tile, hipStream_t st) {
+    if (tile == 0) tile = pick_tile(a.M, a.N, a.K, groups, (uint32_t)num_cus());
+    if (tile == 32u)
+        hipLaunchKernelGGL(k_gemm32, dim3(div_up(a.N, 32u), div_up(div_up(a.M, 32u), 4u), groups), dim3(256), 0, st, a);
+    else
+        hipLaunchKernelGGL(k_gemm, dim3(div_up(a.N, kBN), div_up(a.M, kBM), groups), dim3(256), 0, st, a);
 }
 // C [M][N] = epilogue(A [M][K] W [K][up4(N)]) with plain rows
 static GemmArgs dense(const float *A, const float *W, const float *bias, float *C, uint32_t M, uint32_t N, uint32_t K) {
@@ -403,8 +499,14 @@ size_t rn_asr_workspace(const rn_asr_config_t *config, uint32_t B, uint32_t samp
 
 int rn_asr_forward(const rn_asr_config_t *config, const float *image, void *workspace, size_t workspace_bytes, const float *windows,
                    uint32_t B, uint32_t samples, float *logits, rn_stream_t stream) {
+    return rn_asr_forward_tile(config, image, workspace, workspace_bytes, windows, B, samples, logits, 0u, stream);
+}
+
+int rn_asr_forward_tile(const rn_asr_config_t *config, const float *image, void *workspace, size_t workspace_bytes, const float *windows,
+                        uint32_t B, uint32_t samples, float *logits, uint32_t tile, rn_stream_t stream) {
     const char *why = unsupported(config);
     RN_REQUIRE(!why, "asr_forward: unsupported config: %s", why);
+    RN_REQUIRE(tile == 0u || tile == 32u || tile == 128u, "asr_forward: tile must be 0 (auto), 32 or 128, got %u", tile);
     RN_REQUIRE(image && workspace && windows && logits, "asr_forward: null pointer");
     const rn_asr_config_t &c = *config;
     const Plan pl = make_plan(c, B, samples);
@@ -428,14 +530,14 @@ int rn_asr_forward(const rn_asr_config_t *config, const float *image, void *work
         const uint32_t cin = c.conv_dim[i - 1], co = c.conv_dim[i], M = B * pl.T[i];
         GemmArgs a = dense(cur, image + L.conv_w[i], image + L.conv_b[i], nxt, M, co, c.conv_kernel[i] * cin);
         a.rows_per_batch = pl.T[i]; a.a_batch = (size_t)pl.T[i - 1] * cin; a.a_row = (size_t)c.conv_stride[i] * cin;
-        gemm(a, 1u, st);
+        gemm(a, 1u, tile, st);
         layer_norm(nxt, nxt, image + L.conv_lnw[i], image + L.conv_lnb[i], M, co, eps, 1, st);
         float *tmp = cur; cur = nxt; nxt = tmp;
     }
     const uint32_t cl = c.conv_dim[c.n_conv - 1];
     float *h = ws + pl.h, *x = ws + pl.x, *qkv = ws + pl.qkv, *att = ws + pl.att, *ff = ws + pl.ff, *pad = ws + pl.pad;
     layer_norm(cur, cur, image + L.proj_lnw, image + L.proj_lnb, rows, cl, eps, 0, st);
-    gemm(dense(cur, image + L.proj_w, image + L.proj_b, h, rows, H, cl), 1u, st);
+    gemm(dense(cur, image + L.proj_w, image + L.proj_b, h, rows, H, cl), 1u, tile, st);
     {   // h += GELU(conv(h) + bias): one GEMM per group over the zero-padded copy
         const size_t total4 = (size_t)B * (T + c.pos_taps) * (H / 4u);
         hipLaunchKernelGGL(k_pad, dim3((uint32_t)((total4 + 255u) / 256u)), dim3(256), 0, st, h, pad, T, c.pos_taps, H / 4u, total4);
@@ -445,27 +547,27 @@ int rn_asr_forward(const rn_asr_config_t *config, const float *image, void *work
         a.seg_len = cg; a.seg_stride = H;
         a.ldw = cg; a.ldc = H; a.a_group = cg; a.w_group = (size_t)c.pos_taps * cg * cg; a.c_group = cg;
         a.res = h; a.gelu = 1;
-        gemm(a, c.pos_groups, st);
+        gemm(a, c.pos_groups, tile, st);
     }
     for (uint32_t l = 0; l < c.layers; l++) {
         const float *y = image + L.layers + (size_t)l * L.layer.size;
         const LayerLayout &o = L.layer;
         layer_norm(h, x, y + o.ln1_w, y + o.ln1_b, rows, H, eps, 0, st);
-        gemm(dense(x, y + o.wqkv, y + o.bqkv, qkv, rows, 3u * H, H), 1u, st);
+        gemm(dense(x, y + o.wqkv, y + o.bqkv, qkv, rows, 3u * H, H), 1u, tile, st);
         hipLaunchKernelGGL(k_attention, dim3(c.heads, B), dim3(256), 0, st, qkv, att, T, H, 0.125f);
         GemmArgs p = dense(att, y + o.wo, y + o.bo, h, rows, H, H);
         p.res = h;
-        gemm(p, 1u, st);
+        gemm(p, 1u, tile, st);
         layer_norm(h, x, y + o.ln2_w, y + o.ln2_b, rows, H, eps, 0, st);
         GemmArgs f1 = dense(x, y + o.w1, y + o.b1, ff, rows, I, H);
         f1.gelu = 1;
-        gemm(f1, 1u, st);
+        gemm(f1, 1u, tile, st);
         GemmArgs f2 = dense(ff, y + o.w2, y + o.b2, h, rows, H, I);
         f2.res = h;
-        gemm(f2, 1u, st);
+        gemm(f2, 1u, tile, st);
     }
     layer_norm(h, x, image + L.enc_lnw, image + L.enc_lnb, rows, H, eps, 0, st);
-    gemm(dense(x, image + L.head_w, image + L.head_b, logits, rows, c.vocab, H), 1u, st);
+    gemm(dense(x, image + L.head_w, image + L.head_b, logits, rows, c.vocab, H), 1u, tile, st);
     return check_launch("asr_forward");
 }
 
@@ -491,6 +593,30 @@ int rn_asr_features(const float *logits, size_t logits_rows, uint32_t C, const u
     const size_t total = (size_t)F * C * 16u;
     hipLaunchKernelGGL(k_features, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, as_stream(stream), logits, a, features);
     return check_launch("asr_features");
+}
+
+int rn_asr_ring_push(const float *logits, uint32_t T, uint32_t C, uint32_t left, uint32_t right, float *ring, uint32_t ring_rows,
+                     uint32_t first_row, uint32_t zero_rows, rn_stream_t stream) {
+    RN_REQUIRE(logits && ring, "asr_ring_push: null pointer");
+    RN_REQUIRE(C >= 1 && C <= 65536u, "asr_ring_push: C must be 1 .. 65536");
+    RN_REQUIRE(left <= right && right <= T, "asr_ring_push: rows %u .. %u of %u", left, right, T);
+    RN_REQUIRE(ring_rows >= 16u && ring_rows <= (1u << 24), "asr_ring_push: ring_rows must be 16 .. 2^24");
+    RN_REQUIRE(first_row < ring_rows, "asr_ring_push: first_row %u of %u", first_row, ring_rows);
+    RN_REQUIRE((uint64_t)(right - left) + zero_rows <= ring_rows, "asr_ring_push: %u rows and %u zero rows into a ring of %u", right - left,
+               zero_rows, ring_rows);
+    const size_t total = (size_t)(right - left + zero_rows) * C;
+    if (total == 0) return RN_OK;
+    hipLaunchKernelGGL(k_ring_push, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, as_stream(stream), logits, C, left, right - left,
+                       ring, ring_rows, first_row, zero_rows);
+    return check_launch("asr_ring_push");
+}
+
+int rn_asr_ring_window(const float *ring, uint32_t ring_rows, uint32_t C, uint32_t k, uint32_t n_slices, float *out, rn_stream_t stream) {
+    RN_REQUIRE(ring && out, "asr_ring_window: null pointer");
+    RN_REQUIRE(C >= 1 && C <= 65536u, "asr_ring_window: C must be 1 .. 65536");
+    RN_REQUIRE(ring_rows >= 16u && ring_rows <= (1u << 24), "asr_ring_window: ring_rows must be 16 .. 2^24");
+    hipLaunchKernelGGL(k_ring_window, dim3(div_up(8u * C * 16u, 256u)), dim3(256), 0, as_stream(stream), ring, ring_rows, C, k, n_slices, out);
+    return check_launch("asr_ring_window");
 }
 
 }  // extern "C"

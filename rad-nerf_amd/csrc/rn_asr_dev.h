@@ -116,5 +116,17 @@ static inline Plan make_plan(const rn_asr_config_t &c, uint32_t B, uint32_t samp
     return p;
 }
 
+// ---- the GEMM's tiling ----------------------------------------------------------------------------------------------------------
+// 32 or 128: which of the two tilings of C = A W runs a product of M x N x K in `groups` groups on a device of `cus` compute
+// units.  Both give the same bits, so the choice moves nothing but time, and it is a function of the shape alone: never of the data
+// or of what else shares the batch.  The 32-row tiling (one wave per 32 x 32 tile) is taken while the 128-row grid would leave
+// compute units idle and its own tiles still find a SIMD each (four per compute unit); K does not enter: both walk it whole.
+static inline uint32_t pick_tile(uint32_t M, uint32_t N, uint32_t K, uint32_t groups, uint32_t cus) {
+    (void)K;
+    const uint64_t wg128 = (uint64_t)((M + 127u) / 128u) * ((N + 127u) / 128u) * groups;
+    const uint64_t waves32 = (uint64_t)((M + 31u) / 32u) * ((N + 31u) / 32u) * groups;
+    return (wg128 < cus && waves32 <= 4ull * cus) ? 32u : 128u;
+}
+
 }  // namespace asr
 }  // namespace rn

@@ -20,7 +20,8 @@ Any other variant is a ValueError naming the config field (`supported`).  On a G
 cut + unfold run in the kernels of csrc/rn_asr.hip (no float atomics: two calls give the same bits, and a window's logits do not
 depend on which other windows share its launch); otherwise -- CPU tensors, float64, RN_ASR=torch -- the same arithmetic runs in
 plain torch.  RN_ASR=torch is the default: at the real size the torch path measured faster (DESIGN.md section 3 has the numbers);
-set RN_ASR=hip where the bits must not depend on the batching.
+set RN_ASR=hip where the bits must not depend on the batching.  RN_ASR_TILE (auto | 32 | 128) names the tiling of the kernels' matrix
+products: 32 x 32 tiles for the few rows of one window, 128 x 128 for a batch, chosen per product from its shape; the same bits either way.
 
 The windows (asr.py:35-251): chunks of 320 samples, `l` zero chunks in front, a window whenever l + m + r chunks have collected,
 the last l + r kept for the next; when the samples run out one terminal window over whatever is held.  Of a window's T logits
@@ -30,7 +31,9 @@ independent (each normalised on its own, none padded, no mask), so here all wind
 A terminal window shorter than the encoder's receptive field (400 samples) contributes no rows -- the reference would raise
 inside the first convolution there.
 
-Live capture and playback, the text decode, resampling and DeepSpeech features are not built here.
+The live loop around this model -- samples arriving 20 ms at a time, one window per m chunks into a ring of logits, one attention
+window per video frame -- is radnerf/live.py.  Microphone capture and playback, the text decode, resampling and DeepSpeech features
+are not built here.
 """
 import ctypes as C
 import json
@@ -366,7 +369,10 @@ class Wav2Vec2CTC(torch.nn.Module):
         import radnerf_hip as hip
         return int(hip._lib.rn_asr_workspace(C.byref(self.c_config()), int(B), int(samples)))
 
-    def forward_hip(self, windows, out=None):
+    def forward_hip(self, windows, out=None, workspace=None):
+        """workspace: a uint8 device tensor of at least workspace_bytes(B, S) bytes to run in (a caller that runs one window
+        after the other keeps one); without it one is allocated per call.  RN_ASR_TILE names the tiling of the matrix
+        products (auto: per product from its shape; the logits have the same bits under every value)."""
         import radnerf_hip as hip
         windows = windows.contiguous()
         B, S = windows.shape
@@ -375,11 +381,12 @@ class Wav2Vec2CTC(torch.nn.Module):
         if nbytes == 0:
             raise ValueError(f"Wav2Vec2CTC: unsupported shape: {B} windows of {S} samples ({T} steps; the kernels take 1 .. {MAX_STEPS} steps)")
         image = self.packed_image()
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=windows.device)
+        ws = workspace if workspace is not None and workspace.numel() >= nbytes else torch.empty(nbytes, dtype=torch.uint8, device=windows.device)
         if out is None:
             out = torch.empty(B, T, self.vocab_size, dtype=torch.float32, device=windows.device)
-        hip.call("rn_asr_forward", C.byref(self.c_config()), hip.ptr(image), ws.data_ptr(), nbytes, hip.ptr(windows), B, S, hip.ptr(out),
-                 hip.stream())
+        tile = {"auto": 0, "32": 32, "128": 128}[switches.get("RN_ASR_TILE")]
+        hip.call("rn_asr_forward_tile", C.byref(self.c_config()), hip.ptr(image), ws.data_ptr(), ws.numel(), hip.ptr(windows), B, S, hip.ptr(out),
+                 tile, hip.stream())
         return out
 
     def forward(self, windows):

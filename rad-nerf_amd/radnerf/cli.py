@@ -12,7 +12,7 @@ Everything this module adds runs once per run, epoch or frame on the host; per t
 launch and Trainer.step, per frame ClipScene.render.  Flags keep the reference's names and defaults.  `-O` records fp16 and
 exp_eye; fp16 only records: the arithmetic follows the RN_* switches (radnerf/switches.py is their only reader, nothing is set
 here).  `--preload` is accepted and ignored (the set is always device-resident uint8).  Not built here, and refused: --gui, --asr*
-(live audio), --emb, --train_camera from this entry point.  --video writes Motion-JPEG in AVI with PCM audio and nothing else:
+(live audio: `python -m radnerf.live` renders from an audio stream, radnerf/live.py), --emb, --train_camera from this entry point.  --video writes Motion-JPEG in AVI with PCM audio and nothing else:
 no MP4 / H.264, no compressed audio; the .npy stays what any other encoder reads.  --aud_wav FILE --asr_weights FILE drive the
 clip from a 16 kHz .wav: its wav2vec2 logits (radnerf/asr.py) go where --aud's would, and with --video the same file is laid
 under the frames unless --audio_wav names another.

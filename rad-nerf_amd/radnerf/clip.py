@@ -72,6 +72,10 @@ class ClipScene(SyntheticScene):
                                  "value into its bias blocks -- render with audio_batch=0, or set opt.fix_eye")
         return None if self._eyes is None else self._eyes[0:1]
 
+    def _auds(self, i):
+        """Frame i's audio window; a scene whose audio comes from elsewhere (radnerf/live.py) overrides this."""
+        return get_audio_features(self.aud_features, self.opt.att, i)
+
     def render(self, i, want_u8=False, audio_code=None):
         """SyntheticScene.render; the frame's whole output dict stays at `last_out` (a caller that drives the scene through a
         renderer gets only the uint8 frame back, and the depth map is wanted next to it)."""
@@ -82,7 +86,7 @@ class ClipScene(SyntheticScene):
         """Inputs of model.render for frame i of the clip (everything resident on the device)."""
         i = int(i) % self.n_frames
         p = mirror_index(i, self.n_poses)
-        base = dict(auds=get_audio_features(self.aud_features, self.opt.att, i), bg_coords=self.bg_coords, poses=self.poses6[p:p + 1],
+        base = dict(auds=self._auds(i), bg_coords=self.bg_coords, poses=self.poses6[p:p + 1],
                     eye=None if self._eyes is None else self._eyes[p:p + 1], index=0, bg_color=self.bg_color,
                     poses_matrix=self.poses[p:p + 1])
         if lazy_rays and self._lazy_rays():

@@ -27,7 +27,7 @@ class FrameSink:
     def push(self, frame_u8, tag=None):
         """Enqueue the copy of a finished uint8 frame [H, W, 3] (device).  Blocks only when every slot holds a frame the host
         has not taken yet (then it waits for the oldest one's consumer: call pop())."""
-        if self._head - self._tail >= self.slots:
+        if self.full():
             raise RuntimeError("FrameSink is full: pop() frames before pushing more")
         slot = self._head % self.slots
         ready = torch.cuda.Event()
@@ -40,6 +40,10 @@ class FrameSink:
         frame_u8.record_stream(self.copy_stream)                      # the allocator must not recycle it before the copy ran
         self._done[slot], self._tag[slot] = done, tag
         self._head += 1
+
+    def full(self):
+        """Every slot holds a frame the host has not taken: pop() before the next push()."""
+        return self._head - self._tail >= self.slots
 
     def ready(self):
         """Frames whose copy has landed (non-blocking)."""

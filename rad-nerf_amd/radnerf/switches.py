@@ -8,7 +8,8 @@ import os
 # (name, default, accepted values, what the switch selects)
 TABLE = (
     ("RN_ADAM", "hip", ("hip", "torch"), "optimizer of `make_optimizer` on the GPU: `HipAdam` (one update kernel for all tensors) or torch's fused Adam"),
-    ("RN_ASR", "torch", ("torch", "hip"), "`Wav2Vec2CTC` (`radnerf/asr.py`) on the GPU in fp32: the same arithmetic in plain torch, or the wav2vec2 kernels (`rn_asr_*`, opt-in: bit-reproducible and independent of the batching, but 56 ms against 44 ms for a minute of audio at the real size, DESIGN.md §3)"),
+    ("RN_ASR", "torch", ("torch", "hip"), "`Wav2Vec2CTC` (`radnerf/asr.py`) on the GPU in fp32: the same arithmetic in plain torch, or the wav2vec2 kernels (`rn_asr_*`, opt-in: bit-reproducible and independent of the batching, but 47.5 ms against 43.4 ms for a minute of audio at the real size and 11.4 ms against 6.5 ms for one live window, DESIGN.md §3)"),
+    ("RN_ASR_TILE", "auto", ("auto", "32", "128"), "with `RN_ASR=hip`: tiling of the wav2vec2 matrix products: `128` (128 x 128 tiles through LDS), `32` (one wave per 32 x 32 tile, for the few rows of one live window) or per product from its shape and the device's compute-unit count; both tilings run the same chain over k per output, so the logits have the same bits under every value"),
     ("RN_AUDIO_TRAIN", "hip", ("hip", "torch"), "`encode_audio` on the GPU: the audio kernels (`radnerf/audio.py`) or the `nn.Module` path"),
     ("RN_DENSE_BUDGET_MB", "384", ("160", "384", "896", "2304"), "with `RN_DENSE_LEVELS=1`: the most memory, in MiB, the dense image of the xyz table may take (`opt.dense_budget_mb`, any number, overrides it); for the T = 2^19 hash grid in fp32 the four values store levels 5-8 (149 MiB), 5-9 (343 MiB), 5-10 (857 MiB) and 5-11 (2215 MiB) as lattices, fp16 tables take half"),
     ("RN_DENSE_LEVELS", "1", ("1", "0"), "fused inference engine: a frame whose xyz table is that of the frame before reads the coarser hashed levels from a dense image built once (`rn_grid_dense_build`: each such level stored as its whole lattice, so neighbouring samples share cache lines; same features, same bits); `0`: every frame gathers from the hashed table"),

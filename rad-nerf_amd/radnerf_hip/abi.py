@@ -243,7 +243,10 @@ FUNCTIONS = {
     "rn_asr_pack": (_int, [_P(AsrConfigT), _ptr, _u32, _ptr, _ptr]),
     "rn_asr_workspace": (_sz, [_P(AsrConfigT), _u32, _u32]),
     "rn_asr_forward": (_int, [_P(AsrConfigT), _ptr, _ptr, _sz, _ptr, _u32, _u32, _ptr, _ptr]),
+    "rn_asr_forward_tile": (_int, [_P(AsrConfigT), _ptr, _ptr, _sz, _ptr, _u32, _u32, _ptr, _u32, _ptr]),
     "rn_asr_features": (_int, [_ptr, _sz, _u32, _P(_u32), _u32, _ptr, _u32, _ptr]),
+    "rn_asr_ring_push": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _u32, _u32, _u32, _ptr]),
+    "rn_asr_ring_window": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _ptr]),
     # ---- include/radnerf_train.h
     "rn_train_head_image_floats": (_sz, []),
     "rn_train_head_workspace_floats": (_sz, [_u32]),
