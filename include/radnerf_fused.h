@@ -577,6 +577,27 @@ int rn_asr_ring_push(const float *logits, uint32_t T, uint32_t C, uint32_t left,
                      uint32_t first_row, uint32_t zero_rows, rn_stream_t stream);
 int rn_asr_ring_window(const float *ring, uint32_t ring_rows, uint32_t C, uint32_t k, uint32_t n_slices, float *out, rn_stream_t stream);
 
+/* ---- any PCM audio -> the 16 kHz mono float signal the wav2vec2 path takes (csrc/rn_resample.hip, radnerf/resample.py) ------------
+ *   rn_pcm_decode  n_frames interleaved frames of `channels` samples in `format` -> out[i] = the FIRST channel of frame i as float:
+ *                  RN_PCM_U8 (v - 128) / 128, RN_PCM_S16LE v / 2^15, RN_PCM_S24LE v / 2^23, RN_PCM_S32LE float(v) * 2^-31 (the
+ *                  conversion rounds to nearest even, the scaling is exact), RN_PCM_F32LE the four bytes as they are.  `raw` needs
+ *                  byte alignment only.  n_frames = 0: RN_OK, no launch.
+ *   rn_resample    band-limited interpolation by a rational ratio L / M (output rate / input rate, in lowest terms) with a table
+ *                  of 2 W + 1 taps per phase.  Output t sits at input time n + p / L, n = (t M) / L, p = (t M) % L in int64:
+ *                      y[t - t0] = sum over k = -W .. W of table[(k + W) * L + p] * X(n + k),   t = t0 .. t0 + n_out - 1
+ *                  one fmaf chain over k ascending from an accumulator of 0.  X(j) = x[j - origin] where 0 <= j - origin < n_buf,
+ *                  else 0: element 0 of the buffer holds input index `origin`.  `table` is TAP-major, [2 W + 1][L] floats (the
+ *                  transpose of resample.phase_table's array).  A sample's bits do not depend on t0, origin, n_out or the tiling.
+ *                  n_out = 0: RN_OK, no launch.  The staged input span of one tile, 255 M / L + 2 W + 2 floats, must fit 64 KiB. */
+#define RN_PCM_U8 0
+#define RN_PCM_S16LE 1
+#define RN_PCM_S24LE 2
+#define RN_PCM_S32LE 3
+#define RN_PCM_F32LE 4
+int rn_pcm_decode(const uint8_t *raw, size_t n_frames, uint32_t channels, int format, float *out, rn_stream_t stream);
+int rn_resample(const float *x, size_t n_buf, int64_t origin, const float *table, uint32_t L, uint32_t M, uint32_t W, int64_t t0,
+                size_t n_out, float *y, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

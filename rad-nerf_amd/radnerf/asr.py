@@ -3,7 +3,7 @@ torch.nn.Module, plus the window loop around it restated as a pure function.
 
     asr = Wav2Vec2CTC.from_files("w2v.pth", "config.json").cuda()        # nothing is fetched: the user names the files
     feats = asr.features_from_samples(read_wav("intro.wav"))             # [F,16,C], the layout of aud_eo.npy
-    python -m radnerf.asr --wav intro.wav --weights w2v.pth [--config config.json] [-l 10 -m 50 -r 10] --out aud_eo.npy
+    python -m radnerf.asr --wav intro.wav --weights w2v.pth [--config config.json] [-l 10 -m 50 -r 10] [--resample] --out aud_eo.npy
 
 The model is `transformers`' Wav2Vec2ForCTC with feat_extract_norm = "layer", conv_bias = True and do_stable_layer_norm = True in
 eval mode without an attention mask (asr.py:324-328) -- the family both of the reference's --asr_model names belong to:
@@ -32,8 +32,8 @@ A terminal window shorter than the encoder's receptive field (400 samples) contr
 inside the first convolution there.
 
 The live loop around this model -- samples arriving 20 ms at a time, one window per m chunks into a ring of logits, one attention
-window per video frame -- is radnerf/live.py.  Microphone capture and playback, the text decode, resampling and DeepSpeech features
-are not built here.
+window per video frame -- is radnerf/live.py.  Audio at another rate or in another sample format goes through radnerf/resample.py
+first (--resample).  Microphone capture and playback, the text decode and DeepSpeech features are not built here.
 """
 import ctypes as C
 import json
@@ -208,7 +208,7 @@ def check_wav(path):
     if width != 2:
         raise ValueError(f"{path} has {8 * width}-bit samples; only PCM16 is read")
     if rate != SAMPLE_RATE:
-        raise ValueError(f"{path} is sampled at {rate} Hz; resample it to {SAMPLE_RATE} Hz first (resampling is not built here)")
+        raise ValueError(f"{path} is sampled at {rate} Hz; resample it to {SAMPLE_RATE} Hz first, or pass --resample (radnerf/resample.py)")
     return channels, n
 
 
@@ -466,8 +466,13 @@ def main(argv=None, log=print):
     p.add_argument("-m", type=int, default=50)
     p.add_argument("-r", type=int, default=10)
     p.add_argument("--out", type=str, required=True)
+    p.add_argument("--resample", action="store_true", help="take any PCM or float .wav, resampled to 16 kHz (radnerf/resample.py)")
     opt = p.parse_args(argv)
-    x = read_wav(opt.wav)
+    if opt.resample:
+        from .resample import samples_16k
+        x = samples_16k(opt.wav, "cuda" if torch.cuda.is_available() else "cpu")
+    else:
+        x = read_wav(opt.wav)
     model = Wav2Vec2CTC.from_files(opt.weights, opt.config or None)
     if torch.cuda.is_available():
         model = model.cuda()

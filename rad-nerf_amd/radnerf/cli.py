@@ -15,7 +15,9 @@ here).  `--preload` is accepted and ignored (the set is always device-resident u
 (live audio: `python -m radnerf.live` renders from an audio stream, radnerf/live.py), --emb, --train_camera from this entry point.  --video writes Motion-JPEG in AVI with PCM audio and nothing else:
 no MP4 / H.264, no compressed audio; the .npy stays what any other encoder reads.  --aud_wav FILE --asr_weights FILE drive the
 clip from a 16 kHz .wav: its wav2vec2 logits (radnerf/asr.py) go where --aud's would, and with --video the same file is laid
-under the frames unless --audio_wav names another.
+under the frames unless --audio_wav names another.  With --resample, --aud_wav takes any PCM or float .wav at any rate: it is
+decoded and resampled to 16 kHz on the device (radnerf/resample.py); a file the AVI writer cannot carry (float samples) goes under
+the frames as the resampled signal in PCM16.
 Continuing from a checkpoint restores model, optimizer, EMA, epoch and step count; it is NOT bit-identical to an uninterrupted
 run, because the occupancy refresh draws from Python's `random`.
 """
@@ -98,6 +100,7 @@ def _parser():
     p.add_argument("--video_fps", type=float, default=25, help="frame rate of --video (not --fps, the reference's ASR rate)")
     p.add_argument("--audio_wav", type=str, default="", help="PCM .wav to lay under --video")
     p.add_argument("--aud_wav", type=str, default="", help="16 kHz PCM .wav that drives the clip: its wav2vec2 logits replace --aud (radnerf/asr.py)")
+    p.add_argument("--resample", action="store_true", help="--aud_wav: take any PCM or float .wav, resampled to 16 kHz on the device")
     p.add_argument("--asr_weights", type=str, default="", help="state dict of Wav2Vec2ForCTC for --aud_wav; nothing is fetched")
     p.add_argument("--asr_config", type=str, default="", help="the model's config.json (default: the large shape)")
     p.add_argument("-l", type=int, default=10, help="--aud_wav: chunks of left context per window")
@@ -155,9 +158,13 @@ def parse(argv=None):
                 p.error(f"--{flag}: {getattr(opt, flag)} is not a file")
         if opt.l < 0 or opt.r < 0 or opt.m < 1:
             p.error("-l and -r must not be negative, -m must be positive")
-        from radnerf.asr import check_wav as check_wav16k
         try:
-            check_wav16k(opt.aud_wav)
+            if opt.resample:
+                from radnerf import resample
+                resample.plan(resample.check_audio(opt.aud_wav)[0])
+            else:
+                from radnerf.asr import check_wav as check_wav16k
+                check_wav16k(opt.aud_wav)
         except ValueError as e:
             p.error(f"--aud_wav: {e}")
     elif opt.asr_weights or opt.asr_config:
@@ -298,20 +305,38 @@ def avi_path(out_dir, name):
 def _video_sink(opt, H, W, device, out_dir, name):
     from radnerf.video import AviWriter, JpegEncoder, VideoSink
     os.makedirs(out_dir, exist_ok=True)
-    writer = AviWriter(avi_path(out_dir, name), H, W, opt.video_fps, audio=opt.audio_wav or opt.aud_wav or None)
+    writer = AviWriter(avi_path(out_dir, name), H, W, opt.video_fps, audio=opt.audio_wav or getattr(opt, "audio_track", None) or opt.aud_wav or None)
     return VideoSink(writer, JpegEncoder(H, W, opt.video_quality, opt.video_subsampling), batch=8, device=device)
+
+
+def resampled_track(path, samples, log=print):
+    """--video with --resample: None when the AVI writer can carry `path` itself (integer PCM at any rate), else the resampled
+    signal as (rate, channels, bytes per sample, PCM16 bytes), with one [INFO] line.  samples: the 16 kHz signal, or a callable
+    that gives it (asked only when the track is needed)."""
+    from radnerf.resample import pcm16_track
+    from radnerf.video import check_wav
+    try:
+        check_wav(path)
+        return None
+    except ValueError:
+        log(f"[INFO] {path}: the video's audio track is the resampled signal, 16 kHz mono PCM16 (the AVI writer takes what the `wave` module reads as PCM)")
+        return pcm16_track(samples() if callable(samples) else samples)
 
 
 def wav_features(opt, model, device, log=print):
     """--aud_wav: the wav2vec2 logits of the file as [F,C,16] on the device, left at opt.aud_features where datafiles' loaders take
     the clip's audio from (in opt.aud's place).  The logit width must be the audio net's input width."""
     from radnerf.asr import Wav2Vec2CTC, read_wav
+    from radnerf.resample import samples_16k
     asr = Wav2Vec2CTC.from_files(opt.asr_weights, opt.asr_config or None)
     want = int(model.audio_in_dim)
     if asr.vocab_size != want:
         raise ValueError(f"--aud_wav: the model of --asr_weights gives logits of width {asr.vocab_size}, the audio net of this checkpoint "
                          f"takes {want} (--asr_model picks it)")
-    feats = asr.to(device).features_from_samples(read_wav(opt.aud_wav), opt.l, opt.m, opt.r, layout="FC16")
+    samples = samples_16k(opt.aud_wav, device) if opt.resample else read_wav(opt.aud_wav)
+    feats = asr.to(device).features_from_samples(samples, opt.l, opt.m, opt.r, layout="FC16")
+    if opt.resample and opt.video and not opt.audio_wav:
+        opt.audio_track = resampled_track(opt.aud_wav, samples, log)
     log(f"[INFO] {opt.aud_wav}: {feats.shape[0]} audio frames of width {feats.shape[1]}")
     opt.aud_features = feats
     return feats

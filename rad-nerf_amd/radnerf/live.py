@@ -24,9 +24,11 @@ schedule    the loop: warm-up pushes, then per frame two pushes and one window; 
             that are left.
 LiveScene   ClipScene whose audio comes from a LiveASR: the same frame dict, the same ray_source path.
 main        the command line: --wav FILE or --pcm - (raw s16le 16 kHz mono); results/<name>.npy, --video, --raw_out FILE|-,
-            --realtime.
+            --realtime.  --wav FILE --resample takes any PCM or float .wav, --pcm - --pcm_rate R --pcm_format F --pcm_channels C any
+            raw stream: resampled_chunks pulls 20 ms source blocks through a resample.Resampler on the device and hands the loop
+            the same chunks of 320 samples at 16 kHz, (W + 1) / R seconds later (the filter's right wing).
 
-Not built: microphone capture, playback, the text decode, resampling, the GUI.
+Not built: microphone capture, playback, the text decode, the GUI.
 """
 import os
 import sys
@@ -289,6 +291,35 @@ def pcm_chunks(stream):
     return read_chunk
 
 
+def block_reader(stream, rate, format, channels):
+    """read_source for resampled_chunks over a binary stream: one blocking read of a 20 ms block, round(rate / 50) frames, per call."""
+    from .resample import FORMATS
+    nbytes = max(1, int(round(rate / CHUNK_RATE))) * int(channels) * FORMATS[format]
+    return lambda: stream.read(nbytes)
+
+
+def resampled_chunks(read_source, resampler):
+    """read_chunk over a source at any rate and format: read_source() gives the next raw block (bytes in the resampler's format;
+    a short or empty block ends the source).  Blocks are pushed through the resampler until 320 output samples are ready and exactly
+    320 are handed out; once the source has ended and been flushed, what is left goes out in whole chunks and then once short
+    (possibly empty) -- the only short chunk, which schedule() reads as the end of the stream.  The samples stay on the resampler's
+    device."""
+    from .resample import FORMATS
+    state = dict(ready=torch.zeros(0, dtype=torch.float32, device=resampler.device), ended=False)
+    block = max(1, int(round(resampler.src / CHUNK_RATE))) * resampler.channels * FORMATS[resampler.format]      # bytes of a whole block
+    def read_chunk():
+        while not state["ended"] and state["ready"].numel() < CHUNK:
+            raw = read_source()
+            got = [resampler.push(raw)] if len(raw) else []
+            if len(raw) < block:
+                state["ended"] = True
+                got.append(resampler.flush())
+            state["ready"] = torch.cat([state["ready"]] + got)
+        out, state["ready"] = state["ready"][:CHUNK], state["ready"][CHUNK:]
+        return out
+    return read_chunk
+
+
 class LiveScene(ClipScene):
     def __init__(self, model, clip, opt, device, live):
         """clip: the poses, eye values, intrinsics and background (its audio is not read); live: the LiveASR the windows come from."""
@@ -311,8 +342,11 @@ def _live_parser():
     import argparse
     p = argparse.ArgumentParser(prog="python -m radnerf.live", add_help=False, allow_abbrev=False,
                                 description="render a clip from an audio stream; every other flag is radnerf.cli's (a --test render)")
-    p.add_argument("--wav", type=str, default="", help="16 kHz PCM16 .wav to stream")
+    p.add_argument("--wav", type=str, default="", help="16 kHz PCM16 .wav to stream; with --resample any PCM or float .wav")
     p.add_argument("--pcm", type=str, default="", help="'-': raw s16le 16 kHz mono on stdin, two chunks per frame (or a file / FIFO)")
+    p.add_argument("--pcm_rate", type=int, default=SAMPLE_RATE, help="--pcm: the stream's sample rate; another than 16000 is resampled on the device")
+    p.add_argument("--pcm_format", type=str, default="s16le", choices=("u8", "s16le", "s24le", "s32le", "f32le"), help="--pcm: the sample format")
+    p.add_argument("--pcm_channels", type=int, default=1, help="--pcm: interleaved channels; the first is taken")
     p.add_argument("--raw_out", type=str, default="", help="FILE or '-': the frames as rgb24, written as they are produced")
     p.add_argument("--realtime", action="store_true", help="hold frame k back until k / video_fps seconds after the first")
     p.add_argument("--fps", type=int, default=CHUNK_RATE, help="audio chunks per second; only 50 (20 ms chunks) is built")
@@ -354,11 +388,22 @@ def parse(argv=None):
             lp.error(f"--{flag}: {getattr(opt, flag)} is not a file")
     if opt.pcm and opt.pcm != "-" and not os.path.exists(opt.pcm):
         lp.error(f"--pcm: {opt.pcm} does not exist")
-    if opt.wav:
-        try:
+    if not opt.pcm and (opt.pcm_rate, opt.pcm_format, opt.pcm_channels) != (SAMPLE_RATE, "s16le", 1):
+        lp.error("--pcm_rate / --pcm_format / --pcm_channels describe the stream of --pcm; a --wav file describes itself")
+    if opt.pcm_channels < 1:
+        lp.error(f"--pcm_channels {opt.pcm_channels}: at least one channel")
+    opt.pcm_resample = bool(opt.pcm) and (opt.pcm_rate, opt.pcm_format, opt.pcm_channels) != (SAMPLE_RATE, "s16le", 1)
+    try:
+        if opt.pcm_resample:
+            from .resample import plan as resample_plan
+            resample_plan(opt.pcm_rate)
+        if opt.wav and opt.resample:
+            from . import resample
+            resample.plan(resample.check_audio(opt.wav)[0])
+        elif opt.wav:
             check_wav(opt.wav)
-        except ValueError as e:
-            lp.error(f"--wav: {e}")
+    except ValueError as e:
+        lp.error(f"{'--wav' if opt.wav else '--pcm_rate'}: {e}")
     try:
         check_schedule(opt.l, opt.m, opt.r, opt.ring_windows, opt.tail)
     except ValueError as e:
@@ -393,17 +438,33 @@ def main(argv=None, log=None, decode=None, stdin=None):
     renderer = FrameParallelRenderer(scene, rank=0, world=1, dist=None, gather_to="rank0")
     model.enc_a = None
 
-    if opt.wav:
+    latency = live.warm_up_chunks / CHUNK_RATE
+    if opt.wav and opt.resample:
+        import io
+        from .resample import Resampler, read_audio
+        rate, channels, fmt, raw = read_audio(opt.wav)
+        resampler = Resampler(rate, SAMPLE_RATE, fmt, channels, device=device)
+        read_chunk = resampled_chunks(block_reader(io.BytesIO(raw), rate, fmt, channels), resampler)
+        latency += resampler.latency
+        if opt.video and not opt.audio_wav:
+            opt.audio_track = cli.resampled_track(opt.wav, lambda: resampler.whole(raw), log)
+    elif opt.wav:
         read_chunk = chunks_of(read_wav(opt.wav))
     else:
-        read_chunk = pcm_chunks(stdin if stdin is not None else (sys.stdin.buffer if opt.pcm == "-" else open(opt.pcm, "rb")))
-    latency = live.warm_up_chunks / CHUNK_RATE
+        stream = stdin if stdin is not None else (sys.stdin.buffer if opt.pcm == "-" else open(opt.pcm, "rb"))
+        if opt.pcm_resample:
+            from .resample import Resampler
+            resampler = Resampler(opt.pcm_rate, SAMPLE_RATE, opt.pcm_format, opt.pcm_channels, device=device)
+            read_chunk = resampled_chunks(block_reader(stream, opt.pcm_rate, opt.pcm_format, opt.pcm_channels), resampler)
+            latency += resampler.latency
+        else:
+            read_chunk = pcm_chunks(stream)
     log(f"[INFO] live ASR: windows of {opt.l} + {opt.m} + {opt.r} chunks, expected latency = {latency:.6f}s")
 
     name = f"{opt.name}_ep{epoch:04d}_live"
     out_dir = os.path.join(opt.workspace, "results")
     os.makedirs(out_dir, exist_ok=True)
-    if opt.video and not opt.audio_wav:
+    if opt.video and not opt.audio_wav and getattr(opt, "audio_track", None) is None:
         opt.audio_wav = opt.wav                                         # the streamed file is laid under its own frames
     sink = cli._video_sink(opt, scene.H, scene.W, device, out_dir, name) if opt.video else None
     raw = host = None

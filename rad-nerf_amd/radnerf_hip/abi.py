@@ -25,6 +25,7 @@ RN_TORSO_PLAN_MAX_BYTES = 256 << 20
 RN_LOOP_FIRST_MARCHED, RN_LOOP_CLOSE_FRAME, RN_LOOP_COOP = 1, 2, 4
 RN_HEAD_ST_ACTIVE, RN_HEAD_ST_ITERS, RN_HEAD_ST_LIVE, RN_HEAD_ST_SLOTS = 4, 16, 17, 18
 RN_HEAD_ST_UNFINISHED, RN_HEAD_ST_STALLED, RN_HEAD_ST_HIST = 19, 22, 32
+RN_PCM_U8, RN_PCM_S16LE, RN_PCM_S24LE, RN_PCM_S32LE, RN_PCM_F32LE = 0, 1, 2, 3, 4
 
 
 class GridT(C.Structure):
@@ -247,6 +248,8 @@ FUNCTIONS = {
     "rn_asr_features": (_int, [_ptr, _sz, _u32, _P(_u32), _u32, _ptr, _u32, _ptr]),
     "rn_asr_ring_push": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _u32, _u32, _u32, _ptr]),
     "rn_asr_ring_window": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _ptr]),
+    "rn_pcm_decode": (_int, [_ptr, _sz, _u32, _int, _ptr, _ptr]),
+    "rn_resample": (_int, [_ptr, _sz, _i64, _ptr, _u32, _u32, _u32, _i64, _sz, _ptr, _ptr]),
     # ---- include/radnerf_train.h
     "rn_train_head_image_floats": (_sz, []),
     "rn_train_head_workspace_floats": (_sz, [_u32]),
