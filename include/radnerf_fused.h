@@ -598,6 +598,31 @@ int rn_pcm_decode(const uint8_t *raw, size_t n_frames, uint32_t channels, int fo
 int rn_resample(const float *x, size_t n_buf, int64_t origin, const float *table, uint32_t L, uint32_t M, uint32_t W, int64_t t0,
                 size_t n_out, float *y, rn_stream_t stream);
 
+/* ---- a dataset directory's image files: background plate, gt and torso layers (data_utils/process.py:63-237) ---------------------
+ * Integer and table-driven throughout, csrc/rn_prep_dev.h states every convention: a result is a function of the inputs alone.
+ * Images are uint8 RGB(A), row-major; labels [F,H,W] uint8: 0 other, 1 head, 2 neck, 3 torso, 4 background.  F, H, W >= 1, sides
+ * <= 16384 and F * H * W < 2^31; anything else, or a null pointer, is RN_ERR_INVALID_ARG before a launch (rn_prep_workspace: 0).
+ *
+ *   rn_prep_workspace         bytes of scratch any of the three calls needs for F frames (fill: F = 1); 16-byte aligned.
+ *   rn_prep_plate_accumulate  per frame d2 = the exact squared distance of every pixel to the nearest pixel whose label is not 4
+ *                             (2^30 everywhere in a frame without one).  Frames in order: where d2 > best_d2 [H,W], best_d2 = d2,
+ *                             best_id [H,W] = frame0 + f and plate [H,W,3] = the frame's pixel.  The caller sets best_d2 to -1 before
+ *                             the first batch; any split of the frames into batches gives the same three arrays.
+ *   rn_prep_plate_fill        sure = best_d2 > thresh_d2.  *n_sure (device) = the number of sure pixels; every other pixel of
+ *                             `plate` takes the colour of its nearest sure pixel -- of equidistant ones the smallest row, then the
+ *                             smallest column.  n_sure = 0: plate is left as it is.
+ *   rn_prep_layers            gt [F,H,W,3] = the frame with the plate where the label is 4.  torso [F,H,W,4] = gt with the plate under
+ *                             the head, the two vertical in-paints darkened by darken[k] (53 doubles from the host:
+ *                             0.98 ** k), the 5 x 5 blur on the neck in-paint's pixels, alpha 255 on the dilated neck, the torso and
+ *                             both in-paints, RGBA = 0 elsewhere. */
+size_t rn_prep_workspace(uint32_t F, uint32_t H, uint32_t W);
+int rn_prep_plate_accumulate(const uint8_t *frames, const uint8_t *labels, uint32_t F, uint32_t H, uint32_t W, uint32_t frame0,
+                             int32_t *best_d2, int32_t *best_id, uint8_t *plate, void *workspace, rn_stream_t stream);
+int rn_prep_plate_fill(const int32_t *best_d2, uint8_t *plate, uint32_t H, uint32_t W, int32_t thresh_d2, uint32_t *n_sure, void *workspace,
+                       rn_stream_t stream);
+int rn_prep_layers(const uint8_t *frames, const uint8_t *labels, const uint8_t *plate, const double *darken, uint32_t F, uint32_t H, uint32_t W,
+                   uint8_t *gt, uint8_t *torso, void *workspace, rn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,10 @@ FUNCTIONS = {
     "rn_asr_ring_window": (_int, [_ptr, _u32, _u32, _u32, _u32, _ptr, _ptr]),
     "rn_pcm_decode": (_int, [_ptr, _sz, _u32, _int, _ptr, _ptr]),
     "rn_resample": (_int, [_ptr, _sz, _i64, _ptr, _u32, _u32, _u32, _i64, _sz, _ptr, _ptr]),
+    "rn_prep_workspace": (_sz, [_u32, _u32, _u32]),
+    "rn_prep_plate_accumulate": (_int, [_ptr, _ptr, _u32, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "rn_prep_plate_fill": (_int, [_ptr, _ptr, _u32, _u32, C.c_int32, _ptr, _ptr, _ptr]),
+    "rn_prep_layers": (_int, [_ptr, _ptr, _ptr, _ptr, _u32, _u32, _u32, _ptr, _ptr, _ptr, _ptr]),
     # ---- include/radnerf_train.h
     "rn_train_head_image_floats": (_sz, []),
     "rn_train_head_workspace_floats": (_sz, [_u32]),
