@@ -55,10 +55,11 @@ DCT = np.where(_k[:, None] == 0, np.sqrt(1 / 8), 0.5 * np.cos((2 * _k[None, :] +
 
 
 # ------------------------------------------------------------------------------------------------------------ frames
-def scene(H, W, seed):
+def scene(H, W, seed, turned=False):
     """uint8 [H, W, 3]: an RGB gradient, a flat disc, uniform noise (top left), random pure black / white (bottom left) and an
     8-pixel checkerboard (bottom right; on the block grid, every other 16 rows shifted by half a cell): together they reach every
-    branch of the coder."""
+    branch of the coder.  turned: by 180 degrees, so that the scan ends in the noise and not in the checkerboard, whose chroma
+    blocks code to zero bits alone."""
     rng = np.random.default_rng(seed)
     y, x = np.mgrid[0:H, 0:W]
     img = np.stack([255 * x / max(W - 1, 1), 255 * y / max(H - 1, 1), 255 * (x + y) / max(H + W - 2, 1)], -1)
@@ -71,7 +72,80 @@ def scene(H, W, seed):
     br = (y >= H // 2) & (x >= 2 * W // 3)
     check = (((x + 4 * ((y // 16) % 2)) // 8 + y // 8) % 2) * 255
     img[br] = check[br][:, None]
-    return np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(img[::-1, ::-1]) if turned else img
+
+
+def dc_differences(coefs, sub):
+    """int64 [blocks]: the DC difference every block codes (against the previous block of its component, 0 before the first)."""
+    coefs = np.asarray(coefs).reshape(-1, 64)
+    comps = np.tile(block_layout(1, 1, sub)[3], len(coefs) // block_layout(1, 1, sub)[2])
+    out = np.zeros(len(coefs), np.int64)
+    for c in range(3):
+        out[comps == c] = np.diff(coefs[comps == c, 0].astype(np.int64), prepend=0)
+    return out
+
+
+def block_checker(H, W, cell):
+    """uint8 [H, W, 3]: pure black and pure white cells of `cell` pixels from the origin (cell = 8 at 4:4:4, 16 at 4:2:0: on the
+    block grid).  Every block is flat: DC -1024 or 1016 at quality 100, a difference of 2040 (category 11) between neighbours, every
+    AC quotient zero up to rounding noise: nothing is near a tie."""
+    y, x = np.mgrid[0:H, 0:W]
+    v = (((y // cell + x // cell) % 2) * 255).astype(np.uint8)
+    return np.repeat(v[..., None], 3, -1)
+
+
+def dense_coefficients(blocks, seed):
+    """int16 [blocks, 64] (zigzag) for the entropy coder alone: every AC of {+-1023, +-511, 255}, DC -1024 and 1023 in turns of three
+    blocks (at 4:4:4 every component's predictor difference is then +-2047).  The positive values' extra bits are all ones, so
+    about a fifth of the scan's bytes are 0xFF."""
+    rng = np.random.default_rng(seed)
+    out = rng.choice(np.array([-1023, -511, 255, 511, 1023], np.int16), (blocks, 64))
+    out[:, 0] = np.where((np.arange(blocks) // 3) % 2 == 0, -1024, 1023)
+    return out
+
+
+def unstuffed(scan):
+    """uint8 array of a scan's bytes before stuffing."""
+    return np.frombuffer(scan.replace(b"\xff\x00", b"\xff"), np.uint8)
+
+
+def ff_seams(scan, chunk=4096, vector=16):
+    """Where the 0xFF bytes of a scan lie in its unstuffed stream: dict of counts -- 0xFF bytes in all (`ff`), at the last byte of a
+    chunk / of a vector (`chunk_end`, `vector_end`), and pairs of 0xFF on both sides of such a seam (`chunk_pair`, `vector_pair`)."""
+    ff = unstuffed(scan) == 0xFF
+    at = np.flatnonzero(ff[:-1])
+    pair = at[ff[at + 1]]
+    return dict(ff=int(ff.sum()), chunk_end=int((at % chunk == chunk - 1).sum()), vector_end=int((at % vector == vector - 1).sum()),
+                chunk_pair=int((pair % chunk == chunk - 1).sum()), vector_pair=int((pair % vector == vector - 1).sum()))
+
+
+# Inputs of the tests that a CPU test (tests/test_video.py) holds to their conditions and the GPU tests (tests/test_gpu_video.py) run.
+# (shape, subsampling, blocks): on both sides of the 1024 entries one round of the device's scan takes (1024 is no multiple of 3 or 6),
+# and past two rounds.  They run on turned scenes: a round that ends in blocks of zero bits would not show a lost carry
+ROUND_SHAPES = [((88, 248), "444", 1023), ((144, 152), "444", 1026), ((160, 272), "420", 1020), ((144, 304), "420", 1026),
+                ((144, 304), "444", 2052)]
+LOW_SHAPES = [((17, 19), "420"), ((17, 19), "444"), ((40, 24), "420"), ((40, 24), "444"), ((144, 304), "420")]
+LOW_QUALITIES = [1, 10, 49]                                     # the 5000 / q branch of the IJG rule; every step is 255 at 1
+CHECKERS = [((48, 64), "444", 8), ((48, 64), "420", 16), ((88, 248), "444", 8), ((160, 272), "420", 16)]      # (shape, subsampling, cell)
+# Sides of 1, below one block, of exactly one MCU: {shape: the seeds of `scene` in use}; the reference alone flags at most 1.6 % of
+# the coefficients of each at both subsamplings and qualities 50 and 100, so the tie rule's 2 % cap judges the device and not the seed.
+TINY_SEEDS = {(1, 1): (1, 2, 3), (1, 40): (1, 2, 3), (40, 1): (1, 2, 3), (7, 33): (1, 2, 3), (8, 8): (2, 4, 6), (16, 16): (2, 4, 7),
+              (3, 200): (1, 2, 3)}
+# dense_coefficients seeds of the two long frames at 144 x 152, 4:4:4 (1026 blocks): each scan has a 0xFF at the end of a 4096-byte chunk
+# and of a 16-byte vector, and a pair of 0xFF across both kinds of seam
+DENSE_HW, DENSE_SEEDS = (144, 152), (1, 5)
+# dense_coefficients seed of an 8 x 8 frame at 4:4:4 (3 blocks) whose last byte holds one bit of data and seven of padding, and is 0xFF
+PADDED_FF_SEED = 8
+
+
+def dense_batch():
+    """int16 [3, 1026, 64]: the two long frames and a short one (zeros but for every 100th block) behind them."""
+    blocks = block_layout(*DENSE_HW, "444")
+    blocks = blocks[0] * blocks[1] * blocks[2]
+    short = np.zeros((blocks, 64), np.int16)
+    short[::100] = dense_coefficients(blocks, 3)[::100]
+    return np.stack([dense_coefficients(blocks, DENSE_SEEDS[0]), dense_coefficients(blocks, DENSE_SEEDS[1]), short])
 
 
 # ----------------------------------------------------------------------------------------------------------- encoder
@@ -186,7 +260,8 @@ class BitWriter:
 
 
 def entropy(coefs, sub, stats=None):
-    """The scan of one frame: coefs int [blocks, 64] (zigzag) -> bytes.  stats: a dict that collects symbol counts."""
+    """The scan of one frame: coefs int [blocks, 64] (zigzag) -> bytes.  stats: a dict that collects symbol counts (and the
+    last scan's `pad_bits`)."""
     per = 6 if str(sub) == "420" else 3
     comps = [0, 0, 0, 0, 1, 2] if per == 6 else [0, 1, 2]
     st = dict(zrl=0, eob=0, c63=0, dc11=0, ac10=0, stuffed=0, blocks=0) if stats is None else stats
@@ -224,6 +299,7 @@ def entropy(coefs, sub, stats=None):
         else:
             st["c63"] += 1
         st["blocks"] += 1
+    st["pad_bits"] = -w.n % 8                                     # of this scan: how many 1-bits fill its last byte
     w.flush()
     st["stuffed"] += w.stuffed
     return bytes(w.out)

@@ -1,6 +1,7 @@
 """Video write-out without a GPU (rad-nerf_amd/radnerf/video.py, csrc/rn_jpeg.hip, csrc/rn_jpeg_dev.h):
   * the float64 restatement of tests/jpegref64.py against libjpeg (PIL): its files decode, its quality is PIL's own, its decoder
-    agrees with PIL's, and the test frames reach every branch of the coder;
+    agrees with PIL's, and the test frames reach every branch of the coder; the conditions on the inputs of tests/test_gpu_video.py
+    (few ties, 0xFF bytes on the seams, the largest DC difference);
   * csrc/rn_jpeg_dev.h built into a stand-alone host program against that restatement: coefficients under the tie rule, scan bytes
     byte for byte;
   * the headers video.py writes, AviWriter through the RIFF reader, the argument checks of the entry points and of the command line."""
@@ -25,11 +26,17 @@ SIZES = [(48, 64), (17, 19), (90, 90), (40, 24)]
 SUBS = ["420", "444"]
 QUALITIES = [50, 75, 90, 100]
 CASES = [(hw, sub, q) for hw in SIZES for sub in SUBS for q in QUALITIES]
+# what the device runs beyond CASES (tests/test_gpu_video.py): qualities below 50 on two small shapes and past one scan round, and
+# the degenerate sizes; a degenerate size uses its first seed of R.TINY_SEEDS
+LOW_CASES = [(hw, sub, q) for hw, sub in R.LOW_SHAPES for q in R.LOW_QUALITIES]
+TINY_CASES = [(hw, sub, q) for hw in R.TINY_SEEDS for sub in SUBS for q in (50, 100)]
 
 
 @pytest.fixture(scope="module")
 def frames():
-    return {hw: R.scene(*hw, 1) for hw in SIZES}
+    out = {hw: R.scene(*hw, 1) for hw in SIZES + [(144, 304)]}
+    out.update({hw: R.scene(*hw, seeds[0]) for hw, seeds in R.TINY_SEEDS.items()})
+    return out
 
 
 @pytest.fixture(scope="module")
@@ -97,7 +104,7 @@ def test_the_cases_reach_every_branch_of_the_coder(encoded):
 
 
 def test_reference_round_trips_its_own_coefficients(frames):
-    for hw, sub, q in [((17, 19), "420", 100), ((40, 24), "444", 50)]:
+    for hw, sub, q in [((17, 19), "420", 100), ((40, 24), "444", 50)] + LOW_CASES + TINY_CASES:
         want = R.coefficients(frames[hw], q, sub)
         _, got, _, _ = R.decode_coefficients(R.encode(frames[hw], q, sub))
         assert np.array_equal(got, want)
@@ -110,6 +117,101 @@ def test_reference_flags_few_coefficients(frames):
                 for seed in (1, 2, 3))
     print(f"largest flagged share {worst:.4f}")
     assert worst <= 0.01
+
+
+def _flagged_share(frame, q, sub):
+    return R.flagged(R.quotients(frame, q, sub)[0]).mean()
+
+
+def test_reference_flags_few_coefficients_past_one_scan_round_and_below_quality_50():
+    """The same condition on the frames the device runs past 1024 blocks (turned scenes, qualities 50 and 100, seeds 1-3) and at
+    qualities 1, 10 and 49; and the rounds after the first are not empty of bits."""
+    for hw, sub, blocks in R.ROUND_SHAPES:
+        mh, mw, per, _ = R.block_layout(*hw, sub)
+        assert mh * mw * per == blocks
+    assert max(b for _, _, b in R.ROUND_SHAPES if b < 1024) == 1023 and min(b for _, _, b in R.ROUND_SHAPES if b > 1024) == 1026
+    assert max(b for _, _, b in R.ROUND_SHAPES) > 2048
+    high = 0.0
+    for hw, sub, blocks in R.ROUND_SHAPES:
+        for q in (50, 100):
+            for seed in (1, 2, 3):
+                frame = R.scene(*hw, seed, turned=True)
+                assert np.array_equal(frame[::-1, ::-1], R.scene(*hw, seed))
+                high = max(high, _flagged_share(frame, q, sub))
+                # every round after the first holds a non-zero DC difference: its code has a 1-bit (every code but those of category
+                # 0 has), which a wrong carry puts elsewhere.  R.scene as it is ends in flat chroma blocks: DC 00, EOB 00
+                diffs = R.dc_differences(R.coefficients(frame, q, sub), sub)
+                assert len(diffs) == blocks and all(diffs[lo:lo + 1024].any() for lo in range(1024, blocks, 1024))
+    low = max(_flagged_share(R.scene(*hw, seed), q, sub) for hw, sub in R.LOW_SHAPES for q in R.LOW_QUALITIES for seed in (1, 2, 3))
+    print(f"largest flagged share {high:.4f} past one round, {low:.4f} below quality 50")
+    assert high <= 0.01 and low <= 0.01
+
+
+def test_reference_flags_few_coefficients_at_degenerate_sizes():
+    """A frame of 192 coefficients passes the 2 % cap with four ties, so the seeds are chosen (R.TINY_SEEDS): the reference alone flags
+    at most 1.6 % at each shape, both subsamplings, qualities 50 and 100."""
+    assert set(R.TINY_SEEDS) == {(1, 1), (1, 40), (40, 1), (7, 33), (8, 8), (16, 16), (3, 200)}
+    for hw, seeds in R.TINY_SEEDS.items():
+        assert len(set(seeds)) == 3
+        for seed in seeds:
+            frame = R.scene(*hw, seed)
+            assert frame.shape == hw + (3,) and frame.dtype == np.uint8
+            worst = max(_flagged_share(frame, q, sub) for sub in SUBS for q in (50, 100))
+            print(f"{hw} seed {seed}: largest flagged share {worst:.4f}")
+            assert worst <= 0.016
+
+
+@pytest.mark.parametrize("hw,sub,cell", R.CHECKERS)
+def test_block_checker_reaches_the_largest_dc_difference_without_a_tie(hw, sub, cell):
+    """Black and white cells on the block grid at quality 100: no quotient is flagged (each lies within 1e-9 of an integer), luma's
+    DC differences reach category 11 from real pixels, and the file round-trips."""
+    for frame in (R.block_checker(*hw, cell), 255 - R.block_checker(*hw, cell)):
+        assert frame.shape == hw + (3,) and frame.dtype == np.uint8 and set(np.unique(frame)) == {0, 255}
+        quot, comp = R.quotients(frame, 100, sub)
+        assert not R.flagged(quot).any() and np.abs(quot - np.rint(quot)).max() < 1e-9
+        want = R.round_half_away(quot)
+        assert set(np.unique(want[comp == 0, 0])) == {-1024, 1016} and not want[:, 1:].any() and not want[comp > 0].any()
+        stats = dict(zrl=0, eob=0, c63=0, dc11=0, ac10=0, stuffed=0, blocks=0)
+        data = R.encode(frame, 100, sub, stats)
+        assert stats["dc11"] > 0                                   # chroma is flat: every one of them is luma's
+        _, got, _, _ = R.decode_coefficients(data)
+        assert np.array_equal(got, want)
+
+
+def _scan_file(hw, scan):
+    return R.headers(*hw, 100, "444") + scan + b"\xff\xd9"
+
+
+def test_dense_coefficients_put_0xff_on_every_seam():
+    """What tests/test_gpu_video.py's dense batch relies on: about a fifth of each long scan is 0xFF, over 40 chunks of 4096 unstuffed
+    bytes; among them a 0xFF at the last byte of a chunk, at the last byte of a thread's 16, and pairs of 0xFF across both kinds of
+    seam; the short frame is short; every scan decodes to its coefficients."""
+    batch = R.dense_batch()
+    mh, mw, per, _ = R.block_layout(*R.DENSE_HW, "444")
+    assert batch.shape == (3, mh * mw * per, 64) and batch.dtype == np.int16 and mh * mw * per == 1026
+    scans = [R.entropy(c, "444") for c in batch]
+    for c, scan in zip(batch[:2], scans[:2]):
+        assert set(np.unique(c[:, 1:])) == {-1023, -511, 255, 511, 1023} and set(np.unique(c[:, 0])) == {-1024, 1023}
+        seams = R.ff_seams(scan)
+        print(len(scan), seams)
+        assert len(R.unstuffed(scan)) > 40 * 4096 and seams["ff"] == len(scan) - len(R.unstuffed(scan)) >= 0.15 * len(scan)
+        for what in ("chunk_end", "vector_end", "chunk_pair", "vector_pair"):
+            assert seams[what] > 0, what
+    assert not np.array_equal(batch[0], batch[1]) and 0 < len(scans[2]) < 4096 and b"\xff\x00" in scans[2]
+    for c, scan in zip(batch, scans):
+        _, got, _, _ = R.decode_coefficients(_scan_file(R.DENSE_HW, scan))
+        assert np.array_equal(got, c)
+
+
+def test_padded_last_byte_is_0xff():
+    """Three dense blocks (8 x 8 at 4:4:4) whose stream ends one bit into a byte, a 1: the seven bits of padding make it 0xFF, and the
+    scan ends FF 00."""
+    coefs = R.dense_coefficients(3, R.PADDED_FF_SEED)
+    stats = dict(zrl=0, eob=0, c63=0, dc11=0, ac10=0, stuffed=0, blocks=0)
+    scan = R.entropy(coefs, "444", stats)
+    assert stats["pad_bits"] == 7 and scan[-2:] == b"\xff\x00"
+    _, got, _, _ = R.decode_coefficients(_scan_file((8, 8), scan))
+    assert np.array_equal(got, coefs)
 
 
 # --------------------------------------------------------------------------------------- the dev header on the host
@@ -202,7 +304,7 @@ def host_program(tmp_path_factory):
     return run
 
 
-@pytest.mark.parametrize("hw,sub,q", CASES)
+@pytest.mark.parametrize("hw,sub,q", CASES + LOW_CASES + TINY_CASES)
 def test_dev_header_against_the_reference(host_program, frames, hw, sub, q):
     """Coefficients: equal to the float64 reference's except where its quotient lies within 4e-3 of a half-integer (fp32 carries about
     1e-4 absolute on a DC term of 1024 through colour, 64 DCT terms and the division at quality 100; 4e-3 leaves an order of
@@ -214,12 +316,24 @@ def test_dev_header_against_the_reference(host_program, frames, hw, sub, q):
     assert scan == R.entropy(coefs, sub)
 
 
+@pytest.mark.parametrize("hw,sub,cell", R.CHECKERS)
+def test_dev_header_on_block_checkers(host_program, hw, sub, cell):
+    """No quotient of a block checker is near a tie: fp32 gives the float64 coefficients themselves, DC differences of 2040 among them."""
+    frame = R.block_checker(*hw, cell)
+    coefs, scan = host_program(frame, 100, sub)
+    assert not R.compare_coefficients(coefs, frame, 100, sub).any() and np.array_equal(coefs, R.coefficients(frame, 100, sub))
+    assert scan == R.entropy(coefs, sub)
+
+
 # ------------------------------------------------------------------------------------------------------ video.py, host side
 def test_headers_and_tables_are_the_references(hiplib):
     from radnerf import video
-    for q in (1, 37, 50, 90, 100):
+    for q in (1, 10, 37, 49, 50, 90, 100):
         for a, b in zip(video.quant_tables(q), R.quant_tables(q)):
             assert np.array_equal(a, b)
+    assert all((t == 255).all() for t in video.quant_tables(1))
+    for q in R.LOW_QUALITIES:
+        assert video.jfif_header(40, 24, q, "420") == R.headers(40, 24, q, "420")
     for sub in SUBS:
         assert video.jfif_header(17, 19, 75, sub) == R.headers(17, 19, 75, sub)
     with pytest.raises(ValueError):
