@@ -148,6 +148,16 @@ typedef struct {
                                              without looking their cells up and ends its walk where it leaves that box, instead of
                                              testing every cell up to `far`.  Speed only: no set bit lies outside the box, so the
                                              samples are the same, bit for bit.  NULL (and every other configuration): the full walk. */
+    float *dir_term;                      /* [N][64], 16-byte aligned (N <= 2^24), or NULL.  Scratch, never zeroed: the colour net's
+                                             first layer starts from a term that depends on the ray's direction and the frame's
+                                             bias only (bias + 8 MFMA steps over SH(dir)), the same for every sample of a ray.  The
+                                             fp32 network launch of loop iteration 0 stores it from every live sample's own
+                                             accumulators, the launches of iterations >= 1 load it instead of recomputing it (a ray
+                                             that reaches iteration 1 had a live sample in iteration 0).  Speed only: the loaded
+                                             term is the value the sample would compute, bit for bit.  NULL (and RN_F16 /
+                                             RN_F32_SPLIT): every sample computes its own.  rn_head_iterate_ex decides by the
+                                             iteration number, so a loop enqueued over several calls works the same; a frame's loop
+                                             starts at iteration 0. */
 } rn_head_t;
 
 /* near/far + loop initialisation (rays_alive = arange(N), rays_t = nears, accumulators = 0, step = 0). */

@@ -100,6 +100,10 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
     const int lane_off = h * 64 + j * 2;
     const float *bias_amb = lds + kInferPacked, *bias_sig = lds + kInferPacked + 64, *bias_col = lds + kInferPacked + 128;
 
+    // direction terms (DirTerm, rn_fused_dev.h): wave-uniform, fixed for the launch
+    const bool term_load = p.dt.rows && !p.dt.store, term_store = p.dt.rows && p.dt.store;
+    const uint32_t step_rcp = p.dt.rows ? dir_term_step_rcp(p.dt.state) : 0u;
+
     const TileSchedule sched(n_tiles, kF32Waves, (uint32_t)wave);
     for (uint32_t tile = sched.first; tile < sched.end; tile += sched.stride) {
         const uint32_t entry = tile * 32 + j;  // both lane halves work on the same 32 samples
@@ -171,6 +175,24 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
             p.ambient[2 * (size_t)sample + 1] = amb[1];
         }
 
+        // ---- a0 is dead from here to the colour net: an iteration >= 1 of the frame loop fetches its ray's direction term
+        // into it now (8 x 16 bytes per lane), so the loads pass under the ambient gather and the sigma net's 64 MFMAs
+        if (term_load) {
+            const uint32_t row = dir_term_row(p.dt.alive, step_rcp, p.dt.n_rays, live, sample);
+            if (__ballot(row == ~0u) != 0ull) acc_zero(a0);  // dead lanes of a tail tile (wave-uniform: no other tile pays for it)
+            if (row != ~0u) {
+                // a 32-bit byte offset on the scalar base (n_rays <= 2^24, checked by rn_head_iterate_ex): a 64-bit per-lane base would be one more
+                // loop-invariant register pair than this kernel has
+                const float4 *src = reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(p.dt.rows) + (row * 256u + (uint32_t)h * 128u));
+#pragma unroll
+                for (int g = 0; g < 8; g++) {
+                    const float4 t = src[g];
+                    a0.v[g >> 2][4 * (g & 3) + 0] = t.x; a0.v[g >> 2][4 * (g & 3) + 1] = t.y;
+                    a0.v[g >> 2][4 * (g & 3) + 2] = t.z; a0.v[g >> 2][4 * (g & 3) + 3] = t.w;
+                }
+            }
+        }
+
         // ---- ambient grid: enc_w = encoder_ambient(ambient, bound=1) -> sigma L0 steps 16..31
         RN_PHASE_MARK(2);
         {
@@ -218,9 +240,11 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
         }
 
         // ---- color net: [SH(d) | geo_feat | ind_code] 84 -> 64 -> 3, sigmoid; the geo_feat columns of its first layer are
-        // packed times sigma L2's geo_feat rows, so their 32 steps take the sigma net's hidden activations (a1)
-        acc_bias(a0, bias_col, h);
-        {
+        // packed times sigma L2's geo_feat rows, so their 32 steps take the sigma net's hidden activations (a1).
+        // The bias and the 8 SH steps are the ray's direction term: the same bits for every sample of the ray (exact FMA chains
+        // over the same operands in the same order), so only the loop's iteration 0 and launches outside the loop run them.
+        if (!term_load) {
+            acc_bias(a0, bias_col, h);
             float sh[16];
             float dx = 0.0f, dy = 0.0f, dz = 0.0f;
             if (live) {
@@ -234,6 +258,16 @@ __global__ void __launch_bounds__(kF32Threads, kF32Waves / 4) k_nerf_fused(Fused
                 const uint32_t m = 0u - (uint32_t)h;
                 const uint32_t b = (__float_as_uint(sh[2 * s]) & ~m) | (__float_as_uint(sh[2 * s + 1]) & m);
                 step32(a0, lds + IOFF_C0, s, lane_off, __uint_as_float(b));
+            }
+            if (term_store) {  // every live sample of iteration 0 writes its ray's row (n_step > 1 there: the same bytes again)
+                const uint32_t row = dir_term_row(p.dt.alive, step_rcp, p.dt.n_rays, live, sample);
+                if (row != ~0u) {
+                    float4 *dst = reinterpret_cast<float4 *>(reinterpret_cast<char *>(p.dt.rows) + (row * 256u + (uint32_t)h * 128u));
+#pragma unroll
+                    for (int g = 0; g < 8; g++)
+                        dst[g] = make_float4(a0.v[g >> 2][4 * (g & 3) + 0], a0.v[g >> 2][4 * (g & 3) + 1],
+                                             a0.v[g >> 2][4 * (g & 3) + 2], a0.v[g >> 2][4 * (g & 3) + 3]);
+                }
             }
         }
 #pragma unroll
@@ -279,8 +313,8 @@ static void launch_fused(const FusedParams &p, hipStream_t s) {
 
 int run_fused(const float *xyzs, const float *dirs, const float *deltas, uint32_t M, const int32_t *m_dev, const rn_grid_t *gx,
               const rn_grid_t *gw, const float *packed, const float *bias, float bound, float *sigmas, float *rgbs, float *ambient,
-              int mlp_dtype, hipStream_t s, const int32_t *slots) {
-    FusedParams p{xyzs, dirs, deltas, M, m_dev, grid_args(gx), grid_args(gw), packed, bias, bound, sigmas, rgbs, ambient, slots};
+              int mlp_dtype, hipStream_t s, const int32_t *slots, const DirTerm &dt) {
+    FusedParams p{xyzs, dirs, deltas, M, m_dev, grid_args(gx), grid_args(gw), packed, bias, bound, sigmas, rgbs, ambient, slots, dt};
     if (mlp_dtype == RN_F32_SPLIT) {
         launch_fused_x2(p, gx->dtype, gw->dtype, (uint32_t)num_cus(), s);
     } else if (mlp_dtype == RN_F16) {

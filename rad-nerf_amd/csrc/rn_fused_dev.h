@@ -103,6 +103,19 @@ inline GridArgs grid_args(const rn_grid_t *g) {
     return GridArgs{g->embeddings, g->offsets, make_level_consts(g->L, g->S, g->H), g->gridtype};
 }
 
+// Direction terms of the frame loop (rn_head_t.dir_term): the colour net's first-layer accumulators after the bias and the
+// 8 SH(dir) steps are the same for every sample of a ray within a frame, so the launch of loop iteration 0 stores them, one
+// row of 64 floats per ray ([lane half][32 accumulator registers], the register order), and the launches of the later
+// iterations load them instead of recomputing them.  The ray of a sample: slot / n_step is its position in the alive list
+// the iteration reads.  rows == NULL: every sample computes its own (every launch outside the loop).
+struct DirTerm {
+    float *rows;            // [n_rays][64], 16-byte aligned, or NULL
+    const int32_t *state;   // the iteration's state bank: [2] = n_step
+    const int32_t *alive;   // the alive list the iteration reads (before its compositor marks the rays that end)
+    uint32_t n_rays;
+    uint32_t store;         // 1: this launch writes the rows (iteration 0); 0: it reads them
+};
+
 struct FusedParams {
     const float *xyzs, *dirs, *deltas;
     uint32_t M;
@@ -116,6 +129,7 @@ struct FusedParams {
     // deltas[2 j] == 0).  Inside the frame loop the marchers write it, so the network skips the dead slots of rays that
     // ended in the middle of their n_step samples (16 % of the slots of the benchmark stream).
     const int32_t *slots;
+    DirTerm dt;   // read by k_nerf_fused only: the 16-bit kernels wait on their gathers and spend one or two MFMAs on SH
 };
 
 // XCD-aware tile schedule.  Workgroups are dealt round-robin over the 8 XCDs (workgroup b lands on XCD b % 8; used for
@@ -197,6 +211,26 @@ __device__ __forceinline__ void load_dir(const float *dirs, bool live, uint32_t 
     }
 }
 
+// DirTerm: ceil(2^32 / n_step) for n_step >= 2, 0 for n_step == 1.  slot / n_step == __umulhi(slot, that) exactly while
+// slot * (n_step - 1) < 2^32 (multiplier * n_step exceeds 2^32 by at most n_step - 1): n_step <= 8, so for every slot below
+// 2^29 -- an integer multiply-shift, no float reciprocal.
+__device__ __forceinline__ uint32_t dir_term_step_rcp(const int32_t *state) {
+    const uint32_t n_step = (uint32_t)state[2];
+    return n_step > 1u ? 0xFFFFFFFFu / n_step + 1u : 0u;
+}
+// DirTerm: the row (ray) of sample slot `sample`, or ~0u for a dead lane and for anything outside the list or the buffer
+__device__ __forceinline__ uint32_t dir_term_row(const int32_t *alive, uint32_t step_rcp, uint32_t n_rays, bool live, uint32_t sample) {
+    uint32_t row = ~0u;
+    if (live) {
+        const uint32_t pos = step_rcp ? __umulhi(sample, step_rcp) : sample;
+        if (pos < n_rays) {
+            const uint32_t ray = (uint32_t)alive[pos];
+            if (ray < n_rays) row = ray;
+        }
+    }
+    return row;
+}
+
 // (grid table dtypes) -> the <TX, TW> instantiation: calls f(TX{}, TW{}) with float or __half values as type tags
 template <typename F>
 static inline void dispatch_grid_dtypes(int gx_dtype, int gw_dtype, F &&f) {
@@ -218,7 +252,7 @@ static inline int check_train_grid(const rn_grid_t *g, uint32_t D, const char *w
 int check_fused_grid(const rn_grid_t *g, uint32_t D, const char *name);
 int run_fused(const float *xyzs, const float *dirs, const float *deltas, uint32_t M, const int32_t *m_dev, const rn_grid_t *gx,
               const rn_grid_t *gw, const float *packed, const float *bias, float bound, float *sigmas, float *rgbs, float *ambient,
-              int mlp_dtype, hipStream_t s, const int32_t *slots = nullptr);
+              int mlp_dtype, hipStream_t s, const int32_t *slots = nullptr, const DirTerm &dt = DirTerm{});
 // The 16-bit matrix-core variants (rn_fused_f16.hip); `gx_dtype` / `gw_dtype` are the grid table dtypes.
 void launch_fused_h16(const FusedParams &p, int gx_dtype, int gw_dtype, uint32_t blocks, hipStream_t s);
 void launch_pack_nerf_h16(const RawW &w, float *packed, hipStream_t s);

@@ -472,6 +472,8 @@ int rn_head_iterate_ex(const rn_head_t *h, const rn_grid_t *grid_xyz, const rn_g
     RN_REQUIRE(packed && bias && ((uintptr_t)packed & 15u) == 0, "head_iterate: packed/bias");
     if (int rc = check_fused_grid(grid_xyz, 3, "head_iterate(xyz grid)")) return rc;
     if (int rc = check_fused_grid(grid_amb, 2, "head_iterate(ambient grid)")) return rc;
+    RN_REQUIRE(!h->dir_term || (((uintptr_t)h->dir_term & 15u) == 0 && h->N <= (1u << 24)),
+               "head_iterate: dir_term must be 16-byte aligned and N <= 2^24 with it");
     hipStream_t s = as_stream(stream);
     const dim3 rgrid(div_up(h->N, kLoopBlock)), rblock(kLoopBlock);
     // caller's scratch: survivor counts | live-sample partial sums of even iterations | ... of odd iterations
@@ -490,8 +492,10 @@ int rn_head_iterate_ex(const rn_head_t *h, const rn_grid_t *grid_xyz, const rn_g
                                h->deltas, h->state, block_live[it & 1u], st + 6, h->live_slots, h->occ_box, h->N);
         // the network runs over the iteration's live list when the caller gave room for one (st[6] entries), else over all
         // st[3] slots, skipping the dead ones by their deltas
+        // direction terms: iteration 0 writes each live ray's row, the later ones read theirs (DirTerm, rn_fused_dev.h)
+        const DirTerm dt{h->dir_term, st, alive, h->N, it == 0 ? 1u : 0u};
         run_fused(h->xyzs, h->dirs, h->deltas, h->N, h->live_slots ? st + 6 : st + 3, grid_xyz, grid_amb, packed, bias, h->bound,
-                  h->sigmas, h->rgbs, nullptr, mlp_dtype, s, h->live_slots);
+                  h->sigmas, h->rgbs, nullptr, mlp_dtype, s, h->live_slots, dt);
         const MarchArgs m{h->rays_t, h->rays_o, h->rays_d, h->fars, h->bound, h->dt_gamma, h->cascade, h->grid_size, h->bitfield,
                           h->xyzs, h->dirs, h->deltas, block_live[(it + 1) & 1u], h->live_slots, h->occ_box};
         const bool march_next = it + 1 < first_iter + n_iters;

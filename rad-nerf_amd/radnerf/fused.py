@@ -31,6 +31,8 @@ from .frame_cache import FrameCaches, LoopStats
 
 _lib = hip._lib
 
+DIR_TERM_MAX_RAYS = 1 << 20     # rays per frame up to which a FusedState keeps direction terms (256 bytes each)
+
 
 def _grid_desc(enc, table):
     g = GridT()
@@ -308,7 +310,24 @@ class FusedState:
         self.stats_prev = [0, 0, 0]
         self.block_counts = torch.zeros(3 * ((N + 255) // 256 + 1), dtype=i32, device=d)
         self.live_slots = torch.empty(N, dtype=i32, device=d)   # live-sample list of the iteration in flight
+        self.dir_term, self._dir_term_tried = None, False      # dir_terms() allocates on first use
         self._N = N
+
+    def dir_terms(self):
+        """The rays' direction terms for rn_head_t.dir_term, [N, 64] fp32, or None: RN_DIR_TERM=0 (nothing is allocated for a
+        process that never switches it on), more than 2^20 rays, or no memory for it.  Written by every frame's first loop
+        iteration before anything reads it, so never zeroed; 256 bytes per ray (64 MiB at 512 x 512), one buffer per state.
+        The allocation is tried once per scratch(N): a failure is held, a frame never tries again."""
+        if not switches.on("RN_DIR_TERM"):
+            return None
+        if not self._dir_term_tried:
+            self._dir_term_tried = True
+            if self._N <= DIR_TERM_MAX_RAYS:
+                try:
+                    self.dir_term = torch.empty(self._N, 64, dtype=torch.float32, device=self.dev)
+                except torch.cuda.OutOfMemoryError:
+                    pass
+        return self.dir_term
 
     def read_loop_stats(self):
         """The frame just enqueued, for LoopStats: the device counters accumulate across frames, a frame's numbers are the
@@ -337,6 +356,7 @@ class FusedState:
         # walks the rays in 8 x 8 pixel blocks (more shared grid rows per wave; no pixel changes)
         h.order_w = int(getattr(model, "ray_order_width", 0) or 0)
         h.occ_box = hip.ptr(self.occ_box())
+        h.dir_term = hip.ptr(self.dir_terms())
         return h
 
 

@@ -13,6 +13,7 @@ TABLE = (
     ("RN_AUDIO_TRAIN", "hip", ("hip", "torch"), "`encode_audio` on the GPU: the audio kernels (`radnerf/audio.py`) or the `nn.Module` path"),
     ("RN_DENSE_BUDGET_MB", "384", ("160", "384", "896", "2304"), "with `RN_DENSE_LEVELS=1`: the most memory, in MiB, the dense image of the xyz table may take (`opt.dense_budget_mb`, any number, overrides it); for the T = 2^19 hash grid in fp32 the four values store levels 5-8 (149 MiB), 5-9 (343 MiB), 5-10 (857 MiB) and 5-11 (2215 MiB) as lattices, fp16 tables take half"),
     ("RN_DENSE_LEVELS", "1", ("1", "0"), "fused inference engine: a frame whose xyz table is that of the frame before reads the coarser hashed levels from a dense image built once (`rn_grid_dense_build`: each such level stored as its whole lattice, so neighbouring samples share cache lines; same features, same bits); `0`: every frame gathers from the hashed table"),
+    ("RN_DIR_TERM", "1", ("1", "0"), "fused inference engine, fp32 network kernel: the colour net's direction term (bias + 8 MFMA steps over SH(dir), the same for every sample of a ray) is stored per ray by the loop's first iteration and loaded by the later ones (`rn_head_t.dir_term`, 256 bytes per ray, frames of up to 2^20 rays; same bits); `0`: every sample computes it"),
     ("RN_LIVE_LIST", "1", ("1", "0"), "fused inference engine: hand the loop the list of live sample slots (`0`: every launch scans all slots)"),
     ("RN_MLP_TRAIN", "hip", ("hip", "torch"), "the per-operator MLP stacks under autograd: `rn_mlp64_*` (`radnerf/mlp_train.py`) or `nn.Linear`"),
     ("RN_OCC_BOX", "1", ("1", "0"), "fused inference engine: hand the loop the box around the occupancy grid's set bits (`rn_occ_box`, built once per grid): with one cascade and a constant step a ray tests only the cells between its entry into and its exit from that box (same bits); `0`: every ray tests every cell from `near` to `far`"),

@@ -48,7 +48,8 @@ class HeadT(C.Structure):
                 ("grid_size", _u32), ("T_thresh", _f32), ("nears", _ptr), ("fars", _ptr), ("weights_sum", _ptr),
                 ("depth", _ptr), ("image", _ptr), ("rays_alive_a", _ptr), ("rays_alive_b", _ptr), ("rays_t", _ptr),
                 ("xyzs", _ptr), ("dirs", _ptr), ("deltas", _ptr), ("sigmas", _ptr), ("rgbs", _ptr), ("state", _ptr),
-                ("block_counts", _ptr), ("live_slots", _ptr), ("order_w", _u32), ("occ_box", _ptr)]
+                ("block_counts", _ptr), ("live_slots", _ptr), ("order_w", _u32), ("occ_box", _ptr),
+                ("dir_term", _ptr)]
 
 
 class TorsoWeightsT(C.Structure):
